@@ -9,8 +9,12 @@ a true relative residual <= 1e-10, right-hand sides and wavefields resident in H
 dealt round-robin over ranks (weak scaling: every rank does `steps` items; no data-path collective).
 
 Prints ONE JSON line (rank 0).  `value` = wavefields completed by all ranks / max-over-ranks time.
-Extra passes over the same K items, reported beside it (never as `value`): `unprofiled` (per-launch events off), `every_front_computed` (nothing skipped
-on the point sources), `support_declared` (the sparse source matrix's support handed to the solver), `strong_scaling_job` (the 4096-wavefield job once).
+A plain run sets up, warms up, times the K steps and prints that line.  With --full, extra passes over the same K items are reported beside it (never as
+`value`): `unprofiled` (per-launch events off), `every_front_computed` (nothing skipped on the point sources), `support_declared` (the sparse source matrix's
+support handed to the solver), `strong_scaling_job` (the 4096-wavefield job once), the serial roofline pass, and the other legs (host API, configs 2 / 4 / 5,
+CPU baselines and the parity check against their LU).
+--dump-outputs DIR: what the last timed step computed (a fixed, seeded sample of its wavefields, their column norms, per-source residuals and passes) as
+DIR/<name>.npy in float64, written right after the timed region.
 """
 import argparse
 import json
@@ -96,6 +100,32 @@ def work_item(w, nbatch_per_freq):
     """global work-item index -> (frequency index, source-batch index).  Consecutive items walk the
     frequency list with stride 5 (co-prime with 16) so short runs sample low and high frequencies."""
     return (w * 5) % NFREQ, (w // NFREQ) % nbatch_per_freq
+
+
+DUMP_ROWS = 8192          # grid cells of the wavefield sample: 8192 x 256 sources x (re, im) x 8 B = 33.6 MB
+DUMP_SEED = 20240512
+
+
+def dump_outputs(d, u, info, node):
+    """--dump-outputs: what a caller of the timed path receives from one step -- the wavefields of its sources (device array u, (N, B) node-major or
+    (B, N) rhs-major) and one record per source -- as float64 .npy files under d.  The wavefields are 4.3 GB at the default size, so the files hold the
+    values at a fixed, seeded set of DUMP_ROWS grid cells and the 2-norm of every wavefield over the whole grid."""
+    import torch
+    os.makedirs(d, exist_ok=True)
+    uu = u if node else u.t()                                # (N, B) view either way
+    N, B = uu.shape
+    cells = np.sort(np.random.default_rng(DUMP_SEED).choice(N, size=min(N, DUMP_ROWS), replace=False))
+    sample = uu.index_select(0, torch.from_numpy(cells).to(u.device))
+    sq = torch.zeros(B, dtype=torch.float64, device=u.device)
+    for r0 in range(0, N, 1 << 16):                          # (in slices: no temporary the size of the whole field)
+        sq += uu[r0:r0 + (1 << 16)].abs().square().sum(0)
+    arrays = {'wavefield_sample': torch.view_as_real(sample.contiguous()).cpu().numpy(),      # (cells, B, 2): real and imaginary parts
+              'wavefield_sample_cells': cells.astype(np.float64),                               # flat grid index (iz * nx + ix) of every sampled row
+              'wavefield_norms': torch.sqrt(sq).cpu().numpy(),
+              'relres': np.array([i['relres'] for i in info], np.float64),
+              'iterations': np.array([i['iterations'] for i in info], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(d, name + '.npy'), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def cpu_baseline(cfg, freqs, q_host, sample_rhs=8):
@@ -601,6 +631,11 @@ def main():
                     help='work items whose factorisations the device pipeline enqueues together (helm_prefactor_many: the fronts of `group` frequencies in the same '
                          'batched launches; 1: every frequency factored by itself, rounds 1-5)')
     ap.add_argument('--streams', type=int, default=1, help='work items in flight per GPU (host threads, one operator handle / HIP stream each)')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, run the extra passes (roofline, unprofiled, every front, declared support, strong-scaling job), the stencil '
+                         'microbenchmark and the other legs (host API, configs 2 / 4 / 5, CPU baselines, parity vs LU); the --no-* options switch single ones off')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write what the last timed step computed as DIR/<name>.npy (float64, < 64 MB: a seeded sample of the wavefields)')
     args = ap.parse_args()
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
@@ -666,10 +701,10 @@ def main():
         d_u = torch.empty((B, N), dtype=torch.complex128, device=dev)
 
     # the support of the sparse source matrix, as Discretization.rhsSupportFromSparse makes it (one byte per cell, bit b = block b of 64 sources has an entry there):
-    # used by the extra `support_declared` pass only -- the headline lets the library find the nonzeros of the dense right-hand sides itself
+    # used by the extra `support_declared` pass only (--full) -- the headline lets the library find the nonzeros of the dense right-hand sides itself
     use_support = [False]
     d_support = None
-    if node:
+    if node and args.full:
         coo_ = q_sparse.tocoo()
         bits_ = np.zeros(((N + 3) // 4) * 4, np.uint8)
         np.bitwise_or.at(bits_, coo_.row, (1 << (coo_.col >> 6)).astype(np.uint8))
@@ -678,6 +713,8 @@ def main():
     ops = {}
 
     stamps = []                          # completion time of every work item (diagnostics: `item_done_ms` of the timed region)
+    in_timed = [False]                   # True while the timed region runs
+    last_out = {}                        # work item -> (wavefield array, per-source info) of its solve in the timed region (--dump-outputs)
     tl = []                              # (what, item, time) marks of the prepare / solve steps (`first_items_timeline_ms`)
 
     def prepare_item(w, profile):
@@ -714,6 +751,8 @@ def main():
         t = op.lastTiming()
         del op.factors                   # nothing is carried over between steps
         stamps.append(time.perf_counter())
+        if args.dump_outputs and in_timed[0]:
+            last_out[w] = (ubuf, info)   # (what a caller receives from item w)
         return fi, info, t
 
     def run_item(w, profile, ubuf=None):
@@ -787,6 +826,7 @@ def main():
     cg0 = cgroup_cpu()
     cpu0 = time.process_time()
     _zl0.runtime_stats(reset=True)       # what the timed region makes the HIP runtime create (allocations, events, first launches) is counted from here
+    in_timed[0] = True
     t0 = time.perf_counter()
     results = [None] * len(timed_items)
     if args.streams <= 1:
@@ -822,6 +862,7 @@ def main():
     agg = aggregate(results)
     barrier()
     elapsed = time.perf_counter() - t0
+    in_timed[0] = False
     memtrace('after the timed region')
     rt_timed = _zl0.runtime_stats()
     cg1 = cgroup_cpu()
@@ -842,6 +883,10 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         return float(tt.item())
     elapsed = max_over_ranks(elapsed)
+    # what the timed path computed in its last step, before any pass of --full overwrites the wavefield array
+    if args.dump_outputs and rank == 0 and timed_items:
+        dump_outputs(args.dump_outputs, *last_out[timed_items[-1]], node=node)
+    last_out.clear()
 
     # Kernel-level roofline: in the pipelined region the factorisation of item k+1 shares the CUs with the solves of item k, so the
     # per-launch durations there measure the sharing (both kernels stretch).  The same K items therefore run once more strictly one after
@@ -851,7 +896,7 @@ def main():
     # sources would be credited with flops it did not do.  (The pipelined figures `in_pipeline` come from the timed region, where the skipping
     # is on: their TFLOP/s are marked `counts_skipped_flops`.)
     agg_k = agg
-    if args.streams <= 1 and not args.no_roofline_pass:
+    if args.full and args.streams <= 1 and not args.no_roofline_pass:
         barrier()
         os.environ['HELM_ND_SPARSE_RHS'] = '0'
         if args.pipeline and args.group > 1:
@@ -873,7 +918,7 @@ def main():
 
     # the same K work items once more with the per-launch HIP events off: what the event traffic of the roofline measurement costs
     elapsed_plain = None
-    if args.streams <= 1 and not args.no_plain_pass:
+    if args.full and args.streams <= 1 and not args.no_plain_pass:
         barrier(True)
         t1 = time.perf_counter()
         run_items(timed_items, False)
@@ -882,7 +927,7 @@ def main():
     # ... and once more with the forward pass computing every front whatever the right-hand sides hold (HELM_ND_SPARSE_RHS=0): what the job costs
     # when the sources are NOT the point sources of a survey (a dense right-hand side sets every flag itself and lands here too)
     elapsed_dense = None
-    if args.streams <= 1 and not args.no_plain_pass and args.method in ('auto', 'direct'):
+    if args.full and args.streams <= 1 and not args.no_plain_pass and args.method in ('auto', 'direct'):
         os.environ['HELM_ND_SPARSE_RHS'] = '0'
         barrier(True)
         t1 = time.perf_counter()
@@ -894,7 +939,7 @@ def main():
     # ... and with the support of the sparse source matrix declared to the solver (helm_set_rhs_support; the reference's sources ARE scipy-sparse matrices): the leaf
     # level of the forward pass then does not read the dense right-hand sides to look for their nonzeros
     elapsed_support = None
-    if args.streams <= 1 and not args.no_plain_pass and args.method in ('auto', 'direct') and d_support is not None:
+    if args.full and args.streams <= 1 and not args.no_plain_pass and args.method in ('auto', 'direct') and d_support is not None:
         use_support[0] = True
         barrier(True)
         t1 = time.perf_counter()
@@ -907,7 +952,7 @@ def main():
     # 16 work items dealt round-robin over the ranks (events off) -- the strong-scaling figure of the same launch, so that a driver that only ever
     # calls `bench.py --gpus N` gets both curves
     strong_job = None
-    if args.scaling == 'weak' and args.streams <= 1 and not args.no_plain_pass:
+    if args.full and args.scaling == 'weak' and args.streams <= 1 and not args.no_plain_pass:
         job_items = [w for w in range(NFREQ * nb) if w % world == rank]
         barrier(True)
         t1 = time.perf_counter()
@@ -933,7 +978,7 @@ def main():
         rank_ms = [float(t.item()) for t in every]
     # config 4 on every rank (its frequencies are sharded over the ranks and the gradient crosses the all-reduce)
     c4 = None
-    if not args.no_config4 and args.method in ('auto', 'direct'):
+    if args.full and not args.no_config4 and args.method in ('auto', 'direct'):
         try:
             c4 = config4_leg(local, world, rank, dist, backend)
         except Exception as exc:
@@ -949,7 +994,7 @@ def main():
                'BiCGSTAB right-preconditioned by shifted-Laplacian multigrid with damped-Jacobi smoothing + PML line relaxation')
         where = (('a pass over the same K work items strictly one after the other (no other kernel on the GPU; the factorisations of %d items per set of launches as in the timed '
                   'region), events on, HELM_ND_SPARSE_RHS=0 (every booked flop and byte is executed); in_pipeline = the same quantities from the timed region'
-                  % (args.group if args.pipeline else 1)) if args.streams <= 1 else 'the timed region')
+                  % (args.group if args.pipeline else 1)) if agg_k is not agg else 'the timed region')
 
         def stencil_block(a):
             ach = (a['apply_bytes'] / (a['apply_ms'] * 1e-3)) / 1e9 if a['apply_ms'] > 0 else 0.0
@@ -990,7 +1035,7 @@ def main():
             'value': value, 'unit': 'wavefields/s', 'n_gpus': world, 'steps': nsteps, 'warmup': args.warmup,
             'ms_per_step': 1e3 * elapsed / nsteps, 'higher_is_better': True, 'scaling': args.scaling,
             'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-            'timed_region': 'K work items through the device pipeline with per-launch HIP events on; `unprofiled` repeats the same K items with the events off',
+            'timed_region': 'K work items through the device pipeline with per-launch HIP events on; `unprofiled` (--full) repeats the same K items with the events off',
             'pipeline': (('device pipeline of zephyr_amd.dispatch (MultiFreq parallel mode): items k+1 .. k+%d are created and assembled, their factorisations enqueued TOGETHER '
                           '(helm_prefactor_many: the fronts of %d frequencies in the same batched launches, high-priority stream) while the items before them are being solved'
                           % (args.group, args.group)) if args.pipeline and args.group > 1 else
@@ -1042,7 +1087,7 @@ def main():
         micro_target = out['stencil_roofline'] if direct else out['roofline']
         # stencil-apply microbenchmark of SURVEY.md 8(d) (outside the timed region): Y = A X on random X, B right-hand sides,
         # algorithmic bytes N*(32*B + 144), HIP events on the solver stream
-        if world == 1:
+        if world == 1 and args.full:
             try:
                 import ctypes
                 from zephyr_amd import _lib
@@ -1085,7 +1130,7 @@ def main():
                     pass
             return None, None
         try:
-            if direct:
+            if args.full and direct:
                 pz, src_z = pmc('pmc_traffic_zgemm')
                 if pz:
                     out['roofline']['traffic'] = pz['traffic_bytes_per_launch']
@@ -1103,14 +1148,14 @@ def main():
                 if pr:
                     out['stencil_roofline']['traffic'] = pr['traffic_bytes_per_launch']
                     out['stencil_roofline']['traffic_source'] = src_r + ' (HBM bytes per residual-kernel launch)'
-            else:
+            elif args.full:
                 pk = json.load(open(os.path.join(ROOT, 'profiles', 'r01_krylov_pmc_traffic.json')))
                 if pk.get('batch') == B and pk.get('grid') == [n, n]:
                     out['roofline']['traffic'] = pk['traffic_bytes_per_launch_outer_applies']
                     out['roofline']['traffic_source'] = 'profiles/r01_krylov_pmc_traffic.json'
         except Exception:
             pass
-        if world == 1 and not args.no_host_api and direct:
+        if args.full and world == 1 and not args.no_host_api and direct:
             # The reference's actual call shape (discretization.py:101-103, distributors.py:127-173): `MultiFreq(systemConfig) * q` with a
             # scipy-sparse source matrix in and one (N, nsrc) numpy array per frequency out -- all 16 frequencies of the job, every
             # wavefield copied back to the host (4.3 GB per frequency over PCIe into pinned memory).  PCIe-inclusive: never `value`.
@@ -1164,7 +1209,7 @@ def main():
             memtrace('after the host-API leg')
             d_u = torch.empty((N, B) if node else (B, N), dtype=torch.complex128, device=dev)
         out['config4'] = c4
-        if world == 1 and not args.no_config2 and direct:
+        if args.full and world == 1 and not args.no_config2 and direct:
             try:
                 del d_u
                 torch.cuda.empty_cache()
@@ -1172,7 +1217,7 @@ def main():
             except Exception as exc:
                 out['config2'] = 'failed: %s' % exc
             d_u = torch.empty((N, B) if node else (B, N), dtype=torch.complex128, device=dev)
-        if world == 1 and not args.no_config5 and n == 1024:
+        if args.full and world == 1 and not args.no_config5 and n == 1024:
             try:
                 del d_u
                 torch.cuda.empty_cache()
@@ -1180,7 +1225,7 @@ def main():
             except Exception as exc:
                 out['config5'] = 'failed: %s' % exc
             d_u = torch.empty((N, B) if node else (B, N), dtype=torch.complex128, device=dev)
-        if world == 1 and not args.no_cpu:
+        if args.full and world == 1 and not args.no_cpu:
             cb, u_lu = cpu_baseline(cfg, freqs, q_all)
             out['cpu_baseline'] = cb
             # parity gate of the bench itself: the LU wavefields the CPU leg just computed against the GPU path on the same frequency / sources

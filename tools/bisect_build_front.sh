@@ -2,12 +2,13 @@
 # round 6: k_nd_build_front, round 4's tree (r4tree/, a git worktree of 2f09bde^) against the current one: the same serial command under the profiler,
 # per-launch durations by launch shape
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$1
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 F="--no-cpu --no-config5 --no-host-api --no-pipeline --steps 8 --warmup 2 --no-plain-pass --no-roofline-pass"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/r4 -o s -- python3 $GRAFT_REPO_ROOT/r4tree/bench.py $F > $OUT/r4.json 2> $OUT/r4.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/r6 -o s -- python3 $GRAFT_REPO_ROOT/bench.py $F --no-config2 --no-config4 > $OUT/r6.json 2> $OUT/r6.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/r6 -o s -- python3 $ROOT/bench.py --full $F --no-config2 --no-config4 > $OUT/r6.json 2> $OUT/r6.err
 python3 - $OUT <<'PY'
 import csv, sys, collections, glob, os
 out = sys.argv[1]

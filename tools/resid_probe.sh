@@ -7,7 +7,7 @@ OUT=gpurun_out/$1; mkdir -p $OUT
 export TMPDIR=/tmp
 for m in 1 0; do
   export HELM_ND_SPARSE_RHS=$m
-  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/m$m -o t -- python3 bench.py --steps 6 --warmup 2 --no-pipeline --no-cpu --no-config5 --no-config2 --no-config4 --no-host-api --no-plain-pass --no-roofline-pass > $OUT/m$m.json 2> $OUT/m$m.err
+  timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/m$m -o t -- python3 bench.py --full --steps 6 --warmup 2 --no-pipeline --no-cpu --no-config5 --no-config2 --no-config4 --no-host-api --no-plain-pass --no-roofline-pass > $OUT/m$m.json 2> $OUT/m$m.err
   f=$(find $OUT/m$m -name "*kernel_stats.csv" | head -1)
   echo "HELM_ND_SPARSE_RHS=$m"
   [ -n "$f" ] && python3 - "$f" <<'PY'

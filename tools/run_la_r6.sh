@@ -9,7 +9,7 @@ cd $GRAFT_REPO_ROOT
 for r in $(seq 1 $REPS); do
   for c in $CASES; do
     IFS=: read L S <<< "$c"
-    HELM_BENCH_LOOKAHEAD=$L HELM_POOL_SPARE=$S python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-config5 --no-config2 --no-config4 --no-host-api > $OUT/l${L}s${S}_$r.json 2> $OUT/l${L}s${S}_$r.err
+    HELM_BENCH_LOOKAHEAD=$L HELM_POOL_SPARE=$S python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-config5 --no-config2 --no-config4 --no-host-api > $OUT/l${L}s${S}_$r.json 2> $OUT/l${L}s${S}_$r.err
     python3 - $OUT/l${L}s${S}_$r.json $L $S <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

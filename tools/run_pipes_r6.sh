@@ -9,7 +9,7 @@ cd $GRAFT_REPO_ROOT
 for r in $(seq 1 $REPS); do
   for c in $CASES; do
     IFS=: read P G S <<< "$c"
-    HELM_BENCH_PIPES=$P HELM_POOL_SPARE=$S HELM_ALLOC_TRACE=1 python3 bench.py --gpus 1 --steps 20 --warmup 5 --group $G --no-cpu --no-config5 --no-config2 --no-config4 --no-host-api > $OUT/p${P}g${G}s${S}_$r.json 2> $OUT/p${P}g${G}s${S}_$r.err
+    HELM_BENCH_PIPES=$P HELM_POOL_SPARE=$S HELM_ALLOC_TRACE=1 python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --group $G --no-cpu --no-config5 --no-config2 --no-config4 --no-host-api > $OUT/p${P}g${G}s${S}_$r.json 2> $OUT/p${P}g${G}s${S}_$r.err
     python3 - $OUT/p${P}g${G}s${S}_$r.json $P $G $S <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -1,17 +1,18 @@
 #!/bin/bash
 # Round-6 profile collection on the GPU box (run from the repo root through gpurun):  tools/run_profiles_r6.sh <outdir under gpurun_out> [githash]
 set -u
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$1
 mkdir -p $OUT
 cd $GRAFT_REPO_ROOT
 echo "${2:-unknown}" > $OUT/githash.txt
 # the driver's command, as the FIRST GPU process of this box
-python3 bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err
-python3 bench.py > $OUT/bench_n1.json 2> $OUT/bench_n1.err
+python3 bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err
+python3 bench.py --full > $OUT/bench_n1.json 2> $OUT/bench_n1.err
 # the headline alone, fresh processes one after the other (the other leases of profiles/r06_headline_repro.json come from separate gpurun calls)
-for i in 1 2 3; do python3 bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu --no-config5 --no-config2 --no-config4 --no-host-api > $OUT/headline_$i.json 2> /dev/null; done
+for i in 1 2 3; do python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu --no-config5 --no-config2 --no-config4 --no-host-api > $OUT/headline_$i.json 2> /dev/null; done
 cd /tmp && export TMPDIR=/tmp
-B="$GRAFT_REPO_ROOT/bench.py --no-cpu --no-config5 --no-config2 --no-config4 --no-host-api --steps 8 --warmup 3 --no-plain-pass"
+B="$ROOT/bench.py --full --no-cpu --no-config5 --no-config2 --no-config4 --no-host-api --steps 8 --warmup 3 --no-plain-pass"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_pipe -o s -- python3 $B --no-roofline-pass > $OUT/bench_pipelined_under_rocprof.json 2> $OUT/stats_pipe.err
 python3 $GRAFT_REPO_ROOT/tools/trace_overlap.py $(find $OUT/stats_pipe -name "*kernel_trace.csv" | head -1) 3 > $OUT/pipeline_overlap.txt 2>&1
 HELM_ND_SPARSE_RHS=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_serial -o s -- python3 $B --no-pipeline > $OUT/bench_serial_under_rocprof.json 2> $OUT/stats_serial.err
@@ -21,7 +22,7 @@ HELM_ND_SPARSE_RHS=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OU
 export HELM_ND_SPARSE_RHS=0
 for C in FETCH_SIZE WRITE_SIZE; do
   # (two work items, their factorisations in one set of launches like the timed region's; the timed region and the roofline pass each run them once)
-  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/pmc_$C -- python3 $GRAFT_REPO_ROOT/bench.py --steps 2 --warmup 0 --no-cpu --no-config5 --no-config2 --no-config4 --no-host-api --no-plain-pass > $OUT/pmc_$C.json 2> $OUT/pmc_$C.err
+  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/pmc_$C -- python3 $ROOT/bench.py --full --steps 2 --warmup 0 --no-cpu --no-config5 --no-config2 --no-config4 --no-host-api --no-plain-pass > $OUT/pmc_$C.json 2> $OUT/pmc_$C.err
 done
 unset HELM_ND_SPARSE_RHS
 for C in FETCH_SIZE WRITE_SIZE; do
