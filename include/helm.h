@@ -386,6 +386,30 @@ int helm_debug_inverse_bench(int device, int n, const double *A, int reps, int r
 int helm_mg3_axis(int n, int npml, double h, double cpml, double om_re, double om_im, int level, double *x, int *lay, double *lap,
                   int *pc, double *pw, int *n_next, int *rf, double *rw);
 
+/* --- grid transfer of the multiscale family (zephyr_amd/csrc/regrid.hip) ------------------------------------------------------- */
+/* Replaces SplineGridInterpolator.__mul__ (zephyr/backend/interpolation.py:180-205): RectBivariateSpline(kx=3, ky=3, s=0) of a field on
+ * one regular grid evaluated on another with the same origin -- not-a-knot cubic interpolation along each axis, points beyond the input's
+ * extent clamped to its edge -- for the down- / up-scalers of MultiGridHelper (zephyr/backend/distributors.py:515-572).
+ * One axis (host only, no GPU needed): n_in nodes i h_in -> n_out points j h_out.  Returns the window width W (1 .. 64) and fills, when
+ * not NULL, start[n_out] and taps[n_out * W] (cap: entries taps holds): output j = sum_t taps[j W + t] in[start[j] + t].  Taps below
+ * 2^-60 of their row's largest are dropped. */
+int helm_regrid_axis(int n_in, double h_in, int n_out, double h_out, int *start, double *taps, int cap);
+/* Opaque transfer plan from grid A (nz_a, nx_a; spacings dz_a, dx_a) to grid B on `device`: both axes' taps uploaded once.  NULL on error
+ * (helm_last_error(NULL)). */
+typedef struct helm_regrid helm_regrid;
+helm_regrid *helm_regrid_create(int device, int nz_a, int nx_a, double dz_a, double dx_a, int nz_b, int nx_b, double dz_b, double dx_b,
+                                double zorig, double xorig);
+void helm_regrid_destroy(helm_regrid *plan);
+/* out[f] = beta out[f] + mul (.) (gain T in[f]) for k complex128 fields (device pointers); element i of field f at in[f in_fstride +
+ * i in_estride] (a (k, N) block: fstride N, estride 1 -- the fast layout; an (N, k) block: fstride 1, estride k), likewise out.  mul: N_b
+ * complex values on the device, NULL for 1; beta == 0: out is not read.  Runs on op's stream (NULL: the plan's own), so it is ordered after
+ * what the caller queued there without a host wait, and returns when the transfer is done.  Its intermediate comes from the library's pool. */
+int helm_regrid_apply_device(helm_regrid *plan, helm_op *op, int k, const void *dIn, long long in_fstride, long long in_estride, void *dOut,
+                             long long out_fstride, long long out_estride, double gain_re, double gain_im, double beta, const void *dMul);
+/* the same on host arrays (dense (k, N) or (N, k) blocks, mul: N_b complex or NULL), moved through the library's pinned chunks */
+int helm_regrid_apply(helm_regrid *plan, int k, const double *in, long long in_fstride, long long in_estride, double *out, long long out_fstride,
+                      long long out_estride, double gain_re, double gain_im, double beta, const double *mul);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,9 +7,11 @@ from .analytical import AnalyticalHelmholtz
 from .base import BaseModelDependent, BaseAnisotropic
 from .config import AttributeMapper, BaseSCCache, SCFilter
 from .discretization import BaseDiscretization, DiscretizationWrapper, prefactor_many
-from .distributors import BaseDist, BaseMPDist, MultiFreq, SerialMultiFreq, ViscoMultiFreq
+from .distributors import (BaseDist, BaseMPDist, MultiFreq, SerialMultiFreq, ViscoMultiFreq, MultiGridHelper, MultiGridMultiFreq,
+                           ViscoMultiGridMultiFreq)
 from .eurus import Eurus, EurusHD
 from .helm3d import Helm3D
+from .interpolation import BaseGridInterpolator, SplineGridInterpolator
 from .minizephyr import MiniZephyr, MiniZephyrHD, MiniZephyr25D
 from .source import (FakeSource, SimpleSource, StackedSimpleSource, SparseKaiserSource, KaiserSource,
                      AnisotropicKaiserSource)
@@ -23,6 +25,6 @@ def trim():
 __all__ = [
     'AnalyticalHelmholtz', 'BaseModelDependent', 'BaseAnisotropic', 'AttributeMapper', 'BaseSCCache', 'SCFilter',
     'BaseDiscretization', 'DiscretizationWrapper', 'prefactor_many', 'BaseDist', 'BaseMPDist', 'MultiFreq', 'SerialMultiFreq',
-    'ViscoMultiFreq', 'Eurus', 'EurusHD', 'Helm3D', 'MiniZephyr', 'MiniZephyrHD', 'MiniZephyr25D', 'FakeSource', 'SimpleSource',
+    'ViscoMultiFreq', 'MultiGridHelper', 'MultiGridMultiFreq', 'ViscoMultiGridMultiFreq', 'BaseGridInterpolator', 'SplineGridInterpolator', 'Eurus', 'EurusHD', 'Helm3D', 'MiniZephyr', 'MiniZephyrHD', 'MiniZephyr25D', 'FakeSource', 'SimpleSource',
     'StackedSimpleSource', 'SparseKaiserSource', 'KaiserSource', 'AnisotropicKaiserSource', 'trim',
 ]

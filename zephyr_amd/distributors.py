@@ -16,6 +16,7 @@ import numpy as np
 import scipy.sparse as sp
 
 from .base import BaseModelDependent
+from .config import BaseSCCache, SCFilter
 from .discretization import DiscretizationWrapper
 from . import dispatch
 
@@ -363,3 +364,171 @@ class ViscoMultiFreq(MultiFreq, BaseModelDependent):
             u.update(self.addFields)
             updates.append(u)
         return updates
+
+
+class MultiGridHelper(BaseModelDependent, BaseSCCache):
+    """Per-frequency computation grids (distributors.py:515-572): frequency f is solved on the native grid coarsened by
+    median((cMin / f / dx / targetGPW).real, maxScale, minScale), so that the slowest wave keeps about `targetGPW` grid points per
+    wavelength.  `downScalers[i]` carries a native-grid field to frequency i's grid, `upScalers[i]` back; frequencies of the same scale share
+    one interpolator."""
+
+    initMap = {
+        'cMin':             (True,     None,         np.complex128),
+        'freqs':            (True,     None,         list),
+        'targetGPW':        (True,     None,         np.float64),
+        'GridInterpolator': (False,    '_gi',        None),
+        'maxScale':         (False,    '_maxScale',  np.float64),
+        'minScale':         (False,    '_minScale',  np.float64),
+    }
+
+    @property
+    def maxScale(self):
+        return getattr(self, '_maxScale', 10.)
+
+    @property
+    def minScale(self):
+        return getattr(self, '_minScale', 1.)
+
+    @property
+    def GridInterpolator(self):
+        from .interpolation import SplineGridInterpolator
+        return getattr(self, '_gi', SplineGridInterpolator)
+
+    @property
+    def GIFilter(self):
+        if '_GIFilter' not in self.__dict__:
+            self._GIFilter = SCFilter(self.GridInterpolator)
+        return self._GIFilter
+
+    @property
+    def scales(self):
+        'down-scaling factors, one per frequency'
+        return [float(np.median(((self.cMin / freq / self.dx / self.targetGPW).real, self.maxScale, self.minScale))) for freq in self.freqs]
+
+    @property
+    def downScalers(self):
+        'transfers native grid -> frequency grid'
+        if '_downScalers' not in self.__dict__:
+            made = {}
+            for scale in self.scales:
+                if scale not in made:
+                    sc = dict(self.systemConfig)
+                    sc['scale'] = scale
+                    made[scale] = self.GridInterpolator(self.GIFilter(sc))
+            self._downScalers = [made[scale] for scale in self.scales]
+        return self._downScalers
+
+    @property
+    def upScalers(self):
+        'transfers frequency grid -> native grid (exactly onto it)'
+        if '_upScalers' not in self.__dict__:
+            self._upScalers = [ds.T for ds in self.downScalers]
+        return self._upScalers
+
+
+class MultiGridMultiFreq(MultiFreq, BaseModelDependent):
+    """MultiFreq whose sub-problem i runs on the grid of MultiGridHelper's scale i (distributors.py:384-420): the model is down-scaled onto
+    it, and the sub-problem's config carries that grid's nx, nz, dx, dz.  Right-hand sides handed to `* rhs` live on those grids, and so do
+    the wavefields that come back.  Unlike the reference, every other per-cell model array (rho; Eurus' theta, eps, delta) is down-scaled
+    too -- the reference hands the native-size arrays on, which a sub-problem of another size cannot take."""
+
+    initMap = {
+        'c':                (True,     '_c',         np.complex128),
+        'freqs':            (True,     None,         list),
+        'cMin':             (True,     None,         np.float64),
+        'targetGPW':        (True,     None,         np.float64),
+    }
+
+    CELL_KEYS = ('rho', 'theta', 'eps', 'delta')
+
+    @property
+    def c(self):
+        if isinstance(self._c, np.ndarray) and self._c.ndim > 0:
+            return self._c
+        return self._c * np.ones((self.nz, self.nx), dtype=np.complex128)
+
+    @property
+    def mgHelper(self):
+        if '_mgHelper' not in self.__dict__:
+            sc = dict(self.systemConfig)
+            sc['freqs'] = self.freqs
+            self._mgHelper = MultiGridHelper(sc)
+        return self._mgHelper
+
+    def _cellUpdates(self, ds):
+        'the other per-cell model arrays on the grid of `ds` (scalars pass through in the config as they are)'
+        out = {}
+        for key in self.CELL_KEYS:
+            v = self.systemConfig.get(key)
+            if isinstance(v, np.ndarray) and v.ndim > 0 and v.size == self.nz * self.nx:
+                out[key] = ds * np.ravel(v).astype(np.float64)
+        return out
+
+    def _velocities(self):
+        'complex velocity of each frequency on the native grid'
+        c = self.c.ravel()
+        return [c for _ in self.freqs]
+
+    def _extraUpdates(self, i, ds):
+        return {}
+
+    @property
+    def spUpdates(self):
+        if '_mgUpdates' not in self.__dict__:
+            helper = self.mgHelper
+            vals, cells = [], {}
+            for i, (cF, ds) in enumerate(zip(self._velocities(), helper.downScalers)):
+                if id(ds) not in cells:
+                    cells[id(ds)] = self._cellUpdates(ds)
+                u = {'freq': self.freqs[i], 'c': ds * cF}
+                u.update(cells[id(ds)])
+                u.update(self._extraUpdates(i, ds))
+                u.update(ds.scaleUpdate)
+                vals.append(u)
+            self._mgUpdates = vals
+        out = []
+        for u in self._mgUpdates:
+            u = dict(u)
+            u.update(self.addFields)
+            out.append(u)
+        return out
+
+
+class ViscoMultiGridMultiFreq(ViscoMultiFreq, MultiGridMultiFreq):
+    """MultiGridMultiFreq with a complex velocity from Q and Kolsky-Futterman dispersion (distributors.py:441-512): the complex velocity of a
+    frequency is formed on the native grid, then down-scaled; an array Q is down-scaled into the sub-problem's config as well."""
+
+    initMap = {
+        'c':              (True,     '_c',         np.float64),
+    }
+
+    maskKeys = {'freqs', 'Q', 'freqBase'}
+
+    @property
+    def c(self):
+        if isinstance(self._c, np.ndarray) and self._c.ndim > 0:
+            return self._c
+        return self._c * np.ones((self.nz, self.nx), dtype=np.float64)
+
+    def _velocities(self):
+        out = []
+        for freq in self.freqs:
+            if self.disperseFreqs:
+                fact = 1. + (np.log(freq / self.freqBase) / (np.pi * self.Q))
+                assert not self._any(fact < 0.1)
+                cR = fact * self.c
+                c = cR + (0.5j * cR / self.Q)            # + because of the FT convention
+            else:
+                c = self.c.ravel() + (0.5j * self.c.ravel() / np.ravel(self.Q))
+            out.append(np.ravel(c))
+        return out
+
+    def _extraUpdates(self, i, ds):
+        Q = self.__dict__.get('_Q')
+        if isinstance(Q, np.ndarray) and Q.ndim > 0:
+            return {'Q': ds * np.ravel(Q).astype(np.float64)}
+        return {}
+
+    @property
+    def spUpdates(self):
+        return MultiGridMultiFreq.spUpdates.fget(self)

@@ -18,8 +18,8 @@ import scipy.sparse as sp
 
 from .base import BaseModelDependent
 from .config import BaseSCCache
-from .distributors import MultiFreq, ViscoMultiFreq
-from .survey import HelmBaseSurvey, Helm2DSurvey, Helm25DSurvey
+from .distributors import MultiFreq, ViscoMultiFreq, ViscoMultiGridMultiFreq
+from .survey import HelmBaseSurvey, HelmMultiGridSurvey, Helm2DSurvey, Helm25DSurvey
 from . import parallel
 from . import dispatch
 from . import _lib
@@ -200,12 +200,12 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         return (u for _, u in self._solveOwned(qf))
 
     def fields(self, m=None):
-        'list of forward wavefields for ALL frequencies on this rank (no sharding)'
+        'list of forward wavefields for ALL frequencies on this rank (no sharding), on the native grid (problem.py:181-191: post-processed)'
         if not self.ispaired:
             raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
         self.updateModel(m)
         qf = self.survey.getSources()
-        return list(self.system * qf)
+        return [pp(u) for u, pp in zip(self.system * qf, self.survey.postProcessors)]
 
     # ---- sensitivity times vector ------------------------------------------------------------------------
     def Jvec(self, m=None, v=None, u=None):
@@ -228,7 +228,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         dpert = np.zeros((sv.nrec, sv.nsrc, sv.nfreq), dtype=np.complex128)
         for ifreq, uFreq in self._solveOwned(qv):
             srcTerms = qf[ifreq].T * uFreq
-            recTerms = sv.rVec(0) * uFreq
+            recTerms = sv.rVec(0, ifreq) * uFreq
             dpert[:, :, ifreq] = np.asarray(recTerms).reshape((sv.nrec, 1)) * np.asarray(srcTerms).reshape((1, sv.nsrc))
         if self._sharded:
             dpert = parallel.allreduce_sum(dpert)
@@ -255,6 +255,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         owned = self.ownedFreqs
         g = np.zeros(self.nrow, dtype=np.complex128)
         if u is None and self._deviceGradientAvailable():
+            if isinstance(sv, HelmMultiGridSurvey):
+                return self._JtvecDeviceMultiGrid(qb, owned)
             return self._JtvecDevice(qb, owned)
         if u is None:
             qf = sv.getSources()
@@ -361,6 +363,79 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             g += _lib.from_device(G)
         return parallel.allreduce_sum(g) if self._sharded else g
 
+    def _JtvecDeviceMultiGrid(self, qb, owned):
+        """mux branch of a multiscale survey with wavefields kept in HBM.  Per work item: [qf | qb] of its sources solved on the frequency's
+        own grid, the imaging sum P = scaleTerm^2 sum_s uF (.) uB accumulated there, then G += pp(scaler) (.) pp(P) in one grid transfer
+        (problem.py:152: the product of two up-scaled fields), the up-scaled scaler -(omega^2 / c^3) made once per frequency from the
+        operator's coarse c.  G is on the native grid; the partial gradients of the GPUs are summed as on the single-grid path."""
+        import torch
+        sv = self.survey
+        nsrc, N = sv.nsrc, self.nrow
+        scale = complex(self.system.scaleTerm)
+        qf = sv.getSources()
+        pps = sv.postProcessors
+        if not owned:
+            g = np.zeros(N, dtype=np.complex128)
+            return parallel.allreduce_sum(g) if self._sharded else g
+        devs, items = self._deviceItems(owned, nsrc)
+
+        def one(wstate, op, ifreq, c0, c1):
+            dev = torch.device('cuda', op.device)
+            state = wstate.setdefault(('buffers', op.device), {})
+            k, Ni = c1 - c0, int(op.nrow)
+            if 'G' not in state:
+                state['G'] = torch.zeros(N, dtype=torch.complex128, device=dev)
+            if state.get('elems', 0) < 2 * k * Ni:               # (sized by the largest item so far)
+                state['U'] = torch.empty(2 * k * Ni, dtype=torch.complex128, device=dev)
+                state['R'] = torch.empty(2 * k * Ni, dtype=torch.complex128, device=dev)
+                state['elems'] = 2 * k * Ni
+            if state.get('pcap', 0) < Ni:
+                state['P'] = torch.empty(Ni, dtype=torch.complex128, device=dev)
+                state['unit'] = torch.empty(Ni, dtype=torch.complex128, device=dev)
+                state['pcap'] = Ni
+            U, R = state['U'], state['R']
+            P, unit = state['P'][:Ni], state['unit'][:Ni]
+            parts = []
+            for off, m in ((0, qf[ifreq]), (k, qb[ifreq])):
+                mc = m if (c0 == 0 and c1 == m.shape[1]) else sp.csc_matrix(m)[:, c0:c1]
+                if not (sp.isspmatrix_csr(mc) or sp.isspmatrix_csc(mc)) or not mc.has_canonical_format:
+                    mc = sp.csr_matrix(mc)
+                    mc.sum_duplicates()
+                coo = mc.tocoo(copy=False)
+                parts.append((coo.row, coo.col + off, coo.data))
+            trip = (np.concatenate([p_[0] for p_ in parts]), np.concatenate([p_[1] for p_ in parts]), np.concatenate([p_[2] for p_ in parts]), (Ni, 2 * k))
+            op.rhsFromSparseDevice(trip, R.data_ptr())
+            # the up-scaled gradient scaler of this frequency (one per worker and frequency)
+            scalers = state.setdefault('scalers', {})
+            if ifreq not in scalers:
+                cd = _lib.to_device(np.asarray(op.c).ravel(), dev, np.complex128)
+                omega = 2 * np.pi * sv.freqs[ifreq]
+                sc = (1.0 / (cd * cd * cd)) * complex(-(omega ** 2))
+                S = torch.empty(N, dtype=torch.complex128, device=dev)
+                _lib.wait_torch_stream(dev)
+                pps[ifreq].apply_device(sc, S, k=1)
+                scalers[ifreq] = S
+            P.zero_()
+            unit.fill_(scale * scale)
+            _lib.wait_torch_stream(dev)
+            op.solveDevice(R.data_ptr(), U.data_ptr(), 2 * k, Ni)
+            op.imagingAccumulateDevice(U.data_ptr(), U.data_ptr() + k * Ni * 16, k, unit.data_ptr(), P.data_ptr())
+            pps[ifreq].apply_device(P, state['G'], k=1, op=op, beta=1., mul=scalers[ifreq])
+            return None
+        states, _ = self._runOnDevices(devs, items, one)
+        parts = [b['G'] for st in states for key, b in st.items() if isinstance(key, tuple) and 'G' in b]
+        if len(parts) == 1:
+            G = parts[0]
+            if self._sharded:
+                parallel.allreduce_sum_device(G)
+            torch.cuda.synchronize(G.device)
+            return _lib.from_device(G)
+        g = np.zeros(N, dtype=np.complex128)
+        for G in parts:
+            torch.cuda.synchronize(G.device)
+            g += _lib.from_device(G)
+        return parallel.allreduce_sum(g) if self._sharded else g
+
     def _dpredDevice(self, owned):
         '''predicted data with the wavefields kept in HBM (fixed receiver array): per work item (frequency, source batch) the sparse sources are
         expanded on the item's GPU, solved there, and only the receiver samples R u (nrec x sources) come back'''
@@ -371,8 +446,14 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         data = np.zeros((nrec, nsrc, sv.nfreq), dtype=np.complex128)
         if not owned:
             return data
-        Rm = sp.csr_matrix(sv.rVec(0))
-        Rm.sum_duplicates()
+        multi = isinstance(sv, HelmMultiGridSurvey)
+        Rms = {}
+        for ifreq in (owned if multi else owned[:1]):       # one receiver CSR per grid (a multiscale survey: per distinct scale)
+            gk = sv._gridKey(ifreq)
+            if gk not in Rms:
+                Rm = sp.csr_matrix(sv.rVec(0, ifreq))
+                Rm.sum_duplicates()
+                Rms[gk] = Rm
         qf = sv.getSources()
         devs, items = self._deviceItems(owned, nsrc)
 
@@ -380,19 +461,40 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             dev = torch.device('cuda', op.device)
             state = wstate.setdefault(('buffers', op.device), {})
             k = c1 - c0
-            if 'csr' not in state:
-                state['csr'] = (_lib.to_device(Rm.indptr, dev, np.int64), _lib.to_device(Rm.indices, dev, np.int64), _lib.to_device(Rm.data, dev, np.complex128), nrec)
-            if state.get('cap', 0) < k:
-                state['R'] = torch.empty((k, N), dtype=torch.complex128, device=dev)
-                state['U'] = torch.empty((k, N), dtype=torch.complex128, device=dev)
-                state['out'] = torch.empty((nrec, k), dtype=torch.complex128, device=dev)
-                state['cap'] = k
-            R, U = state['R'], state['U']
+            if not multi:
+                if 'csr' not in state:
+                    Rm = Rms[None]
+                    state['csr'] = (_lib.to_device(Rm.indptr, dev, np.int64), _lib.to_device(Rm.indices, dev, np.int64), _lib.to_device(Rm.data, dev, np.complex128), nrec)
+                csr = state['csr']
+                if state.get('cap', 0) < k:
+                    state['R'] = torch.empty((k, N), dtype=torch.complex128, device=dev)
+                    state['U'] = torch.empty((k, N), dtype=torch.complex128, device=dev)
+                    state['out'] = torch.empty((nrec, k), dtype=torch.complex128, device=dev)
+                    state['cap'] = k
+                R, U = state['R'], state['U']
+                Ni = N
+            else:
+                # the wavefields stay on the frequency's own grid: its sources, its receivers, buffers sized by the largest item so far
+                gk = sv._gridKey(ifreq)
+                csrs = state.setdefault('csrs', {})
+                if gk not in csrs:
+                    Rm = Rms[gk]
+                    csrs[gk] = (_lib.to_device(Rm.indptr, dev, np.int64), _lib.to_device(Rm.indices, dev, np.int64), _lib.to_device(Rm.data, dev, np.complex128), nrec)
+                csr = csrs[gk]
+                Ni = int(op.nrow)
+                if state.get('elems', 0) < k * Ni:
+                    state['Rf'] = torch.empty(k * Ni, dtype=torch.complex128, device=dev)
+                    state['Uf'] = torch.empty(k * Ni, dtype=torch.complex128, device=dev)
+                    state['elems'] = k * Ni
+                if state.get('cap', 0) < k:
+                    state['out'] = torch.empty((nrec, k), dtype=torch.complex128, device=dev)
+                    state['cap'] = k
+                R, U = state['Rf'][:k * Ni], state['Uf'][:k * Ni]
             out = state['out'] if state['cap'] == k else torch.empty((nrec, k), dtype=torch.complex128, device=dev)
             q = qf[ifreq] if isinstance(qf, (list, tuple)) else qf
             op.rhsFromSparseDevice(sp.csc_matrix(q)[:, c0:c1], R.data_ptr())
-            op.solveDevice(R.data_ptr(), U.data_ptr(), k, N)
-            op.sampleDevice(U.data_ptr(), k, state['csr'], out.data_ptr())      # (returns when the samples are there: helm_sample_device waits for its own stream)
+            op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+            op.sampleDevice(U.data_ptr(), k, csr, out.data_ptr())      # (returns when the samples are there: helm_sample_device waits for its own stream)
             data[:, c0:c1, ifreq] = scale * _lib.from_device(out)          # (disjoint slices per item: no two workers write the same entries)
             return None
         self._runOnDevices(devs, items, one)
@@ -420,6 +522,13 @@ class Helm2DProblem(HelmBaseProblem):
 class Helm2DViscoProblem(Helm2DProblem):
 
     SystemWrapper = ViscoMultiFreq
+
+
+class Helm2DViscoMultiGridProblem(Helm2DProblem):
+    """Visco-acoustic multiscale problem (zephyr/middleware/problem.py:220-222): every frequency on its own grid (ViscoMultiGridMultiFreq),
+    paired with a Helm2DMultiGridSurvey built from the same config."""
+
+    SystemWrapper = ViscoMultiGridMultiFreq
 
 
 class Helm25DProblem(HelmBaseProblem):

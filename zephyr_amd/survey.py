@@ -87,14 +87,14 @@ class HelmBaseSurvey(BaseSCCache):
         'one column per location from the survey\'s source generator, column j scaled by terms[j]'
         return self.RHSGenerator(self.systemConfig)(locs) * sp.diags((terms,), (0,))
 
-    def sVecs(self):
-        'source matrix S diag(ssTerms), (N, nsrc); made once'
+    def sVecs(self, ifreq=None):
+        'source matrix S diag(ssTerms), (N, nsrc); made once (one grid for every frequency: `ifreq` does not matter here)'
         cache = self.__dict__.setdefault('_vecCache', {})
         if 'S' not in cache:
             cache['S'] = self._weightedColumns(self.sLocs, self.ssTerms)
         return cache['S']
 
-    def rVec(self, isrc):
+    def rVec(self, isrc, ifreq=None):
         'receiver sampling matrix of source isrc, (nrec, N): one for all sources with a fixed array, one per source when the array moves with it'
         cache = self.__dict__.setdefault('_vecCache', {})
         moving = self.mode != 'fixed'
@@ -105,7 +105,11 @@ class HelmBaseSurvey(BaseSCCache):
         return cache[key]
 
     def rVecs(self, ifreq):
-        return (self.rVec(i) for i in range(self.nsrc))
+        return (self.rVec(i, ifreq) for i in range(self.nsrc))
+
+    def _gridKey(self, ifreq):
+        'which cached vectors frequency ifreq uses (None: the one grid of this survey)'
+        return None
 
     # ---- hot-path pieces ------------------------------------------------------------------------------
     def getSources(self):
@@ -119,20 +123,20 @@ class HelmBaseSurvey(BaseSCCache):
             return [qs * sp.diags((t.conjugate(),), (0,)) for t in ts]
         return qs
 
-    def _projectOne(self, uFreq, out):
+    def _projectOne(self, uFreq, out, ifreq=0):
         'out[:, isrc] = R_isrc uFreq[:, isrc] for one frequency'
         if self.mode == 'fixed':
-            out[:, :] = self.rVec(0) * uFreq
+            out[:, :] = self.rVec(0, ifreq) * uFreq
         else:
             for isrc in range(self.nsrc):
-                out[:, isrc] = self.rVec(isrc) * uFreq[:, isrc]
+                out[:, isrc] = self.rVec(isrc, ifreq) * uFreq[:, isrc]
 
     def _lazyProjectFields(self, u, owned=None):
         'data[:, isrc, ifreq] = R uF_ifreq[:, isrc] (survey.py:152-160); `owned` lists the frequency indices `u` yields'
         data = np.zeros((self.nrec, self.nsrc, self.nfreq), dtype=np.complex128)
         idx = range(self.nfreq) if owned is None else owned
         for ifreq, uFreq in zip(idx, u):
-            self._projectOne(np.asarray(uFreq), data[:, :, ifreq])
+            self._projectOne(np.asarray(uFreq), data[:, :, ifreq], ifreq)
         return data
 
     def getResidualSources(self, resid):
@@ -143,25 +147,29 @@ class HelmBaseSurvey(BaseSCCache):
             # rows per frequency (R^T restricted to them stays CSR: ~81 entries per receiver whatever nrec is -- densified it would be O(nrec^2)),
             # handed back as a CSR matrix built from its arrays (sorted rows, every column present): no sparse-sparse product, no sort.
             cache = self.__dict__.setdefault('_vecCache', {})
-            if 'RtRows' not in cache:
-                Rt = sp.csr_matrix(self.rVec(0).T)
-                Rt.sum_duplicates()
-                rows = np.flatnonzero(np.diff(Rt.indptr))
-                cache['RtRows'] = (rows, sp.csr_matrix(Rt[rows, :]), Rt.shape[0])
-            rows, Rsub, N = cache['RtRows']
             ns = resid.shape[1]
-            indptr = np.zeros(N + 1, dtype=np.int64)
-            indptr[rows + 1] = ns
-            np.cumsum(indptr, out=indptr)
-            indices = np.tile(np.arange(ns, dtype=np.int32), rows.size)
-            out = []
+            out, layouts = [], {}
             for ifreq in range(self.nfreq):
+                gk = self._gridKey(ifreq)                 # (one R per grid: a multiscale survey has one per distinct scale)
+                key = 'RtRows' if gk is None else ('RtRows', gk)
+                if key not in cache:
+                    Rt = sp.csr_matrix(self.rVec(0, ifreq).T)
+                    Rt.sum_duplicates()
+                    rows = np.flatnonzero(np.diff(Rt.indptr))
+                    cache[key] = (rows, sp.csr_matrix(Rt[rows, :]), Rt.shape[0])
+                rows, Rsub, N = cache[key]
+                if key not in layouts:
+                    indptr = np.zeros(N + 1, dtype=np.int64)
+                    indptr[rows + 1] = ns
+                    np.cumsum(indptr, out=indptr)
+                    layouts[key] = (indptr, np.tile(np.arange(ns, dtype=np.int32), rows.size))
+                indptr, indices = layouts[key]
                 block = np.asarray(Rsub @ np.ascontiguousarray(resid[:, :, ifreq]))      # sparse (rows, nrec) x dense (nrec, nsrc) -> dense (rows, nsrc)
                 m = sp.csr_matrix((block.ravel(), indices, indptr), shape=(N, ns))
                 m.has_sorted_indices = True
                 out.append(m)
             return out
-        return [sp.hstack([self.rVec(isrc).T * sp.csc_matrix(resid[:, isrc, ifreq].reshape((self.nrec, 1)))
+        return [sp.hstack([self.rVec(isrc, ifreq).T * sp.csc_matrix(resid[:, isrc, ifreq].reshape((self.nrec, 1)))
                            for isrc in range(self.nsrc)])
                 for ifreq in range(self.nfreq)]
 
@@ -171,7 +179,7 @@ class HelmBaseSurvey(BaseSCCache):
             raise Exception('%s instance is not paired to a problem' % (self.__class__.__name__,))
         if u is None:
             owned = self.prob.ownedFreqs
-            if self.mode == 'fixed' and sp.issparse(self.sVecs()) and self.prob._deviceGradientAvailable():
+            if self.mode == 'fixed' and sp.issparse(self.sVecs(0)) and self.prob._deviceGradientAvailable():
                 self.prob.updateModel(m)
                 data = self.prob._dpredDevice(owned)          # wavefields never leave HBM
             else:
@@ -190,11 +198,98 @@ class HelmBaseSurvey(BaseSCCache):
         return [lambda x: x for _ in self.freqs]
 
 
+class HelmMultiGridSurvey(HelmBaseSurvey):
+    """Survey of a multiscale problem (zephyr/middleware/survey.py:209-334): frequency i lives on the grid of MultiGridHelper's scale i.
+    Source and receiver vectors are made by the survey's source generator on that grid (one cache per distinct scale), `getSources()` and
+    `getResidualSources()` return per-frequency matrices on those grids, and the pre- / post-processors are the down- / up-scalers.
+    The config carries what MultiGridHelper needs (cMin, targetGPW; maxScale, minScale optional).  Unlike the reference, a receiver array
+    that moves with the source (mode 'relative') is cached per scale and source."""
+
+    @property
+    def mgHelper(self):
+        if '_mgHelper' not in self.__dict__:
+            from .distributors import MultiGridHelper
+            sc = dict(self.systemConfig)
+            sc['freqs'] = list(self.freqs)
+            self._mgHelper = MultiGridHelper(sc)
+        return self._mgHelper
+
+    @property
+    def postProcessors(self):
+        return self.mgHelper.upScalers
+
+    @property
+    def preProcessors(self):
+        return self.mgHelper.downScalers
+
+    def _gridKey(self, ifreq):
+        return self.mgHelper.scales[ifreq]
+
+    def scaledConfig(self, ifreq):
+        'the survey config on the grid of frequency ifreq (survey.py:246-253)'
+        scs = self.__dict__.setdefault('_scScales', {})
+        key = self._gridKey(ifreq)
+        if key not in scs:
+            sc = dict(self.systemConfig)
+            sc.update(self.mgHelper.downScalers[ifreq].scaleUpdate)
+            scs[key] = sc
+        return scs[key]
+
+    def _weightedColumnsOn(self, ifreq, locs, terms):
+        return self.RHSGenerator(self.scaledConfig(ifreq))(locs) * sp.diags((terms,), (0,))
+
+    def sVecs(self, ifreq=0):
+        'source matrix S diag(ssTerms) on the grid of frequency ifreq, (N_ifreq, nsrc)'
+        cache = self.__dict__.setdefault('_vecCache', {})
+        key = ('S', self._gridKey(ifreq))
+        if key not in cache:
+            cache[key] = self._weightedColumnsOn(ifreq, self.sLocs, self.ssTerms)
+        return cache[key]
+
+    def rVec(self, isrc, ifreq=0):
+        'receiver sampling matrix of source isrc on the grid of frequency ifreq, (nrec, N_ifreq)'
+        cache = self.__dict__.setdefault('_vecCache', {})
+        moving = self.mode != 'fixed'
+        gk = self._gridKey(ifreq)
+        key = ('R', gk, isrc) if moving else ('R', gk)
+        if key not in cache:
+            where = self.rLocs + self.sLocs[isrc] if moving else self.rLocs
+            cache[key] = self._weightedColumnsOn(ifreq, where, self.srTerms).T
+        return cache[key]
+
+    def getSources(self):
+        'per-frequency source matrices on their grids (survey.py:289-297)'
+        ts = self.tsTerms
+        if isinstance(ts, (list, np.ndarray)):
+            out = []
+            for ifreq, t in enumerate(np.asarray(ts)):
+                qs = self.sVecs(ifreq)
+                out.append(qs * sp.diags((t.conjugate(),), (0,)) if np.ndim(t) > 0 else qs * t.conjugate())
+            return out
+        return [self.sVecs(ifreq) * np.conjugate(ts) for ifreq in range(self.nfreq)]
+
+    def _projectOne(self, uFreq, out, ifreq=0):
+        # (wavefields up-scaled to the native grid, as fields() returns them, are brought back to the frequency's grid first: survey.py:264-275)
+        if uFreq.shape[0] != self.rVec(0, ifreq).shape[1]:
+            uFreq = self.preProcessors[ifreq] * uFreq
+        HelmBaseSurvey._projectOne(self, uFreq, out, ifreq)
+
+
 class Helm2DSurvey(HelmBaseSurvey):
+    pass
+
+
+class Helm2DMultiGridSurvey(Helm2DSurvey, HelmMultiGridSurvey):
+    'zephyr/middleware/survey.py:337-340'
     pass
 
 
 class Helm25DSurvey(HelmBaseSurvey):
     'zephyr/middleware/survey.py:343-346'
+    pass
+
+
+class Helm25DMultiGridSurvey(Helm25DSurvey, HelmMultiGridSurvey):
+    'zephyr/middleware/survey.py:349-350'
     pass
 
