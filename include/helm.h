@@ -374,6 +374,43 @@ int helm_debug_inverse(int device, int n, double *A, int batch);
 /* average milliseconds per launch of one strided-batched GEMM shape (random operands, `reps` timed launches); variant < 16: the tile the
  * library would choose, 16 (t + 1): tile configuration t (0 64x64 ... 7 16x64) forced */
 int helm_debug_zgemm_bench(int device, int M, int N, int K, int batch, int variant, int reps, double *ms_out);
+/* (test hook, host only, no GPU) What a product of this shape would be launched as, computed by the code the launch itself runs.  nf_div: the number of
+ * frequencies the batch is shared between (1: none; the choice is made for batch / nf_div).  force_tile: -1 none, 0-8 that tile (8 with at most 16 columns, as in production); force_slab: 0 none, 8 / 16 (16
+ * exists for tiles 6 and 7 only).  have_handle: the call carries a handle (split over the inner dimension keeps its scratch there).  mode: 0 dense operands,
+ * HELM_ZG_TABLE row-table operands, HELM_ZG_MASKS dense operands with masks, + HELM_ZG_TM64 one row tile per matrix.
+ * report[0] tile 0-8, [1] K slab 8 / 16 (16: latency mode), [2] 1: the 16 MT + 1-row tile (XR: 49 x 64 with the slab of 8; [0] is then the tile the shape would have had without it), [3] split factor of the inner dimension (0: none), [4] its chunk. */
+#define HELM_ZG_TABLE 1
+#define HELM_ZG_MASKS 2
+#define HELM_ZG_TM64  4
+int helm_debug_zgemm_choice(int M, int N, int K, int batch, int nf_div, int force_tile, int force_slab, int have_handle, int mode, int report[5]);
+/* (test hook) One product C = beta C + alpha A B on host data with everything the direct solver varies.  Complex operands are (re, im) pairs of doubles and every
+ * length below counts complex elements.  Buffers the kernel must leave alone (padding, masked blocks, rows without an output row, C when beta == 0) come back as
+ * they went in.  Malformed input is refused with HELM_ERR_ARG before a device is touched. */
+typedef struct helm_zgemm_ex {
+    int device, M, N, K, batch;
+    int lda, ldb, ldc;                   /* leading dimensions of the dense operands (elements) */
+    long long sa, sb, sc;                /* batch strides; 0 allowed for A and B */
+    double alpha[2], beta[2];
+    const double *A; long long a_len;
+    double *B; long long b_len;          /* dense B (NULL with tabB); written only when c_is_b */
+    double *C; long long c_len;          /* dense C, in / out (NULL with tabCo or c_is_b) */
+    int force_tile, force_slab;          /* as in helm_debug_zgemm_choice */
+    int xcd_map;                         /* -1: helm_tuning.nd_xcd_map; 0, 1, 2: that value for this call */
+    int ntc;                             /* 1: nontemporal stores of C */
+    int zr0, zr1, zc0, zc1, sk0, sk1;    /* beta masks (rows / columns of C taken as zero) and the diagonal block that is neither read nor written */
+    int tm64, c_is_b;                    /* one row tile per matrix (M <= 64); c_is_b: C overwrites B (ldc = ldb, sc = sb; B comes back) */
+    /* row-table mode: any of the three tables given (host ints, widened to the library's int4 entries; a negative entry: zero row of B / C not read / row not stored).
+     * Item z uses entries [z tab_stride + off, ...): K of tabB, M of tabCi and tabCo.  The arenas are arena_rows x ldx, row-major. */
+    const int *tabB, *tabCi, *tabCo; long long tab_len;
+    int tab_stride, offB, offCi, offCo;
+    int ldx; long long arena_rows;
+    const double *Bx, *Bx2, *Cix;        /* Bx2 (rows k < k2 of B; NULL: Bx); Cix may be the same host pointer as Bx or Cox: then it is the same device arena */
+    double *Cox, *Cox2;                  /* in / out; Cox may be the same host pointer as Bx */
+    int k2, cj_out; double oscale[2];
+    int *act;                            /* NULL, or batch x ceil(N / 64) ints: zeroed, handed to the launch as the sparse-right-hand-side flags, returned */
+    int report[5];                       /* out: as helm_debug_zgemm_choice, for the launch that was made */
+} helm_zgemm_ex;
+int helm_debug_zgemm_ex(helm_zgemm_ex *p);
 int helm_debug_inverse_bench(int device, int n, const double *A, int reps, int recurse_n, double *ms_out);
 
 /* --- diagnostics of the 3-D multigrid hierarchy (host only, no GPU needed; zephyr_amd/csrc/mg3d.hip) ------------------ */

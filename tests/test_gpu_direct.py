@@ -26,12 +26,24 @@ def crand(rng, *shape):
                                          # ... and few enough of them that the inner dimension is split over workgroups (chunks that do not divide it, an empty last chunk)
                                          (300, 16, 1027, 1), (1900, 16, 3001, 2), (129, 7, 1024, 5), (40, 16, 1032, 9),
                                          # 49-row fronts (the leaves): three blocks of 16 rows on the matrix cores + one row on the vector ALUs
-                                         (49, 256, 81, 5), (49, 64, 49, 3), (49, 100, 7, 2), (49, 300, 83, 2), (49, 32, 49, 4)])
+                                         (49, 256, 81, 5), (49, 64, 49, 3), (49, 100, 7, 2), (49, 300, 83, 2), (49, 32, 49, 4),
+                                         # enough 64 x 64 tiles to leave latency mode: the unforced choice is tile 0, 1, 3, 4, 5, 6 with the K slab of 8, 7 with the
+                                         # K slab of 8, 8 unsplit (tests/zgemm_shapes.py NATURAL; tests/test_zgemm_choice.py checks the choice without a GPU)
+                                         (64, 256, 64, 64), (32, 128, 40, 300), (64, 32, 32, 300), (32, 64, 32, 300), (16, 128, 16, 300), (200, 256, 64, 20),
+                                         (8, 64, 8, 300), (128, 16, 200, 400)])
 def test_batched_zgemm(helm_lib, M, N, K, batch):
+    """Besides the normwise check: every element within 4 (K + 4) u (|alpha| |A| |B| + |beta| |C|) of the product in numpy.clongdouble, the bound every
+    summation order of an fp64 complex dot product satisfies (derivation: tests/test_gpu_zgemm_tiles.py)."""
+    from tests import zgemm_shapes as zs
     rng = np.random.default_rng(M * 7 + N)
     A, B, C = crand(rng, batch, M, K), crand(rng, batch, K, N), crand(rng, batch, M, N)
+    x87 = zs.have_x87()
+    if x87:
+        P, SP = np.matmul(A.astype(np.clongdouble), B.astype(np.clongdouble)), np.matmul(np.abs(A), np.abs(B))
     for alpha, beta in ((1 + 0j, 0j), (-1 + 0j, 1 + 0j), (0.3 - 0.2j, 0.5 + 0.1j)):
         ref = alpha * (A @ B) + (beta * C if beta != 0 else 0)
+        if x87:          # (before the call: with beta != 0 the product is written over C)
+            refx, S = np.clongdouble(alpha) * P + (np.clongdouble(beta) * C.astype(np.clongdouble) if beta != 0 else 0), abs(alpha) * SP + abs(beta) * np.abs(C)
         out = np.ascontiguousarray(C if beta != 0 else np.full_like(C, np.nan))     # beta == 0 must not read C
         al, be = np.array([alpha.real, alpha.imag]), np.array([beta.real, beta.imag])
         rc = helm_lib.helm_debug_zgemm(0, M, N, K, al.ctypes.data_as(ctypes.c_void_p), np.ascontiguousarray(A).ctypes.data_as(ctypes.c_void_p),
@@ -39,6 +51,10 @@ def test_batched_zgemm(helm_lib, M, N, K, batch):
                                        out.ctypes.data_as(ctypes.c_void_p), batch)
         assert rc == 0
         assert np.abs(out - ref).max() <= 1e-12 * max(1.0, np.abs(ref).max()) * K
+        if x87:
+            worst = zs.worst_ratio(out, refx, S, K)
+            print('%d x %d x %d x %d alpha %s beta %s: worst |out - ref| / bound = %.4f' % (M, N, K, batch, alpha, beta, worst))
+            assert worst <= 1.0
 
 
 @pytest.mark.parametrize('n,batch', [(1, 2), (5, 3), (32, 4), (33, 2), (64, 5), (100, 2), (257, 1),

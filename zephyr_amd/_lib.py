@@ -66,6 +66,25 @@ class RuntimeStats(ctypes.Structure):
                 ('sync_calls', ctypes.c_longlong), ('sync_ms', ctypes.c_double), ('slow_syncs', ctypes.c_longlong), ('worst_sync_ms', ctypes.c_double)]
 
 
+class ZgemmEx(ctypes.Structure):
+    'helm_zgemm_ex of include/helm.h: one product with everything the direct solver varies (test hook helm_debug_zgemm_ex)'
+    _fields_ = [('device', ctypes.c_int), ('M', ctypes.c_int), ('N', ctypes.c_int), ('K', ctypes.c_int), ('batch', ctypes.c_int),
+                ('lda', ctypes.c_int), ('ldb', ctypes.c_int), ('ldc', ctypes.c_int),
+                ('sa', ctypes.c_longlong), ('sb', ctypes.c_longlong), ('sc', ctypes.c_longlong),
+                ('alpha', ctypes.c_double * 2), ('beta', ctypes.c_double * 2),
+                ('A', ctypes.c_void_p), ('a_len', ctypes.c_longlong), ('B', ctypes.c_void_p), ('b_len', ctypes.c_longlong),
+                ('C', ctypes.c_void_p), ('c_len', ctypes.c_longlong),
+                ('force_tile', ctypes.c_int), ('force_slab', ctypes.c_int), ('xcd_map', ctypes.c_int), ('ntc', ctypes.c_int),
+                ('zr0', ctypes.c_int), ('zr1', ctypes.c_int), ('zc0', ctypes.c_int), ('zc1', ctypes.c_int), ('sk0', ctypes.c_int), ('sk1', ctypes.c_int),
+                ('tm64', ctypes.c_int), ('c_is_b', ctypes.c_int),
+                ('tabB', ctypes.c_void_p), ('tabCi', ctypes.c_void_p), ('tabCo', ctypes.c_void_p), ('tab_len', ctypes.c_longlong),
+                ('tab_stride', ctypes.c_int), ('offB', ctypes.c_int), ('offCi', ctypes.c_int), ('offCo', ctypes.c_int),
+                ('ldx', ctypes.c_int), ('arena_rows', ctypes.c_longlong),
+                ('Bx', ctypes.c_void_p), ('Bx2', ctypes.c_void_p), ('Cix', ctypes.c_void_p), ('Cox', ctypes.c_void_p), ('Cox2', ctypes.c_void_p),
+                ('k2', ctypes.c_int), ('cj_out', ctypes.c_int), ('oscale', ctypes.c_double * 2),
+                ('act', ctypes.c_void_p), ('report', ctypes.c_int * 5)]
+
+
 # every symbol include/helm.h declares, with its ctypes signature
 _c_dp = ctypes.POINTER(ctypes.c_double)
 _SIGNATURES = {
@@ -129,6 +148,8 @@ _SIGNATURES = {
                                      ctypes.c_void_p]),
     'helm_debug_zgemm': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]),
+    'helm_debug_zgemm_choice': (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(ctypes.c_int)]),
+    'helm_debug_zgemm_ex': (ctypes.c_int, [ctypes.POINTER(ZgemmEx)]),
     'helm_debug_inverse': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
     'helm_debug_zgemm_bench': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.POINTER(ctypes.c_double)]),

@@ -218,9 +218,13 @@ struct GroupTrace {
 
 // ---- nd_gemm.hip ----
 // strided-batched C = beta C + alpha A B on the matrix cores; op may be null (diagnostic entry points): default stream, no profiling
+// what gemm() launches for a shape (gemm_choice, nd_gemm.hip): tile 0-8, K slab 8 / 16 (16: latency mode), the 16 MT + 1-row tile, split of the inner dimension
+struct GemmChoice { int tile = 0, kslab = 8, xr = 0, ksplit = 0, kc = 0; };
 int gemm(helm_op *op, int M, int Nn, int K, cplx alpha, const cplx *A, int lda, long long sa, const cplx *B, int ldb, long long sb,
-         cplx beta, cplx *C, int ldc, long long sc, int batch, const GemmRows *rows = nullptr);
-extern int g_gemm_tile;         // >= 0: forces the tile configuration (helm_debug_zgemm_bench)
+         cplx beta, cplx *C, int ldc, long long sc, int batch, const GemmRows *rows = nullptr, GemmChoice *made = nullptr);
+extern int g_gemm_tile;         // >= 0: forces the tile configuration (helm_debug_zgemm_bench, helm_debug_zgemm_ex)
+extern int g_gemm_slab;         // with g_gemm_tile 6 / 7: 16 forces the K slab of 16 (helm_debug_zgemm_ex); otherwise a forced tile takes the slab of 8
+extern int g_gemm_xcd;          // >= 0: replaces helm_tuning.nd_xcd_map (helm_debug_zgemm_ex)
 bool gemm_sep_bwd_small(helm_op *op, int smax, int mmax, int nrhs, const cplx *Finv, const cplx *F12, int lda, long long sa, int batch, const GemmRows &rows);
 // ---- nd_gj.hip ----
 // in-place inverse of `batch` n x n blocks (row-major, leading dimension ld, batch stride `stride`); W: workspace with batch stride ws, at least n*n elements per matrix
