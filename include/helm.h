@@ -23,6 +23,9 @@
  *   helm_reserve                   <- (same pool: its workers' scratch, allocated before they start)
  *   helm_imaging_accumulate_device <- zero-lag imaging condition in HelmBaseProblem.Jtvec
  *                                     zephyr/middleware/problem.py:152,162
+ *   helm_axpby_device,
+ *   helm_sample_accumulate_device  <- MiniZephyr25D.__mul__: the sum over ky sub-problems
+ *                                     (`reduce(np.add, ...)`, scaled)     minizephyr.py:435-460
  *   helm_destroy                   <- `del obj.factors` / __del__         discretization.py:86-99
  *
  * Conventions
@@ -254,6 +257,15 @@ int helm_rhs_support_from_coo(helm_op *op, const void *d_row, const void *d_col,
  * row r (rowptr, col: int64; val: complex128; U: nsrc x ld; out: nrec x nsrc complex128; device pointers). */
 int helm_sample_device(helm_op *op, const void *dU, int nsrc, long long ld, const void *d_rowptr, const void *d_col,
                        const void *d_val, int nrec, void *d_out);
+/* The same into an accumulator: out = beta * out + alpha * R u (complex alpha, beta; arguments as for helm_sample_device).  Sampling is linear, so the
+ * data of a sum of wavefields (the cross-line wavenumbers of MiniZephyr25D, minizephyr.py:435-460) are summed here and the summed field is never formed.
+ * beta == 0: out is not read (it may be uninitialised). */
+int helm_sample_accumulate_device(helm_op *op, const void *dU, int nsrc, long long ld, const void *d_rowptr, const void *d_col,
+                                  const void *d_val, int nrec, double alpha_re, double alpha_im, double beta_re, double beta_im, void *d_out);
+/* Y[i] = beta * Y[i] + alpha * X[i], i < n: complex128 device arrays (16-byte aligned, X != Y, not overlapping), on the handle's stream; returns when Y is
+ * complete.  The sum over sub-problems of a composite operator (MiniZephyr25D: the last term carries the composite's scaleTerm in alpha and beta, so there
+ * is no scaling pass).  beta == 0: Y is not read (it may be uninitialised). */
+int helm_axpby_device(helm_op *op, double alpha_re, double alpha_im, const void *dX, double beta_re, double beta_im, void *dY, long long n);
 
 /* Device buffers are recycled by size class; a class holds as many as the busiest moment so far needed.  How many operators a pipelined job has alive at its
  * busiest is a matter of thread timing, so a job that got by with three buffers of a class in its first items may ask for a fourth later -- a hipMalloc of GBs

@@ -141,6 +141,11 @@ _SIGNATURES = {
                                                 ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong]),
     'helm_sample_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    'helm_sample_accumulate_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                                     ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                                     ctypes.c_void_p]),
+    'helm_axpby_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
+                                         ctypes.c_void_p, ctypes.c_longlong]),
     'helm_direct_plan': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
     'helm_direct_plan_front': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
     'helm_mg3_axis': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_int,
@@ -306,6 +311,18 @@ def from_device(t):
     host = pinned_empty(tuple(t.shape), _TORCH_NP[str(t.dtype)])
     torch.from_numpy(host).copy_(t)
     return np.array(host)
+
+
+def from_device_pinned(t):
+    """torch tensor on a GPU -> numpy array that IS the pinned buffer it was copied into (from_device without the second copy on the host: for results of
+    hundreds of MB, like the arrays BaseDiscretization._solve returns).  The block goes back to the library's pool when the array is dropped."""
+    import torch
+    t = t.contiguous()
+    if t.numel() * t.element_size() < (64 << 10):
+        return t.cpu().numpy()
+    host = pinned_empty(tuple(t.shape), _TORCH_NP[str(t.dtype)])
+    torch.from_numpy(host).copy_(t)
+    return host
 
 
 def wait_torch_stream(dev, spin_ms=None):

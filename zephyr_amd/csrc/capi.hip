@@ -2714,6 +2714,32 @@ extern "C" int helm_sample_device(helm_op *op, const void *dU, int nsrc, long lo
     return HELM_OK;
 }
 
+// out = beta out + alpha R u: helm_sample_device into an accumulator (the ky sum of 2.5-D data; beta == 0: out is not read)
+extern "C" int helm_sample_accumulate_device(helm_op *op, const void *dU, int nsrc, long long ld, const void *d_rowptr, const void *d_col, const void *d_val, int nrec,
+                                             double alpha_re, double alpha_im, double beta_re, double beta_im, void *d_out) {
+    helm_tuning_refresh();
+    if (!op || !dU || !d_rowptr || !d_col || !d_val || !d_out || nsrc < 1 || nrec < 1 || ld < 1) return HELM_ERR_ARG;
+    HIP_TRY(op, hipSetDevice(op->device));
+    int rc = helm_launch_sample_acc(op, (const cplx *)dU, nsrc, ld, (const long long *)d_rowptr, (const long long *)d_col, (const cplx *)d_val, nrec,
+                                    cmake(alpha_re, alpha_im), cmake(beta_re, beta_im), (cplx *)d_out);
+    if (rc) return rc;
+    HIP_TRY(op, hipStreamSynchronize(op->stream));
+    return HELM_OK;
+}
+
+// Y = beta Y + alpha X over n complex128 values on the device (the ky accumulation of the 2.5-D composite; beta == 0: Y is not read).  Returns when Y is
+// complete: the next term of the sum is added on ANOTHER handle's stream.
+extern "C" int helm_axpby_device(helm_op *op, double alpha_re, double alpha_im, const void *dX, double beta_re, double beta_im, void *dY, long long n) {
+    helm_tuning_refresh();
+    if (!op || !dX || !dY || n < 1 || dX == dY) return HELM_ERR_ARG;
+    if ((((uintptr_t)dX) | ((uintptr_t)dY)) & 15) return HELM_ERR_ARG;       // (complex128 values are read and written as 16-byte vectors)
+    HIP_TRY(op, hipSetDevice(op->device));
+    int rc = helm_launch_axpby(op, cmake(alpha_re, alpha_im), (const cplx *)dX, cmake(beta_re, beta_im), (cplx *)dY, n);
+    if (rc) return rc;
+    HIP_TRY(op, hipStreamSynchronize(op->stream));
+    return HELM_OK;
+}
+
 extern "C" int helm_imaging_accumulate_device(helm_op *op, const void *dUF, const void *dUB, int nsrc, const void *dScaler, void *dG) {
     helm_tuning_refresh();
     if (!op || !dUF || !dUB || !dScaler || !dG || nsrc < 1) return HELM_ERR_ARG;

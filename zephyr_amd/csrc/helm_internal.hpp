@@ -351,6 +351,9 @@ int helm_launch_imaging(helm_op *op, const cplx *uf, const cplx *ub, int nsrc, c
 int helm_launch_zero(helm_op *op, cplx *p, long long n);
 int helm_launch_rhs_from_coo(helm_op *op, const long long *row, const int *col, const cplx *val, long long nnz, cplx *R, int nrhs, long long rows, int node_major = 0);
 int helm_launch_sample(helm_op *op, const cplx *U, int nsrc, long long ld, const long long *rowptr, const long long *col, const cplx *val, int nrec, cplx *out);
+int helm_launch_sample_acc(helm_op *op, const cplx *U, int nsrc, long long ld, const long long *rowptr, const long long *col, const cplx *val, int nrec,
+                           cplx alpha, cplx beta, cplx *out);                                  // out = beta out + alpha R u (beta == 0: out is not read)
+int helm_launch_axpby(helm_op *op, cplx alpha, const cplx *X, cplx beta, cplx *Y, long long n);  // Y = beta Y + alpha X (beta == 0: Y is not read)
 int helm_launch_rowscale_inplace(helm_op *op, cplx *v, const double *rs, long long NV, int nrhs);
 int helm_launch_abs(helm_op *op, const cplx *in, cplx *out, long long n, double sign);      // out = sign |in|
 int helm_launch_gardner_rho(helm_op *op);     // d_rho = 310 Re(d_c)^0.25

@@ -991,6 +991,58 @@ int helm_launch_sample(helm_op *op, const cplx *U, int nsrc, long long ld, const
     return HELM_OK;
 }
 
+// receiver sampling into an accumulator: out[r][s] = beta out[r][s] + alpha sum_k val[k] U[s][col[k]] (the ky sum of a 2.5-D survey's data: sampling is
+// linear, so the summed wavefields are never formed).  beta0: out is write-only -- an uninitialised accumulator is legal for the first term.
+__global__ __launch_bounds__(256) void k_sample_acc(const cplx *__restrict__ U, int nsrc, long long ld, const long long *__restrict__ rowptr,
+                                                    const long long *__restrict__ col, const cplx *__restrict__ val, int nrec, cplx alpha, cplx beta, int beta0,
+                                                    cplx *__restrict__ out) {
+    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= (long long)nrec * nsrc) return;
+    const int r = (int)(t / nsrc), sidx = (int)(t % nsrc);
+    cplx acc = cmake(0.0, 0.0);
+    for (long long k = rowptr[r]; k < rowptr[r + 1]; ++k) cfma(acc, val[k], U[(long long)sidx * ld + col[k]]);
+    cplx o = cmul(alpha, acc);
+    if (!beta0) cfma(o, beta, out[t]);
+    out[t] = o;
+}
+int helm_launch_sample_acc(helm_op *op, const cplx *U, int nsrc, long long ld, const long long *rowptr, const long long *col, const cplx *val, int nrec,
+                           cplx alpha, cplx beta, cplx *out) {
+    const long long tot = (long long)nrec * nsrc;
+    const int beta0 = (beta.x == 0.0 && beta.y == 0.0) ? 1 : 0;
+    HELM_LAUNCH(k_sample_acc, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, op->stream, U, nsrc, ld, rowptr, col, val, nrec, alpha, beta, beta0, out);
+    HIP_TRY(op, hipGetLastError());
+    return HELM_OK;
+}
+
+// Y = beta Y + alpha X over n complex128 values: the ky accumulation of the 2.5-D composite.  A pure streaming pass (48 B per element, 32 with BETA0):
+// one 16-byte load / store per lane and element, 64-bit indices.  A workgroup takes 256 CONSECUTIVE elements, one per lane, and there is a workgroup per 256
+// elements up to AXPBY_BLOCKS (n <= 2^30: a single trip through the loop), striding beyond: measured on 0.27 .. 8.6 GB operands, this order ran at 5.8-5.9 TB/s
+// where 2048 workgroups striding with four elements 8 MB apart in flight per lane ran at 4.5-5.0, and two to eight elements per lane in a workgroup-contiguous
+// tile at 5.3-5.6.  BETA0: Y is write-only.
+constexpr int AXPBY_BLOCKS = 1 << 22;
+// one element.  Contraction is pinned off: each complex product is rounded on its own (within sqrt(5) u of the exact one in modulus) and ONE addition follows
+// (+ u), the error model (sqrt(5) + 1) u (|alpha||x| + |beta||y|) the tests hold this kernel to; a chain of four FMAs per component has no such bound.  The
+// kernel moves 48 B per element: the three extra roundings are free.
+__device__ __forceinline__ cplx axpby1(cplx alpha, cplx x, cplx beta, cplx y) {
+#pragma clang fp contract(off)
+    const cplx p = cmake(alpha.x * x.x - alpha.y * x.y, alpha.x * x.y + alpha.y * x.x);
+    const cplx r = cmake(beta.x * y.x - beta.y * y.y, beta.x * y.y + beta.y * y.x);
+    return cmake(p.x + r.x, p.y + r.y);
+}
+template <bool BETA0>
+__global__ __launch_bounds__(256) void k_axpby(const cplx *__restrict__ X, cplx *__restrict__ Y, long long n, cplx alpha, cplx beta) {
+    const long long stride = (long long)gridDim.x * blockDim.x;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
+        Y[i] = BETA0 ? cmul(alpha, X[i]) : axpby1(alpha, X[i], beta, Y[i]);
+}
+int helm_launch_axpby(helm_op *op, cplx alpha, const cplx *X, cplx beta, cplx *Y, long long n) {
+    const dim3 grid((unsigned)std::min<long long>((n + 255) / 256, AXPBY_BLOCKS));
+    if (beta.x == 0.0 && beta.y == 0.0) HELM_LAUNCH(k_axpby<true>, grid, dim3(256), 0, op->stream, X, Y, n, alpha, beta);
+    else HELM_LAUNCH(k_axpby<false>, grid, dim3(256), 0, op->stream, X, Y, n, alpha, beta);
+    HIP_TRY(op, hipGetLastError());
+    return HELM_OK;
+}
+
 // Gardner's relation, the reference's density default: rho = 310 Re(c)^0.25 (discretization.py:70)
 __global__ __launch_bounds__(256) void k_gardner_rho(const cplx *__restrict__ c, double *__restrict__ rho, long long n) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)

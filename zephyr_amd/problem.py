@@ -282,8 +282,11 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if not subs or not hasattr(subs[0], 'solveDevice'):
             return False
         from .discretization import DiscretizationWrapper
-        if isinstance(subs[0], DiscretizationWrapper):        # composite sub-problems (2.5-D ky sums) own no single device operator
-            return False
+        if isinstance(subs[0], DiscretizationWrapper):
+            # composite sub-problems (2.5-D ky sums) own no single device operator: they serve when they form their sum in HBM themselves
+            # (MiniZephyr25D.solveDevice / sampleSumDevice), on a single-grid survey -- the multiscale 2.5-D pairing stays on the host path
+            if not getattr(subs[0], 'kySumOnDevice', False) or isinstance(self.survey, HelmMultiGridSurvey):
+                return False
         try:
             from . import _lib
             if _lib.load().helm_device_count() <= 0:
@@ -461,6 +464,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             dev = torch.device('cuda', op.device)
             state = wstate.setdefault(('buffers', op.device), {})
             k = c1 - c0
+            summed = hasattr(op, 'sampleSumDevice')           # a composite (2.5-D ky sum): its samples are accumulated per ky, it keeps its own wavefield scratch
             if not multi:
                 if 'csr' not in state:
                     Rm = Rms[None]
@@ -468,7 +472,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
                 csr = state['csr']
                 if state.get('cap', 0) < k:
                     state['R'] = torch.empty((k, N), dtype=torch.complex128, device=dev)
-                    state['U'] = torch.empty((k, N), dtype=torch.complex128, device=dev)
+                    state['U'] = None if summed else torch.empty((k, N), dtype=torch.complex128, device=dev)
                     state['out'] = torch.empty((nrec, k), dtype=torch.complex128, device=dev)
                     state['cap'] = k
                 R, U = state['R'], state['U']
@@ -493,8 +497,11 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             out = state['out'] if state['cap'] == k else torch.empty((nrec, k), dtype=torch.complex128, device=dev)
             q = qf[ifreq] if isinstance(qf, (list, tuple)) else qf
             op.rhsFromSparseDevice(sp.csc_matrix(q)[:, c0:c1], R.data_ptr())
-            op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
-            op.sampleDevice(U.data_ptr(), k, csr, out.data_ptr())      # (returns when the samples are there: helm_sample_device waits for its own stream)
+            if summed:
+                op.sampleSumDevice(R.data_ptr(), k, csr, out.data_ptr(), rows=Ni)      # (sampling is linear: the N x k sum over ky is never formed)
+            else:
+                op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+                op.sampleDevice(U.data_ptr(), k, csr, out.data_ptr())      # (returns when the samples are there: helm_sample_device waits for its own stream)
             data[:, c0:c1, ifreq] = scale * _lib.from_device(out)          # (disjoint slices per item: no two workers write the same entries)
             return None
         self._runOnDevices(devs, items, one)
