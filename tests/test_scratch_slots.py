@@ -1,4 +1,4 @@
-"""CPU: the direct path's scratch-slot table (zephyr_amd/csrc/capi.hip) is kept PER DEVICE -- the in-process counterpart of the reference's pool,
+"""CPU: the direct path's scratch-slot table (zephyr_amd/csrc/runtime.hip) is kept PER DEVICE -- the in-process counterpart of the reference's pool,
 where every worker has an address space of its own (zephyr/backend/distributors.py:80-96,161-168).  helm_debug_ws_selftest drives the table's
 own booking / lease code with host memory and logical devices, so the eight-GPU case is testable without a GPU."""
 import pytest

@@ -140,7 +140,7 @@ struct helm_op {
     double a_freq_re = 0, a_freq_im = 0, a_tau = 0, a_ky = 0, a_cpml = 0;   // parameters of the last assemble
     struct MgPrecond *mg = nullptr;
     struct Mg3Precond *mg3 = nullptr;    // 3-D multigrid preconditioner (mg3d.hip)
-    bool mg3_no_keep = false;            // this frequency retreated from the layer-preserving hierarchy to the standard cycle (capi.hip)
+    bool mg3_no_keep = false;            // this frequency retreated from the layer-preserving hierarchy to the standard cycle (krylov.hip)
     int mg3_rhs_hint = 0;                // right-hand sides of the solve call that builds the preconditioner (0: unknown): few of them favour a cheap set-up
     struct NdFactor *direct[4] = {nullptr, nullptr, nullptr, nullptr};   // sparse direct factors per block, valid until the next assemble
     bool direct_failed = false;
@@ -186,7 +186,7 @@ struct helm_op {
 
 void helm_set_error(helm_op *op, const char *msg);
 
-// ---- kernel registry (capi.hip) -------------------------------------------------------------------
+// ---- kernel registry (runtime.hip) -----------------------------------------------------------------
 // The HIP runtime resolves a kernel lazily: the first launch of a symbol on a device looks it up in the code object and builds its dispatch
 // record (tens to hundreds of microseconds of host time, 1.8 ms for the nine kernels of a tree level in a cold process).  A job meets some
 // instantiations only at some frequencies (pivoted leaves, the pivoted-LU treatment of ill-conditioned fronts, refinement widths), i.e. possibly
@@ -208,7 +208,7 @@ struct HelmFirstLaunch {
 };
 #define HELM_LAUNCH(KERNEL, ...) do { HelmFirstLaunch fl_(HelmKernelReg<(KERNEL)>::slot); hipLaunchKernelGGL(KERNEL, __VA_ARGS__); } while (0)
 
-// ---- runtime-object bookkeeping (capi.hip) ----------------------------------------------------------
+// ---- runtime-object bookkeeping (runtime.hip) --------------------------------------------------------
 // Every call of the library that makes the HIP runtime create something -- device memory, pinned memory, an event, a stream -- goes through a
 // counting wrapper (the function-like macros below catch the calls of every translation unit; `(hipMalloc)(...)` is how the wrappers reach the
 // real entry points).  helm_debug_runtime_stats() reports the counts: a job whose pools were booked (helm_reserve, warm-up items) must show
@@ -237,23 +237,38 @@ hipError_t helm_timed_memcpy(void *dst, const void *src, size_t bytes, hipMemcpy
 #define hipStreamCreateWithPriority(S, F, PR) helm_counted_stream_create((S), (F), (PR), true)
 helm_tuning helm_tuning_now();                            // the options in force (helm_set_tuning, else defaults + environment; include/helm.h)
 void helm_tuning_refresh();                               // look at the environment again (API entry points call this; nothing below them does)
+int helm_env_int(const char *name, int d);                // an integer switch of the environment that is not part of helm_tuning, read at every call
+// HELM_ALLOC_TRACE=1: every allocator call that reaches the driver and takes more than a millisecond is reported on stderr
+// (always counted -- helm_debug_alloc_stats -- so that a test can assert that a job issued none after its bookings)
+struct AllocTrace { const char *what; size_t bytes; double t0; AllocTrace(const char *w, size_t b); ~AllocTrace(); };
 
 // Size-keyed cache of large device buffers (coefficient planes, factors, per-call temporaries): a job walks through many
 // operators of identical shape, and hipMalloc/hipFree of GB-sized buffers cost milliseconds each.  helm_trim() empties it.
 void *helm_pool_alloc(int device, size_t bytes);          // nullptr on failure
 void helm_pool_free(int device, void *p, size_t bytes);   // the buffer must no longer be in use by any stream
 size_t helm_pool_idle_bytes(int device);                  // what the pool holds idle on that device (not in hipMemGetInfo's free figure)
+size_t helm_pool_idle_count(int device, size_t bytes);    // idle buffers of exactly that size
+void helm_pool_top_up(int device, int spare);             // spares of the big size classes beyond their high-water mark (no operator of the device alive)
 hipError_t helm_malloc_retry(int device, void **p, size_t bytes);   // hipMalloc; on failure the device's idle pool is emptied and the call repeated
 void *helm_hostpool_alloc(size_t bytes);                  // pinned host memory, recycled by size
 int helm_download_staged(helm_op *op, void *dst, const void *src, size_t bytes);    // device -> caller's host array, the same way
-int helm_upload_staged(helm_op *op, void *dst, const void *src, size_t bytes);      // caller's host array -> device on op->stream through the library's pinned chunks (capi.hip); returns when the copy is done
+int helm_upload_staged(helm_op *op, void *dst, const void *src, size_t bytes);      // caller's host array -> device on op->stream through the library's pinned chunks (runtime.hip); returns when the copy is done
 void helm_hostpool_free(void *p, size_t bytes);
 hipStream_t helm_stream_acquire(int device, int prio);    // prio 0 normal, 1 highest, -1 lowest; recycled across handles
 void helm_stream_release(int device, int prio, hipStream_t s);
+// scratch slots of the direct path, per device: a lease (device, slot) on an idle slot of at least `bytes`, nullptr when all are taken or the allocation fails
+void *ws_checkout(int device, size_t bytes, int *slot_out);
+void ws_checkin(int slot);
+int ws_reserve(int device, size_t bytes, int concurrent);         // `concurrent` slots of that device hold at least `bytes`; returns how many are ready
+// scratch of an enqueued factorisation: handed over, it goes back to the pool behind everything enqueued on `st` so far, at the next sweep that finds it finished
+void scratch_defer(int device, hipStream_t st, void *ws, size_t bytes);
+void scratch_sweep(int device, bool wait);                // (wait: for everything deferred on that device)
+void scratch_sweep_all_wait();                            // the same on every device, waiting
 void helm_pf_retire(helm_op *op);                         // wait for / book / clean up a factorisation started by helm_prefactor
-int helm_ensure_scaled(helm_op *op);
+int helm_ensure_scaled(helm_op *op);                      // d_Cs, d_dinv for the operator currently assembled
 int helm_need_all_blocks(helm_op *op);                   // Eurus operators assembled lazily (M1 only): bring M2..M4 into being before anything reads them
-int helm_events_grow(helm_op *op, int n);                 // n more timing events for the handle (recycled across handles)                      // d_Cs, d_dinv for the operator currently assembled
+int helm_events_grow(helm_op *op, int n);                 // n more timing events for the handle (recycled across handles)
+void helm_events_release(helm_op *op);                    // the handle's timing events go back to the process-wide free list
 
 // ---- multigrid preconditioner (mg.hip) ---------------------------------------------------------
 struct MgPrecond;
@@ -346,7 +361,6 @@ int helm_launch_rowscaled_system(helm_op *op);    // d_S, d_rs
 int helm_launch_prep_rhs_rs(helm_op *op, const cplx *dRHS, long long rhs_ld, long long row_off, cplx premul, const double *rs,
                             cplx *out, long long out_ld, long long out_off, int nrhs);
 int helm_launch_prep_rhs(helm_op *op, const cplx *dRHS, long long rhs_ld, long long row_off, cplx premul, const cplx *sub, cplx *out, int nrhs); // out = premul*rhs - sub
-int helm_launch_prep_rhs_norm(helm_op *op, const cplx *dRHS, long long rhs_ld, long long row_off, cplx premul, const cplx *sub, cplx *out, int nrhs);
 int helm_launch_imaging(helm_op *op, const cplx *uf, const cplx *ub, int nsrc, const cplx *scaler, cplx *g);
 int helm_launch_zero(helm_op *op, cplx *p, long long n);
 int helm_launch_rhs_from_coo(helm_op *op, const long long *row, const int *col, const cplx *val, long long nnz, cplx *R, int nrhs, long long rows, int node_major = 0);

@@ -83,7 +83,6 @@ constexpr int TX = 64;
 //   0  X is read                                                       (everything else)
 //   1  X = omega_j * dinv (.) W, also stored to U        [multigrid: first Jacobi sweep fused into the residual]
 //   2  X = X + P E (bilinear prolongation of E)          [multigrid: coarse correction fused into the post-smoothing sweep]
-//   3  X is read conjugated                               [direct path: residual of a wavefield already stored as conj(x)]
 template <class V, int P, bool SCALED, bool ADJ, int EPI, int XMODE = 0>
 __global__ __launch_bounds__(256) void k_stencil_t(StencilParamsT<V> q) {
     constexpr int TZ = 4 * P;
@@ -149,8 +148,6 @@ __global__ __launch_bounds__(256) void k_stencil_t(StencilParamsT<V> q) {
                 if (oj && J + 1 < q.nxc) { const V c3 = e[(long long)(I + 1) * q.nxc + J + 1]; a.x += 0.25 * c3.x; a.y += 0.25 * c3.y; }
             }
             return cadd(v, a);
-        } else if (XMODE == 3) {
-            return cconj(q.X[(long long)b * q.ld + idx]);
         } else {
             return q.X[(long long)b * q.ld + idx];
         }
@@ -308,23 +305,6 @@ __global__ __launch_bounds__(256) void k_prep_rhs(const cplx *__restrict__ rhs, 
         if (scale) v = cmul(scale[i], v);
         out[(long long)b * N + i] = v;
     }
-}
-
-// k_prep_rhs with the partial (out, out) of k_norm2 folded in (direct path: one pass over the right-hand sides less)
-__global__ __launch_bounds__(256) void k_prep_rhs_norm(const cplx *__restrict__ rhs, long long rhs_ld, long long row_off, cplx premul,
-                                                       const cplx *__restrict__ sub, cplx *__restrict__ out, long long N,
-                                                       double *__restrict__ part, int nblk) {
-    __shared__ double red[4];
-    const int b = blockIdx.y;
-    double s[1] = {0.0};
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
-        cplx v = cmul(premul, rhs[(long long)b * rhs_ld + row_off + i]);
-        if (sub) v = csub(v, sub[(long long)b * N + i]);
-        out[(long long)b * N + i] = v;
-        s[0] += cabs2(v);
-    }
-    block_sum<1>(s, red);
-    if (threadIdx.x == 0) part[((long long)b * 4) * nblk + blockIdx.x] = s[0];
 }
 
 // BiCGSTAB / CGNR start: x = 0, r = r0 = bbar, p = v = 0, partial (r, r)
@@ -780,8 +760,6 @@ int helm_launch_apply(helm_op *op, const ApplyArgs &a) {
         HELM_LAUNCH((k_stencil_t<cplx, STENCIL_P, false, false, EPI_RESID, 1>), grid, dim3(256), 0, op->stream, q);
     } else if (a.xmode == 2 && a.epi == EPI_JACOBI && !a.scaled && !a.adjoint) {
         HELM_LAUNCH((k_stencil_t<cplx, STENCIL_P, false, false, EPI_JACOBI, 2>), grid, dim3(256), 0, op->stream, q);
-    } else if (a.xmode == 3 && a.epi == EPI_RESID && !a.scaled && !a.adjoint) {
-        HELM_LAUNCH((k_stencil_t<cplx, STENCIL_P, false, false, EPI_RESID, 3>), grid, dim3(256), 0, op->stream, q);
     } else if (a.xmode != 0) {
         HELM_FAIL(op, HELM_ERR_ARG, "unsupported fused stencil mode");
     } else if (a.scaled) {
@@ -815,14 +793,6 @@ int helm_launch_prep_rhs(helm_op *op, const cplx *dRHS, long long rhs_ld, long l
                          const cplx *sub, cplx *out, int nrhs) {
     dim3 grid(vec_blocks(op->Nv), nrhs);
     HELM_LAUNCH(k_prep_rhs, grid, dim3(256), 0, op->stream, dRHS, rhs_ld, row_off, premul, sub, (const cplx *)nullptr, out, op->Nv);
-    HIP_TRY(op, hipGetLastError());
-    return HELM_OK;
-}
-
-// out = premul*rhs - sub and the partial sums of ||out||^2 (reduce with FIN_NORM over helm_vec_num_blocks partials)
-int helm_launch_prep_rhs_norm(helm_op *op, const cplx *dRHS, long long rhs_ld, long long row_off, cplx premul, const cplx *sub, cplx *out, int nrhs) {
-    dim3 grid(vec_blocks(op->Nv), nrhs);
-    HELM_LAUNCH(k_prep_rhs_norm, grid, dim3(256), 0, op->stream, dRHS, rhs_ld, row_off, premul, sub, out, op->Nv, (double *)op->d_part, (int)grid.x);
     HIP_TRY(op, hipGetLastError());
     return HELM_OK;
 }

@@ -1,4 +1,4 @@
-// Multigrid preconditioners for the 3-D 27-point operator (right-preconditioned BiCGSTAB of capi.hip).
+// Multigrid preconditioners for the 3-D 27-point operator (right-preconditioned BiCGSTAB of krylov.hip).
 //
 // 1. Standard cycle (first half of this file; grids below 20 points per wavelength, fallback): one V(1,1) cycle on the
 //    complex-shifted operator (1/tau_M = 1/tau + omega beta / 2) with a weak absorbing layer (cPML_M), rediscretised on coarser

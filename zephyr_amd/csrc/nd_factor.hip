@@ -19,7 +19,7 @@
 //             backward: x_S = F11^-1 (y_S - F12 x_B), top-down.  Pure GEMMs on node-major right-hand sides
 //             X[cell][rhs], no atomics, bit-reproducible.                                                 nd_passes.hip
 //   accuracy  the true residual q' - A x of what is returned is evaluated with the stencil (nd_resid.hip); right-hand sides
-//             above rtol take a step of iterative refinement (capi.hip).
+//             above rtol take a step of iterative refinement (solve_direct.hip).
 //
 // All dense arithmetic is fp64 complex on the matrix cores (v_mfma_f64_16x16x4_f64, nd_gemm_body.hpp).
 #include "nd_internal.hpp"

@@ -1,5 +1,5 @@
 // Nested-dissection direct solver: what its translation units share (nd_plan / nd_gemm / nd_gj / nd_leaf / nd_factor / nd_passes / nd_resid .hip).
-// direct.hpp is the solver's interface to the rest of the library (capi.hip, mg3d.hip); this header is internal to the solver.
+// direct.hpp is the solver's interface to the rest of the library (solve_direct.hip, capi.hip, mg3d.hip); this header is internal to the solver.
 #pragma once
 #include "helm_internal.hpp"
 #include "direct.hpp"

@@ -182,7 +182,7 @@ NdPlanDev::~NdPlanDev() {
 
 namespace {
 std::mutex g_plan_mu;
-// (never destroyed: a plan's destructor hands its tables to the device pool of capi.hip, which may be gone first when the process exits)
+// (never destroyed: a plan's destructor hands its tables to the device pool of runtime.hip, which may be gone first when the process exits)
 std::map<int, std::vector<std::shared_ptr<NdPlanDev>>> &g_plans = *new std::map<int, std::vector<std::shared_ptr<NdPlanDev>>>();
 
 std::shared_ptr<NdPlanDev> plan_lookup(int device, int pnz, int pnx, int leaf, int dof) {      // (g_plan_mu held)
