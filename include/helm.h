@@ -26,6 +26,9 @@
  *   helm_axpby_device,
  *   helm_sample_accumulate_device  <- MiniZephyr25D.__mul__: the sum over ky sub-problems
  *                                     (`reduce(np.add, ...)`, scaled)     minizephyr.py:435-460
+ *   helm_sample_rows_device,
+ *   helm_rhs_from_samples_device   <- a receiver array that moves with the source (geom mode 'relative'):
+ *                                     HelmBaseSurvey rVec / getResidualSources   zephyr/middleware/survey.py:114-125,171-188
  *   helm_destroy                   <- `del obj.factors` / __del__         discretization.py:86-99
  *
  * Conventions
@@ -262,6 +265,23 @@ int helm_sample_device(helm_op *op, const void *dU, int nsrc, long long ld, cons
  * beta == 0: out is not read (it may be uninitialised). */
 int helm_sample_accumulate_device(helm_op *op, const void *dU, int nsrc, long long ld, const void *d_rowptr, const void *d_col,
                                   const void *d_val, int nrec, double alpha_re, double alpha_im, double beta_re, double beta_im, void *d_out);
+/* The same with a row stride per source: source s samples CSR row r + s * row_stride.  row_stride == 0 is helm_sample_accumulate_device (one receiver
+ * array for every source, bit for bit); row_stride >= nrec serves a receiver array that moves with the source (geom mode 'relative', survey.py:43-47,114-125):
+ * the per-source matrices stacked into one CSR, row s * row_stride + r.  A batch of sources c0 .. c1-1 is d_rowptr + c0 * row_stride with nsrc = c1 - c0.
+ * out: nrec x nsrc as above.  Other values of row_stride: HELM_ERR_ARG. */
+int helm_sample_rows_device(helm_op *op, const void *dU, int nsrc, long long ld, const void *d_rowptr, const void *d_col,
+                            const void *d_val, int nrec, long long row_stride, double alpha_re, double alpha_im, double beta_re, double beta_im,
+                            void *d_out);
+/* Back-sources of a moving receiver array from the residual samples of one frequency (survey.py:171-188): R (nsrc x rows, zeroed by the call),
+ * R[s - src0][cell] = sum_r R_s[r][cell] * resid[r][s - src0] for the sources src0 .. src0 + nsrc - 1.  The sum is a gather over a plan sorted by
+ * (source, cell): touched pair t has source d_tsrc[t] (int32, absolute), cell d_tcell[t] (int64) and the entries d_tptr[t] .. d_tptr[t+1] (int64) of
+ * d_trec (int32 receiver) and d_tval (complex128 weight), ordered by receiver; one thread sums a pair in that order, so repeated calls give the same bits.
+ * d_resid: nrec x ld_resid complex128 (ld_resid >= nsrc).  A batch of sources is a contiguous range of pairs: offset d_tptr, d_tsrc and d_tcell by the
+ * batch's first pair and leave d_trec / d_tval at their base.  ntouch == 0 gives all zeros.  The plan is trusted (cells < rows, receivers < nrec, sources
+ * within the batch): validate it where it is built.  All device pointers; returns when R is complete. */
+int helm_rhs_from_samples_device(helm_op *op, const void *d_resid, long long ld_resid, int nrec, int nsrc, int src0, const void *d_tptr,
+                                 const void *d_tsrc, const void *d_tcell, const void *d_trec, const void *d_tval, long long ntouch, void *dR,
+                                 long long rows);
 /* Y[i] = beta * Y[i] + alpha * X[i], i < n: complex128 device arrays (16-byte aligned, X != Y, not overlapping), on the handle's stream; returns when Y is
  * complete.  The sum over sub-problems of a composite operator (MiniZephyr25D: the last term carries the composite's scaleTerm in alpha and beta, so there
  * is no scaling pass).  beta == 0: Y is not read (it may be uninitialised). */

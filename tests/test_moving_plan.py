@@ -1,0 +1,195 @@
+"""CPU: the host side of the device paths for a receiver array that moves with the source (geom mode 'relative') -- the per-source receiver
+matrices stacked into one CSR, the adjoint plan (getResidualSources as a gather over (source, cell) pairs) evaluated in numpy, source batches as
+sub-ranges of both, the host path against the reference's golden g12, and the argument checks of the two C entry points."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import scipy.sparse as sp
+
+from tests.doubles import OracleMiniZephyrHD
+from zephyr_amd import _lib
+from zephyr_amd.problem import Helm2DProblem
+from zephyr_amd.survey import Helm2DSurvey, Helm2DMultiGridSurvey
+
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden')
+U = 2.0 ** -53
+
+
+def nrm(a, b):
+    return np.linalg.norm(a - b) / np.linalg.norm(b)
+
+
+def g6_config(**kw):
+    g = np.load(os.path.join(GOLD, 'g6_survey.npz'))
+    nz, nx = g['c'].shape
+    sc = dict(nx=nx, nz=nz, dx=10., dz=10., c=g['c'], rho=g['rho'], nPML=6, freqs=list(g['freqs']), Disc=OracleMiniZephyrHD, parallel=False,
+              sterms=g['sterms'], geom=dict(src=g['src'], rec=g['rec_relative'], mode='relative'))
+    sc.update(kw)
+    return g, sc
+
+
+def multigrid_config():
+    'the multiscale pairing of tests/test_gpu_multiscale.py with a streamer whose receivers lie between the nodes of every scale'
+    rng = np.random.default_rng(6)
+    nz, nx = 80, 96
+    c = 1800. + 700. * rng.random((nz, nx))
+    src = np.stack([np.linspace(150., 800., 5), np.full(5, 120.)], axis=1)
+    rec = np.stack([np.linspace(-73., 91., 6), np.linspace(213.5, 240., 6)], axis=1)
+    rterms = np.array([1., 0.5 - 0.25j, 2., -1., 0.75j, 1.5])
+    return dict(nx=nx, nz=nz, dx=10., dz=10., c=c, nPML=8, freqs=[3., 6., 30.], cMin=1800., targetGPW=10.,
+                geom=dict(src=src, rec=rec, rterms=rterms, mode='relative'))
+
+
+def surveys():
+    _, sc = g6_config()
+    out = [('g6', Helm2DSurvey(sc), [0])]
+    sv = Helm2DMultiGridSurvey(multigrid_config())
+    scales = sv.mgHelper.scales
+    assert len(set(scales)) >= 2                                   # more than one grid
+    out.append(('multigrid', sv, [scales.index(s) for s in sorted(set(scales))]))
+    return out
+
+
+def canonical(m):
+    m = sp.csr_matrix(m)
+    m.sum_duplicates()
+    return m
+
+
+def plan_apply(plan, panel, c0, c1):
+    """the gather of helm_rhs_from_samples_device in numpy: (qb (rows, c1 - c0), sum |val||resid| per entry of qb, L per entry), every pair summed in
+    stored order"""
+    k = c1 - c0
+    out = np.zeros((plan['rows'], k), dtype=np.complex128)
+    mag = np.zeros((plan['rows'], k))
+    cnt = np.zeros((plan['rows'], k), dtype=np.int64)
+    tptr, tsrc, tcell, trec, tval = (plan[n] for n in ('tptr', 'tsrc', 'tcell', 'trec', 'tval'))
+    for t in range(int(plan['src_ptr'][c0]), int(plan['src_ptr'][c1])):
+        s = int(tsrc[t]) - c0
+        assert 0 <= s < k
+        acc, m = 0j, 0.
+        for e in range(int(tptr[t]), int(tptr[t + 1])):
+            acc += tval[e] * panel[trec[e], s]
+            m += abs(tval[e]) * abs(panel[trec[e], s])
+        out[tcell[t], s], mag[tcell[t], s], cnt[tcell[t], s] = acc, m, tptr[t + 1] - tptr[t]
+    return out, mag, cnt
+
+
+def test_stacked_csr_is_the_vstack_of_the_per_source_matrices():
+    for name, sv, ifreqs in surveys():
+        for ifreq in ifreqs:
+            M = sv.stackedReceivers(ifreq)
+            ref = canonical(sp.vstack([canonical(sv.rVec(s, ifreq)) for s in range(sv.nsrc)]))
+            assert sp.isspmatrix_csr(M) and M.shape == ref.shape == (sv.nsrc * sv.nrec, sv.rVec(0, ifreq).shape[1])
+            assert np.array_equal(M.indptr, ref.indptr) and np.array_equal(M.indices, ref.indices), (name, ifreq)
+            assert np.array_equal(M.data, ref.data), (name, ifreq)                # to the bit
+            assert sv.stackedReceivers(ifreq) is M                                    # cached per grid key
+    _, sv, _ = surveys()[0]
+    assert np.all(np.diff(sv.stackedReceivers(0).indptr) == 81)                       # (2 ireg + 1)^2 entries per receiver, explicit zeros kept
+    _, mg, ifreqs = surveys()[1]
+    assert mg.stackedReceivers(ifreqs[0]).shape[1] != mg.stackedReceivers(ifreqs[-1]).shape[1]
+
+
+def test_adjoint_plan_on_g6_has_shared_cells():
+    _, sv, _ = surveys()[0]
+    plan = sv.adjointPlan(0)
+    nnz, ntouch = plan['tval'].size, plan['tsrc'].size
+    assert nnz == sv.stackedReceivers(0).nnz == 13 * 5 * 81
+    per = np.diff(plan['tptr'])
+    assert ntouch < nnz and per.max() >= 2 and per.min() == 1 and per.sum() == nnz           # receivers of a source overlap: the adjoint must SUM
+    assert plan['tptr'].dtype == np.int64 and plan['tsrc'].dtype == np.int32 and plan['tcell'].dtype == np.int64
+    assert plan['trec'].dtype == np.int32 and plan['tval'].dtype == np.complex128 and plan['src_ptr'].dtype == np.int64
+    assert plan['src_ptr'][0] == 0 and plan['src_ptr'][-1] == ntouch and np.all(np.diff(plan['src_ptr']) > 0)
+    # sorted by (source, cell), receivers ascending within a pair, no pair twice
+    key = plan['tsrc'].astype(np.int64) * plan['rows'] + plan['tcell']
+    assert np.all(np.diff(key) > 0)
+    for t in np.flatnonzero(per > 1)[:50]:
+        assert np.all(np.diff(plan['trec'][plan['tptr'][t]:plan['tptr'][t + 1]]) > 0)
+    assert sv.adjointPlan(0) is plan
+
+
+def test_plan_evaluated_in_numpy_matches_getResidualSources():
+    """same non-zero pattern, and every entry within 2 (L + 4) 3.3 u sum |val||resid| (L entries of the pair: a complex dot product of L terms, both sides'
+    rounding -- the bound form of tests/test_gpu_25d_device.py)"""
+    for name, sv, ifreqs in surveys():
+        rng = np.random.default_rng(12)
+        resid = rng.standard_normal((sv.nrec, sv.nsrc, sv.nfreq)) + 1j * rng.standard_normal((sv.nrec, sv.nsrc, sv.nfreq))
+        qb = sv.getResidualSources(resid)
+        for ifreq in ifreqs:
+            plan = sv.adjointPlan(ifreq)
+            ref = np.asarray(qb[ifreq].toarray())
+            assert ref.shape == (plan['rows'], sv.nsrc)
+            got, mag, cnt = plan_apply(plan, resid[:, :, ifreq], 0, sv.nsrc)
+            assert np.array_equal(got != 0, ref != 0), (name, ifreq)
+            assert np.count_nonzero(ref) > 0
+            bound = 2 * (cnt + 4) * 3.3 * U * mag
+            err = np.abs(got - ref)
+            assert (err <= bound).all(), (name, ifreq, float((err[bound > 0] / bound[bound > 0]).max()))
+            if name == 'multigrid':
+                assert cnt.max() >= 2                                     # overlapping patches off the nodes: sums of several nonzero terms
+
+
+def test_source_batches_are_sub_ranges():
+    _, sv, _ = surveys()[0]
+    rng = np.random.default_rng(13)
+    resid = rng.standard_normal((sv.nrec, sv.nsrc)) + 1j * rng.standard_normal((sv.nrec, sv.nsrc))
+    plan, M = sv.adjointPlan(0), sv.stackedReceivers(0)
+    full, _, _ = plan_apply(plan, resid, 0, sv.nsrc)
+    Ufield = rng.standard_normal((M.shape[1], sv.nsrc)) + 1j * rng.standard_normal((M.shape[1], sv.nsrc))
+    data = np.stack([sv.rVec(s) @ Ufield[:, s] for s in range(sv.nsrc)], axis=1)
+    nrec = sv.nrec
+    for c0, c1 in ((0, 6), (6, 13)):
+        part, _, _ = plan_apply(plan, np.ascontiguousarray(resid[:, c0:c1]), c0, c1)
+        assert np.array_equal(part, full[:, c0:c1])
+        # the CSR rows of the batch: indptr[c0 * nrec : c1 * nrec + 1], column and value arrays at their base
+        ptr = M.indptr[c0 * nrec:c1 * nrec + 1]
+        for s in range(c0, c1):
+            for r in range(nrec):
+                row = r + (s - c0) * nrec
+                e = slice(ptr[row], ptr[row + 1])
+                assert abs(M.data[e] @ Ufield[M.indices[e], s] - data[r, s]) <= 1e-12 * np.abs(data).max()
+
+
+def test_host_path_matches_the_reference_golden():
+    g, sc = g6_config(hostGradient=True)
+    g12 = np.load(os.path.join(GOLD, 'g12_moving_survey.npz'))
+    prob, sv = Helm2DProblem(sc), Helm2DSurvey(sc)
+    prob.pair(sv)
+    assert not prob._deviceGradientAvailable()
+    assert np.array_equal(g12['dpred'], g['dpred_relative'])
+    assert nrm(sv.dpred(), g12['dpred']) < 1e-10
+    gm = prob.Jtvec(None, g12['resid'])
+    assert np.iscomplexobj(gm) and nrm(gm, g12['g_mux']) < 1e-10
+    gu = prob.Jtvec(None, g12['resid'], u=prob.fields())
+    assert gu.dtype == np.float64 and nrm(gu, g12['g_u']) < 1e-10
+    with pytest.raises(ValueError):
+        prob.Jvec(None, np.ones(prob.nrow))                       # the reference's relative branch multiplies mismatched shapes
+
+
+def test_entry_points_refuse_bad_arguments_without_a_gpu(helm_lib):
+    assert 'helm_sample_rows_device' in _lib.exported_symbols() and 'helm_rhs_from_samples_device' in _lib.exported_symbols()
+    p = ctypes.c_void_p
+    fake_op, a, b = p(0x1000), p(0x2000), p(0x3000)              # never dereferenced: every call below must return before it looks at the handle
+    sr = helm_lib.helm_sample_rows_device
+    good = dict(op=fake_op, dU=a, nsrc=2, ld=8, rowptr=a, col=a, val=a, nrec=3, stride=3, out=b)
+
+    def sample(**kw):
+        v = dict(good, **kw)
+        return sr(v['op'], v['dU'], v['nsrc'], v['ld'], v['rowptr'], v['col'], v['val'], v['nrec'], v['stride'], 1., 0., 0., 0., v['out'])
+    for key in ('op', 'dU', 'rowptr', 'col', 'val', 'out'):
+        assert sample(**{key: None}) == -1, key
+    assert sample(nsrc=0) == -1 and sample(nrec=0) == -1 and sample(ld=0) == -1
+    assert sample(stride=2) == -1 and sample(stride=1) == -1 and sample(stride=-3) == -1          # 0 or at least nrec
+    rs = helm_lib.helm_rhs_from_samples_device
+    good2 = dict(op=fake_op, resid=a, ld=4, nrec=3, nsrc=4, src0=0, tptr=a, tsrc=a, tcell=a, trec=a, tval=a, ntouch=7, R=b, rows=100)
+
+    def rhs(**kw):
+        v = dict(good2, **kw)
+        return rs(v['op'], v['resid'], v['ld'], v['nrec'], v['nsrc'], v['src0'], v['tptr'], v['tsrc'], v['tcell'], v['trec'], v['tval'], v['ntouch'],
+                  v['R'], v['rows'])
+    for key in ('op', 'resid', 'tptr', 'tsrc', 'tcell', 'trec', 'tval', 'R'):
+        assert rhs(**{key: None}) == -1, key
+    assert rhs(op=None, ntouch=0) == -1 and rhs(R=None, ntouch=0) == -1 and rhs(resid=None, ntouch=0) == -1
+    assert rhs(nrec=0) == -1 and rhs(nsrc=0) == -1 and rhs(src0=-1) == -1 and rhs(ld=3) == -1 and rhs(rows=0) == -1 and rhs(ntouch=-1) == -1

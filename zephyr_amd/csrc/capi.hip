@@ -764,6 +764,37 @@ extern "C" int helm_sample_accumulate_device(helm_op *op, const void *dU, int ns
     return HELM_OK;
 }
 
+// helm_sample_accumulate_device with a row stride per source: source s samples CSR row r + s * row_stride (0: one array for all sources; >= nrec: the
+// per-source matrices of an array that moves with the source, stacked into one CSR of nsrc * row_stride rows)
+extern "C" int helm_sample_rows_device(helm_op *op, const void *dU, int nsrc, long long ld, const void *d_rowptr, const void *d_col, const void *d_val, int nrec,
+                                       long long row_stride, double alpha_re, double alpha_im, double beta_re, double beta_im, void *d_out) {
+    helm_tuning_refresh();
+    if (!op || !dU || !d_rowptr || !d_col || !d_val || !d_out || nsrc < 1 || nrec < 1 || ld < 1) return HELM_ERR_ARG;
+    if (row_stride != 0 && row_stride < nrec) return HELM_ERR_ARG;
+    HIP_TRY(op, hipSetDevice(op->device));
+    int rc = helm_launch_sample_acc(op, (const cplx *)dU, nsrc, ld, (const long long *)d_rowptr, (const long long *)d_col, (const cplx *)d_val, nrec,
+                                    cmake(alpha_re, alpha_im), cmake(beta_re, beta_im), (cplx *)d_out, row_stride);
+    if (rc) return rc;
+    HIP_TRY(op, hipStreamSynchronize(op->stream));
+    return HELM_OK;
+}
+
+// Back-sources R_s^T resid[:, s] of the sources src0 .. src0 + nsrc - 1 from the residual samples of one frequency (survey.py:171-188, the moving-array
+// branch): only the nrec x nsrc samples cross PCIe, the dense right-hand sides are made here.  The plan arrays are trusted (the caller validated them when it
+// built them: cells < rows, receivers < nrec, sources ascending within [src0, src0 + nsrc)).
+extern "C" int helm_rhs_from_samples_device(helm_op *op, const void *d_resid, long long ld_resid, int nrec, int nsrc, int src0, const void *d_tptr, const void *d_tsrc,
+                                            const void *d_tcell, const void *d_trec, const void *d_tval, long long ntouch, void *dR, long long rows) {
+    helm_tuning_refresh();
+    if (!op || !d_resid || !dR || nrec < 1 || nsrc < 1 || src0 < 0 || ld_resid < nsrc || rows < 1 || ntouch < 0) return HELM_ERR_ARG;
+    if (ntouch > 0 && (!d_tptr || !d_tsrc || !d_tcell || !d_trec || !d_tval)) return HELM_ERR_ARG;
+    HIP_TRY(op, hipSetDevice(op->device));
+    int rc = helm_launch_rhs_from_samples(op, (const cplx *)d_resid, ld_resid, nsrc, src0, (const long long *)d_tptr, (const int *)d_tsrc, (const long long *)d_tcell,
+                                          (const int *)d_trec, (const cplx *)d_tval, ntouch, (cplx *)dR, rows);
+    if (rc) return rc;
+    HIP_TRY(op, hipStreamSynchronize(op->stream));
+    return HELM_OK;
+}
+
 // Y = beta Y + alpha X over n complex128 values on the device (the ky accumulation of the 2.5-D composite; beta == 0: Y is not read).  Returns when Y is
 // complete: the next term of the sum is added on ANOTHER handle's stream.
 extern "C" int helm_axpby_device(helm_op *op, double alpha_re, double alpha_im, const void *dX, double beta_re, double beta_im, void *dY, long long n) {

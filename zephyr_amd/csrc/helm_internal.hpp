@@ -366,7 +366,9 @@ int helm_launch_zero(helm_op *op, cplx *p, long long n);
 int helm_launch_rhs_from_coo(helm_op *op, const long long *row, const int *col, const cplx *val, long long nnz, cplx *R, int nrhs, long long rows, int node_major = 0);
 int helm_launch_sample(helm_op *op, const cplx *U, int nsrc, long long ld, const long long *rowptr, const long long *col, const cplx *val, int nrec, cplx *out);
 int helm_launch_sample_acc(helm_op *op, const cplx *U, int nsrc, long long ld, const long long *rowptr, const long long *col, const cplx *val, int nrec,
-                           cplx alpha, cplx beta, cplx *out);                                  // out = beta out + alpha R u (beta == 0: out is not read)
+                           cplx alpha, cplx beta, cplx *out, long long row_stride = 0);        // out = beta out + alpha R u (beta == 0: out is not read); source s samples CSR row r + s * row_stride
+int helm_launch_rhs_from_samples(helm_op *op, const cplx *resid, long long ld, int nsrc, int src0, const long long *tptr, const int *tsrc, const long long *tcell,
+                                 const int *trec, const cplx *tval, long long ntouch, cplx *R, long long rows);      // R (nsrc x rows, zeroed here) from a gather plan over (source, cell) pairs
 int helm_launch_axpby(helm_op *op, cplx alpha, const cplx *X, cplx beta, cplx *Y, long long n);  // Y = beta Y + alpha X (beta == 0: Y is not read)
 int helm_launch_rowscale_inplace(helm_op *op, cplx *v, const double *rs, long long NV, int nrhs);
 int helm_launch_abs(helm_op *op, const cplx *in, cplx *out, long long n, double sign);      // out = sign |in|

@@ -944,42 +944,71 @@ int helm_launch_rhs_from_coo(helm_op *op, const long long *row, const int *col, 
     return HELM_OK;
 }
 
-// receiver sampling out[r][s] = sum_k val[k] U[s][col[k]] over the entries k of sparse row r (one thread per (r, s), fixed order)
+// receiver sampling out[r][s] = sum_k val[k] U[s][col[k]] over the entries k of sparse row r + s * row_stride (one thread per (r, s), fixed order).
+// row_stride = 0: one receiver array for every source; row_stride >= nrec: source s has rows [s * row_stride, s * row_stride + nrec) of its own (an array
+// that moves with the source, the per-source matrices stacked into one CSR).
 __global__ __launch_bounds__(256) void k_sample(const cplx *__restrict__ U, int nsrc, long long ld, const long long *__restrict__ rowptr,
-                                                const long long *__restrict__ col, const cplx *__restrict__ val, int nrec, cplx *__restrict__ out) {
+                                                const long long *__restrict__ col, const cplx *__restrict__ val, int nrec, long long row_stride,
+                                                cplx *__restrict__ out) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long long)nrec * nsrc) return;
     const int r = (int)(t / nsrc), sidx = (int)(t % nsrc);
+    const long long row = r + sidx * row_stride;
     cplx acc = cmake(0.0, 0.0);
-    for (long long k = rowptr[r]; k < rowptr[r + 1]; ++k) cfma(acc, val[k], U[(long long)sidx * ld + col[k]]);
+    for (long long k = rowptr[row]; k < rowptr[row + 1]; ++k) cfma(acc, val[k], U[(long long)sidx * ld + col[k]]);
     out[t] = acc;
 }
 int helm_launch_sample(helm_op *op, const cplx *U, int nsrc, long long ld, const long long *rowptr, const long long *col, const cplx *val, int nrec, cplx *out) {
     const long long tot = (long long)nrec * nsrc;
-    HELM_LAUNCH(k_sample, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, op->stream, U, nsrc, ld, rowptr, col, val, nrec, out);
+    HELM_LAUNCH(k_sample, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, op->stream, U, nsrc, ld, rowptr, col, val, nrec, 0LL, out);
     HIP_TRY(op, hipGetLastError());
     return HELM_OK;
 }
 
-// receiver sampling into an accumulator: out[r][s] = beta out[r][s] + alpha sum_k val[k] U[s][col[k]] (the ky sum of a 2.5-D survey's data: sampling is
-// linear, so the summed wavefields are never formed).  beta0: out is write-only -- an uninitialised accumulator is legal for the first term.
+// receiver sampling into an accumulator: out[r][s] = beta out[r][s] + alpha sum_k val[k] U[s][col[k]] over row r + s * row_stride (the ky sum of a 2.5-D
+// survey's data: sampling is linear, so the summed wavefields are never formed).  beta0: out is write-only -- an uninitialised accumulator is legal for
+// the first term.
 __global__ __launch_bounds__(256) void k_sample_acc(const cplx *__restrict__ U, int nsrc, long long ld, const long long *__restrict__ rowptr,
-                                                    const long long *__restrict__ col, const cplx *__restrict__ val, int nrec, cplx alpha, cplx beta, int beta0,
-                                                    cplx *__restrict__ out) {
+                                                    const long long *__restrict__ col, const cplx *__restrict__ val, int nrec, long long row_stride,
+                                                    cplx alpha, cplx beta, int beta0, cplx *__restrict__ out) {
     const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= (long long)nrec * nsrc) return;
     const int r = (int)(t / nsrc), sidx = (int)(t % nsrc);
+    const long long row = r + sidx * row_stride;
     cplx acc = cmake(0.0, 0.0);
-    for (long long k = rowptr[r]; k < rowptr[r + 1]; ++k) cfma(acc, val[k], U[(long long)sidx * ld + col[k]]);
+    for (long long k = rowptr[row]; k < rowptr[row + 1]; ++k) cfma(acc, val[k], U[(long long)sidx * ld + col[k]]);
     cplx o = cmul(alpha, acc);
     if (!beta0) cfma(o, beta, out[t]);
     out[t] = o;
 }
 int helm_launch_sample_acc(helm_op *op, const cplx *U, int nsrc, long long ld, const long long *rowptr, const long long *col, const cplx *val, int nrec,
-                           cplx alpha, cplx beta, cplx *out) {
+                           cplx alpha, cplx beta, cplx *out, long long row_stride) {
     const long long tot = (long long)nrec * nsrc;
     const int beta0 = (beta.x == 0.0 && beta.y == 0.0) ? 1 : 0;
-    HELM_LAUNCH(k_sample_acc, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, op->stream, U, nsrc, ld, rowptr, col, val, nrec, alpha, beta, beta0, out);
+    HELM_LAUNCH(k_sample_acc, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, op->stream, U, nsrc, ld, rowptr, col, val, nrec, row_stride, alpha, beta, beta0, out);
+    HIP_TRY(op, hipGetLastError());
+    return HELM_OK;
+}
+
+// Back-sources of a receiver array that moves with the source, R[s - src0][cell] = sum_r R_s[r][cell] resid[r][s - src0], as a GATHER over the touched
+// (source, cell) pairs: pair t owns the entries tptr[t] .. tptr[t+1] of (trec, tval), ordered by receiver, and is written by exactly one thread in that
+// order.  Receivers of one source share cells (their patches overlap), so a scatter over the entries would need atomics and the sum would depend on
+// their order; this one is the same bits on every run.  resid: [nrec][ld], column s - src0 belongs to source s.  R: [nsrc][rows], zeroed by the launcher.
+__global__ __launch_bounds__(256) void k_rhs_from_samples(const cplx *__restrict__ resid, long long ld, int src0, const long long *__restrict__ tptr,
+                                                          const int *__restrict__ tsrc, const long long *__restrict__ tcell, const int *__restrict__ trec,
+                                                          const cplx *__restrict__ tval, long long ntouch, cplx *__restrict__ R, long long rows) {
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < ntouch; t += (long long)gridDim.x * blockDim.x) {
+        const int s = tsrc[t] - src0;
+        cplx acc = cmake(0.0, 0.0);
+        for (long long e = tptr[t]; e < tptr[t + 1]; ++e) cfma(acc, tval[e], resid[(long long)trec[e] * ld + s]);
+        R[(long long)s * rows + tcell[t]] = acc;
+    }
+}
+int helm_launch_rhs_from_samples(helm_op *op, const cplx *resid, long long ld, int nsrc, int src0, const long long *tptr, const int *tsrc, const long long *tcell,
+                                 const int *trec, const cplx *tval, long long ntouch, cplx *R, long long rows) {
+    HIP_TRY(op, hipMemsetAsync(R, 0, (size_t)nsrc * rows * sizeof(cplx), op->stream));
+    if (ntouch > 0) HELM_LAUNCH(k_rhs_from_samples, dim3((unsigned)std::min<long long>((ntouch + 255) / 256, 65535)), dim3(256), 0, op->stream,
+                                resid, ld, src0, tptr, tsrc, tcell, trec, tval, ntouch, R, rows);
     HIP_TRY(op, hipGetLastError());
     return HELM_OK;
 }

@@ -328,11 +328,32 @@ class BaseDiscretization(BaseModelDependent):
         return bits
 
     def sampleDevice(self, d_u, nsrc, csr_dev, d_out):
-        'd_out[nrec][nsrc] = R u for the CSR receiver matrix uploaded by the caller: csr_dev = (rowptr, col, val, nrec) device tensors'
-        rowptr, col, val, nrec = csr_dev
-        _lib.check(_lib.load().helm_sample_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), int(self.nrow), ctypes.c_void_p(rowptr.data_ptr()),
-                                                  ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()), int(nrec),
-                                                  ctypes.c_void_p(d_out)), self.handle)
+        """d_out[nrec][nsrc] = R u for the CSR receiver matrix uploaded by the caller: csr_dev = (rowptr, col, val, nrec[, row_stride]) device tensors.
+        row_stride (default 0: one array for every source) = nrec: source s samples row s * nrec + r of the stacked matrices of a moving array
+        (survey.stackedReceivers; `rowptr` then starts at the first source of the batch)."""
+        rowptr, col, val, nrec = csr_dev[:4]
+        stride = int(csr_dev[4]) if len(csr_dev) > 4 else 0
+        lib = _lib.load()
+        if stride == 0:
+            _lib.check(lib.helm_sample_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), int(self.nrow), ctypes.c_void_p(rowptr.data_ptr()),
+                                              ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()), int(nrec),
+                                              ctypes.c_void_p(d_out)), self.handle)
+        else:
+            _lib.check(lib.helm_sample_rows_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), int(self.nrow), ctypes.c_void_p(rowptr.data_ptr()),
+                                                   ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()), int(nrec), stride,
+                                                   1.0, 0.0, 0.0, 0.0, ctypes.c_void_p(d_out)), self.handle)
+
+    def rhsFromSamplesDevice(self, d_resid, ld, plan_dev, c0, c1, d_rhs, rows=None):
+        """Fill the device buffer d_rhs ([c1 - c0][rows] complex128) with the back-sources R_s^T resid[:, s] of the sources c0 .. c1-1 of a moving receiver
+        array.  d_resid: device pointer to the residual samples of one frequency, [nrec][ld] with column s - c0 that of source s; plan_dev: the survey's
+        adjointPlan with its arrays as device tensors (src_ptr stays on the host).  Only the samples cross PCIe."""
+        t0, t1 = int(plan_dev['src_ptr'][c0]), int(plan_dev['src_ptr'][c1])
+        rows = int(self.nrow if rows is None else rows)
+        _lib.check(_lib.load().helm_rhs_from_samples_device(
+            self.handle, ctypes.c_void_p(d_resid), int(ld), int(plan_dev['nrec']), int(c1 - c0), int(c0),
+            ctypes.c_void_p(plan_dev['tptr'].data_ptr() + 8 * t0), ctypes.c_void_p(plan_dev['tsrc'].data_ptr() + 4 * t0),
+            ctypes.c_void_p(plan_dev['tcell'].data_ptr() + 8 * t0), ctypes.c_void_p(plan_dev['trec'].data_ptr()),
+            ctypes.c_void_p(plan_dev['tval'].data_ptr()), t1 - t0, ctypes.c_void_p(d_rhs), rows), self.handle)
 
     def setProfiling(self, on=True):
         'time every stencil-apply launch of subsequent solves with HIP events on the solver stream'

@@ -185,6 +185,9 @@ class MiniZephyr25D(BaseDiscretization, DiscretizationWrapper):
     def rhsFromSparseDevice(self, q, d_rhs, layout='rhs'):
         return self.subProblems[0].rhsFromSparseDevice(q, d_rhs, layout=layout)         # (the right-hand sides are the same for all ky)
 
+    def rhsFromSamplesDevice(self, d_resid, ld, plan_dev, c0, c1, d_rhs, rows=None):
+        return self.subProblems[0].rhsFromSamplesDevice(d_resid, ld, plan_dev, c0, c1, d_rhs, rows=rows)
+
     def rhsSupportFromSparse(self, q):
         return self.subProblems[0].rhsSupportFromSparse(q)
 
@@ -237,21 +240,23 @@ class MiniZephyr25D(BaseDiscretization, DiscretizationWrapper):
         return infos
 
     def sampleSumDevice(self, d_rhs, nrhs, csr_dev, d_out, rows=None):
-        """d_out[nrec][nrhs] = scaleTerm * sum_ky R u_ky for the receiver CSR csr_dev = (rowptr, col, val, nrec) (device tensors; right-hand sides in layout
-        'rhs'): sampling is linear, so each ky's samples are accumulated and the summed wavefields are never formed."""
+        """d_out[nrec][nrhs] = scaleTerm * sum_ky R u_ky for the receiver CSR csr_dev = (rowptr, col, val, nrec[, row_stride]) (device tensors, as for
+        BaseDiscretization.sampleDevice; right-hand sides in layout 'rhs'): sampling is linear, so each ky's samples are accumulated and the summed
+        wavefields are never formed."""
         import torch
         lib = _lib.load()
         rows = int(self.nrow if rows is None else rows)
-        rowptr, col, val, nrec = csr_dev
+        rowptr, col, val, nrec = csr_dev[:4]
+        stride = int(csr_dev[4]) if len(csr_dev) > 4 else 0
         scratch = torch.empty(rows * int(nrhs), dtype=torch.complex128, device=torch.device('cuda', self.device))
         infos = []
 
         def each(k, sub):
             infos.append(sub.solveDevice(d_rhs, scratch.data_ptr(), nrhs, rows))
             a, b = self._kyCoefficients(k)
-            _lib.check(lib.helm_sample_accumulate_device(sub.handle, ctypes.c_void_p(scratch.data_ptr()), int(nrhs), rows, ctypes.c_void_p(rowptr.data_ptr()),
-                                                         ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()), int(nrec), a.real, a.imag, b.real, b.imag,
-                                                         ctypes.c_void_p(d_out)), sub.handle)
+            _lib.check(lib.helm_sample_rows_device(sub.handle, ctypes.c_void_p(scratch.data_ptr()), int(nrhs), rows, ctypes.c_void_p(rowptr.data_ptr()),
+                                                   ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()), int(nrec), stride, a.real, a.imag, b.real, b.imag,
+                                                   ctypes.c_void_p(d_out)), sub.handle)
         self._kyLoop(each)
         self.lastInfo = infos
         return infos

@@ -36,6 +36,34 @@ def _norm2(d):
     return float(np.sqrt(np.add.reduce(np.square(d.real)) + (np.add.reduce(np.square(d.imag)) if np.iscomplexobj(d) else 0.0)))
 
 
+def _muxTriplets(mats, c0, c1, rows):
+    """(row, col, val, shape) of [m_0[:, c0:c1] | m_1[:, c0:c1] | ...] from the matrices' own arrays (no format conversion, no sort of 10^5..10^6 entries):
+    what rhsFromSparseDevice takes as triplets"""
+    k = c1 - c0
+    parts = []
+    for j, m in enumerate(mats):
+        mc = m if (c0 == 0 and c1 == m.shape[1]) else sp.csc_matrix(m)[:, c0:c1]
+        if not (sp.isspmatrix_csr(mc) or sp.isspmatrix_csc(mc)) or not mc.has_canonical_format:
+            mc = sp.csr_matrix(mc)
+            mc.sum_duplicates()
+        coo = mc.tocoo(copy=False)
+        parts.append((coo.row, coo.col + j * k, coo.data))
+    return (np.concatenate([p_[0] for p_ in parts]), np.concatenate([p_[1] for p_ in parts]), np.concatenate([p_[2] for p_ in parts]), (rows, len(parts) * k))
+
+
+def _planOnDevice(state, sv, ifreq, dev):
+    'the survey\'s adjoint plan of frequency ifreq\'s grid with its arrays on `dev`: uploaded once per worker and grid key'
+    plans = state.setdefault('plans', {})
+    gk = sv._gridKey(ifreq)
+    if gk not in plans:
+        plan = sv.adjointPlan(ifreq)
+        pd = dict(plan)
+        for name in ('tptr', 'tsrc', 'tcell', 'trec', 'tval'):
+            pd[name] = _lib.to_device(plan[name], dev)
+        plans[gk] = pd
+    return plans[gk]
+
+
 class HelmBaseProblem(BaseModelDependent, BaseSCCache):
 
     initMap = {
@@ -251,13 +279,19 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         sv = self.survey
         nsrc = sv.nsrc
         resid = np.asarray(v).reshape((sv.nrec, sv.nsrc, sv.nfreq))
-        qb = sv.getResidualSources(resid)
         owned = self.ownedFreqs
-        g = np.zeros(self.nrow, dtype=np.complex128)
         if u is None and self._deviceGradientAvailable():
+            # a fixed array keeps its host-built back-sources (sparse, sent up as triplets); those of an array that moves with the source are made on the
+            # device from the residual samples (helm_rhs_from_samples_device): qb = None
+            qb = sv.getResidualSources(resid) if sv.mode == 'fixed' else None
+            if qb is None:
+                for ifreq in owned:                           # (the survey's cached plans are made here, not by two worker threads at once)
+                    sv.adjointPlan(ifreq)
             if isinstance(sv, HelmMultiGridSurvey):
-                return self._JtvecDeviceMultiGrid(qb, owned)
-            return self._JtvecDevice(qb, owned)
+                return self._JtvecDeviceMultiGrid(qb, owned, resid)
+            return self._JtvecDevice(qb, owned, resid)
+        qb = sv.getResidualSources(resid)
+        g = np.zeros(self.nrow, dtype=np.complex128)
         if u is None:
             qf = sv.getSources()
             qm = [sp.hstack((qf[i], qb[i])) if i in owned else None for i in range(sv.nfreq)]
@@ -296,10 +330,25 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         except Exception:
             return False
 
-    def _JtvecDevice(self, qb, owned):
+    def _fillMuxDevice(self, state, op, dev, qf_i, qb_i, resid, ifreq, c0, c1, d_R, rows):
+        """d_R ([2k][rows], k = c1 - c0) = [qf | qb] of the sources c0 .. c1-1 of frequency ifreq.  qb_i given (fixed array): both halves as sparse triplets.
+        qb_i None (the array moves with the source): the qf half from triplets, the qb half by the gather of the survey's adjoint plan from the item's
+        residual samples resid[:, c0:c1, ifreq] -- 16 nrec k bytes up instead of ~81 entries of 28 B per sample, and no sparse products on the host."""
+        k = c1 - c0
+        if qb_i is not None:
+            op.rhsFromSparseDevice(_muxTriplets((qf_i, qb_i), c0, c1, rows), d_R)
+            return
+        op.rhsFromSparseDevice(_muxTriplets((qf_i,), c0, c1, rows), d_R)
+        plan = _planOnDevice(state, self.survey, ifreq, dev)
+        panel = _lib.to_device(resid[:, c0:c1, ifreq], dev, np.complex128)       # (nrec, k), one contiguous panel
+        _lib.wait_torch_stream(dev)
+        op.rhsFromSamplesDevice(panel.data_ptr(), k, plan, c0, c1, d_R + k * rows * 16, rows=rows)
+
+    def _JtvecDevice(self, qb, owned, resid=None):
         '''mux branch with wavefields kept in HBM: per work item (frequency, source batch) upload [qf | qb] of its sources, solve them on
         the item's GPU, accumulate scaler * sum_s uF (.) uB with the imaging kernel into that GPU's partial gradient; partial gradients are
-        summed on the host, then ONE all-reduce over ranks when the frequencies are sharded.'''
+        summed on the host, then ONE all-reduce over ranks when the frequencies are sharded.  qb None: the back-sources of a moving receiver
+        array, made on the device from `resid` (nrec, nsrc, nfreq).'''
         import torch
         sv = self.survey
         nsrc, N = sv.nsrc, self.nrow
@@ -324,17 +373,9 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
                 state['R'] = torch.empty((2 * k, N), dtype=torch.complex128, device=dev)
                 state['cap'] = 2 * k
             U, R = state['U'], state['R']
-            # [qf | qb] of the item's sources as triplets, made from the two matrices' own arrays (no format conversion, no sort of 10^5..10^6 entries)
-            parts = []
-            for off, m in ((0, qf[ifreq] if isinstance(qf, (list, tuple)) else qf), (k, qb[ifreq])):
-                mc = m if (c0 == 0 and c1 == m.shape[1]) else sp.csc_matrix(m)[:, c0:c1]
-                if not (sp.isspmatrix_csr(mc) or sp.isspmatrix_csc(mc)) or not mc.has_canonical_format:
-                    mc = sp.csr_matrix(mc)
-                    mc.sum_duplicates()
-                coo = mc.tocoo(copy=False)
-                parts.append((coo.row, coo.col + off, coo.data))
-            trip = (np.concatenate([p_[0] for p_ in parts]), np.concatenate([p_[1] for p_ in parts]), np.concatenate([p_[2] for p_ in parts]), (N, 2 * k))
-            op.rhsFromSparseDevice(trip, R.data_ptr())      # sparse triplets up, dense on the device
+            # [qf | qb] of the item's sources: sparse triplets (or residual samples) up, dense on the device
+            self._fillMuxDevice(state, op, dev, qf[ifreq] if isinstance(qf, (list, tuple)) else qf, None if qb is None else qb[ifreq], resid, ifreq, c0, c1,
+                                R.data_ptr(), N)
             if plain_scaler:
                 # -(omega^2 / c^3) scale^2 on the GPU from one upload of the model per worker: on the host the complex power and division of problem.py:74-81 cost
                 # 6 ms per frequency at 512^2 (numpy), in the thread whose only other job is to keep the solve stream fed
@@ -366,7 +407,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             g += _lib.from_device(G)
         return parallel.allreduce_sum(g) if self._sharded else g
 
-    def _JtvecDeviceMultiGrid(self, qb, owned):
+    def _JtvecDeviceMultiGrid(self, qb, owned, resid=None):
         """mux branch of a multiscale survey with wavefields kept in HBM.  Per work item: [qf | qb] of its sources solved on the frequency's
         own grid, the imaging sum P = scaleTerm^2 sum_s uF (.) uB accumulated there, then G += pp(scaler) (.) pp(P) in one grid transfer
         (problem.py:152: the product of two up-scaled fields), the up-scaled scaler -(omega^2 / c^3) made once per frequency from the
@@ -398,16 +439,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
                 state['pcap'] = Ni
             U, R = state['U'], state['R']
             P, unit = state['P'][:Ni], state['unit'][:Ni]
-            parts = []
-            for off, m in ((0, qf[ifreq]), (k, qb[ifreq])):
-                mc = m if (c0 == 0 and c1 == m.shape[1]) else sp.csc_matrix(m)[:, c0:c1]
-                if not (sp.isspmatrix_csr(mc) or sp.isspmatrix_csc(mc)) or not mc.has_canonical_format:
-                    mc = sp.csr_matrix(mc)
-                    mc.sum_duplicates()
-                coo = mc.tocoo(copy=False)
-                parts.append((coo.row, coo.col + off, coo.data))
-            trip = (np.concatenate([p_[0] for p_ in parts]), np.concatenate([p_[1] for p_ in parts]), np.concatenate([p_[2] for p_ in parts]), (Ni, 2 * k))
-            op.rhsFromSparseDevice(trip, R.data_ptr())
+            self._fillMuxDevice(state, op, dev, qf[ifreq], None if qb is None else qb[ifreq], resid, ifreq, c0, c1, R.data_ptr(), Ni)
             # the up-scaled gradient scaler of this frequency (one per worker and frequency)
             scalers = state.setdefault('scalers', {})
             if ifreq not in scalers:
@@ -440,8 +472,9 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         return parallel.allreduce_sum(g) if self._sharded else g
 
     def _dpredDevice(self, owned):
-        '''predicted data with the wavefields kept in HBM (fixed receiver array): per work item (frequency, source batch) the sparse sources are
-        expanded on the item's GPU, solved there, and only the receiver samples R u (nrec x sources) come back'''
+        '''predicted data with the wavefields kept in HBM: per work item (frequency, source batch) the sparse sources are expanded on the item's GPU,
+        solved there, and only the receiver samples R u (nrec x sources) come back.  A receiver array that moves with the source is sampled through
+        the survey's stacked CSR, source s from its own rows s * nrec .. (row stride nrec); a fixed one through the one matrix (stride 0).'''
         import torch
         sv = self.survey
         nsrc, nrec, N = sv.nsrc, sv.nrec, self.nrow
@@ -450,12 +483,17 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if not owned:
             return data
         multi = isinstance(sv, HelmMultiGridSurvey)
+        moving = sv.mode != 'fixed'
+        stride = nrec if moving else 0
         Rms = {}
         for ifreq in (owned if multi else owned[:1]):       # one receiver CSR per grid (a multiscale survey: per distinct scale)
             gk = sv._gridKey(ifreq)
             if gk not in Rms:
-                Rm = sp.csr_matrix(sv.rVec(0, ifreq))
-                Rm.sum_duplicates()
+                if moving:
+                    Rm = sv.stackedReceivers(ifreq)
+                else:
+                    Rm = sp.csr_matrix(sv.rVec(0, ifreq))
+                    Rm.sum_duplicates()
                 Rms[gk] = Rm
         qf = sv.getSources()
         devs, items = self._deviceItems(owned, nsrc)
@@ -494,6 +532,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
                     state['out'] = torch.empty((nrec, k), dtype=torch.complex128, device=dev)
                     state['cap'] = k
                 R, U = state['Rf'][:k * Ni], state['Uf'][:k * Ni]
+            if moving:                                        # the rows of this batch's sources start at c0 * nrec
+                csr = (csr[0][c0 * nrec:], csr[1], csr[2], nrec, stride)
             out = state['out'] if state['cap'] == k else torch.empty((nrec, k), dtype=torch.complex128, device=dev)
             q = qf[ifreq] if isinstance(qf, (list, tuple)) else qf
             op.rhsFromSparseDevice(sp.csc_matrix(q)[:, c0:c1], R.data_ptr())

@@ -111,6 +111,56 @@ class HelmBaseSurvey(BaseSCCache):
         'which cached vectors frequency ifreq uses (None: the one grid of this survey)'
         return None
 
+    def _weightedColumnsOn(self, ifreq, locs, terms):
+        '_weightedColumns on the grid of frequency ifreq (one grid for every frequency here)'
+        return self._weightedColumns(locs, terms)
+
+    # ---- a moving array as ONE matrix: what the device paths of problem.py upload ---------------------------------
+    def stackedReceivers(self, ifreq=0):
+        """The receiver matrices of every source in one CSR, (nsrc * nrec, N): row s * nrec + r is row r of rVec(s).  Made by ONE call of the generator
+        rVec uses, on the concatenated locations -- the same entries to the bit, so whatever the host path does with a location (clipping at the edges,
+        a free surface) is what the device samples.  One per grid key; the rows of the sources c0 .. c1-1 are the contiguous range
+        indptr[c0 * nrec : c1 * nrec + 1]."""
+        cache = self.__dict__.setdefault('_vecCache', {})
+        key = ('Rstack', self._gridKey(ifreq))
+        if key not in cache:
+            moving = self.mode != 'fixed'
+            where = np.concatenate([self.rLocs + self.sLocs[s] if moving else self.rLocs for s in range(self.nsrc)])
+            M = sp.csr_matrix(self._weightedColumnsOn(ifreq, where, np.tile(self.srTerms, self.nsrc)).T)
+            M.sum_duplicates()
+            cache[key] = M
+        return cache[key]
+
+    def adjointPlan(self, ifreq=0):
+        """getResidualSources as a gather: the entries of stackedReceivers sorted by (source, cell, receiver) and grouped into the touched (source, cell)
+        pairs.  A dict of
+            tptr (ntouch + 1, int64)   entries tptr[t] .. tptr[t+1] of trec / tval belong to pair t
+            tsrc (ntouch, int32), tcell (ntouch, int64)   the pair's source and grid cell
+            trec (nnz, int32), tval (nnz, complex128)     receiver and weight of every entry, by receiver within a pair
+            src_ptr (nsrc + 1, int64)  pairs src_ptr[c0] .. src_ptr[c1] are those of the sources c0 .. c1-1: a batch is a sub-range, nothing is copied
+        so that  qb[cell, s] = sum_e tval[e] resid[trec[e], s]  over the entries of pair (s, cell), summed in stored order (receivers of one source share
+        cells: the patches of neighbours overlap).  Validated here -- helm_rhs_from_samples_device trusts it."""
+        cache = self.__dict__.setdefault('_vecCache', {})
+        key = ('Rplan', self._gridKey(ifreq))
+        if key not in cache:
+            M = self.stackedReceivers(ifreq)
+            nrec, nsrc, N = self.nrec, self.nsrc, M.shape[1]
+            row = np.repeat(np.arange(M.shape[0], dtype=np.int64), np.diff(M.indptr))
+            src, rec, cell = row // nrec, row % nrec, M.indices.astype(np.int64)
+            order = np.lexsort((rec, cell, src))                 # by source, then cell, then receiver
+            src, rec, cell, val = src[order], rec[order], cell[order], M.data[order]
+            first = np.ones(src.size, dtype=bool)
+            first[1:] = (src[1:] != src[:-1]) | (cell[1:] != cell[:-1])
+            starts = np.flatnonzero(first)
+            plan = dict(tptr=np.append(starts, src.size).astype(np.int64), tsrc=src[starts].astype(np.int32), tcell=cell[starts].astype(np.int64),
+                        trec=rec.astype(np.int32), tval=np.ascontiguousarray(val, dtype=np.complex128), nrec=nrec, nsrc=nsrc, rows=N)
+            plan['src_ptr'] = np.searchsorted(plan['tsrc'], np.arange(nsrc + 1)).astype(np.int64)
+            if src.size and not (0 <= cell.min() and cell.max() < N and 0 <= rec.min() and rec.max() < nrec and 0 <= src.min() and src.max() < nsrc
+                                 and np.all(np.diff(plan['tsrc']) >= 0) and np.all(np.diff(plan['tptr']) >= 1)):
+                raise ValueError('adjoint plan of the receiver array addresses cells, receivers or sources outside the survey')
+            cache[key] = plan
+        return cache[key]
+
     # ---- hot-path pieces ------------------------------------------------------------------------------
     def getSources(self):
         'per-frequency source matrices qf[f] = S diag(ssTerms) conj(tsTerms[f]) (survey.py:162-169)'
@@ -179,7 +229,7 @@ class HelmBaseSurvey(BaseSCCache):
             raise Exception('%s instance is not paired to a problem' % (self.__class__.__name__,))
         if u is None:
             owned = self.prob.ownedFreqs
-            if self.mode == 'fixed' and sp.issparse(self.sVecs(0)) and self.prob._deviceGradientAvailable():
+            if sp.issparse(self.sVecs(0)) and self.prob._deviceGradientAvailable():
                 self.prob.updateModel(m)
                 data = self.prob._dpredDevice(owned)          # wavefields never leave HBM
             else:
