@@ -443,6 +443,49 @@ typedef struct helm_zgemm_ex {
     int report[5];                       /* out: as helm_debug_zgemm_choice, for the launch that was made */
 } helm_zgemm_ex;
 int helm_debug_zgemm_ex(helm_zgemm_ex *p);
+/* (test hook) One stage of the node-major plumbing around the direct solver's passes (zephyr_amd/csrc/nd_resid.hip) on host data, through the launchers the
+ * solver itself calls: the lane / row-group choice, the loop over chunks of 256 columns, the offsets of the partial sums and their reduction are the code under
+ * test.  Complex operands are (re, im) pairs of doubles and every length counts complex elements.  The handle is a temporary one for an (nz, nx) grid.
+ * Everything a stage may write is copied back whole (padding included), so the caller can see what was left alone.  Malformed input is refused with
+ * HELM_ERR_ARG before a device is touched.  The buffers by stage:
+ *   RESID          r = q' - A x on nz * nx cells with the nine planes given (not assembled): Xin[cell * ldin + j], Q[cell * ldq + map(j)], j < ncol; qmap (ncol
+ *                  entries below ldq, distinct when r is stored) or NULL; store: r to Rout (same indexing as Q; NULL: over Q); Uout[cell * ldu + j] =
+ *                  conj(oscale x); qmask: one byte per cell, bit b = block b of 64 columns may hold a nonzero (not with qmap); xin_is_u: Xin holds
+ *                  u = conj(oscale x) and q' = oscale q.  Out: rr[ncol] = ||r||^2, qq[ncol] = ||q'||^2 when qnorm, reduced as true_residual_norms
+ *                  (solve_direct.hip) does; report = {lanes, row groups, workgroups, launches, tiles}.
+ *   PREP           Rout[i * ncol + r] = oscale * Xin[r * rhs_ld + row_off + i] - Q[r * N + i] (Q: the `sub` operand, NULL for none) for ncol right-hand
+ *                  sides of N rows; qq[ncol] = ||.||^2; report[2] = workgroups along the rows, [4] = tiles of 32 rows.
+ *   PACK           Rout[cell * ncol + j] = Xin[cell * ldin + qmap[j]], N cells, ncol = k columns
+ *   SCATTER_ADD    Q[cell * ldq + qmap[j]] += Xin[cell * ncol + j] (qmap distinct)
+ *   RECOVER_X      Rout[i] = conj(Xin[i]) / oscale, N * ncol elements
+ *   TRANSPOSE_OUT  Xin (N x ncol) -> Rout (ncol x N), conjugated when conj
+ *   TRANSPOSE      the same through nd_transpose (the branch goes by N > ncol)
+ * nblk_cap (RESID, PREP): partial sums per column the launch may use; 0: what the solver passes, max(2 helm_apply_num_blocks, helm_vec_num_blocks). */
+#define HELM_NM_RESID         0
+#define HELM_NM_PREP          1
+#define HELM_NM_PACK          2
+#define HELM_NM_SCATTER_ADD   3
+#define HELM_NM_RECOVER_X     4
+#define HELM_NM_TRANSPOSE_OUT 5
+#define HELM_NM_TRANSPOSE     6
+typedef struct helm_nm_stage {
+    int device, stage, nz, nx;
+    long long N;                         /* rows of every stage but RESID (which has nz * nx) */
+    int ncol, nblk_cap;
+    const double *planes; long long planes_len;
+    const double *Xin; long long xin_len; int ldin;
+    double *Q; long long q_len; int ldq;
+    const int *qmap;
+    int store, qnorm, xin_is_u, conj;
+    double *Rout; long long rout_len;
+    double *Uout; long long uout_len; int ldu;
+    double oscale[2];                    /* RESID, RECOVER_X: oscale; PREP: premul */
+    const unsigned char *qmask;
+    long long rhs_ld, row_off;           /* PREP */
+    double *rr, *qq;                     /* out, ncol doubles each */
+    int report[5];                       /* out */
+} helm_nm_stage;
+int helm_debug_nm_stage(helm_nm_stage *p);
 int helm_debug_inverse_bench(int device, int n, const double *A, int reps, int recurse_n, double *ms_out);
 
 /* --- diagnostics of the 3-D multigrid hierarchy (host only, no GPU needed; zephyr_amd/csrc/mg3d.hip) ------------------ */

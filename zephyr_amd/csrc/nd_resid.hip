@@ -1,6 +1,7 @@
 // Direct solver, node-major plumbing around the passes: layout transposes, the right-hand-side preparation, and the TRUE residual
 // q' - A x of the returned wavefields evaluated with the 9-point stencil (what makes the direct path's result a checked one).
 #include "nd_internal.hpp"
+#include "solve_internal.hpp"      // helm_launch_fin_ex, ensure_part (the test hook reduces as true_residual_norms does)
 
 namespace {
 
@@ -303,6 +304,9 @@ __global__ void k_axpy_one(cplx *y, const cplx *x, long long n, int conj) {
         y[i] = cadd(y[i], conj ? cconj(x[i]) : x[i]);
 }
 
+// helm_debug_nm_stage: where nd_resid_nm leaves {lanes, row groups, workgroups, launches, tiles} of the launches it made (null outside the hook)
+int *g_nm_report = nullptr;
+
 }  // namespace
 
 void launch_transpose(hipStream_t st, const cplx *in, long long rows, long long cols, cplx *out, int swap, int conj) {
@@ -343,6 +347,7 @@ int nd_resid_nm(helm_op *op, const cplx *planes, const cplx *Xin, int ldin, cplx
         if (op->ev_used + 2 <= op->ev_pool.size()) { e0 = op->ev_pool[op->ev_used]; e1 = op->ev_pool[op->ev_used + 1]; }
     }
     if (e0) hipEventRecord(e0, op->stream);
+    if (g_nm_report) { g_nm_report[0] = lx; g_nm_report[1] = ly; g_nm_report[2] = nblk; g_nm_report[3] = (ncol + 255) / 256; g_nm_report[4] = ntiles; }
     for (int c0 = 0; c0 < ncol; c0 += 256) {          // more than 256 columns: one launch per 256 (partials of later chunks follow the first)
         const int nc = std::min(256, ncol - c0);
         if (ly == 1)        // full-width batches: four waves share a tile, its coefficients staged in LDS; the wavefield (read by nobody on the GPU) stored nontemporally
@@ -404,3 +409,163 @@ int nd_axpy_one(helm_op *op, cplx *y, const cplx *x, long long n, int conj) {
     return HELM_OK;
 }
 
+
+// ---- test hook ------------------------------------------------------------------------------------------------------------------------------------
+namespace {
+// The hook's handle at the caller's grid from here to the end of the scope.  helm_create wants three nodes along each axis, so the handle is made at
+// max(nz, 3) x max(nx, 3) and its size fields are the caller's while a stage runs.  What the stages read of them, and nothing else of the handle's grid:
+//   nd_resid_nm                                   op->nz, op->nx (tile count, kernel arguments); op->N (bytes of a timing record, profiling only)
+//   helm_apply_num_blocks, helm_vec_num_blocks    op->nz, op->nx, op->ny; op->Nv, op->N -- through them ensure_part and the hook's own nblk_solver
+//   the other nd_* launchers, helm_launch_fin_ex  none: their sizes are arguments
+// Nothing allocated under the guard is sized by these fields on release: ensure_part keeps the byte count it allocated (op->part_bytes, scal_cap,
+// h_scal_bytes) and helm_destroy frees by those.  The destructor runs before helm_destroy, which sees the grid helm_create made.
+struct NmGridGuard {
+    helm_op *op; int nz, nx; long long N, Nv;
+    NmGridGuard(helm_op *o, int gz, int gx) : op(o), nz(o->nz), nx(o->nx), N(o->N), Nv(o->Nv) { o->nz = gz; o->nx = gx; o->N = o->Nv = (long long)gz * gx; }
+    ~NmGridGuard() { op->nz = nz; op->nx = nx; op->N = N; op->Nv = Nv; }
+    NmGridGuard(const NmGridGuard &) = delete;
+    NmGridGuard &operator=(const NmGridGuard &) = delete;
+};
+
+// k column indices below ld (and, where a stage writes through them, no two the same); returns the largest, or -1
+long long nm_cols_max(const int *c, int k, long long ld, bool distinct) {
+    if (!c || ld <= 0 || ld > (1LL << 24)) return -1;
+    std::vector<char> seen(distinct ? (size_t)ld : 0, 0);
+    long long mx = -1;
+    for (int j = 0; j < k; ++j) {
+        if (c[j] < 0 || c[j] >= ld) return -1;
+        if (distinct) { if (seen[c[j]]) return -1; seen[c[j]] = 1; }
+        mx = std::max<long long>(mx, c[j]);
+    }
+    return mx;
+}
+bool nm_flag(int v) { return v == 0 || v == 1; }
+
+// host-side check of a helm_nm_stage: every address the stage can form lies inside a buffer the caller handed in
+bool nm_stage_ok(const helm_nm_stage &p) {
+    if (p.device < 0 || p.nz <= 0 || p.nx <= 0 || p.ncol <= 0 || p.nblk_cap < 0) return false;
+    if ((long long)p.nz * p.nx > (1LL << 24) || p.ncol > (1 << 16)) return false;
+    if (!nm_flag(p.store) || !nm_flag(p.qnorm) || !nm_flag(p.xin_is_u) || !nm_flag(p.conj)) return false;
+    const long long k = p.ncol;
+    if (p.stage == HELM_NM_RESID) {
+        const long long N = (long long)p.nz * p.nx;
+        if (!p.planes || p.planes_len < 9 * N || !p.rr || (p.qnorm && !p.qq)) return false;
+        if (!p.Xin || p.ldin < k || p.xin_len < (N - 1) * p.ldin + k) return false;
+        if (p.qmask && p.qmap) return false;
+        long long qw = k;                                    // columns of Q the stage reaches
+        if (p.qmap) { qw = nm_cols_max(p.qmap, p.ncol, p.ldq, p.store != 0) + 1; if (qw <= 0) return false; }
+        if (!p.Q || p.ldq < qw || p.q_len < (N - 1) * p.ldq + qw) return false;
+        if (p.Rout && (!p.store || p.Rout == p.Q || p.rout_len < (N - 1) * p.ldq + qw)) return false;
+        if (p.Uout && (p.ldu < k || p.uout_len < (N - 1) * p.ldu + k || p.Uout == p.Q || p.Uout == p.Rout)) return false;
+        return true;
+    }
+    const long long N = p.N;
+    if (N <= 0 || N > (1LL << 24) || !p.Xin || (!p.Rout && p.stage != HELM_NM_SCATTER_ADD)) return false;
+    switch (p.stage) {
+    case HELM_NM_PREP:
+        if (p.row_off < 0 || p.rhs_ld < p.row_off + N || p.xin_len < (k - 1) * p.rhs_ld + p.row_off + N || !p.qq) return false;
+        return (!p.Q || p.q_len >= k * N) && p.rout_len >= N * k;
+    case HELM_NM_PACK: {
+        const long long mx = nm_cols_max(p.qmap, p.ncol, p.ldin, false);
+        return mx >= 0 && p.xin_len >= (N - 1) * p.ldin + mx + 1 && p.rout_len >= N * k;
+    }
+    case HELM_NM_SCATTER_ADD: {
+        const long long mx = nm_cols_max(p.qmap, p.ncol, p.ldq, true);
+        return mx >= 0 && p.Q && p.q_len >= (N - 1) * p.ldq + mx + 1 && p.xin_len >= N * k;
+    }
+    case HELM_NM_RECOVER_X:
+        if (p.oscale[0] == 0.0 && p.oscale[1] == 0.0) return false;
+        return p.xin_len >= N * k && p.rout_len >= N * k;
+    case HELM_NM_TRANSPOSE_OUT:
+    case HELM_NM_TRANSPOSE:
+        return p.xin_len >= N * k && p.rout_len >= N * k;
+    default: return false;
+    }
+}
+}  // namespace
+
+extern "C" int helm_debug_nm_stage(helm_nm_stage *pp) {
+    if (!pp) return HELM_ERR_ARG;
+    helm_nm_stage &p = *pp;
+    if (!nm_stage_ok(p)) { helm_set_error(nullptr, "helm_debug_nm_stage: malformed arguments"); return HELM_ERR_ARG; }
+    helm_tuning_refresh();
+    if (hipSetDevice(p.device) != hipSuccess) return HELM_ERR_DEVICE;
+    std::vector<std::pair<const void *, void *>> dev;            // host pointer -> device copy
+    bool bad = false;
+    auto up = [&](const void *h, size_t bytes) -> void * {
+        if (!h) return nullptr;
+        void *d = nullptr;
+        if (hipMalloc(&d, bytes) != hipSuccess || hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) { bad = true; if (d) hipFree(d); return nullptr; }
+        dev.push_back(std::make_pair(h, d));
+        return d;
+    };
+    auto down = [&](void *h, size_t bytes) { for (auto &e : dev) if (e.first == h && hipMemcpy(h, e.second, bytes, hipMemcpyDeviceToHost) != hipSuccess) bad = true; };
+    const bool resid = p.stage == HELM_NM_RESID;
+    const long long N = resid ? (long long)p.nz * p.nx : p.N;
+    const cplx *dP = (const cplx *)up(p.planes, resid ? (size_t)p.planes_len * 16 : 0);
+    const cplx *dXin = (const cplx *)up(p.Xin, (size_t)p.xin_len * 16);
+    cplx *dQ = (cplx *)up(p.Q, (size_t)p.q_len * 16);
+    cplx *dR = (cplx *)up(p.Rout, (size_t)p.rout_len * 16);
+    cplx *dU = resid ? (cplx *)up(p.Uout, (size_t)p.uout_len * 16) : nullptr;
+    const int *dMap = (const int *)up(p.qmap, (size_t)p.ncol * sizeof(int));
+    const unsigned char *dMask = resid ? (const unsigned char *)up(p.qmask, (size_t)N) : nullptr;
+    for (int i = 0; i < 5; ++i) p.report[i] = 0;
+    int rc = HELM_OK;
+    helm_op *op = nullptr;
+    if (!bad) {
+        const int fs[4] = {0, 0, 0, 0};
+        op = helm_create(p.device, 0, std::max(p.nz, 3), std::max(p.nx, 3), 1.0, 1.0, 2, fs);
+        if (!op) bad = true;
+    }
+    if (!bad) {
+        NmGridGuard grid(op, p.nz, p.nx);
+        const int nblk_solver = std::max(2 * helm_apply_num_blocks(op), helm_vec_num_blocks(op));
+        const int cap = p.nblk_cap > 0 ? p.nblk_cap : nblk_solver;
+        const cplx osc = cmake(p.oscale[0], p.oscale[1]);
+        int nb_part = 0;
+        double *d_aux = nullptr;
+        if (resid || p.stage == HELM_NM_PREP) {
+            // room for 4 partial sums per column from each workgroup (never more of those than tiles), the 2 ncol results behind them as in solve_block_direct
+            const long long tiles = resid ? (long long)((p.nz + 3) / 4) * ((p.nx + RESID_SEG - 1) / RESID_SEG) : (N + 31) / 32;
+            const long long wgs = std::max<long long>(1, std::min<long long>(tiles, std::min(cap, 2048)));
+            const long long cnt = std::max<long long>(p.ncol, (p.ncol * wgs + nblk_solver - 1) / nblk_solver);
+            rc = ensure_part(op, (int)cnt);
+            d_aux = (double *)((char *)op->d_part + (size_t)cnt * 4 * nblk_solver * sizeof(double));
+        }
+        if (rc == HELM_OK) switch (p.stage) {
+        case HELM_NM_RESID: {
+            NdResidExtra ex;
+            ex.qnorm = p.qnorm; ex.Uout = dU; ex.ldu = p.ldu; ex.oscale = osc; ex.qmask = dMask; ex.xin_is_u = p.xin_is_u;
+            const bool plain = !p.qnorm && !dU && !dMask && !p.xin_is_u;          // (the solver's own calls without by-products pass no extras)
+            g_nm_report = p.report;
+            rc = nd_resid_nm(op, dP, dXin, p.ldin, dQ, p.ldq, dMap, p.ncol, p.store, dR, (double *)op->d_part, cap, &nb_part, plain ? nullptr : &ex);
+            g_nm_report = nullptr;
+            if (rc == HELM_OK) helm_launch_fin_ex(op, p.qnorm ? FIN_NORM2 : FIN_NORM, p.ncol, nb_part, nullptr, d_aux);
+            break;
+        }
+        case HELM_NM_PREP:
+            rc = nd_prep_transpose_norm(op, dXin, p.rhs_ld, p.row_off, osc, dQ, dR, N, p.ncol, (double *)op->d_part, cap, &nb_part);
+            if (rc == HELM_OK) helm_launch_fin_ex(op, FIN_NORM, p.ncol, nb_part, nullptr, d_aux + p.ncol);
+            p.report[2] = nb_part; p.report[3] = 1; p.report[4] = (int)((N + 31) / 32);
+            break;
+        case HELM_NM_PACK:          rc = nd_pack_cols(op, dXin, p.ldin, dMap, p.ncol, dR, N); break;
+        case HELM_NM_SCATTER_ADD:   rc = nd_scatter_add_cols(op, dQ, p.ldq, dMap, p.ncol, dXin, N); break;
+        case HELM_NM_RECOVER_X:     rc = nd_recover_x(op, dXin, dR, N * p.ncol, osc); break;
+        case HELM_NM_TRANSPOSE_OUT: rc = nd_transpose_out(op, dXin, N, p.ncol, dR, p.conj); break;
+        default:                    rc = nd_transpose(op, dXin, N, (long long)p.ncol, dR); break;
+        }
+        hipError_t e = hipStreamSynchronize(op->stream);
+        if (e == hipSuccess) e = hipGetLastError();
+        if (e != hipSuccess) bad = true;
+        if (!bad && rc == HELM_OK) {
+            if (p.Q) down(p.Q, (size_t)p.q_len * 16);
+            if (p.Rout) down(p.Rout, (size_t)p.rout_len * 16);
+            if (resid && p.Uout) down(p.Uout, (size_t)p.uout_len * 16);
+            if (resid && hipMemcpy(p.rr, d_aux, p.ncol * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) bad = true;
+            if ((resid ? p.qnorm != 0 : p.stage == HELM_NM_PREP) && hipMemcpy(p.qq, d_aux + p.ncol, p.ncol * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) bad = true;
+        }
+    }
+    for (auto &d : dev) if (d.second) hipFree(d.second);
+    if (op) helm_destroy(op);
+    return bad ? HELM_ERR_DEVICE : rc;
+}

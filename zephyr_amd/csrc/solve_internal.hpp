@@ -1,5 +1,5 @@
 // What the units of the solve driver share (capi.hip: dispatch and the C ABI; solve_direct.hip: the direct path and helm_prefactor*; krylov.hip: the
-// Krylov drivers).  Internal to those three.
+// Krylov drivers).  Internal to those three and to the test hook of nd_resid.hip, which reduces its partial sums the way the direct path does.
 #pragma once
 #include "helm_internal.hpp"
 #include "direct.hpp"
