@@ -247,6 +247,17 @@ def require_gpu():
     return n
 
 
+def gpu_usable():
+    'True when the library loads and sees a GPU and torch sees one too (the device paths keep their buffers in torch tensors); any failure means no'
+    try:
+        if load().helm_device_count() <= 0:
+            return False
+        import torch
+        return torch.cuda.device_count() > 0
+    except Exception:
+        return False
+
+
 class _PinnedBlock(object):
     'owner of one helm_host_alloc buffer; numpy arrays made from it keep it alive (it is their .base)'
 

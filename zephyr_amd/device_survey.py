@@ -1,0 +1,304 @@
+"""Device pipeline of a survey: `Survey.dpred` and the mux branch of `Problem.Jtvec` with the wavefields kept in HBM.
+
+Both are the same loop.  The owned frequencies are dealt as work items (frequency, source batch) over the GPUs (`deviceItems`), every item runs on
+the worker thread of its GPU with the next item's factorisation started ahead of time (`runOnDevices`), and its device memory comes from the
+`Workspace` of its worker and GPU, which lives for one call.  An item of `dpred` expands its sources, solves and samples; an item of `gradient` fills
+[qf | qb], solves and adds its imaging sum to the worker's partial gradient by one of two adding steps, chosen once per call.
+
+Three rules hold everywhere below.
+
+* Stream hand-over.  The library runs on its own streams.  Every torch operation whose result a library call reads (an upload, an element-wise
+  product, `zero_()`, `fill_()`, a fresh tensor the library writes) is followed by `_lib.wait_torch_stream(dev)` before that call.
+* Main-thread preparation.  The survey's caches are not thread-safe: whatever the survey caches (`adjointPlan`, `stackedReceivers`, the fixed
+  array's CSR, `getSources`, `getResidualSources`, the post-processors) is made on the calling thread before the workers start.
+* Helper lookups.  `to_device`, `from_device` and `from_device_pinned` are reached as attributes of `_lib` at call time (`_lib.from_device(...)`),
+  never imported by name: the transfer-counting tests replace them on the module.
+"""
+import math
+
+import numpy as np
+import scipy.sparse as sp
+
+from . import _lib
+from . import dispatch
+from . import parallel
+
+
+class Workspace(object):
+    """Device memory of one worker on one GPU for one call of dpred / Jtvec: named complex128 buffers whose storage only grows, the constants that
+    are uploaded once (`cached`), and the worker's partial gradient `G`."""
+
+    def __init__(self, device):
+        self.device = device            # (a torch.device)
+        self.G = None                   # (the partial gradient of this worker and GPU: made on first use by the gradient pipeline)
+        self._storage = {}
+        self._constants = {}
+
+    def buffer(self, name, shape):
+        'a contiguous complex128 view of exactly `shape` (a number of elements, or a tuple) over the storage of `name`: new storage only when the request exceeds it'
+        import torch
+        shape = tuple(shape) if isinstance(shape, (tuple, list)) else (int(shape),)
+        n = math.prod(int(s) for s in shape)
+        store = self._storage.get(name)
+        if store is None or store.numel() < n:
+            store = self._storage[name] = torch.empty(n, dtype=torch.complex128, device=self.device)
+        return store[:n].view(shape)
+
+    def cached(self, key, make, keep=None):
+        'make() once per key.  `keep`: an object that has to live as long as the entry (one whose id is part of the key)'
+        if key not in self._constants:
+            self._constants[key] = (make(), keep)
+        return self._constants[key][0]
+
+
+# ---- dealing and running the items -------------------------------------------------------------------------------------------------------------
+def deviceItems(sysw, owned, ncols):
+    """Work items (worker, operator, ifreq, c0, c1) for the owned frequencies: frequency-major over the system wrapper's devices (a GPU keeps the operators
+    of its frequencies); with fewer frequencies than GPUs the `ncols` source columns of a frequency are split over the spare ones."""
+    subs = sysw.subProblems
+    devs = list(sysw.devices) if hasattr(sysw, 'devices') else [subs[0].device]
+    nw = len(devs)
+    split = max(1, nw // max(1, len(owned))) if hasattr(sysw, '_replica') else 1
+    split = min(split, max(1, ncols))
+    items = []
+    for pos, ifreq in enumerate(owned):
+        bounds = [ncols * j // split for j in range(split + 1)]
+        for j in range(split):
+            if j == 0:          # the frequency's own operator, on the worker of the GPU it lives on
+                op = subs[ifreq]
+                w = devs.index(op.device) if op.device in devs else (pos * split) % nw
+                if split > 1 and devs[(pos * split) % nw] == op.device:
+                    w = (pos * split) % nw
+            else:               # a copy of it on a spare GPU for another batch of its sources
+                w = (pos * split + j) % nw
+                op = sysw._replica(ifreq, j, devs[w])
+            items.append((w, op, ifreq, bounds[j], bounds[j + 1]))
+    return devs, items
+
+
+def runOnDevices(devs, items, fn):
+    """Run fn(ws, op, ifreq, c0, c1) for every item on the worker thread of its GPU, the factorisation of the worker's next item started ahead of
+    time.  `ws` is the worker's Workspace on the GPU of the operator it is running.  Returns the workspaces, in worker order."""
+    import torch
+    workers = [{} for _ in devs]          # per worker: device index -> Workspace
+    queues = [[] for _ in devs]
+    # the factorisations of a worker's next two operators are enqueued together (discretization.prefactor_many: the fronts of both frequencies in the same
+    # batched launches); an item's own prepare step then only builds and assembles its operator
+    from .discretization import prefactor_many
+    group = 2 if all(getattr(type(op), 'VARIANT', None) in (_lib.HELM_MINIZEPHYR, _lib.HELM_EURUS) for _, op, _, _, _ in items) else 1      # (2-D operators: what helm_prefactor_many takes)
+    for w, op, ifreq, c0, c1 in items:
+        def solve(_p, w=w, op=op, ifreq=ifreq, c0=c0, c1=c1):
+            ws = workers[w].get(op.device)
+            if ws is None:
+                ws = workers[w][op.device] = Workspace(torch.device('cuda', op.device))
+            return fn(ws, op, ifreq, c0, c1)
+        if group > 1:
+            prep = (lambda op=op: (op.handle, op)[1])
+        else:
+            prep = op.prefactor if hasattr(op, 'prefactor') else None
+        queues[w].append(dispatch.WorkItem(solve, prep))
+    pipes = dispatch.dispatch(list(zip(devs, queues)), lookahead=1, group=group, group_prepare=prefactor_many if group > 1 else None)
+    try:
+        [it.future.result() for q in queues for it in q]
+    finally:
+        for p in pipes:
+            p.join()
+    return [ws for worker in workers for ws in worker.values()]
+
+
+# ---- [qf | qb] of an item ----------------------------------------------------------------------------------------------------------------------
+def _muxTriplets(mats, c0, c1, rows):
+    """(row, col, val, shape) of [m_0[:, c0:c1] | m_1[:, c0:c1] | ...] from the matrices' own arrays (no format conversion, no sort of 10^5..10^6 entries):
+    what rhsFromSparseDevice takes as triplets"""
+    k = c1 - c0
+    parts = []
+    for j, m in enumerate(mats):
+        mc = m if (c0 == 0 and c1 == m.shape[1]) else sp.csc_matrix(m)[:, c0:c1]
+        if not (sp.isspmatrix_csr(mc) or sp.isspmatrix_csc(mc)) or not mc.has_canonical_format:
+            mc = sp.csr_matrix(mc)
+            mc.sum_duplicates()
+        coo = mc.tocoo(copy=False)
+        parts.append((coo.row, coo.col + j * k, coo.data))
+    return (np.concatenate([p_[0] for p_ in parts]), np.concatenate([p_[1] for p_ in parts]), np.concatenate([p_[2] for p_ in parts]), (rows, len(parts) * k))
+
+
+def _planOnDevice(ws, sv, ifreq):
+    'the survey\'s adjoint plan of frequency ifreq\'s grid with its arrays on the workspace\'s GPU: uploaded once per worker and grid key'
+    def upload():
+        plan = sv.adjointPlan(ifreq)
+        pd = dict(plan)
+        for name in ('tptr', 'tsrc', 'tcell', 'trec', 'tval'):
+            pd[name] = _lib.to_device(plan[name], ws.device)
+        return pd
+    return ws.cached(('plan', sv._gridKey(ifreq)), upload)
+
+
+def _fillMuxDevice(ws, sv, op, qf_i, qb_i, resid, ifreq, c0, c1, d_R, rows):
+    """d_R ([2k][rows], k = c1 - c0) = [qf | qb] of the sources c0 .. c1-1 of frequency ifreq.  qb_i given (fixed array): both halves as sparse triplets.
+    qb_i None (the array moves with the source): the qf half from triplets, the qb half by the gather of the survey's adjoint plan from the item's
+    residual samples resid[:, c0:c1, ifreq] -- 16 nrec k bytes up instead of ~81 entries of 28 B per sample, and no sparse products on the host."""
+    k = c1 - c0
+    if qb_i is not None:
+        op.rhsFromSparseDevice(_muxTriplets((qf_i, qb_i), c0, c1, rows), d_R)
+        return
+    op.rhsFromSparseDevice(_muxTriplets((qf_i,), c0, c1, rows), d_R)
+    plan = _planOnDevice(ws, sv, ifreq)
+    panel = _lib.to_device(resid[:, c0:c1, ifreq], ws.device, np.complex128)       # (nrec, k), one contiguous panel
+    _lib.wait_torch_stream(ws.device)
+    op.rhsFromSamplesDevice(panel.data_ptr(), k, plan, c0, c1, d_R + k * rows * 16, rows=rows)
+
+
+def _inverseCube(c, dev):
+    '1 / c^3 on `dev` from one upload of the model array c'
+    cd = _lib.to_device(np.asarray(c).ravel(), dev, np.complex128)
+    return 1.0 / (cd * cd * cd)
+
+
+# ---- the two ways an item's imaging sum reaches G ----------------------------------------------------------------------------------------------
+# An adding step is called once per item, before the solve, and returns (scaler, target, finish): the item's imaging kernel accumulates
+# scaler (.) sum_s uF (.) uB into `target`, then finish() runs (None: nothing left to do).  A step may enqueue torch work for what it returns; it
+# does not wait for it -- the item body issues the one wait_torch_stream between the step and the solve.
+
+def _addOnNativeGrid(prob, scale):
+    """The wavefields are on the gradient's grid: the imaging kernel goes straight into G with the scaler -(omega^2 / c^3) scale^2, one kernel per item."""
+    sv = prob.survey
+    plain_scaler = prob._plainGradientScaler()
+
+    def step(ws, op, ifreq, Ni):
+        dev = ws.device
+        if plain_scaler:
+            # -(omega^2 / c^3) scale^2 on the GPU from one upload of the model per worker: on the host the complex power and division of problem.py:74-81 cost
+            # 6 ms per frequency at 512^2 (numpy), in the thread whose only other job is to keep the solve stream fed
+            cm = op.c
+            inv = ws.cached(('inv_c3', id(cm)), lambda: _inverseCube(cm, dev), keep=cm)          # (the id stays this array's while the worker lives)
+            omega = 2 * np.pi * sv.freqs[ifreq]
+            scaler = inv * complex(-(omega ** 2) * scale * scale)
+        else:
+            scaler = _lib.to_device(prob.gradientScaler(ifreq) * scale * scale, dev, np.complex128)
+        return scaler, ws.G, None
+    return step
+
+
+def _addUpscaled(prob, scale):
+    """Every frequency on its own grid (a multiscale survey): the imaging sum P = scale^2 sum_s uF (.) uB is accumulated there, then
+    G += pp(scaler) (.) pp(P) in one grid transfer (problem.py:152: the product of two up-scaled fields), the up-scaled scaler -(omega^2 / c^3)
+    made once per worker and frequency from the operator's coarse c."""
+    import torch
+    sv, N = prob.survey, prob.nrow
+    pps = sv.postProcessors
+
+    def step(ws, op, ifreq, Ni):
+        dev = ws.device
+        P, unit = ws.buffer('P', Ni), ws.buffer('unit', Ni)
+
+        def upscaled_scaler():
+            omega = 2 * np.pi * sv.freqs[ifreq]
+            sc = _inverseCube(op.c, dev) * complex(-(omega ** 2))
+            S = torch.empty(N, dtype=torch.complex128, device=dev)
+            _lib.wait_torch_stream(dev)
+            pps[ifreq].apply_device(sc, S, k=1)
+            return S
+        S = ws.cached(('scaler', ifreq), upscaled_scaler)
+        P.zero_()
+        unit.fill_(scale * scale)
+        G = ws.G
+        return unit, P, lambda: pps[ifreq].apply_device(P, G, k=1, op=op, beta=1., mul=S)
+    return step
+
+
+# ---- the pipelines -----------------------------------------------------------------------------------------------------------------------------
+def gradient(prob, qb, owned, resid):
+    """Mux branch of Jtvec with the wavefields kept in HBM: per work item (frequency, source batch) [qf | qb] of its sources is made on the item's GPU
+    and solved there on the frequency's own grid, and scaler * sum_s uF (.) uB is added to that GPU's partial gradient.  The partial gradients are
+    summed on the host, then ONE all-reduce over ranks when the frequencies are sharded.  qb None: the back-sources of a moving receiver array,
+    made on the device from `resid` (nrec, nsrc, nfreq)."""
+    import torch
+    from .survey import HelmMultiGridSurvey
+    sv = prob.survey
+    nsrc, N = sv.nsrc, prob.nrow
+    scale = complex(prob.system.scaleTerm)
+    qf = sv.getSources()
+    if not owned:
+        g = np.zeros(N, dtype=np.complex128)
+        return parallel.allreduce_sum(g) if prob._sharded else g
+    if qb is None:
+        for ifreq in owned:
+            sv.adjointPlan(ifreq)
+    devs, items = deviceItems(prob.system, owned, nsrc)
+    add = _addUpscaled(prob, scale) if isinstance(sv, HelmMultiGridSurvey) else _addOnNativeGrid(prob, scale)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        if ws.G is None:
+            ws.G = torch.zeros(N, dtype=torch.complex128, device=ws.device)
+        U, R = ws.buffer('U', 2 * k * Ni), ws.buffer('R', 2 * k * Ni)
+        # [qf | qb] of the item's sources: sparse triplets (or residual samples) up, dense on the device
+        _fillMuxDevice(ws, sv, op, qf[ifreq] if isinstance(qf, (list, tuple)) else qf, None if qb is None else qb[ifreq], resid, ifreq, c0, c1, R.data_ptr(), Ni)
+        scaler, target, finish = add(ws, op, ifreq, Ni)
+        _lib.wait_torch_stream(ws.device)                # (covers the torch work the adding step has just enqueued -- scaler product, zero_(), fill_(): keep it between the two)
+        op.solveDevice(R.data_ptr(), U.data_ptr(), 2 * k, Ni)
+        op.imagingAccumulateDevice(U.data_ptr(), U.data_ptr() + k * Ni * 16, k, scaler.data_ptr(), target.data_ptr())
+        if finish is not None:
+            finish()
+    parts = [ws.G for ws in runOnDevices(devs, items, one) if ws.G is not None]
+    if len(parts) == 1:
+        G = parts[0]
+        if prob._sharded:
+            parallel.allreduce_sum_device(G)
+        torch.cuda.synchronize(G.device)
+        return _lib.from_device(G)
+    g = np.zeros(N, dtype=np.complex128)
+    for G in parts:                                   # per-GPU partial gradients: 16 B per grid point each
+        torch.cuda.synchronize(G.device)
+        g += _lib.from_device(G)
+    return parallel.allreduce_sum(g) if prob._sharded else g
+
+
+def dpred(prob, owned):
+    """Predicted data (nrec, nsrc, nfreq) with the wavefields kept in HBM: per work item (frequency, source batch) the sparse sources are expanded on the
+    item's GPU and solved there on the frequency's own grid, and only the receiver samples R u (nrec x sources) come back.  One receiver CSR per grid
+    key (None: the one grid of a single-grid survey).  A receiver array that moves with the source is sampled through the survey's stacked CSR, source
+    s from its own rows s * nrec .. (row stride nrec); a fixed one through the one matrix (stride 0)."""
+    sv = prob.survey
+    nsrc, nrec = sv.nsrc, sv.nrec
+    scale = complex(prob.system.scaleTerm)
+    data = np.zeros((nrec, nsrc, sv.nfreq), dtype=np.complex128)
+    if not owned:
+        return data
+    moving = sv.mode != 'fixed'
+    stride = nrec if moving else 0
+    Rms = {}
+    for ifreq in owned:
+        gk = sv._gridKey(ifreq)
+        if gk not in Rms:
+            if moving:
+                Rm = sv.stackedReceivers(ifreq)
+            else:
+                Rm = sp.csr_matrix(sv.rVec(0, ifreq))
+                Rm.sum_duplicates()
+            Rms[gk] = Rm
+    qf = sv.getSources()
+    devs, items = deviceItems(prob.system, owned, nsrc)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        summed = hasattr(op, 'sampleSumDevice')           # a composite (2.5-D ky sum): its samples are accumulated per ky, it keeps its own wavefield scratch
+        dev, gk = ws.device, sv._gridKey(ifreq)
+        Rm = Rms[gk]
+        # the receiver CSR as sampleDevice / sampleSumDevice take it, (rowptr, col, val, nrec): uploaded once per worker and grid key
+        csr = ws.cached(('csr', gk), lambda: (_lib.to_device(Rm.indptr, dev, np.int64), _lib.to_device(Rm.indices, dev, np.int64),
+                                         _lib.to_device(Rm.data, dev, np.complex128), nrec))
+        if moving:                                        # the rows of this batch's sources start at c0 * nrec
+            csr = (csr[0][c0 * nrec:], csr[1], csr[2], nrec, stride)
+        R, out = ws.buffer('R', k * Ni), ws.buffer('out', (nrec, k))
+        q = qf[ifreq] if isinstance(qf, (list, tuple)) else qf
+        op.rhsFromSparseDevice(sp.csc_matrix(q)[:, c0:c1], R.data_ptr())
+        if summed:
+            op.sampleSumDevice(R.data_ptr(), k, csr, out.data_ptr(), rows=Ni)      # (sampling is linear: the N x k sum over ky is never formed)
+        else:
+            U = ws.buffer('U', k * Ni)
+            op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+            op.sampleDevice(U.data_ptr(), k, csr, out.data_ptr())      # (returns when the samples are there: helm_sample_device waits for its own stream)
+        data[:, c0:c1, ifreq] = scale * _lib.from_device(out)          # (disjoint slices per item: no two workers write the same entries)
+    runOnDevices(devs, items, one)
+    return data

@@ -121,7 +121,7 @@ class MiniZephyr25D(BaseDiscretization, DiscretizationWrapper):
         return getattr(self, '_scaleTerm', 1.) * np.exp(1j * np.pi) / (4 * np.pi)
 
     # ---- the ky sum on the device -------------------------------------------------------------------------
-    # The composite presents itself to the device pipelines (problem._JtvecDevice / _dpredDevice, BaseMPDist) as ONE device operator: right-hand
+    # The composite presents itself to the device pipelines (device_survey.gradient / dpred, BaseMPDist) as ONE device operator: right-hand
     # sides are expanded / uploaded once (they are shared by all ky), every ky is solved into a scratch buffer in HBM and added to the caller's
     # buffer by helm_axpby_device, and what leaves the GPU is the sum (or its receiver samples).
 
@@ -151,11 +151,7 @@ class MiniZephyr25D(BaseDiscretization, DiscretizationWrapper):
         if not self.kySumOnDevice:
             return False
         if '_gpuThere' not in self.__dict__:
-            try:
-                import torch
-                self._gpuThere = _lib.load().helm_device_count() > 0 and torch.cuda.device_count() > 0
-            except Exception:
-                self._gpuThere = False
+            self._gpuThere = _lib.gpu_usable()
         return self._gpuThere
 
     # (BaseDiscretization's `factors` looks at the handle of the object itself, which a composite does not have)

@@ -83,26 +83,28 @@ class HelmBaseSurvey(BaseSCCache):
         return gen
 
     # ---- source / receiver vectors (survey.py:109-128) ------------------------------------------------
-    def _weightedColumns(self, locs, terms):
-        'one column per location from the survey\'s source generator, column j scaled by terms[j]'
-        return self.RHSGenerator(self.systemConfig)(locs) * sp.diags((terms,), (0,))
+    def _vecKey(self, kind, ifreq, *source):
+        'key (kind, grid key of frequency ifreq[, source]) of an entry of the vector cache: the one spelling of its keys'
+        return (kind, self._gridKey(ifreq)) + source
 
-    def sVecs(self, ifreq=None):
-        'source matrix S diag(ssTerms), (N, nsrc); made once (one grid for every frequency: `ifreq` does not matter here)'
+    def _cachedOn(self, kind, ifreq, make, *source):
+        'the entry of the vector cache under _vecKey(kind, ifreq[, source]), made by make() on first use'
         cache = self.__dict__.setdefault('_vecCache', {})
-        if 'S' not in cache:
-            cache['S'] = self._weightedColumns(self.sLocs, self.ssTerms)
-        return cache['S']
-
-    def rVec(self, isrc, ifreq=None):
-        'receiver sampling matrix of source isrc, (nrec, N): one for all sources with a fixed array, one per source when the array moves with it'
-        cache = self.__dict__.setdefault('_vecCache', {})
-        moving = self.mode != 'fixed'
-        key = ('R', isrc) if moving else 'R'
+        key = self._vecKey(kind, ifreq, *source)
         if key not in cache:
-            where = self.rLocs + self.sLocs[isrc] if moving else self.rLocs
-            cache[key] = self._weightedColumns(where, self.srTerms).T
+            cache[key] = make()
         return cache[key]
+
+    def sVecs(self, ifreq=0):
+        'source matrix S diag(ssTerms) on the grid of frequency ifreq, (N_ifreq, nsrc); made once per grid'
+        return self._cachedOn('S', ifreq, lambda: self._weightedColumnsOn(ifreq, self.sLocs, self.ssTerms))
+
+    def rVec(self, isrc, ifreq=0):
+        """receiver sampling matrix of source isrc on the grid of frequency ifreq, (nrec, N_ifreq): one for all sources with a fixed array, one per source
+        when the array moves with it"""
+        moving = self.mode != 'fixed'
+        return self._cachedOn('R', ifreq, lambda: self._weightedColumnsOn(ifreq, self.rLocs + self.sLocs[isrc] if moving else self.rLocs, self.srTerms).T,
+                              *((isrc,) if moving else ()))
 
     def rVecs(self, ifreq):
         return (self.rVec(i, ifreq) for i in range(self.nsrc))
@@ -111,9 +113,13 @@ class HelmBaseSurvey(BaseSCCache):
         'which cached vectors frequency ifreq uses (None: the one grid of this survey)'
         return None
 
+    def scaledConfig(self, ifreq):
+        'the survey config on the grid of frequency ifreq (one grid for every frequency here)'
+        return self.systemConfig
+
     def _weightedColumnsOn(self, ifreq, locs, terms):
-        '_weightedColumns on the grid of frequency ifreq (one grid for every frequency here)'
-        return self._weightedColumns(locs, terms)
+        'one column per location from the survey\'s source generator on the grid of frequency ifreq, column j scaled by terms[j]'
+        return self.RHSGenerator(self.scaledConfig(ifreq))(locs) * sp.diags((terms,), (0,))
 
     # ---- a moving array as ONE matrix: what the device paths of problem.py upload ---------------------------------
     def stackedReceivers(self, ifreq=0):
@@ -121,15 +127,13 @@ class HelmBaseSurvey(BaseSCCache):
         rVec uses, on the concatenated locations -- the same entries to the bit, so whatever the host path does with a location (clipping at the edges,
         a free surface) is what the device samples.  One per grid key; the rows of the sources c0 .. c1-1 are the contiguous range
         indptr[c0 * nrec : c1 * nrec + 1]."""
-        cache = self.__dict__.setdefault('_vecCache', {})
-        key = ('Rstack', self._gridKey(ifreq))
-        if key not in cache:
+        def stack():
             moving = self.mode != 'fixed'
             where = np.concatenate([self.rLocs + self.sLocs[s] if moving else self.rLocs for s in range(self.nsrc)])
             M = sp.csr_matrix(self._weightedColumnsOn(ifreq, where, np.tile(self.srTerms, self.nsrc)).T)
             M.sum_duplicates()
-            cache[key] = M
-        return cache[key]
+            return M
+        return self._cachedOn('Rstack', ifreq, stack)
 
     def adjointPlan(self, ifreq=0):
         """getResidualSources as a gather: the entries of stackedReceivers sorted by (source, cell, receiver) and grouped into the touched (source, cell)
@@ -140,9 +144,7 @@ class HelmBaseSurvey(BaseSCCache):
             src_ptr (nsrc + 1, int64)  pairs src_ptr[c0] .. src_ptr[c1] are those of the sources c0 .. c1-1: a batch is a sub-range, nothing is copied
         so that  qb[cell, s] = sum_e tval[e] resid[trec[e], s]  over the entries of pair (s, cell), summed in stored order (receivers of one source share
         cells: the patches of neighbours overlap).  Validated here -- helm_rhs_from_samples_device trusts it."""
-        cache = self.__dict__.setdefault('_vecCache', {})
-        key = ('Rplan', self._gridKey(ifreq))
-        if key not in cache:
+        def build():
             M = self.stackedReceivers(ifreq)
             nrec, nsrc, N = self.nrec, self.nsrc, M.shape[1]
             row = np.repeat(np.arange(M.shape[0], dtype=np.int64), np.diff(M.indptr))
@@ -158,8 +160,8 @@ class HelmBaseSurvey(BaseSCCache):
             if src.size and not (0 <= cell.min() and cell.max() < N and 0 <= rec.min() and rec.max() < nrec and 0 <= src.min() and src.max() < nsrc
                                  and np.all(np.diff(plan['tsrc']) >= 0) and np.all(np.diff(plan['tptr']) >= 1)):
                 raise ValueError('adjoint plan of the receiver array addresses cells, receivers or sources outside the survey')
-            cache[key] = plan
-        return cache[key]
+            return plan
+        return self._cachedOn('Rplan', ifreq, build)
 
     # ---- hot-path pieces ------------------------------------------------------------------------------
     def getSources(self):
@@ -200,8 +202,7 @@ class HelmBaseSurvey(BaseSCCache):
             ns = resid.shape[1]
             out, layouts = [], {}
             for ifreq in range(self.nfreq):
-                gk = self._gridKey(ifreq)                 # (one R per grid: a multiscale survey has one per distinct scale)
-                key = 'RtRows' if gk is None else ('RtRows', gk)
+                key = self._vecKey('RtRows', ifreq)       # (one R per grid: a multiscale survey has one per distinct scale; the key serves `layouts` too)
                 if key not in cache:
                     Rt = sp.csr_matrix(self.rVec(0, ifreq).T)
                     Rt.sum_duplicates()
@@ -284,28 +285,6 @@ class HelmMultiGridSurvey(HelmBaseSurvey):
             sc.update(self.mgHelper.downScalers[ifreq].scaleUpdate)
             scs[key] = sc
         return scs[key]
-
-    def _weightedColumnsOn(self, ifreq, locs, terms):
-        return self.RHSGenerator(self.scaledConfig(ifreq))(locs) * sp.diags((terms,), (0,))
-
-    def sVecs(self, ifreq=0):
-        'source matrix S diag(ssTerms) on the grid of frequency ifreq, (N_ifreq, nsrc)'
-        cache = self.__dict__.setdefault('_vecCache', {})
-        key = ('S', self._gridKey(ifreq))
-        if key not in cache:
-            cache[key] = self._weightedColumnsOn(ifreq, self.sLocs, self.ssTerms)
-        return cache[key]
-
-    def rVec(self, isrc, ifreq=0):
-        'receiver sampling matrix of source isrc on the grid of frequency ifreq, (nrec, N_ifreq)'
-        cache = self.__dict__.setdefault('_vecCache', {})
-        moving = self.mode != 'fixed'
-        gk = self._gridKey(ifreq)
-        key = ('R', gk, isrc) if moving else ('R', gk)
-        if key not in cache:
-            where = self.rLocs + self.sLocs[isrc] if moving else self.rLocs
-            cache[key] = self._weightedColumnsOn(ifreq, where, self.srTerms).T
-        return cache[key]
 
     def getSources(self):
         'per-frequency source matrices on their grids (survey.py:289-297)'
