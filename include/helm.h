@@ -29,6 +29,10 @@
  *   helm_sample_rows_device,
  *   helm_rhs_from_samples_device   <- a receiver array that moves with the source (geom mode 'relative'):
  *                                     HelmBaseSurvey rVec / getResidualSources   zephyr/middleware/survey.py:114-125,171-188
+ *   helm_pack_c64_device,
+ *   helm_imaging_accumulate_c64_device,
+ *   helm_sample_rows_c64_device    <- forward fields handed to dpred / Jtvec as `u=` (problem.py:124-164, survey.py:190-198),
+ *                                     kept in HBM at half size
  *   helm_destroy                   <- `del obj.factors` / __del__         discretization.py:86-99
  *
  * Conventions
@@ -286,6 +290,22 @@ int helm_rhs_from_samples_device(helm_op *op, const void *d_resid, long long ld_
  * complete.  The sum over sub-problems of a composite operator (MiniZephyr25D: the last term carries the composite's scaleTerm in alpha and beta, so there
  * is no scaling pass).  beta == 0: Y is not read (it may be uninitialised). */
 int helm_axpby_device(helm_op *op, double alpha_re, double alpha_im, const void *dX, double beta_re, double beta_im, void *dY, long long n);
+
+/* --- forward wavefields kept as complex64 with one power-of-two scale per column ---------------------- */
+/* The optional half-size store of DeviceFields (zephyr_amd/fieldstore.py, fieldsDtype='complex64').  Column s of dU (nsrc columns of ld complex128 values,
+ * each contiguous, 16-byte aligned) is written to dOut as complex64 values (float)(x * 2^-e_s), rounded to nearest, and e_s to dExp (nsrc int32):
+ * e_s is the binary exponent of m_s = max_i max(|Re x_i|, |Im x_i|), 2^e_s <= m_s < 2^(e_s+1), clamped to +-1021; 0 for a zero column.  A consumer reads
+ * (double)x^ * 2^e_s.  Per component |x^ - x| <= 2^-24 |x| where |x| >= 2^(e_s-126), and <= 2^(e_s-126) below.  The column maximum is reduced in a fixed
+ * order without atomics: the same bits on every run.  All device pointers; returns when dOut and dExp are complete. */
+int helm_pack_c64_device(helm_op *op, const void *dU, int nsrc, long long ld, void *dOut, void *dExp);
+/* helm_imaging_accumulate_device with the forward field read from that store: G[i] += scaler[i] * sum_s (UF32[s][i] * 2^dExp[s]) * UB[s][i].  dUB, dScaler
+ * and dG are complex128 as there; columns are N = helm_num_points(op) apart. */
+int helm_imaging_accumulate_c64_device(helm_op *op, const void *dUF32, const void *dExp, const void *dUB, int nsrc, const void *dScaler, void *dG);
+/* helm_sample_rows_device with the wavefields read from that store (dU32: nsrc columns of ld complex64 values, dExp: their exponents): the other arguments,
+ * the row stride and the result are those of helm_sample_rows_device. */
+int helm_sample_rows_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, const void *d_rowptr, const void *d_col,
+                                const void *d_val, int nrec, long long row_stride, double alpha_re, double alpha_im, double beta_re, double beta_im,
+                                void *d_out);
 
 /* Device buffers are recycled by size class; a class holds as many as the busiest moment so far needed.  How many operators a pipelined job has alive at its
  * busiest is a matter of thread timing, so a job that got by with three buffers of a class in its first items may ask for a fourth later -- a hipMalloc of GBs

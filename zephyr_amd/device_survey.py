@@ -5,6 +5,9 @@ the worker thread of its GPU with the next item's factorisation started ahead of
 `Workspace` of its worker and GPU, which lives for one call.  An item of `dpred` expands its sources, solves and samples; an item of `gradient` fills
 [qf | qb], solves and adds its imaging sum to the worker's partial gradient by one of two adding steps, chosen once per call.
 
+The same loop serves forward fields that outlive a call (`fieldstore.DeviceFields`, at the end of the module): `fields` solves them into a store,
+`dpredFromFields` samples the store and `gradientFromFields` images against it, both over the items the store recorded.
+
 Three rules hold everywhere below.
 
 * Stream hand-over.  The library runs on its own streams.  Every torch operation whose result a library call reads (an upload, an element-wise
@@ -76,23 +79,26 @@ def deviceItems(sysw, owned, ncols):
     return devs, items
 
 
-def runOnDevices(devs, items, fn):
+def runOnDevices(devs, items, fn, factor=True):
     """Run fn(ws, op, ifreq, c0, c1) for every item on the worker thread of its GPU, the factorisation of the worker's next item started ahead of
-    time.  `ws` is the worker's Workspace on the GPU of the operator it is running.  Returns the workspaces, in worker order."""
+    time (factor=False: the items solve nothing, nothing is prepared).  `ws` is the worker's Workspace on the GPU of the operator it is running.
+    Returns the workspaces, in worker order."""
     import torch
     workers = [{} for _ in devs]          # per worker: device index -> Workspace
     queues = [[] for _ in devs]
     # the factorisations of a worker's next two operators are enqueued together (discretization.prefactor_many: the fronts of both frequencies in the same
     # batched launches); an item's own prepare step then only builds and assembles its operator
     from .discretization import prefactor_many
-    group = 2 if all(getattr(type(op), 'VARIANT', None) in (_lib.HELM_MINIZEPHYR, _lib.HELM_EURUS) for _, op, _, _, _ in items) else 1      # (2-D operators: what helm_prefactor_many takes)
+    group = 2 if factor and all(getattr(type(op), 'VARIANT', None) in (_lib.HELM_MINIZEPHYR, _lib.HELM_EURUS) for _, op, _, _, _ in items) else 1      # (2-D operators: what helm_prefactor_many takes)
     for w, op, ifreq, c0, c1 in items:
         def solve(_p, w=w, op=op, ifreq=ifreq, c0=c0, c1=c1):
             ws = workers[w].get(op.device)
             if ws is None:
                 ws = workers[w][op.device] = Workspace(torch.device('cuda', op.device))
             return fn(ws, op, ifreq, c0, c1)
-        if group > 1:
+        if not factor:
+            prep = None
+        elif group > 1:
             prep = (lambda op=op: (op.handle, op)[1])
         else:
             prep = op.prefactor if hasattr(op, 'prefactor') else None
@@ -240,7 +246,13 @@ def gradient(prob, qb, owned, resid):
         op.imagingAccumulateDevice(U.data_ptr(), U.data_ptr() + k * Ni * 16, k, scaler.data_ptr(), target.data_ptr())
         if finish is not None:
             finish()
-    parts = [ws.G for ws in runOnDevices(devs, items, one) if ws.G is not None]
+    return _sumPartials(prob, [ws.G for ws in runOnDevices(devs, items, one) if ws.G is not None])
+
+
+def _sumPartials(prob, parts):
+    "the gradient from the workers' partial gradients: summed on the host, then ONE all-reduce over ranks when the frequencies are sharded"
+    import torch
+    N = prob.nrow
     if len(parts) == 1:
         G = parts[0]
         if prob._sharded:
@@ -252,6 +264,33 @@ def gradient(prob, qb, owned, resid):
         torch.cuda.synchronize(G.device)
         g += _lib.from_device(G)
     return parallel.allreduce_sum(g) if prob._sharded else g
+
+
+def _receiverMatrices(sv, owned):
+    """{grid key: receiver CSR} for the owned frequencies (None: the one grid of a single-grid survey): the survey's stacked matrices for an array that
+    moves with the source, the one matrix of a fixed array.  Made on the calling thread (the survey caches them)."""
+    Rms = {}
+    for ifreq in owned:
+        gk = sv._gridKey(ifreq)
+        if gk not in Rms:
+            if sv.mode != 'fixed':
+                Rm = sv.stackedReceivers(ifreq)
+            else:
+                Rm = sp.csr_matrix(sv.rVec(0, ifreq))
+                Rm.sum_duplicates()
+            Rms[gk] = Rm
+    return Rms
+
+
+def _csrOnDevice(ws, Rm, gk, nrec, stride, c0):
+    """the receiver CSR as sampleDevice / sampleSumDevice take it, (rowptr, col, val, nrec[, stride]): uploaded once per worker and grid key; with a row
+    stride (a moving array) the rows of the batch's sources start at c0 * nrec"""
+    dev = ws.device
+    csr = ws.cached(('csr', gk), lambda: (_lib.to_device(Rm.indptr, dev, np.int64), _lib.to_device(Rm.indices, dev, np.int64),
+                                     _lib.to_device(Rm.data, dev, np.complex128), nrec))
+    if stride:
+        csr = (csr[0][c0 * nrec:], csr[1], csr[2], nrec, stride)
+    return csr
 
 
 def dpred(prob, owned):
@@ -267,29 +306,15 @@ def dpred(prob, owned):
         return data
     moving = sv.mode != 'fixed'
     stride = nrec if moving else 0
-    Rms = {}
-    for ifreq in owned:
-        gk = sv._gridKey(ifreq)
-        if gk not in Rms:
-            if moving:
-                Rm = sv.stackedReceivers(ifreq)
-            else:
-                Rm = sp.csr_matrix(sv.rVec(0, ifreq))
-                Rm.sum_duplicates()
-            Rms[gk] = Rm
+    Rms = _receiverMatrices(sv, owned)
     qf = sv.getSources()
     devs, items = deviceItems(prob.system, owned, nsrc)
 
     def one(ws, op, ifreq, c0, c1):
         k, Ni = c1 - c0, int(op.nrow)
         summed = hasattr(op, 'sampleSumDevice')           # a composite (2.5-D ky sum): its samples are accumulated per ky, it keeps its own wavefield scratch
-        dev, gk = ws.device, sv._gridKey(ifreq)
-        Rm = Rms[gk]
-        # the receiver CSR as sampleDevice / sampleSumDevice take it, (rowptr, col, val, nrec): uploaded once per worker and grid key
-        csr = ws.cached(('csr', gk), lambda: (_lib.to_device(Rm.indptr, dev, np.int64), _lib.to_device(Rm.indices, dev, np.int64),
-                                         _lib.to_device(Rm.data, dev, np.complex128), nrec))
-        if moving:                                        # the rows of this batch's sources start at c0 * nrec
-            csr = (csr[0][c0 * nrec:], csr[1], csr[2], nrec, stride)
+        gk = sv._gridKey(ifreq)
+        csr = _csrOnDevice(ws, Rms[gk], gk, nrec, stride, c0)
         R, out = ws.buffer('R', k * Ni), ws.buffer('out', (nrec, k))
         q = qf[ifreq] if isinstance(qf, (list, tuple)) else qf
         op.rhsFromSparseDevice(sp.csc_matrix(q)[:, c0:c1], R.data_ptr())
@@ -302,3 +327,140 @@ def dpred(prob, owned):
         data[:, c0:c1, ifreq] = scale * _lib.from_device(out)          # (disjoint slices per item: no two workers write the same entries)
     runOnDevices(devs, items, one)
     return data
+
+
+# ---- forward fields kept between calls (fieldstore.DeviceFields) ------------------------------------------------------------------------------
+# `fields` solves the forward wavefields once into a store that outlives the call; `dpredFromFields` and `gradientFromFields` are dpred and the
+# u-given branch of Jtvec over the store's OWN items (not a fresh deal), so that every item finds its slice on the GPU it was solved on.
+
+def _storedItems(sysw, F):
+    "(devs, items) as runOnDevices takes them from the items a store recorded: the frequency's own operator for its first batch, the system's replica j for batch j"
+    devs = list(sysw.devices) if hasattr(sysw, 'devices') else [sysw.subProblems[0].device]
+    batch, items = {}, []
+    for w, dev, ifreq, c0, c1 in F.items:
+        j = batch.get(ifreq, 0)
+        batch[ifreq] = j + 1
+        op = sysw.subProblems[ifreq] if j == 0 else sysw._replica(ifreq, j, dev)
+        items.append((w, op, ifreq, c0, c1))
+    return devs, items
+
+
+def fields(prob, owned, dtype='complex128'):
+    """The forward wavefields of the owned frequencies solved into a DeviceFields: per work item the sparse sources are expanded on the item's GPU and
+    solved straight into the item's slice of the store (complex128), or into the workspace and packed into it (complex64).  Nothing comes down."""
+    import torch
+    from .fieldstore import DeviceFields, DTYPES, check_fits
+    from .survey import HelmMultiGridSurvey
+    sv = prob.survey
+    if isinstance(sv, HelmMultiGridSurvey):
+        raise NotImplementedError('fieldsDevice serves single-grid surveys: on a multiscale survey the u-given branch of Jtvec multiplies the native-grid forward '
+                                  'field by the up-scaled back-propagated one per source (two grid transfers per source), which has not been built on the device')
+    if dtype not in DTYPES:
+        raise ValueError('fieldsDtype is %r: one of %s' % (dtype, ', '.join(DTYPES)))
+    nsrc = sv.nsrc
+    scale = complex(prob.system.scaleTerm)
+    stamp = prob._modelStamp
+    if not owned:
+        return DeviceFields(sv.nfreq, nsrc, [], [], None if dtype == 'complex128' else [], stamp, scale, dtype)
+    qf = sv.getSources()
+    devs, items = deviceItems(prob.system, owned, nsrc)
+    packed = dtype == 'complex64'
+    esize = 8 if packed else 16
+    # what every GPU has to hold: its slices (and exponents), and the largest working set of an item there (R; U as well when the store is packed)
+    need, work = {}, {}
+    for _, op, _, c0, c1 in items:
+        k, Ni = c1 - c0, int(op.nrow)
+        need[op.device] = need.get(op.device, 0) + k * Ni * esize + (4 * k if packed else 0)
+        work[op.device] = max(work.get(op.device, 0), k * Ni * 16 * (2 if packed else 1))
+    check_fits({d: need[d] + work[d] for d in need}, {d: torch.cuda.mem_get_info(d)[0] for d in need})
+    tdtype = torch.complex64 if packed else torch.complex128
+    slices = [torch.empty((c1 - c0, int(op.nrow)), dtype=tdtype, device=torch.device('cuda', op.device)) for _, op, _, c0, c1 in items]
+    exps = [torch.empty(c1 - c0, dtype=torch.int32, device=sl.device) for sl, (_, _, _, c0, c1) in zip(slices, items)] if packed else None
+    F = DeviceFields(sv.nfreq, nsrc, [(w, op.device, ifreq, c0, c1) for w, op, ifreq, c0, c1 in items], slices, exps, stamp, scale, dtype)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        sl, ex = F.slice(ifreq, c0)
+        R = ws.buffer('R', k * Ni)
+        q = qf[ifreq] if isinstance(qf, (list, tuple)) else qf
+        op.rhsFromSparseDevice(sp.csc_matrix(q)[:, c0:c1], R.data_ptr())
+        _lib.wait_torch_stream(ws.device)
+        if not packed:
+            op.solveDevice(R.data_ptr(), sl.data_ptr(), k, Ni)           # (no copy: the solve's output IS the slice)
+        else:
+            U = ws.buffer('U', k * Ni)
+            op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+            op.packDevice(U.data_ptr(), k, sl.data_ptr(), ex.data_ptr(), rows=Ni)      # (returns when the slice and its exponents are complete)
+    try:
+        runOnDevices(devs, items, one)
+    except BaseException:
+        F.release()
+        raise
+    return F
+
+
+def dpredFromFields(prob, F):
+    """Predicted data (nrec, nsrc, nfreq) from forward fields already in HBM: no solve, every item samples its slice of the store (row stride 0 for a fixed
+    array, nrec for one that moves with the source) and only the receiver samples come back."""
+    F.checkCurrent(prob)
+    sv = prob.survey
+    nsrc, nrec = sv.nsrc, sv.nrec
+    scale = F.scale
+    data = np.zeros((nrec, nsrc, sv.nfreq), dtype=np.complex128)
+    if not F.items:
+        return data
+    stride = nrec if sv.mode != 'fixed' else 0
+    Rms = _receiverMatrices(sv, F.ownedFreqs)
+    devs, items = _storedItems(prob.system, F)
+
+    def one(ws, op, ifreq, c0, c1):
+        k = c1 - c0
+        sl, ex = F.slice(ifreq, c0)
+        gk = sv._gridKey(ifreq)
+        csr = _csrOnDevice(ws, Rms[gk], gk, nrec, stride, c0)
+        out = ws.buffer('out', (nrec, k))
+        _lib.wait_torch_stream(ws.device)
+        op.sampleDevice(sl.data_ptr(), k, csr, out.data_ptr(), d_exp=None if ex is None else ex.data_ptr())
+        data[:, c0:c1, ifreq] = scale * _lib.from_device(out)
+    runOnDevices(devs, items, one, factor=False)
+    return data
+
+
+def gradientFromFields(prob, F, qb, resid):
+    """The u-given branch of Jtvec (problem.py:154-162) with the forward fields read from the store: per item only the k back-sources are made and solved
+    (nsrc columns per frequency, not 2 nsrc), scaler * sum_s uF (.) uB goes into the GPU's partial gradient, and the real part of the sum is returned.
+    qb None: the back-sources of a moving receiver array, made on the device from `resid` (nrec, nsrc, nfreq)."""
+    import torch
+    F.checkCurrent(prob)
+    sv = prob.survey
+    N = prob.nrow
+    scale = F.scale
+    if not F.items:
+        g = np.zeros(N, dtype=np.complex128)
+        return (parallel.allreduce_sum(g) if prob._sharded else g).real
+    if qb is None:
+        for ifreq in F.ownedFreqs:
+            sv.adjointPlan(ifreq)
+    devs, items = _storedItems(prob.system, F)
+    add = _addOnNativeGrid(prob, scale)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        sl, ex = F.slice(ifreq, c0)
+        if ws.G is None:
+            ws.G = torch.zeros(N, dtype=torch.complex128, device=ws.device)
+        U, R = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
+        if qb is not None:
+            op.rhsFromSparseDevice(_muxTriplets((qb[ifreq],), c0, c1, Ni), R.data_ptr())
+        else:
+            plan = _planOnDevice(ws, sv, ifreq)
+            panel = _lib.to_device(resid[:, c0:c1, ifreq], ws.device, np.complex128)
+            _lib.wait_torch_stream(ws.device)
+            op.rhsFromSamplesDevice(panel.data_ptr(), k, plan, c0, c1, R.data_ptr(), rows=Ni)
+        scaler, target, finish = add(ws, op, ifreq, Ni)
+        _lib.wait_torch_stream(ws.device)
+        op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+        op.imagingAccumulateDevice(sl.data_ptr(), U.data_ptr(), k, scaler.data_ptr(), target.data_ptr(), d_exp=None if ex is None else ex.data_ptr())
+        if finish is not None:
+            finish()
+    return _sumPartials(prob, [ws.G for ws in runOnDevices(devs, items, one) if ws.G is not None]).real

@@ -277,11 +277,22 @@ class BaseDiscretization(BaseModelDependent):
             raise ArithmeticError('%d of %d right-hand sides did not reach rtol=%g' % (rc, nrhs, self.rtol))
         return self.lastInfo
 
-    def imagingAccumulateDevice(self, d_uf, d_ub, nsrc, d_scaler, d_g):
-        'G += scaler * sum_s UF[s] * UB[s] on the device (zero-lag imaging condition, problem.py:152); all device pointers'
+    def imagingAccumulateDevice(self, d_uf, d_ub, nsrc, d_scaler, d_g, d_exp=None):
+        """G += scaler * sum_s UF[s] * UB[s] on the device (zero-lag imaging condition, problem.py:152); all device pointers.  d_exp given: UF is a
+        complex64 store with those column exponents (packDevice)."""
         lib = _lib.load()
+        if d_exp is not None:
+            _lib.check(lib.helm_imaging_accumulate_c64_device(self.handle, ctypes.c_void_p(d_uf), ctypes.c_void_p(d_exp), ctypes.c_void_p(d_ub), int(nsrc),
+                                                              ctypes.c_void_p(d_scaler), ctypes.c_void_p(d_g)), self.handle)
+            return
         _lib.check(lib.helm_imaging_accumulate_device(self.handle, ctypes.c_void_p(d_uf), ctypes.c_void_p(d_ub), int(nsrc),
                                                       ctypes.c_void_p(d_scaler), ctypes.c_void_p(d_g)), self.handle)
+
+    def packDevice(self, d_u, nsrc, d_out, d_exp, rows=None):
+        """The complex64 store of the wavefields d_u ([nsrc][rows] complex128): d_out [nsrc][rows] complex64 values x * 2^-e_s, d_exp the nsrc int32 column
+        exponents e_s (fieldstore.pack_reference states the format).  All device pointers; returns when both are complete."""
+        rows = int(self.nrow if rows is None else rows)
+        _lib.check(_lib.load().helm_pack_c64_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), rows, ctypes.c_void_p(d_out), ctypes.c_void_p(d_exp)), self.handle)
 
     def rhsFromSparseDevice(self, q, d_rhs, layout='rhs'):
         '''Fill the device buffer d_rhs ([ncols][nrow] complex128; layout 'node': [nrow][ncols]) from the scipy-sparse right-hand-side
@@ -327,14 +338,19 @@ class BaseDiscretization(BaseModelDependent):
                                                  ctypes.c_void_p(bits.data_ptr()), int(coo.shape[0]), int(coo.shape[1])), self.handle)
         return bits
 
-    def sampleDevice(self, d_u, nsrc, csr_dev, d_out):
+    def sampleDevice(self, d_u, nsrc, csr_dev, d_out, d_exp=None):
         """d_out[nrec][nsrc] = R u for the CSR receiver matrix uploaded by the caller: csr_dev = (rowptr, col, val, nrec[, row_stride]) device tensors.
         row_stride (default 0: one array for every source) = nrec: source s samples row s * nrec + r of the stacked matrices of a moving array
-        (survey.stackedReceivers; `rowptr` then starts at the first source of the batch)."""
+        (survey.stackedReceivers; `rowptr` then starts at the first source of the batch).  d_exp given: d_u is a complex64 store with those column
+        exponents (packDevice)."""
         rowptr, col, val, nrec = csr_dev[:4]
         stride = int(csr_dev[4]) if len(csr_dev) > 4 else 0
         lib = _lib.load()
-        if stride == 0:
+        if d_exp is not None:
+            _lib.check(lib.helm_sample_rows_c64_device(self.handle, ctypes.c_void_p(d_u), ctypes.c_void_p(d_exp), int(nsrc), int(self.nrow),
+                                                       ctypes.c_void_p(rowptr.data_ptr()), ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()),
+                                                       int(nrec), stride, 1.0, 0.0, 0.0, 0.0, ctypes.c_void_p(d_out)), self.handle)
+        elif stride == 0:
             _lib.check(lib.helm_sample_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), int(self.nrow), ctypes.c_void_p(rowptr.data_ptr()),
                                               ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()), int(nrec),
                                               ctypes.c_void_p(d_out)), self.handle)

@@ -187,13 +187,23 @@ class MiniZephyr25D(BaseDiscretization, DiscretizationWrapper):
     def rhsSupportFromSparse(self, q):
         return self.subProblems[0].rhsSupportFromSparse(q)
 
-    def imagingAccumulateDevice(self, d_uf, d_ub, nsrc, d_scaler, d_g):
-        'the imaging kernel reads no operator data: any ky handle on this GPU serves (one that is alive, if there is one)'
+    def _liveSub(self):
+        'a ky operator for a kernel that reads no operator data (imaging, sampling, packing): any handle on this GPU serves -- one that is alive, if there is one'
         subs = self.subProblems
-        sub = next((s for s in subs if s.factors), subs[0])
-        sub.imagingAccumulateDevice(d_uf, d_ub, nsrc, d_scaler, d_g)
+        return next((s for s in subs if s.factors), subs[0])
+
+    def imagingAccumulateDevice(self, d_uf, d_ub, nsrc, d_scaler, d_g, d_exp=None):
+        sub = self._liveSub()
+        sub.imagingAccumulateDevice(d_uf, d_ub, nsrc, d_scaler, d_g, d_exp=d_exp)
         if self.kyRelease:
             del sub.factors
+
+    def sampleDevice(self, d_u, nsrc, csr_dev, d_out, d_exp=None):
+        'receiver samples of wavefields that are the ky SUM already (device_survey.dpredFromFields: solveDevice formed it in the store)'
+        self._liveSub().sampleDevice(d_u, nsrc, csr_dev, d_out, d_exp=d_exp)
+
+    def packDevice(self, d_u, nsrc, d_out, d_exp, rows=None):
+        self._liveSub().packDevice(d_u, nsrc, d_out, d_exp, rows=rows)
 
     def _kyLoop(self, each):
         'each(k, sub) for k = 0 .. nky-1 in the order of ky_schedule, the factorisations of the next group enqueued while the current one is being solved'

@@ -12,7 +12,8 @@ frequencies than GPUs -- and the per-GPU partial gradients / data panels are sum
 process per GPU (`shardFreqs`, default on when torch.distributed is initialised): frequencies are sharded
 over ranks and the only collective is one all-reduce of the gradient (problem.py:152,162 sum over
 frequencies) or of the receiver data.  The device-resident loops of `dpred` and the mux `Jtvec` (item dealing,
-per-worker buffers, partial gradients) live in `zephyr_amd.device_survey`; `_dpredDevice` / `_JtvecDevice` delegate to it.
+per-worker buffers, partial gradients) live in `zephyr_amd.device_survey`; `_dpredDevice` / `_JtvecDevice` delegate to it.  `fieldsDevice` leaves the
+forward wavefields in HBM (`zephyr_amd.fieldstore.DeviceFields`) for `survey.dpred(m, u=F)` and `Jtvec(m, v, u=F)`.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -24,6 +25,7 @@ from .survey import HelmBaseSurvey, HelmMultiGridSurvey, Helm2DSurvey, Helm25DSu
 from . import parallel
 from . import device_survey
 from . import _lib
+from .fieldstore import DeviceFields
 
 EPS = 1e-15
 
@@ -44,6 +46,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         'SystemWrapper':    (True,     None,        None),
         'shardFreqs':       (False,    '_shard',    bool),
         'hostGradient':     (False,    '_hostGradient', bool),    # force the numpy imaging condition
+        'fieldsDtype':      (False,    '_fieldsDtype', str),      # what fieldsDevice() keeps: 'complex128' (default) or 'complex64' (half the memory)
     }
 
     surveyPair = HelmBaseSurvey
@@ -82,6 +85,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             raise Exception('Class %s doesn\'t know how to update with model of type %s' % (self.__class__.__name__, type(m)))
 
     def clearCache(self):
+        self._modelStamp = self.__dict__.get('_modelStamp', 0) + 1        # (what a DeviceFields remembers: fields of an earlier model are refused)
         sysw = self.__dict__.get('_system', None)
         if sysw is not None:
             del sysw.factors
@@ -162,6 +166,25 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         qf = self.survey.getSources()
         return [pp(u) for u, pp in zip(self.system * qf, self.survey.postProcessors)]
 
+    @property
+    def fieldsDtype(self):
+        "config key: the number format of the store fieldsDevice() fills -- 'complex128' (default), or 'complex64' with one power-of-two scale per column"
+        return getattr(self, '_fieldsDtype', 'complex128')
+
+    def fieldsDevice(self, m=None):
+        """The forward wavefields of the owned frequencies, solved once and LEFT in HBM: a fieldstore.DeviceFields to hand to `survey.dpred(m, u=F)` and
+        `Jtvec(m, v, u=F)`, which then solve nsrc columns per frequency between them and the back-propagation instead of re-solving the forward fields.
+        `F[ifreq]` downloads what `fields()[ifreq]` would be.  Single-grid surveys (2-D, and 2.5-D with the ky sum on the device); without the device
+        path (no GPU, hostGradient, a host ky reduction) this raises and `fields()` is the route."""
+        if not self.ispaired:
+            raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
+        self.updateModel(m)
+        if isinstance(self.survey, HelmMultiGridSurvey):
+            return device_survey.fields(self, [], self.fieldsDtype)            # (raises NotImplementedError with the reason)
+        if not self._deviceGradientAvailable():
+            raise RuntimeError('fieldsDevice needs the device path (GPU operators with solveDevice, no hostGradient, the ky sum on the device): use fields()')
+        return device_survey.fields(self, self.ownedFreqs, self.fieldsDtype)
+
     # ---- sensitivity times vector ------------------------------------------------------------------------
     def Jvec(self, m=None, v=None, u=None):
         """Data perturbation for a model perturbation v (problem.py:87-122): one virtual source
@@ -195,7 +218,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         u is None: "mux" branch -- forward and back-propagated sources are stacked column-wise and
         solved together per frequency; the result is complex (no .real), as in the reference.
         u given (list of forward fields per frequency): only the back-propagation is solved and
-        the real part is returned.
+        the real part is returned.  u a DeviceFields (fieldsDevice): the same with the forward fields
+        read where they were solved, in HBM.
         """
         if not self.ispaired:
             raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
@@ -206,6 +230,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         nsrc = sv.nsrc
         resid = np.asarray(v).reshape((sv.nrec, sv.nsrc, sv.nfreq))
         owned = self.ownedFreqs
+        if isinstance(u, DeviceFields):
+            # forward fields left in HBM by fieldsDevice(): only the back-propagation is solved, on the store's own items
+            u.checkCurrent(self)
+            return device_survey.gradientFromFields(self, u, sv.getResidualSources(resid) if sv.mode == 'fixed' else None, resid)
         if u is None and self._deviceGradientAvailable():
             # a fixed array keeps its host-built back-sources (sparse, sent up as triplets); those of an array that moves with the source are made on the
             # device from the residual samples (helm_rhs_from_samples_device): qb = None

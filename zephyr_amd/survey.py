@@ -10,6 +10,8 @@ import scipy.sparse as sp
 from .config import BaseSCCache
 from .source import SparseKaiserSource
 from . import parallel
+from . import device_survey
+from .fieldstore import DeviceFields
 
 
 class HelmBaseSurvey(BaseSCCache):
@@ -235,6 +237,13 @@ class HelmBaseSurvey(BaseSCCache):
                 data = self.prob._dpredDevice(owned)          # wavefields never leave HBM
             else:
                 data = self._lazyProjectFields(self.prob.lazyFields(m), owned)
+            if self.prob._sharded:
+                data = parallel.allreduce_sum(data)
+            return data.ravel()
+        if isinstance(u, DeviceFields):
+            # forward fields left in HBM by prob.fieldsDevice(): sampled there, only the receiver panels come back
+            self.prob.updateModel(m)
+            data = device_survey.dpredFromFields(self.prob, u)
             if self.prob._sharded:
                 data = parallel.allreduce_sum(data)
             return data.ravel()
