@@ -364,11 +364,13 @@ int helm_debug_stall_watch(int start, double *worst_gap_ms, long long *gaps_over
  * interface; the measured-and-rejected ones are gone, HISTORY.md has what they measured).  Every field can still be given through the
  * environment variable named beside it -- looked at when an API call that starts work is entered (create, assemble, prefactor, solve, apply,
  * get_tuning), by the calling thread and nowhere below it, so a test may flip one BETWEEN two calls, never during one -- and helm_set_tuning
- * replaces the lot for the process (NULL: back to defaults + environment).  Values are clamped to the ranges the code can run with whichever
- * way they arrive (nd_leaf >= 2, nd_plans >= 1, nd_ws_gb > 0, nd_stable_safety >= 1, ws_slots 1..4, pf_prio -1/0/1, mg3_omega in (0, 2]).  Process-wide, like the reference's module-level defaults
+ * replaces the lot for the process (NULL: back to defaults + environment): while such a structure is in force EVERY field follows it and not the
+ * environment, mg3_coarse, mg3_nd_leaf, mg3_bt_twist and mg3_beta (environment-only switches before they joined the structure) included.
+ * Values are clamped to the ranges the code can run with whichever way they arrive (nd_leaf >= 2, nd_plans >= 1, nd_ws_gb > 0, nd_stable_safety >= 1, ws_slots 1..4, pf_prio -1/0/1, mg3_omega in (0, 2], mg3_coarse 0..2,
+ * mg3_nd_leaf >= 2, mg3_beta >= 0 and finite).  Process-wide, like the reference's module-level defaults
  * (distributors.py:28-34); not per handle.  Diagnostics that change no result and no speed stay environment-only: HELM_ND_TRACE,
  * HELM_ND_DEBUG, HELM_GEMM_LOG, HELM_MG3_TRACE, HELM_ALLOC_TRACE, and the test hooks behind HELM_TESTING=1 (HELM_ND_POISON,
- * HELM_ND_SUPPORT_CHECK, HELM_LEAF_DBG, HELM_ND_INJECT_*). */
+ * HELM_ND_SUPPORT_CHECK, HELM_LEAF_DBG, HELM_ND_INJECT_*, HELM_MG3_DEPTH_FORCE_DEEPER, HELM_MG3_DEPTH_SETUP_SCALE, HELM_MG3_KEEP_CAP). */
 typedef struct helm_tuning {
     /* 2-D sparse direct path */
     int    nd_leaf;            /* HELM_ND_LEAF           8     regions with both sides <= this are eliminated whole (leaf fronts) */
@@ -402,6 +404,10 @@ typedef struct helm_tuning {
     int    mg3_otf;            /* HELM_MG3_OTF           1     27-point apply rebuilds its coefficients from c, rho and the PML profiles (1: from 4 right-hand sides per workgroup up, 2: always) */
     int    mg3_f32;            /* HELM_MG3_F32           1     the layer-preserving cycle keeps the work vectors of its finest level in complex64 (input, result and every coarser level stay complex128) */
     double mg3_omega;          /* HELM_MG3_OMEGA         0.9   Jacobi damping of the smoother */
+    int    mg3_coarse;         /* HELM_MG3_COARSE        0     direct solver of the last layer-preserving level: 0 the cheaper one, 1 column dissection (environment: nd), 2 plane-by-plane elimination (bt) */
+    int    mg3_nd_leaf;        /* HELM_MG3_ND_LEAF       2     leaf size of that column dissection */
+    int    mg3_bt_twist;       /* HELM_MG3_BT_TWIST      1     the plane-by-plane elimination runs from both ends and meets in the middle (0: one chain) */
+    double mg3_beta;           /* HELM_MG3_BETA          0     complex shift of the preconditioner; 0: min(8, 0.6 (ppw / 10)^2) for the standard cycle, 0.1 for the layer-preserving one */
     /* host-side waits */
     double sync_spin_ms;       /* HELM_SYNC_SPIN_MS      0     a wait of the library polls for this long before it blocks on the runtime's interrupt (saves the 20-50 us wake-up of each
                                                                wait; costs a CPU per waiting thread -- leave it off under a container CPU quota, where a spinning thread spends the budget the
@@ -508,7 +514,7 @@ typedef struct helm_nm_stage {
 int helm_debug_nm_stage(helm_nm_stage *p);
 int helm_debug_inverse_bench(int device, int n, const double *A, int reps, int recurse_n, double *ms_out);
 
-/* --- diagnostics of the 3-D multigrid hierarchy (host only, no GPU needed; zephyr_amd/csrc/mg3d.hip) ------------------ */
+/* --- diagnostics of the 3-D multigrid hierarchy (host only, no GPU needed; zephyr_amd/csrc/mg3_keep.hip) ------------------ */
 /* One axis of n nodes (spacing h, npml absorbing-layer nodes at each end, damping amplitude cpml) coarsened `level` times by the
  * layer-preserving rule (all layer nodes kept, the interior halved).  Returns the node count nc of that level (< 0: bad arguments)
  * and fills whichever outputs are not NULL: x[nc] coordinates, lay[nc] layer flags, lap[3 nc] complex factors L(-1), L(0), L(+1)

@@ -72,6 +72,7 @@ def test_tuning_struct_round_trip(helm_lib, monkeypatch):
     t = _lib.tuning()
     assert (t.nd_leaf, t.nd_ws_gb, t.nd_sparse_rhs, t.nd_gjstep_min, t.nd_plans, t.ws_slots, t.mg3_keep_levels) == (8, 32.0, 1, 128, 6, 3, -1)
     assert t.mg3_omega == 0.9 and t.nd_stable_safety == 8.0 and t.sync_spin_ms == 0.0      # first and last doubles: the layouts agree end to end
+    assert (t.mg3_coarse, t.mg3_nd_leaf, t.mg3_bt_twist, t.mg3_beta) == (0, 2, 1, 0.0)
     monkeypatch.setenv('HELM_ND_LEAF', '6')
     monkeypatch.setenv('HELM_MG3_OMEGA', '0.7')
     t = _lib.tuning()
@@ -90,6 +91,30 @@ def test_tuning_struct_round_trip(helm_lib, monkeypatch):
     u = _lib.tuning()
     assert (u.nd_leaf, u.nd_plans, u.ws_slots, u.pf_prio) == (2, 1, 1, 0) and u.nd_ws_gb == 32.0 and u.nd_stable_safety == 1.0 and u.mg3_omega == 0.9
     _lib.set_tuning(None)
+
+
+def test_mg3_switches_are_tuning_fields(helm_lib, monkeypatch):
+    """The four 3-D multigrid switches that used to be read from the environment below the API (coarse solver, its leaf size, the twisted
+    elimination, the shift) are fields of helm_tuning: parsed and clamped where every other field is.  Host-only: no GPU call."""
+    from zephyr_amd import _lib
+    for k in list(os.environ):
+        if k.startswith('HELM_'):
+            monkeypatch.delenv(k)
+    _lib.set_tuning(None)
+    t = _lib.tuning()
+    assert (t.mg3_coarse, t.mg3_nd_leaf, t.mg3_bt_twist, t.mg3_beta) == (0, 2, 1, 0.0)
+    for k, v in (('HELM_MG3_COARSE', 'bt'), ('HELM_MG3_ND_LEAF', '4'), ('HELM_MG3_BT_TWIST', '0'), ('HELM_MG3_BETA', '3')):
+        monkeypatch.setenv(k, v)
+    t = _lib.tuning()
+    assert (t.mg3_coarse, t.mg3_nd_leaf, t.mg3_bt_twist, t.mg3_beta) == (2, 4, 0, 3.0)
+    monkeypatch.setenv('HELM_MG3_COARSE', 'nd')
+    assert _lib.tuning().mg3_coarse == 1
+    t.mg3_nd_leaf = 1
+    _lib.set_tuning(t)
+    try:
+        assert _lib.tuning().mg3_nd_leaf == 2
+    finally:
+        _lib.set_tuning(None)
 
 
 def test_code_object_is_gfx950():

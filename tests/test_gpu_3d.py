@@ -197,6 +197,7 @@ def test_3d_retreat_to_the_standard_cycle(helm_lib, monkeypatch):
     op = za.Helm3D(cfg)
     u = op * q
     its = max(i['iterations'] for i in op.lastInfo)
+    monkeypatch.setenv('HELM_TESTING', '1')
     monkeypatch.setenv('HELM_MG3_KEEP_CAP', '3')
     op2 = za.Helm3D(cfg)
     u2 = op2 * q

@@ -49,7 +49,7 @@ def test_config5_grid_one_frequency_properties(helm_lib, monkeypatch, coarse):
 
 
 @pytest.fixture(scope='module')
-def small_lu():
+def small_lu_factors():
     """layered 30 x 32 x 28 model at 8 Hz (22 points per wavelength: ONE layer-preserving coarsening by the 10-points rule, so a forced
     second one solves a 5.6-points level directly -- the regime of the depth model), sparse LU of the oracle's matrix"""
     import scipy.sparse.linalg as spla
@@ -57,15 +57,22 @@ def small_lu():
     iz = np.arange(nz)[:, None, None]
     c = (1800. + 25. * iz + 150. * (iz > 18)) * np.ones((nz, ny, nx))
     rho = 1000. + 300. * (iz > 18) * np.ones((nz, ny, nx))
+    A = h3.coefficients_to_csr3(h3.helm3d_coefficients(nz, ny, nx, c, rho, f, dx=10., nPML=6)).tocsc()
+    cfg = dict(nx=nx, ny=ny, nz=nz, dx=10., c=c, rho=rho, freq=f, nPML=6, rtol=1e-10, maxit=20000, method='mg')
+    return cfg, spla.splu(A)
+
+
+@pytest.fixture(scope='module')
+def small_lu(small_lu_factors):
+    """three point sources on that grid and the LU's wavefields"""
+    cfg, lu = small_lu_factors
+    nz, ny, nx = cfg['nz'], cfg['ny'], cfg['nx']
     N = nz * ny * nx
     q = np.zeros((N, 3), complex)
     q[(15 * ny + 12) * nx + 14, 0] = 1.0
     q[(9 * ny + 18) * nx + 20, 1] = 1.0 - 0.5j
     q[(20 * ny + 9) * nx + 8, 2] = 2.0j
-    A = h3.coefficients_to_csr3(h3.helm3d_coefficients(nz, ny, nx, c, rho, f, dx=10., nPML=6)).tocsc()
-    ref = np.conj(spla.splu(A).solve(q))
-    cfg = dict(nx=nx, ny=ny, nz=nz, dx=10., c=c, rho=rho, freq=f, nPML=6, rtol=1e-10, maxit=20000, method='mg')
-    return cfg, q, ref
+    return cfg, q, np.conj(lu.solve(q))
 
 
 @pytest.mark.parametrize('env', [
@@ -91,6 +98,8 @@ def test_every_depth_branch_matches_sparse_lu(helm_lib, monkeypatch, small_lu, e
     cfg, q, ref = small_lu
     for k, v in env.items():
         monkeypatch.setenv(k, v)
+    if 'HELM_MG3_DEPTH_FORCE_DEEPER' in env:
+        monkeypatch.setenv('HELM_TESTING', '1')                     # (a test hook)
     monkeypatch.setenv('HELM_MG3_KEEP', '2')                        # a hierarchy that cannot be built is an error here, not a silent fallback
     op = za.Helm3D(cfg)
     u = op * q
@@ -101,12 +110,34 @@ def test_every_depth_branch_matches_sparse_lu(helm_lib, monkeypatch, small_lu, e
     del op.factors
 
 
+def test_plane_elimination_with_more_than_16_right_hand_sides(helm_lib, monkeypatch, small_lu_factors):
+    """Seventeen right-hand sides are the first width at which the plane-by-plane elimination leaves its own product kernel for the generic batched
+    GEMM: planes padded to kc * ksplit rows and kept in double precision -- the other branch of the shape that mg3_bt_shape computes for the
+    allocation and for the depth decision's budget alike."""
+    import zephyr_amd as za
+    cfg, lu = small_lu_factors
+    nz, ny, nx = cfg['nz'], cfg['ny'], cfg['nx']
+    monkeypatch.setenv('HELM_MG3_COARSE', 'bt')
+    monkeypatch.setenv('HELM_MG3_KEEP', '2')
+    q = np.zeros((nz * ny * nx, 17), complex)
+    for s in range(17):                                             # distinct interior nodes
+        q[((7 + s % 16) * ny + 9 + (5 * s) % 13) * nx + 8 + (3 * s) % 11, s] = 1.0 + 0.25j * s
+    ref = np.conj(lu.solve(q))
+    op = za.Helm3D(dict(cfg, batch=17))
+    u = op * q
+    info = op.lastInfo
+    assert all(i['status'] == 0 for i in info), info
+    assert nrm(u, ref) <= 1e-7, (nrm(u, ref), info)
+    del op.factors
+
+
 def test_depth_model_uses_what_it_measures(helm_lib, monkeypatch, small_lu, capfd):
     """The depth decision is taken from quantities timed at set-up on THIS grid (plane-inversion rate, one fine-grid apply), not from
     constants of one benchmark: with a single right-hand side and a (pretended) slow inversion it goes deeper, with many right-hand
     sides it does not -- and both hierarchies return the LU's wavefield."""
     import zephyr_amd as za
     cfg, q, ref = small_lu
+    monkeypatch.setenv('HELM_TESTING', '1')
     monkeypatch.setenv('HELM_MG3_KEEP', '2')
     monkeypatch.setenv('HELM_MG3_DEPTH_MODEL', '1')
     monkeypatch.setenv('HELM_MG3_TRACE', '1')

@@ -9,4 +9,3 @@ run HELM_MG3_OMEGA=1.0
 run HELM_MG3_OMEGA=1.1
 run HELM_MG3_OMEGA=0.9 HELM_MG3_BETA=12.0
 run HELM_MG3_OMEGA=1.0 HELM_MG3_BETA=12.0
-run HELM_MG3_OMEGA=1.0 HELM_MG3_NU1=2 HELM_MG3_NU2=1

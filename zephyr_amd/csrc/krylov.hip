@@ -360,11 +360,11 @@ int solve_block_krylov(helm_op *op, int block, const cplx *dRHS, long long rhs_l
             } else {
                 // in AUTO mode a preconditioned run that has not converged after 5000 iterations is handed to CGNR
                 int cap = (use_mg && o.method == HELM_AUTO) ? std::min(o.maxit, 5000) : o.maxit;
-                // the layer-preserving 3-D hierarchy needs tens of iterations; if it has not converged after HELM_MG3_KEEP_CAP (300) the
+                // the layer-preserving 3-D hierarchy needs tens of iterations; if it has not converged after 300 (test hook: HELM_MG3_KEEP_CAP) the
                 // frequency retreats to the standard cycle and goes on from the iterates reached
                 const bool keep3 = use_mg && op->ny > 0 && mg3_is_layer_preserving(op);
                 // (first round only: the retreat below is what the cap is for, and it is taken there)
-                if (keep3 && round == 0) cap = std::min(cap, getenv("HELM_MG3_KEEP_CAP") ? std::max(1, atoi(getenv("HELM_MG3_KEEP_CAP"))) : 300);
+                if (keep3 && round == 0) { const int hook = testing_hook("HELM_MG3_KEEP_CAP"); cap = std::min(cap, hook > 0 ? hook : 300); }
                 rc = run_bicgstab(op, block, B, cap, check_every, 25, restarts);
                 if (rc) return rc;
                 if (keep3 && round == 0) {

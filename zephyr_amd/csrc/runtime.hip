@@ -223,6 +223,9 @@ static void tuning_clamp(helm_tuning &t) {
     t.ws_slots = std::min(4, std::max(1, t.ws_slots));
     t.pf_prio = t.pf_prio > 0 ? 1 : (t.pf_prio < 0 ? -1 : 0);
     if (!(t.mg3_omega > 0) || t.mg3_omega > 2.0) t.mg3_omega = 0.9;
+    t.mg3_coarse = std::min(2, std::max(0, t.mg3_coarse));
+    t.mg3_nd_leaf = std::max(2, t.mg3_nd_leaf);
+    if (!std::isfinite(t.mg3_beta) || t.mg3_beta < 0) t.mg3_beta = 0.0;
     if (!(t.sync_spin_ms >= 0)) t.sync_spin_ms = 0.0;
     t.sync_spin_ms = std::min(t.sync_spin_ms, 60000.0);
     t.sync_sleep_us = std::min(100000, std::max(0, t.sync_sleep_us));
@@ -258,6 +261,10 @@ static helm_tuning tuning_from_env() {
     t.mg3_otf = helm_env_int("HELM_MG3_OTF", 1);
     t.mg3_f32 = helm_env_int("HELM_MG3_F32", 1);
     t.mg3_omega = tune_d("HELM_MG3_OMEGA", 0.9);
+    { const char *cs = getenv("HELM_MG3_COARSE"); t.mg3_coarse = cs && !strcmp(cs, "nd") ? 1 : (cs && !strcmp(cs, "bt") ? 2 : 0); }
+    t.mg3_nd_leaf = helm_env_int("HELM_MG3_ND_LEAF", 2);
+    t.mg3_bt_twist = helm_env_int("HELM_MG3_BT_TWIST", 1);
+    t.mg3_beta = tune_d("HELM_MG3_BETA", 0.0);
     t.sync_spin_ms = tune_d("HELM_SYNC_SPIN_MS", 0.0);
     t.sync_sleep_us = helm_env_int("HELM_SYNC_SLEEP_US", 0);
     tuning_clamp(t);
@@ -453,7 +460,7 @@ void helm_stream_release(int device, int prio, hipStream_t s) {
     hipStreamDestroy(s);
 }
 
-// idle bytes of one device (what hipMemGetInfo's "free" figure does not count although an allocation can have them: the budgets of mg3d.hip add it)
+// idle bytes of one device (what hipMemGetInfo's "free" figure does not count although an allocation can have them: mg3_available_bytes of mg3d.hip adds it)
 size_t helm_pool_idle_bytes(int device) {
     std::lock_guard<std::mutex> lk(g_pool.mu);
     auto it = g_pool.held.find(device);

@@ -1,5 +1,6 @@
 // What the units of the solve driver share (capi.hip: dispatch and the C ABI; solve_direct.hip: the direct path and helm_prefactor*; krylov.hip: the
-// Krylov drivers).  Internal to those three and to the test hook of nd_resid.hip, which reduces its partial sums the way the direct path does.
+// Krylov drivers).  Internal to those three, to the test hook of nd_resid.hip, which reduces its partial sums the way the direct path does, and to
+// mg3_depth.hip, whose test hooks go through testing_hook like theirs.
 #pragma once
 #include "helm_internal.hpp"
 #include "direct.hpp"
@@ -11,10 +12,14 @@ int helm_launch_restart_copy_mask(helm_op *op, VecPtrs w, int nrhs, const int *m
 int helm_launch_norm2(helm_op *op, const cplx *a, int nrhs);
 int helm_launch_krylov_init(helm_op *op, const cplx *bvec, VecPtrs w, int nrhs, double rtol);
 
-// fault-injection hooks of the test-suite: honoured only when the process runs with HELM_TESTING=1 (read per call: the tests flip them)
+// fault-injection and branch-forcing hooks of the test-suite: honoured only when the process runs with HELM_TESTING=1 (read per call: the tests flip them)
 inline int testing_hook(const char *name) {
     const char *t = getenv("HELM_TESTING"), *v = getenv(name);
     return t && atoi(t) != 0 && v ? atoi(v) : 0;
+}
+inline double testing_hook_d(const char *name, double d) {      // a hook with a floating-point value; d: what it is without HELM_TESTING=1
+    const char *t = getenv("HELM_TESTING"), *v = getenv(name);
+    return t && atoi(t) != 0 && v ? atof(v) : d;
 }
 // statuses of one right-hand side across the blocks / passes of a call, by severity: 0 converged < 3 at the fp64 floor (counted as solved)
 // < 1 cap / stalled < 2 breakdown
