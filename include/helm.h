@@ -23,6 +23,8 @@
  *   helm_reserve                   <- (same pool: its workers' scratch, allocated before they start)
  *   helm_imaging_accumulate_device <- zero-lag imaging condition in HelmBaseProblem.Jtvec
  *                                     zephyr/middleware/problem.py:152,162
+ *   helm_energy_accumulate_device,
+ *   helm_energy_accumulate_c64_device <- (no counterpart) HelmBaseProblem.illumination: sum_s |u_s|^2 of wavefields in HBM
  *   helm_axpby_device,
  *   helm_sample_accumulate_device  <- MiniZephyr25D.__mul__: the sum over ky sub-problems
  *                                     (`reduce(np.add, ...)`, scaled)     minizephyr.py:435-460
@@ -242,6 +244,14 @@ int helm_set_profiling(helm_op *op, int on);
 int helm_imaging_accumulate_device(helm_op *op, const void *dUF, const void *dUB, int nsrc,
                                    const void *dScaler, void *dG);
 
+/* --- illumination / diagonal pseudo-Hessian (Shin, Jang & Min 2001) --------------------- */
+/* E[i] += alpha * (W ? W[i] : 1) * sum_{s<nsrc} |U[s*ld + i]|^2,  i < N = helm_num_points(op).  U: nsrc columns of complex128, ld >= N apart, 16-byte
+ * aligned; E and W (may be NULL): N doubles, 8-byte aligned; alpha >= 0, W >= 0.  Plain fp64 without atomics, the sum over s in the order s = 0, 1, ...:
+ * the same bits on every run, and with E >= 0 on entry |result - exact| <= (nsrc + 7) 2^-53 exact per cell (2 roundings per |.|^2, nsrc - 1 additions,
+ * alpha W, its product with the sum, the addition to E).  Null pointers other than dW, nsrc < 1, ld < N, a misaligned pointer, alpha < 0 or NaN:
+ * HELM_ERR_ARG.  All device pointers; returns when E is complete. */
+int helm_energy_accumulate_device(helm_op *op, const void *dU, int nsrc, long long ld, double alpha, const void *dW, void *dE);
+
 /* --- device-resident callers: sparse sources in, receiver samples out ---------------------------------- */
 /* Dense right-hand sides from the COO triplets of the reference's sparse source matrix (survey.py:162-169,
  * source.py:213-317): R (nrhs x rows, zeroed by the call), R[col[k]][row[k]] = val[k]; no duplicate entries.
@@ -301,6 +311,9 @@ int helm_pack_c64_device(helm_op *op, const void *dU, int nsrc, long long ld, vo
 /* helm_imaging_accumulate_device with the forward field read from that store: G[i] += scaler[i] * sum_s (UF32[s][i] * 2^dExp[s]) * UB[s][i].  dUB, dScaler
  * and dG are complex128 as there; columns are N = helm_num_points(op) apart. */
 int helm_imaging_accumulate_c64_device(helm_op *op, const void *dUF32, const void *dExp, const void *dUB, int nsrc, const void *dScaler, void *dG);
+/* helm_energy_accumulate_device with U read from that store (dU32: nsrc columns of ld complex64 values, 8-byte aligned; dExp: their exponents): every
+ * component is (double)x^ * 2^e_s, exact, before it is squared, so the result is that of the complex128 kernel on the unpacked values, under the same bound. */
+int helm_energy_accumulate_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, double alpha, const void *dW, void *dE);
 /* helm_sample_rows_device with the wavefields read from that store (dU32: nsrc columns of ld complex64 values, dExp: their exponents): the other arguments,
  * the row stride and the result are those of helm_sample_rows_device. */
 int helm_sample_rows_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, const void *d_rowptr, const void *d_col,

@@ -126,6 +126,10 @@ _SIGNATURES = {
     'helm_set_profiling': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'helm_imaging_accumulate_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
                                                       ctypes.c_void_p, ctypes.c_void_p]),
+    'helm_energy_accumulate_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_double,
+                                                     ctypes.c_void_p, ctypes.c_void_p]),
+    'helm_energy_accumulate_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong,
+                                                         ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
     'helm_get_tuning': (ctypes.c_int, [ctypes.POINTER(Tuning)]),
     'helm_set_tuning': (ctypes.c_int, [ctypes.POINTER(Tuning)]),
     'helm_pool_spares': (ctypes.c_int, [ctypes.c_int, ctypes.c_int]),

@@ -817,3 +817,15 @@ extern "C" int helm_imaging_accumulate_device(helm_op *op, const void *dUF, cons
     HIP_TRY(op, hipStreamSynchronize(op->stream));
     return HELM_OK;
 }
+
+// E += alpha W sum_s |U_s|^2 (the illumination of HelmBaseProblem.illumination).  Returns when E is complete.
+extern "C" int helm_energy_accumulate_device(helm_op *op, const void *dU, int nsrc, long long ld, double alpha, const void *dW, void *dE) {
+    helm_tuning_refresh();
+    if (!op || !dU || !dE || nsrc < 1 || ld < op->N || !(alpha >= 0.0)) return HELM_ERR_ARG;       // (!(alpha >= 0): negative or NaN)
+    if ((((uintptr_t)dU) & 15) || (((uintptr_t)dE) & 7) || (((uintptr_t)dW) & 7)) return HELM_ERR_ARG;       // (16-byte loads of U; doubles)
+    HIP_TRY(op, hipSetDevice(op->device));
+    int rc = helm_launch_energy(op, (const cplx *)dU, nsrc, ld, alpha, (const double *)dW, (double *)dE);
+    if (rc) return rc;
+    HIP_TRY(op, hipStreamSynchronize(op->stream));
+    return HELM_OK;
+}

@@ -2,7 +2,7 @@
 // complex64 values x * 2^-e_s with ONE power-of-two scale per column, e_s the binary exponent of the column's largest component
 // (2^e_s <= max_i max(|Re|, |Im|) < 2^(e_s+1), clamped to +-1021; 0 for a zero column).  The scaling is exact, so the only rounding is the conversion to
 // fp32 (2^-24 relative where the scaled value is a normal fp32 number), and fields of any magnitude survive where a plain conversion would overflow or
-// flush.  A consumer reads (double)x^ * 2^e_s, exact again.  Three kernels: the pack, and the imaging and sampling loops of kernels.hip with the forward
+// flush.  A consumer reads (double)x^ * 2^e_s, exact again.  Four kernels: the pack, and the imaging, energy and sampling loops of kernels.hip with the forward
 // field read in this format.  The complex128 paths never come here.
 #include "helm_internal.hpp"
 #include <algorithm>
@@ -83,6 +83,37 @@ __global__ __launch_bounds__(256) void k_imaging_c64(const cplxf32 *__restrict__
     }
 }
 
+// E[i] += alpha (W ? W[i] : 1) sum_s |U32[s ld + i] * 2^e_s|^2: k_energy (kernels.hip) with the field read from the complex64 store, 8-byte loads.  Each
+// component is scaled in fp64 before it is squared (exact, and 2^(2 e_s) alone would overflow where the field does not), so the sum is k_energy's sum of
+// the unpacked field, term for term.
+__global__ __launch_bounds__(256) void k_energy_c64(const cplxf32 *__restrict__ U, const int *__restrict__ exps, int nsrc, long long ld, double alpha,
+                                                    const double *__restrict__ W, double *__restrict__ E, long long N) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        const cplxf32 *col = U + i;
+        double acc = 0.0;
+        int s = 0;
+        for (; s + HELM_ENERGY_UNROLL <= nsrc; s += HELM_ENERGY_UNROLL) {
+            cplxf32 f[HELM_ENERGY_UNROLL];
+#pragma unroll
+            for (int j = 0; j < HELM_ENERGY_UNROLL; ++j) f[j] = col[(long long)(s + j) * ld];
+#pragma unroll
+            for (int j = 0; j < HELM_ENERGY_UNROLL; ++j) {
+                const double sc = pow2(exps[s + j]);
+                const double re = (double)f[j].x * sc, im = (double)f[j].y * sc;
+                acc += re * re + im * im;
+            }
+        }
+        for (; s < nsrc; ++s) {
+            const cplxf32 f = col[(long long)s * ld];
+            const double sc = pow2(exps[s]);
+            const double re = (double)f.x * sc, im = (double)f.y * sc;
+            acc += re * re + im * im;
+        }
+        const double w = W ? alpha * W[i] : alpha;
+        E[i] = E[i] + w * acc;
+    }
+}
+
 // k_sample_acc (kernels.hip) with U read from the complex64 store: out[r][s] = beta out[r][s] + alpha sum_k val[k] (U32[s][col[k]] * 2^e_s) over the
 // entries of sparse row r + s * row_stride
 __global__ __launch_bounds__(256) void k_sample_acc_c64(const cplxf32 *__restrict__ U, const int *__restrict__ exps, int nsrc, long long ld,
@@ -129,6 +160,19 @@ extern "C" int helm_imaging_accumulate_c64_device(helm_op *op, const void *dUF32
     const unsigned blocks = (unsigned)std::min<long long>((op->N + 255) / 256, 1 << 20);
     HELM_LAUNCH(k_imaging_c64, dim3(blocks), dim3(256), 0, op->stream, (const cplxf32 *)dUF32, (const int *)dExp, (const cplx *)dUB, nsrc,
                 (const cplx *)dScaler, (cplx *)dG, op->N);
+    HIP_TRY(op, hipGetLastError());
+    HIP_TRY(op, hipStreamSynchronize(op->stream));
+    return HELM_OK;
+}
+
+extern "C" int helm_energy_accumulate_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, double alpha, const void *dW, void *dE) {
+    helm_tuning_refresh();
+    if (!op || !dU32 || !dExp || !dE || nsrc < 1 || ld < op->N || !(alpha >= 0.0)) return HELM_ERR_ARG;       // (!(alpha >= 0): negative or NaN)
+    if ((((uintptr_t)dU32) & 7) || (((uintptr_t)dExp) & 3) || (((uintptr_t)dE) & 7) || (((uintptr_t)dW) & 7)) return HELM_ERR_ARG;       // (8-byte loads of U32; doubles)
+    HIP_TRY(op, hipSetDevice(op->device));
+    const unsigned blocks = (unsigned)std::min<long long>((op->N + 255) / 256, HELM_ENERGY_MAX_BLOCKS);
+    HELM_LAUNCH(k_energy_c64, dim3(blocks), dim3(256), 0, op->stream, (const cplxf32 *)dU32, (const int *)dExp, nsrc, ld, alpha, (const double *)dW,
+                (double *)dE, op->N);
     HIP_TRY(op, hipGetLastError());
     HIP_TRY(op, hipStreamSynchronize(op->stream));
     return HELM_OK;

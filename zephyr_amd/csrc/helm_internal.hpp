@@ -362,6 +362,11 @@ int helm_launch_prep_rhs_rs(helm_op *op, const cplx *dRHS, long long rhs_ld, lon
                             cplx *out, long long out_ld, long long out_off, int nrhs);
 int helm_launch_prep_rhs(helm_op *op, const cplx *dRHS, long long rhs_ld, long long row_off, cplx premul, const cplx *sub, cplx *out, int nrhs); // out = premul*rhs - sub
 int helm_launch_imaging(helm_op *op, const cplx *uf, const cplx *ub, int nsrc, const cplx *scaler, cplx *g);
+// the illumination kernels (k_energy in kernels.hip, k_energy_c64 in fieldstore.hip): columns loaded per lane before the first use, and the grid cap of
+// their grid-stride loop (8 workgroups of 256 lanes per CU on 256 CUs)
+#define HELM_ENERGY_UNROLL 8
+#define HELM_ENERGY_MAX_BLOCKS 2048
+int helm_launch_energy(helm_op *op, const cplx *U, int nsrc, long long ld, double alpha, const double *W, double *E);     // E += alpha W sum_s |U_s|^2
 int helm_launch_zero(helm_op *op, cplx *p, long long n);
 int helm_launch_rhs_from_coo(helm_op *op, const long long *row, const int *col, const cplx *val, long long nnz, cplx *R, int nrhs, long long rows, int node_major = 0);
 int helm_launch_sample(helm_op *op, const cplx *U, int nsrc, long long ld, const long long *rowptr, const long long *col, const cplx *val, int nrec, cplx *out);

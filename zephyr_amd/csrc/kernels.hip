@@ -518,6 +518,31 @@ __global__ __launch_bounds__(256) void k_imaging(const cplx *__restrict__ uf, co
     }
 }
 
+// E[i] += alpha (W ? W[i] : 1) sum_s |U[s ld + i]|^2: one lane per cell, the sum over s in the order s = 0, 1, ...  (no atomics: the same bits on every run).
+// A pure read stream of nsrc N values against N doubles of read-modify-write: HELM_ENERGY_UNROLL independent 16-byte loads are issued before the first
+// square, which at one 256-lane workgroup per 256 cells and a grid capped at ENERGY_MAX_BLOCKS keeps 32 KB per workgroup in flight.
+__global__ __launch_bounds__(256) void k_energy(const cplx *__restrict__ U, int nsrc, long long ld, double alpha, const double *__restrict__ W,
+                                                double *__restrict__ E, long long N) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        const cplx *col = U + i;
+        double acc = 0.0;
+        int s = 0;
+        for (; s + HELM_ENERGY_UNROLL <= nsrc; s += HELM_ENERGY_UNROLL) {
+            cplx x[HELM_ENERGY_UNROLL];
+#pragma unroll
+            for (int j = 0; j < HELM_ENERGY_UNROLL; ++j) x[j] = col[(long long)(s + j) * ld];
+#pragma unroll
+            for (int j = 0; j < HELM_ENERGY_UNROLL; ++j) acc += x[j].x * x[j].x + x[j].y * x[j].y;
+        }
+        for (; s < nsrc; ++s) {
+            const cplx x = col[(long long)s * ld];
+            acc += x.x * x.x + x.y * x.y;
+        }
+        const double w = W ? alpha * W[i] : alpha;
+        E[i] = E[i] + w * acc;
+    }
+}
+
 // ------------------------------------------------------------------------------------------
 // finalize: one workgroup per right-hand side sums the per-workgroup partials in a fixed order
 // (bitwise reproducible) and advances the scalar recurrences.
@@ -1060,6 +1085,13 @@ int helm_launch_zero(helm_op *op, cplx *p, long long n) {
 
 int helm_launch_imaging(helm_op *op, const cplx *uf, const cplx *ub, int nsrc, const cplx *scaler, cplx *g) {
     HELM_LAUNCH(k_imaging, dim3(vec_blocks(op->N)), dim3(256), 0, op->stream, uf, ub, nsrc, scaler, g, op->N);
+    HIP_TRY(op, hipGetLastError());
+    return HELM_OK;
+}
+
+int helm_launch_energy(helm_op *op, const cplx *U, int nsrc, long long ld, double alpha, const double *W, double *E) {
+    const unsigned blocks = (unsigned)std::min<long long>((op->N + 255) / 256, HELM_ENERGY_MAX_BLOCKS);
+    HELM_LAUNCH(k_energy, dim3(blocks), dim3(256), 0, op->stream, U, nsrc, ld, alpha, W, E, op->N);
     HIP_TRY(op, hipGetLastError());
     return HELM_OK;
 }

@@ -6,7 +6,8 @@ the worker thread of its GPU with the next item's factorisation started ahead of
 [qf | qb], solves and adds its imaging sum to the worker's partial gradient by one of two adding steps, chosen once per call.
 
 The same loop serves forward fields that outlive a call (`fieldstore.DeviceFields`, at the end of the module): `fields` solves them into a store,
-`dpredFromFields` samples the store and `gradientFromFields` images against it, both over the items the store recorded.
+`dpredFromFields` samples the store and `gradientFromFields` images against it, both over the items the store recorded.  `illumination` and
+`illuminationFromFields` (last section) are the same two loops again with the energy kernel in the place of the imaging kernel and a float64 partial.
 
 Three rules hold everywhere below.
 
@@ -29,11 +30,12 @@ from . import parallel
 
 class Workspace(object):
     """Device memory of one worker on one GPU for one call of dpred / Jtvec: named complex128 buffers whose storage only grows, the constants that
-    are uploaded once (`cached`), and the worker's partial gradient `G`."""
+    are uploaded once (`cached`), the worker's partial gradient `G` and its partial illumination `H`."""
 
     def __init__(self, device):
         self.device = device            # (a torch.device)
         self.G = None                   # (the partial gradient of this worker and GPU: made on first use by the gradient pipeline)
+        self.H = None                   # (its partial illumination, float64 (N,) or (nfreq, N): made on first use by the illumination pipeline)
         self._storage = {}
         self._constants = {}
 
@@ -464,3 +466,106 @@ def gradientFromFields(prob, F, qb, resid):
         if finish is not None:
             finish()
     return _sumPartials(prob, [ws.G for ws in runOnDevices(devs, items, one) if ws.G is not None]).real
+
+
+# ---- illumination / diagonal pseudo-Hessian ---------------------------------------------------------------------------------------------------
+# H = sum_f w_f (.) sum_s |u_s|^2 of wavefields that are in HBM anyway: `illumination` solves them into the workspace and drops them,
+# `illuminationFromFields` reads a store.  One kernel per item (helm_energy_accumulate_device, or its complex64 form) adds alpha * W (.) sum_s |U_s|^2 to
+# the worker's float64 partial `ws.H`; the store and the workspace hold the unscaled solves, so |scaleTerm|^2 is part of alpha.
+
+def _energyWeight(prob, kind, scale, freqs):
+    """step(ws, op, ifreq) -> (alpha, W): what an item's energy kernel multiplies its sum by, alpha a float and W a float64 device tensor or None.
+    'energy': |scale|^2 and no array.  'pseudoHessian': |gradientScaler|^2 |scale|^2 = omega^4 / |c|^6 |scale|^2 -- with the problem's own scaler
+    W = |1 / c^3|^2 is made once per worker from the cached inv_c3 of _addOnNativeGrid and omega^4 |scale|^2 goes into alpha (no torch work per item);
+    otherwise |prob.gradientScaler(ifreq)|^2 is made here, on the calling thread, and uploaded once per worker and frequency.  A step may enqueue torch work;
+    the item body issues the wait_torch_stream."""
+    a2 = scale.real * scale.real + scale.imag * scale.imag
+    if kind == 'energy':
+        return lambda ws, op, ifreq: (a2, None)
+    sv = prob.survey
+    if prob._plainGradientScaler():
+        def step(ws, op, ifreq):
+            cm = op.c
+            inv = ws.cached(('inv_c3', id(cm)), lambda: _inverseCube(cm, ws.device), keep=cm)
+            W = ws.cached(('abs2_inv_c3', id(cm)), lambda: inv.real * inv.real + inv.imag * inv.imag, keep=cm)
+            omega = 2 * np.pi * sv.freqs[ifreq]
+            return (omega ** 4) * a2, W
+        return step
+    host = {}
+    for ifreq in freqs:
+        w = np.asarray(prob.gradientScaler(ifreq)).ravel()
+        host[ifreq] = np.square(w.real) + np.square(w.imag)
+
+    def step(ws, op, ifreq):
+        return a2, ws.cached(('abs2_scaler', ifreq), lambda: _lib.to_device(host[ifreq], ws.device, np.float64))
+    return step
+
+
+def _energyRow(ws, shape, ifreq):
+    "device pointer of the row of the worker's partial illumination that frequency ifreq adds to (the partial zeroed on first use)"
+    import torch
+    if ws.H is None:
+        ws.H = torch.zeros(shape, dtype=torch.float64, device=ws.device)
+    return ws.H.data_ptr() + (ifreq * shape[1] * 8 if len(shape) == 2 else 0)
+
+
+def _sumEnergyPartials(prob, parts, shape):
+    "the illumination from the workers' partials: summed on the host (8 B per cell and row each), then ONE all-reduce over ranks when the frequencies are sharded"
+    import torch
+    h = np.zeros(shape, dtype=np.float64)
+    for H in parts:
+        torch.cuda.synchronize(H.device)
+        h += _lib.from_device(H)
+    return parallel.allreduce_sum(h) if prob._sharded else h
+
+
+def illumination(prob, owned, kind, side, perFreq):
+    """prob.illumination(u=None) with the wavefields kept in HBM (single-grid surveys): per work item (frequency, column batch) the sparse columns -- the
+    sources, or the receiver array used as sources -- are expanded on the item's GPU, solved into the workspace's U and accumulated into the worker's
+    partial.  Nothing is stored and only the result comes down."""
+    sv = prob.survey
+    N = prob.nrow
+    shape = (sv.nfreq, N) if perFreq else (N,)
+    if not owned:
+        return _sumEnergyPartials(prob, [], shape)
+    scale = complex(prob.system.scaleTerm)
+    if side == 'source':
+        q, ncols = sv.getSources(), sv.nsrc
+    else:
+        q, ncols = sp.csc_matrix(sv.rVec(0, owned[0]).T), sv.nrec            # (one grid: the one matrix of a fixed array; srTerms included, no tsTerms)
+    weight = _energyWeight(prob, kind, scale, owned)
+    devs, items = deviceItems(prob.system, owned, ncols)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        row = _energyRow(ws, shape, ifreq)
+        U, R = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
+        qi = q[ifreq] if isinstance(q, (list, tuple)) else q
+        op.rhsFromSparseDevice(sp.csc_matrix(qi)[:, c0:c1], R.data_ptr())
+        alpha, W = weight(ws, op, ifreq)
+        _lib.wait_torch_stream(ws.device)                # (covers the zeroed partial and the weight: keep it between the torch work and the library calls)
+        op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+        op.energyAccumulateDevice(U.data_ptr(), k, alpha, None if W is None else W.data_ptr(), row, rows=Ni)
+    return _sumEnergyPartials(prob, [ws.H for ws in runOnDevices(devs, items, one) if ws.H is not None], shape)
+
+
+def illuminationFromFields(prob, F, kind, perFreq):
+    """prob.illumination(u=F) from forward fields already in HBM: no solve, every item of the store reads its slice where it lies, in either store
+    format, and adds it to its worker's partial."""
+    F.checkCurrent(prob)
+    sv = prob.survey
+    N = prob.nrow
+    shape = (sv.nfreq, N) if perFreq else (N,)
+    if not F.items:
+        return _sumEnergyPartials(prob, [], shape)
+    weight = _energyWeight(prob, kind, F.scale, F.ownedFreqs)
+    devs, items = _storedItems(prob.system, F)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        sl, ex = F.slice(ifreq, c0)
+        row = _energyRow(ws, shape, ifreq)
+        alpha, W = weight(ws, op, ifreq)
+        _lib.wait_torch_stream(ws.device)
+        op.energyAccumulateDevice(sl.data_ptr(), k, alpha, None if W is None else W.data_ptr(), row, d_exp=None if ex is None else ex.data_ptr(), rows=Ni)
+    return _sumEnergyPartials(prob, [ws.H for ws in runOnDevices(devs, items, one, factor=False) if ws.H is not None], shape)

@@ -288,6 +288,19 @@ class BaseDiscretization(BaseModelDependent):
         _lib.check(lib.helm_imaging_accumulate_device(self.handle, ctypes.c_void_p(d_uf), ctypes.c_void_p(d_ub), int(nsrc),
                                                       ctypes.c_void_p(d_scaler), ctypes.c_void_p(d_g)), self.handle)
 
+    def energyAccumulateDevice(self, d_u, nsrc, alpha, d_w, d_e, d_exp=None, rows=None):
+        """E += alpha * W * sum_s |U[s]|^2 on the device (the illumination of HelmBaseProblem.illumination); d_u [nsrc][rows] complex128, d_e and d_w
+        (None: no weight) nrow float64, alpha >= 0.  d_exp given: d_u is a complex64 store with those column exponents (packDevice).  All device
+        pointers; returns when E is complete."""
+        lib = _lib.load()
+        rows = int(self.nrow if rows is None else rows)
+        w = None if d_w is None else ctypes.c_void_p(d_w)
+        if d_exp is not None:
+            _lib.check(lib.helm_energy_accumulate_c64_device(self.handle, ctypes.c_void_p(d_u), ctypes.c_void_p(d_exp), int(nsrc), rows, float(alpha), w,
+                                                             ctypes.c_void_p(d_e)), self.handle)
+            return
+        _lib.check(lib.helm_energy_accumulate_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), rows, float(alpha), w, ctypes.c_void_p(d_e)), self.handle)
+
     def packDevice(self, d_u, nsrc, d_out, d_exp, rows=None):
         """The complex64 store of the wavefields d_u ([nsrc][rows] complex128): d_out [nsrc][rows] complex64 values x * 2^-e_s, d_exp the nsrc int32 column
         exponents e_s (fieldstore.pack_reference states the format).  All device pointers; returns when both are complete."""

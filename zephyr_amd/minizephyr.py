@@ -198,6 +198,13 @@ class MiniZephyr25D(BaseDiscretization, DiscretizationWrapper):
         if self.kyRelease:
             del sub.factors
 
+    def energyAccumulateDevice(self, d_u, nsrc, alpha, d_w, d_e, d_exp=None, rows=None):
+        'the energy of wavefields that are the ky SUM already (solveDevice formed it)'
+        sub = self._liveSub()
+        sub.energyAccumulateDevice(d_u, nsrc, alpha, d_w, d_e, d_exp=d_exp, rows=rows)
+        if self.kyRelease:
+            del sub.factors
+
     def sampleDevice(self, d_u, nsrc, csr_dev, d_out, d_exp=None):
         'receiver samples of wavefields that are the ky SUM already (device_survey.dpredFromFields: solveDevice formed it in the store)'
         self._liveSub().sampleDevice(d_u, nsrc, csr_dev, d_out, d_exp=d_exp)

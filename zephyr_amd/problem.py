@@ -13,7 +13,8 @@ process per GPU (`shardFreqs`, default on when torch.distributed is initialised)
 over ranks and the only collective is one all-reduce of the gradient (problem.py:152,162 sum over
 frequencies) or of the receiver data.  The device-resident loops of `dpred` and the mux `Jtvec` (item dealing,
 per-worker buffers, partial gradients) live in `zephyr_amd.device_survey`; `_dpredDevice` / `_JtvecDevice` delegate to it.  `fieldsDevice` leaves the
-forward wavefields in HBM (`zephyr_amd.fieldstore.DeviceFields`) for `survey.dpred(m, u=F)` and `Jtvec(m, v, u=F)`.
+forward wavefields in HBM (`zephyr_amd.fieldstore.DeviceFields`) for `survey.dpred(m, u=F)` and `Jtvec(m, v, u=F)`.  `illumination` (no counterpart in the
+reference) returns the source- or receiver-side illumination or the diagonal pseudo-Hessian from those fields, what a gradient is preconditioned with.
 """
 import numpy as np
 import scipy.sparse as sp
@@ -254,6 +255,64 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if self._sharded:
             g = parallel.allreduce_sum(g)
         return g if u is None else g.real
+
+    # ---- illumination / diagonal pseudo-Hessian ------------------------------------------------------------
+    def illumination(self, m=None, u=None, kind='pseudoHessian', side='source', perFreq=False):
+        """What an FWI gradient is divided by: float64 (N,), or (nfreq, N) with perFreq, every entry >= 0.  With uF[f] = fields()[f] and
+        E_f[i] = sum_s |uF[f][i, s]|^2:
+
+        kind 'energy':        sum_f E_f                                 (source-side illumination)
+        kind 'pseudoHessian': sum_f |gradientScaler(f)|^2 (.) E_f       (the diagonal pseudo-Hessian of Shin, Jang & Min 2001)
+        perFreq:              the terms of the sum over f, one row each (rows of frequencies other ranks own arrive through the all-reduce)
+
+        side 'receiver': the same with the receiver array as sources, uR_f = scaleTerm * (sub_f * rVec(0, f).T) -- srTerms included, no tsTerms; fixed
+        arrays only, and u must be None.  A preconditioned gradient is g / (H + lambda * H.max()).
+
+        u a DeviceFields (fieldsDevice): no solve, the store is read where it lies.  u None with the device path on a single-grid survey: the fields are
+        solved into HBM, accumulated there and dropped; only the result comes down.  Otherwise (u a list of host arrays, no GPU, hostGradient, a host ky
+        reduction, a multiscale survey): numpy on the host."""
+        if not self.ispaired:
+            raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
+        if kind not in ('energy', 'pseudoHessian'):
+            raise ValueError('kind is %r: \'energy\' or \'pseudoHessian\'' % (kind,))
+        if side not in ('source', 'receiver'):
+            raise ValueError('side is %r: \'source\' or \'receiver\'' % (side,))
+        sv = self.survey
+        if side == 'receiver':
+            if u is not None:
+                raise ValueError('the receiver-side illumination solves its own fields: u must be None')
+            if sv.mode != 'fixed':
+                raise ValueError('the receiver-side illumination serves fixed receiver arrays (mode is %r)' % (sv.mode,))
+        self.updateModel(m)
+        owned = self.ownedFreqs
+        if isinstance(u, DeviceFields):
+            u.checkCurrent(self)
+            return device_survey.illuminationFromFields(self, u, kind, bool(perFreq))
+        if u is None and not isinstance(sv, HelmMultiGridSurvey) and self._deviceGradientAvailable():
+            return device_survey.illumination(self, owned, kind, side, bool(perFreq))
+        nf = sv.nfreq
+        H = np.zeros((nf, self.nrow) if perFreq else self.nrow, dtype=np.float64)
+        if u is None:
+            q = sv.getSources() if side == 'source' else [sp.csc_matrix(sv.rVec(0, i).T) for i in range(nf)]
+            pps = sv.postProcessors
+            fieldsOf = ((ifreq, pps[ifreq](uf)) for ifreq, uf in self._solveOwned(q))
+        else:
+            uF = list(u)
+            fieldsOf = ((ifreq, uF[ifreq]) for ifreq in owned)
+        for ifreq, uf in fieldsOf:
+            uf = np.asarray(uf)
+            uf = uf.reshape((uf.shape[0], -1))
+            E = np.add.reduce(np.square(uf.real) + np.square(uf.imag), axis=1)          # (no BLAS: _norm2 says why)
+            if kind == 'pseudoHessian':
+                w = np.asarray(self.gradientScaler(ifreq)).ravel()
+                E = (np.square(w.real) + np.square(w.imag)) * E
+            if perFreq:
+                H[ifreq] = E
+            else:
+                H += E
+        if self._sharded:
+            H = parallel.allreduce_sum(H)
+        return H
 
     # ---- device-resident gradient (mux branch) -------------------------------------------------------------
     def _deviceGradientAvailable(self):
