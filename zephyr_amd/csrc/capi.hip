@@ -643,20 +643,6 @@ extern "C" int helm_solve(helm_op *op, const double *RHS, double *U, int nrhs, l
     return rc;
 }
 
-extern "C" int helm_rhs_from_coo_device(helm_op *op, const void *d_row, const void *d_col, const void *d_val, long long nnz, void *dR, int nrhs, long long rows) {
-    return helm_rhs_from_coo_device_layout(op, d_row, d_col, d_val, nnz, dR, nrhs, rows, 0);
-}
-
-extern "C" int helm_rhs_from_coo_device_layout(helm_op *op, const void *d_row, const void *d_col, const void *d_val, long long nnz, void *dR, int nrhs, long long rows, int flags) {
-    helm_tuning_refresh();
-    if (!op || !dR || nrhs < 1 || rows < 1 || nnz < 0 || (nnz > 0 && (!d_row || !d_col || !d_val))) return HELM_ERR_ARG;
-    HIP_TRY(op, hipSetDevice(op->device));
-    int rc = helm_launch_rhs_from_coo(op, (const long long *)d_row, (const int *)d_col, (const cplx *)d_val, nnz, (cplx *)dR, nrhs, rows, (flags & HELM_RHS_NODE_MAJOR) ? 1 : 0);
-    if (rc) return rc;
-    HIP_TRY(op, hipStreamSynchronize(op->stream));
-    return HELM_OK;
-}
-
 // Declared support of right-hand sides (round 4).  The reference hands its sources over as scipy-sparse matrices (survey.py:86-89,162-188): where they are
 // nonzero is part of the input, not something to be found.  bits: one byte per row (cell) on the device, bit b set = the right-hand sides of block b of
 // 64 columns MAY be nonzero in that row (at most 512 right-hand sides); the caller guarantees zeros everywhere else.  One shot: it applies to the next
@@ -669,29 +655,6 @@ extern "C" int helm_set_rhs_support(helm_op *op, const void *d_bits, long long r
     if (!d_bits) { op->rhs_bits = nullptr; op->rhs_bits_q = nullptr; return HELM_OK; }
     if (rows < 1 || nrhs < 1 || nrhs > 512) HELM_FAIL(op, HELM_ERR_ARG, "helm_set_rhs_support: rows >= 1 and 1 <= nrhs <= 512");
     op->rhs_bits = (const unsigned char *)d_bits; op->rhs_bits_rows = rows; op->rhs_bits_nrhs = nrhs; op->rhs_bits_violated = 0;
-    return HELM_OK;
-}
-
-namespace {
-__global__ __launch_bounds__(256) void k_support_from_coo(const long long *row, const int *col, long long nnz, long long rows, int nrhs, unsigned *words) {
-    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < nnz; k += (long long)gridDim.x * blockDim.x) {
-        const long long r = row[k]; const int c = col[k];
-        if (r < 0 || r >= rows || c < 0 || c >= nrhs) continue;
-        atomicOr(&words[r >> 2], (1u << (c >> 6)) << (8 * (int)(r & 3)));
-    }
-}
-}  // namespace
-// bits (rows bytes, rounded up to a multiple of 4, on the device) from the triplets of a sparse right-hand-side matrix (device arrays as for
-// helm_rhs_from_coo_device_layout): what helm_set_rhs_support takes
-extern "C" int helm_rhs_support_from_coo(helm_op *op, const void *d_row, const void *d_col, long long nnz, void *d_bits, long long rows, int nrhs) {
-    helm_tuning_refresh();
-    if (!op || !d_bits || rows < 1 || nrhs < 1 || nrhs > 512 || nnz < 0 || (nnz > 0 && (!d_row || !d_col))) return HELM_ERR_ARG;
-    HIP_TRY(op, hipSetDevice(op->device));
-    HIP_TRY(op, hipMemsetAsync(d_bits, 0, (size_t)((rows + 3) / 4) * 4, op->stream));
-    if (nnz > 0) HELM_LAUNCH(k_support_from_coo, dim3((unsigned)std::min<long long>((nnz + 255) / 256, 4096)), dim3(256), 0, op->stream,
-                                    (const long long *)d_row, (const int *)d_col, nnz, rows, nrhs, (unsigned *)d_bits);
-    HIP_TRY(op, hipGetLastError());
-    HIP_TRY(op, hipStreamSynchronize(op->stream));
     return HELM_OK;
 }
 
@@ -739,93 +702,4 @@ extern "C" int helm_solve_coo(helm_op *op, const long long *row, const int *col,
     if (rc >= 0 && helm_download_staged(op, U, dU, bytes)) rc = HELM_ERR_DEVICE;
     release();
     return rc;
-}
-
-extern "C" int helm_sample_device(helm_op *op, const void *dU, int nsrc, long long ld, const void *d_rowptr, const void *d_col, const void *d_val, int nrec, void *d_out) {
-    helm_tuning_refresh();
-    if (!op || !dU || !d_rowptr || !d_col || !d_val || !d_out || nsrc < 1 || nrec < 1) return HELM_ERR_ARG;
-    HIP_TRY(op, hipSetDevice(op->device));
-    int rc = helm_launch_sample(op, (const cplx *)dU, nsrc, ld, (const long long *)d_rowptr, (const long long *)d_col, (const cplx *)d_val, nrec, (cplx *)d_out);
-    if (rc) return rc;
-    HIP_TRY(op, hipStreamSynchronize(op->stream));
-    return HELM_OK;
-}
-
-// out = beta out + alpha R u: helm_sample_device into an accumulator (the ky sum of 2.5-D data; beta == 0: out is not read)
-extern "C" int helm_sample_accumulate_device(helm_op *op, const void *dU, int nsrc, long long ld, const void *d_rowptr, const void *d_col, const void *d_val, int nrec,
-                                             double alpha_re, double alpha_im, double beta_re, double beta_im, void *d_out) {
-    helm_tuning_refresh();
-    if (!op || !dU || !d_rowptr || !d_col || !d_val || !d_out || nsrc < 1 || nrec < 1 || ld < 1) return HELM_ERR_ARG;
-    HIP_TRY(op, hipSetDevice(op->device));
-    int rc = helm_launch_sample_acc(op, (const cplx *)dU, nsrc, ld, (const long long *)d_rowptr, (const long long *)d_col, (const cplx *)d_val, nrec,
-                                    cmake(alpha_re, alpha_im), cmake(beta_re, beta_im), (cplx *)d_out);
-    if (rc) return rc;
-    HIP_TRY(op, hipStreamSynchronize(op->stream));
-    return HELM_OK;
-}
-
-// helm_sample_accumulate_device with a row stride per source: source s samples CSR row r + s * row_stride (0: one array for all sources; >= nrec: the
-// per-source matrices of an array that moves with the source, stacked into one CSR of nsrc * row_stride rows)
-extern "C" int helm_sample_rows_device(helm_op *op, const void *dU, int nsrc, long long ld, const void *d_rowptr, const void *d_col, const void *d_val, int nrec,
-                                       long long row_stride, double alpha_re, double alpha_im, double beta_re, double beta_im, void *d_out) {
-    helm_tuning_refresh();
-    if (!op || !dU || !d_rowptr || !d_col || !d_val || !d_out || nsrc < 1 || nrec < 1 || ld < 1) return HELM_ERR_ARG;
-    if (row_stride != 0 && row_stride < nrec) return HELM_ERR_ARG;
-    HIP_TRY(op, hipSetDevice(op->device));
-    int rc = helm_launch_sample_acc(op, (const cplx *)dU, nsrc, ld, (const long long *)d_rowptr, (const long long *)d_col, (const cplx *)d_val, nrec,
-                                    cmake(alpha_re, alpha_im), cmake(beta_re, beta_im), (cplx *)d_out, row_stride);
-    if (rc) return rc;
-    HIP_TRY(op, hipStreamSynchronize(op->stream));
-    return HELM_OK;
-}
-
-// Back-sources R_s^T resid[:, s] of the sources src0 .. src0 + nsrc - 1 from the residual samples of one frequency (survey.py:171-188, the moving-array
-// branch): only the nrec x nsrc samples cross PCIe, the dense right-hand sides are made here.  The plan arrays are trusted (the caller validated them when it
-// built them: cells < rows, receivers < nrec, sources ascending within [src0, src0 + nsrc)).
-extern "C" int helm_rhs_from_samples_device(helm_op *op, const void *d_resid, long long ld_resid, int nrec, int nsrc, int src0, const void *d_tptr, const void *d_tsrc,
-                                            const void *d_tcell, const void *d_trec, const void *d_tval, long long ntouch, void *dR, long long rows) {
-    helm_tuning_refresh();
-    if (!op || !d_resid || !dR || nrec < 1 || nsrc < 1 || src0 < 0 || ld_resid < nsrc || rows < 1 || ntouch < 0) return HELM_ERR_ARG;
-    if (ntouch > 0 && (!d_tptr || !d_tsrc || !d_tcell || !d_trec || !d_tval)) return HELM_ERR_ARG;
-    HIP_TRY(op, hipSetDevice(op->device));
-    int rc = helm_launch_rhs_from_samples(op, (const cplx *)d_resid, ld_resid, nsrc, src0, (const long long *)d_tptr, (const int *)d_tsrc, (const long long *)d_tcell,
-                                          (const int *)d_trec, (const cplx *)d_tval, ntouch, (cplx *)dR, rows);
-    if (rc) return rc;
-    HIP_TRY(op, hipStreamSynchronize(op->stream));
-    return HELM_OK;
-}
-
-// Y = beta Y + alpha X over n complex128 values on the device (the ky accumulation of the 2.5-D composite; beta == 0: Y is not read).  Returns when Y is
-// complete: the next term of the sum is added on ANOTHER handle's stream.
-extern "C" int helm_axpby_device(helm_op *op, double alpha_re, double alpha_im, const void *dX, double beta_re, double beta_im, void *dY, long long n) {
-    helm_tuning_refresh();
-    if (!op || !dX || !dY || n < 1 || dX == dY) return HELM_ERR_ARG;
-    if ((((uintptr_t)dX) | ((uintptr_t)dY)) & 15) return HELM_ERR_ARG;       // (complex128 values are read and written as 16-byte vectors)
-    HIP_TRY(op, hipSetDevice(op->device));
-    int rc = helm_launch_axpby(op, cmake(alpha_re, alpha_im), (const cplx *)dX, cmake(beta_re, beta_im), (cplx *)dY, n);
-    if (rc) return rc;
-    HIP_TRY(op, hipStreamSynchronize(op->stream));
-    return HELM_OK;
-}
-
-extern "C" int helm_imaging_accumulate_device(helm_op *op, const void *dUF, const void *dUB, int nsrc, const void *dScaler, void *dG) {
-    helm_tuning_refresh();
-    if (!op || !dUF || !dUB || !dScaler || !dG || nsrc < 1) return HELM_ERR_ARG;
-    HIP_TRY(op, hipSetDevice(op->device));
-    int rc = helm_launch_imaging(op, (const cplx *)dUF, (const cplx *)dUB, nsrc, (const cplx *)dScaler, (cplx *)dG);
-    if (rc) return rc;
-    HIP_TRY(op, hipStreamSynchronize(op->stream));
-    return HELM_OK;
-}
-
-// E += alpha W sum_s |U_s|^2 (the illumination of HelmBaseProblem.illumination).  Returns when E is complete.
-extern "C" int helm_energy_accumulate_device(helm_op *op, const void *dU, int nsrc, long long ld, double alpha, const void *dW, void *dE) {
-    helm_tuning_refresh();
-    if (!op || !dU || !dE || nsrc < 1 || ld < op->N || !(alpha >= 0.0)) return HELM_ERR_ARG;       // (!(alpha >= 0): negative or NaN)
-    if ((((uintptr_t)dU) & 15) || (((uintptr_t)dE) & 7) || (((uintptr_t)dW) & 7)) return HELM_ERR_ARG;       // (16-byte loads of U; doubles)
-    HIP_TRY(op, hipSetDevice(op->device));
-    int rc = helm_launch_energy(op, (const cplx *)dU, nsrc, ld, alpha, (const double *)dW, (double *)dE);
-    if (rc) return rc;
-    HIP_TRY(op, hipStreamSynchronize(op->stream));
-    return HELM_OK;
 }

@@ -361,22 +361,16 @@ int helm_launch_rowscaled_system(helm_op *op);    // d_S, d_rs
 int helm_launch_prep_rhs_rs(helm_op *op, const cplx *dRHS, long long rhs_ld, long long row_off, cplx premul, const double *rs,
                             cplx *out, long long out_ld, long long out_off, int nrhs);
 int helm_launch_prep_rhs(helm_op *op, const cplx *dRHS, long long rhs_ld, long long row_off, cplx premul, const cplx *sub, cplx *out, int nrhs); // out = premul*rhs - sub
-int helm_launch_imaging(helm_op *op, const cplx *uf, const cplx *ub, int nsrc, const cplx *scaler, cplx *g);
-// the illumination kernels (k_energy in kernels.hip, k_energy_c64 in fieldstore.hip): columns loaded per lane before the first use, and the grid cap of
-// their grid-stride loop (8 workgroups of 256 lanes per CU on 256 CUs)
-#define HELM_ENERGY_UNROLL 8
-#define HELM_ENERGY_MAX_BLOCKS 2048
-int helm_launch_energy(helm_op *op, const cplx *U, int nsrc, long long ld, double alpha, const double *W, double *E);     // E += alpha W sum_s |U_s|^2
-int helm_launch_zero(helm_op *op, cplx *p, long long n);
-int helm_launch_rhs_from_coo(helm_op *op, const long long *row, const int *col, const cplx *val, long long nnz, cplx *R, int nrhs, long long rows, int node_major = 0);
-int helm_launch_sample(helm_op *op, const cplx *U, int nsrc, long long ld, const long long *rowptr, const long long *col, const cplx *val, int nrec, cplx *out);
-int helm_launch_sample_acc(helm_op *op, const cplx *U, int nsrc, long long ld, const long long *rowptr, const long long *col, const cplx *val, int nrec,
-                           cplx alpha, cplx beta, cplx *out, long long row_stride = 0);        // out = beta out + alpha R u (beta == 0: out is not read); source s samples CSR row r + s * row_stride
-int helm_launch_rhs_from_samples(helm_op *op, const cplx *resid, long long ld, int nsrc, int src0, const long long *tptr, const int *tsrc, const long long *tcell,
-                                 const int *trec, const cplx *tval, long long ntouch, cplx *R, long long rows);      // R (nsrc x rows, zeroed here) from a gather plan over (source, cell) pairs
-int helm_launch_axpby(helm_op *op, cplx alpha, const cplx *X, cplx beta, cplx *Y, long long n);  // Y = beta Y + alpha X (beta == 0: Y is not read)
 int helm_launch_rowscale_inplace(helm_op *op, cplx *v, const double *rs, long long NV, int nrhs);
 int helm_launch_abs(helm_op *op, const cplx *in, cplx *out, long long n, double sign);      // out = sign |in|
 int helm_launch_gardner_rho(helm_op *op);     // d_rho = 310 Re(d_c)^0.25
 int helm_ensure_host_model(helm_op *op);      // h_c, h_rho, ... (downloaded from the device on first use)
 int helm_adopt_model_device(helm_op *dst, const cplx *d_c, const double *d_rho);     // model of a multigrid level from device arrays (capi.hip)
+
+// ---- survey.hip --------------------------------------------------------------------------------
+// the illumination kernel (k_energy<F>): columns loaded per lane before the first use, and the grid cap of its grid-stride loop (8 workgroups of 256
+// lanes per CU on 256 CUs)
+#define HELM_ENERGY_UNROLL 8
+#define HELM_ENERGY_MAX_BLOCKS 2048
+// R (zeroed here) from the triplets of a sparse right-hand-side matrix; enqueues only (helm_solve_coo of capi.hip goes on to solve)
+int helm_launch_rhs_from_coo(helm_op *op, const long long *row, const int *col, const cplx *val, long long nnz, cplx *R, int nrhs, long long rows, int node_major = 0);

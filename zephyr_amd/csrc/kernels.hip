@@ -501,48 +501,6 @@ __global__ __launch_bounds__(256) void k_prep_rhs_rs(const cplx *__restrict__ rh
         out[(long long)b * out_ld + out_off + i] = cscale(cmul(premul, rhs[(long long)b * rhs_ld + row_off + i]), rs[i]);
 }
 
-__global__ __launch_bounds__(256) void k_zero(cplx *__restrict__ p, long long n) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
-        p[i] = cmake(0.0, 0.0);
-}
-
-// G[i] += scaler[i] * sum_s UF[s][i] * UB[s][i]      (problem.py:152)
-__global__ __launch_bounds__(256) void k_imaging(const cplx *__restrict__ uf, const cplx *__restrict__ ub, int nsrc,
-                                                 const cplx *__restrict__ scaler, cplx *__restrict__ g, long long N) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
-        cplx acc = cmake(0.0, 0.0);
-        for (int s = 0; s < nsrc; ++s) cfma(acc, uf[(long long)s * N + i], ub[(long long)s * N + i]);
-        cplx gv = g[i];
-        cfma(gv, scaler[i], acc);
-        g[i] = gv;
-    }
-}
-
-// E[i] += alpha (W ? W[i] : 1) sum_s |U[s ld + i]|^2: one lane per cell, the sum over s in the order s = 0, 1, ...  (no atomics: the same bits on every run).
-// A pure read stream of nsrc N values against N doubles of read-modify-write: HELM_ENERGY_UNROLL independent 16-byte loads are issued before the first
-// square, which at one 256-lane workgroup per 256 cells and a grid capped at ENERGY_MAX_BLOCKS keeps 32 KB per workgroup in flight.
-__global__ __launch_bounds__(256) void k_energy(const cplx *__restrict__ U, int nsrc, long long ld, double alpha, const double *__restrict__ W,
-                                                double *__restrict__ E, long long N) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
-        const cplx *col = U + i;
-        double acc = 0.0;
-        int s = 0;
-        for (; s + HELM_ENERGY_UNROLL <= nsrc; s += HELM_ENERGY_UNROLL) {
-            cplx x[HELM_ENERGY_UNROLL];
-#pragma unroll
-            for (int j = 0; j < HELM_ENERGY_UNROLL; ++j) x[j] = col[(long long)(s + j) * ld];
-#pragma unroll
-            for (int j = 0; j < HELM_ENERGY_UNROLL; ++j) acc += x[j].x * x[j].x + x[j].y * x[j].y;
-        }
-        for (; s < nsrc; ++s) {
-            const cplx x = col[(long long)s * ld];
-            acc += x.x * x.x + x.y * x.y;
-        }
-        const double w = W ? alpha * W[i] : alpha;
-        E[i] = E[i] + w * acc;
-    }
-}
-
 // ------------------------------------------------------------------------------------------
 // finalize: one workgroup per right-hand side sums the per-workgroup partials in a fixed order
 // (bitwise reproducible) and advances the scalar recurrences.
@@ -954,119 +912,6 @@ int helm_launch_rowscale_inplace(helm_op *op, cplx *v, const double *rs, long lo
     return HELM_OK;
 }
 
-// dense right-hand sides from the triplets of a sparse matrix (no duplicate entries): R[col][row] = val
-__global__ __launch_bounds__(256) void k_rhs_from_coo(const long long *__restrict__ row, const int *__restrict__ col, const cplx *__restrict__ val,
-                                                      long long nnz, cplx *__restrict__ R, long long rows, int nrhs, int node_major) {
-    for (long long k = (long long)blockIdx.x * blockDim.x + threadIdx.x; k < nnz; k += (long long)gridDim.x * blockDim.x) {
-        if (node_major) R[row[k] * nrhs + col[k]] = val[k];          // the reference's (rows, nrhs) C-order array
-        else R[(long long)col[k] * rows + row[k]] = val[k];
-    }
-}
-int helm_launch_rhs_from_coo(helm_op *op, const long long *row, const int *col, const cplx *val, long long nnz, cplx *R, int nrhs, long long rows, int node_major) {
-    HIP_TRY(op, hipMemsetAsync(R, 0, (size_t)nrhs * rows * sizeof(cplx), op->stream));
-    if (nnz > 0) HELM_LAUNCH(k_rhs_from_coo, dim3((unsigned)std::min<long long>((nnz + 255) / 256, 65535)), dim3(256), 0, op->stream, row, col, val, nnz, R, rows, nrhs, node_major);
-    HIP_TRY(op, hipGetLastError());
-    return HELM_OK;
-}
-
-// receiver sampling out[r][s] = sum_k val[k] U[s][col[k]] over the entries k of sparse row r + s * row_stride (one thread per (r, s), fixed order).
-// row_stride = 0: one receiver array for every source; row_stride >= nrec: source s has rows [s * row_stride, s * row_stride + nrec) of its own (an array
-// that moves with the source, the per-source matrices stacked into one CSR).
-__global__ __launch_bounds__(256) void k_sample(const cplx *__restrict__ U, int nsrc, long long ld, const long long *__restrict__ rowptr,
-                                                const long long *__restrict__ col, const cplx *__restrict__ val, int nrec, long long row_stride,
-                                                cplx *__restrict__ out) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long long)nrec * nsrc) return;
-    const int r = (int)(t / nsrc), sidx = (int)(t % nsrc);
-    const long long row = r + sidx * row_stride;
-    cplx acc = cmake(0.0, 0.0);
-    for (long long k = rowptr[row]; k < rowptr[row + 1]; ++k) cfma(acc, val[k], U[(long long)sidx * ld + col[k]]);
-    out[t] = acc;
-}
-int helm_launch_sample(helm_op *op, const cplx *U, int nsrc, long long ld, const long long *rowptr, const long long *col, const cplx *val, int nrec, cplx *out) {
-    const long long tot = (long long)nrec * nsrc;
-    HELM_LAUNCH(k_sample, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, op->stream, U, nsrc, ld, rowptr, col, val, nrec, 0LL, out);
-    HIP_TRY(op, hipGetLastError());
-    return HELM_OK;
-}
-
-// receiver sampling into an accumulator: out[r][s] = beta out[r][s] + alpha sum_k val[k] U[s][col[k]] over row r + s * row_stride (the ky sum of a 2.5-D
-// survey's data: sampling is linear, so the summed wavefields are never formed).  beta0: out is write-only -- an uninitialised accumulator is legal for
-// the first term.
-__global__ __launch_bounds__(256) void k_sample_acc(const cplx *__restrict__ U, int nsrc, long long ld, const long long *__restrict__ rowptr,
-                                                    const long long *__restrict__ col, const cplx *__restrict__ val, int nrec, long long row_stride,
-                                                    cplx alpha, cplx beta, int beta0, cplx *__restrict__ out) {
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= (long long)nrec * nsrc) return;
-    const int r = (int)(t / nsrc), sidx = (int)(t % nsrc);
-    const long long row = r + sidx * row_stride;
-    cplx acc = cmake(0.0, 0.0);
-    for (long long k = rowptr[row]; k < rowptr[row + 1]; ++k) cfma(acc, val[k], U[(long long)sidx * ld + col[k]]);
-    cplx o = cmul(alpha, acc);
-    if (!beta0) cfma(o, beta, out[t]);
-    out[t] = o;
-}
-int helm_launch_sample_acc(helm_op *op, const cplx *U, int nsrc, long long ld, const long long *rowptr, const long long *col, const cplx *val, int nrec,
-                           cplx alpha, cplx beta, cplx *out, long long row_stride) {
-    const long long tot = (long long)nrec * nsrc;
-    const int beta0 = (beta.x == 0.0 && beta.y == 0.0) ? 1 : 0;
-    HELM_LAUNCH(k_sample_acc, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, op->stream, U, nsrc, ld, rowptr, col, val, nrec, row_stride, alpha, beta, beta0, out);
-    HIP_TRY(op, hipGetLastError());
-    return HELM_OK;
-}
-
-// Back-sources of a receiver array that moves with the source, R[s - src0][cell] = sum_r R_s[r][cell] resid[r][s - src0], as a GATHER over the touched
-// (source, cell) pairs: pair t owns the entries tptr[t] .. tptr[t+1] of (trec, tval), ordered by receiver, and is written by exactly one thread in that
-// order.  Receivers of one source share cells (their patches overlap), so a scatter over the entries would need atomics and the sum would depend on
-// their order; this one is the same bits on every run.  resid: [nrec][ld], column s - src0 belongs to source s.  R: [nsrc][rows], zeroed by the launcher.
-__global__ __launch_bounds__(256) void k_rhs_from_samples(const cplx *__restrict__ resid, long long ld, int src0, const long long *__restrict__ tptr,
-                                                          const int *__restrict__ tsrc, const long long *__restrict__ tcell, const int *__restrict__ trec,
-                                                          const cplx *__restrict__ tval, long long ntouch, cplx *__restrict__ R, long long rows) {
-    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < ntouch; t += (long long)gridDim.x * blockDim.x) {
-        const int s = tsrc[t] - src0;
-        cplx acc = cmake(0.0, 0.0);
-        for (long long e = tptr[t]; e < tptr[t + 1]; ++e) cfma(acc, tval[e], resid[(long long)trec[e] * ld + s]);
-        R[(long long)s * rows + tcell[t]] = acc;
-    }
-}
-int helm_launch_rhs_from_samples(helm_op *op, const cplx *resid, long long ld, int nsrc, int src0, const long long *tptr, const int *tsrc, const long long *tcell,
-                                 const int *trec, const cplx *tval, long long ntouch, cplx *R, long long rows) {
-    HIP_TRY(op, hipMemsetAsync(R, 0, (size_t)nsrc * rows * sizeof(cplx), op->stream));
-    if (ntouch > 0) HELM_LAUNCH(k_rhs_from_samples, dim3((unsigned)std::min<long long>((ntouch + 255) / 256, 65535)), dim3(256), 0, op->stream,
-                                resid, ld, src0, tptr, tsrc, tcell, trec, tval, ntouch, R, rows);
-    HIP_TRY(op, hipGetLastError());
-    return HELM_OK;
-}
-
-// Y = beta Y + alpha X over n complex128 values: the ky accumulation of the 2.5-D composite.  A pure streaming pass (48 B per element, 32 with BETA0):
-// one 16-byte load / store per lane and element, 64-bit indices.  A workgroup takes 256 CONSECUTIVE elements, one per lane, and there is a workgroup per 256
-// elements up to AXPBY_BLOCKS (n <= 2^30: a single trip through the loop), striding beyond: measured on 0.27 .. 8.6 GB operands, this order ran at 5.8-5.9 TB/s
-// where 2048 workgroups striding with four elements 8 MB apart in flight per lane ran at 4.5-5.0, and two to eight elements per lane in a workgroup-contiguous
-// tile at 5.3-5.6.  BETA0: Y is write-only.
-constexpr int AXPBY_BLOCKS = 1 << 22;
-// one element.  Contraction is pinned off: each complex product is rounded on its own (within sqrt(5) u of the exact one in modulus) and ONE addition follows
-// (+ u), the error model (sqrt(5) + 1) u (|alpha||x| + |beta||y|) the tests hold this kernel to; a chain of four FMAs per component has no such bound.  The
-// kernel moves 48 B per element: the three extra roundings are free.
-__device__ __forceinline__ cplx axpby1(cplx alpha, cplx x, cplx beta, cplx y) {
-#pragma clang fp contract(off)
-    const cplx p = cmake(alpha.x * x.x - alpha.y * x.y, alpha.x * x.y + alpha.y * x.x);
-    const cplx r = cmake(beta.x * y.x - beta.y * y.y, beta.x * y.y + beta.y * y.x);
-    return cmake(p.x + r.x, p.y + r.y);
-}
-template <bool BETA0>
-__global__ __launch_bounds__(256) void k_axpby(const cplx *__restrict__ X, cplx *__restrict__ Y, long long n, cplx alpha, cplx beta) {
-    const long long stride = (long long)gridDim.x * blockDim.x;
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride)
-        Y[i] = BETA0 ? cmul(alpha, X[i]) : axpby1(alpha, X[i], beta, Y[i]);
-}
-int helm_launch_axpby(helm_op *op, cplx alpha, const cplx *X, cplx beta, cplx *Y, long long n) {
-    const dim3 grid((unsigned)std::min<long long>((n + 255) / 256, AXPBY_BLOCKS));
-    if (beta.x == 0.0 && beta.y == 0.0) HELM_LAUNCH(k_axpby<true>, grid, dim3(256), 0, op->stream, X, Y, n, alpha, beta);
-    else HELM_LAUNCH(k_axpby<false>, grid, dim3(256), 0, op->stream, X, Y, n, alpha, beta);
-    HIP_TRY(op, hipGetLastError());
-    return HELM_OK;
-}
-
 // Gardner's relation, the reference's density default: rho = 310 Re(c)^0.25 (discretization.py:70)
 __global__ __launch_bounds__(256) void k_gardner_rho(const cplx *__restrict__ c, double *__restrict__ rho, long long n) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
@@ -1074,24 +919,6 @@ __global__ __launch_bounds__(256) void k_gardner_rho(const cplx *__restrict__ c,
 }
 int helm_launch_gardner_rho(helm_op *op) {
     HELM_LAUNCH(k_gardner_rho, dim3(vec_blocks(op->N)), dim3(256), 0, op->stream, (const cplx *)op->d_c, op->d_rho, op->N);
-    HIP_TRY(op, hipGetLastError());
-    return HELM_OK;
-}
-
-int helm_launch_zero(helm_op *op, cplx *p, long long n) {
-    HELM_LAUNCH(k_zero, dim3(vec_blocks(n)), dim3(256), 0, op->stream, p, n);
-    return HELM_OK;
-}
-
-int helm_launch_imaging(helm_op *op, const cplx *uf, const cplx *ub, int nsrc, const cplx *scaler, cplx *g) {
-    HELM_LAUNCH(k_imaging, dim3(vec_blocks(op->N)), dim3(256), 0, op->stream, uf, ub, nsrc, scaler, g, op->N);
-    HIP_TRY(op, hipGetLastError());
-    return HELM_OK;
-}
-
-int helm_launch_energy(helm_op *op, const cplx *U, int nsrc, long long ld, double alpha, const double *W, double *E) {
-    const unsigned blocks = (unsigned)std::min<long long>((op->N + 255) / 256, HELM_ENERGY_MAX_BLOCKS);
-    HELM_LAUNCH(k_energy, dim3(blocks), dim3(256), 0, op->stream, U, nsrc, ld, alpha, W, E, op->N);
     HIP_TRY(op, hipGetLastError());
     return HELM_OK;
 }
