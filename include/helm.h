@@ -25,6 +25,9 @@
  *                                     zephyr/middleware/problem.py:152,162
  *   helm_energy_accumulate_device,
  *   helm_energy_accumulate_c64_device <- (no counterpart) HelmBaseProblem.illumination: sum_s |u_s|^2 of wavefields in HBM
+ *   helm_set_transposed            <- (no counterpart) the handle holds A^T: HelmBaseProblem.Jtvec(adjoint='transpose') back-propagates through A^-T
+ *   helm_virtual_sources_device,
+ *   helm_virtual_sources_c64_device <- (no counterpart) HelmBaseProblem.JvecBorn: conj(W (.) u_s), the right-hand sides of Born data
  *   helm_axpby_device,
  *   helm_sample_accumulate_device  <- MiniZephyr25D.__mul__: the sum over ky sub-problems
  *                                     (`reduce(np.add, ...)`, scaled)     minizephyr.py:435-460
@@ -148,6 +151,16 @@ int helm_set_model(helm_op *op, const double *c, const double *rho,
  * (MiniZephyr only); cPML Eurus C-PML amplitude (eurus.py:500-504). */
 int helm_assemble(helm_op *op, double freq_re, double freq_im, double tau, double ky, double cPML);
 
+/* The transposed operator.  on != 0: the NEXT helm_assemble leaves the coefficient planes of A^T in the handle (on == 0: of A again), and everything that reads
+ * them works on A^T from then on -- the direct factorisation and its true-residual check (relres is that of A^T x = premul q), the Jacobi-scaled planes and the
+ * Krylov methods, the levels of the 2-D multigrid preconditioner, helm_apply, helm_get_diagonals: helm_solve* returns conj(A^-T (premul rhs)).  The 9-point
+ * MiniZephyr operator is not symmetric (its rows are scaled by PML and density terms), so this, not the forward solve, back-propagates a residual exactly.
+ * With slot k = 3 (dz + 1) + (dx + 1) and off_k = dz nx + dx:  CT[k][i] = C[8 - k][i + off_k]  where cell (iz + dz, ix + dx) is inside the grid, else 0.
+ * The call itself drops what was derived from the planes (factors, also those in flight; scaled planes; preconditioner) when it changes the setting, and leaves
+ * the planes as they are until the next helm_assemble.  2-D MiniZephyr handles; Eurus and 3-D handles: HELM_ERR_UNSUPPORTED. */
+int helm_set_transposed(helm_op *op, int on);
+int helm_get_transposed(const helm_op *op);    /* 1: the planes in the handle (helm_get_diagonals) are those of A^T, 0: of A */
+
 int helm_num_blocks(const helm_op *op);        /* 1 (MiniZephyr) or 4 (Eurus) */
 long long helm_num_points(const helm_op *op);  /* N = nz*nx */
 
@@ -251,6 +264,13 @@ int helm_imaging_accumulate_device(helm_op *op, const void *dUF, const void *dUB
  * alpha W, its product with the sum, the addition to E).  Null pointers other than dW, nsrc < 1, ld < N, a misaligned pointer, alpha < 0 or NaN:
  * HELM_ERR_ARG.  All device pointers; returns when E is complete. */
 int helm_energy_accumulate_device(helm_op *op, const void *dU, int nsrc, long long ld, double alpha, const void *dW, void *dE);
+/* R[s ldr + i] = conj(W[i] U[s ldu + i]), s < nsrc, i < N: the right-hand sides of Born data from stored forward fields (W = model perturbation times the
+ * gradient scaler).  U: nsrc columns of ldu >= N complex128 values (or, _c64, complex64 values with the int32 column exponents dExp of helm_pack_c64_device);
+ * W: N complex128; R: nsrc columns of ldr >= N complex128, not overlapping U or W; 16-byte aligned (U32: 8, dExp: 4).  Per component |error| <= 3 2^-53 times
+ * the sum of the absolute values of its two products; no atomics, the same bits on every run.  Null pointers, nsrc < 1, ldu or ldr < N, a misaligned or
+ * overlapping pointer: HELM_ERR_ARG.  All device pointers; returns when R is complete. */
+int helm_virtual_sources_device(helm_op *op, const void *dU, int nsrc, long long ldu, const void *dW, void *dR, long long ldr);
+int helm_virtual_sources_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ldu, const void *dW, void *dR, long long ldr);
 
 /* --- device-resident callers: sparse sources in, receiver samples out ---------------------------------- */
 /* Dense right-hand sides from the COO triplets of the reference's sparse source matrix (survey.py:162-169,

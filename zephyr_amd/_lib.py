@@ -102,6 +102,12 @@ _SIGNATURES = {
                                       ctypes.c_void_p, ctypes.c_void_p]),
     'helm_assemble': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                      ctypes.c_double, ctypes.c_double]),
+    'helm_set_transposed': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'helm_get_transposed': (ctypes.c_int, [ctypes.c_void_p]),
+    'helm_virtual_sources_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
+                                                   ctypes.c_longlong]),
+    'helm_virtual_sources_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_longlong]),
     'helm_num_blocks': (ctypes.c_int, [ctypes.c_void_p]),
     'helm_num_points': (ctypes.c_longlong, [ctypes.c_void_p]),
     'helm_get_diagonals': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),

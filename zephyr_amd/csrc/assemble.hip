@@ -271,6 +271,28 @@ __global__ __launch_bounds__(256) void k_assemble_eurus(EuParams P, const cplx *
     }
 }
 
+// The planes of A^T from the planes of A.  Row i of A holds A[i][i + off_k] = C[k][i] with k = 3 (dz + 1) + (dx + 1), off_k = dz nx + dx; hence
+// A^T[i][i + off_k] = A[i + off_k][i] = C[8 - k][i + off_k] (slot 8 - k is the offset -off_k), and zero where cell (iz + dz, ix + dx) lies outside the grid.
+// The test is per axis: i + off_k of a cell at a row end is a valid linear index of the NEXT grid row.  Pure data movement, out of place: one lane per
+// cell, nine loads and nine stores that are each contiguous across the wave (neighbouring lanes read neighbouring cells of one plane), no atomics.
+__global__ __launch_bounds__(256) void k_transpose_planes(const cplx *__restrict__ C, cplx *__restrict__ CT, int nz, int nx) {
+    const long long N = (long long)nz * nx;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const int iz = (int)(i / nx), ix = (int)(i % nx);
+    cplx v[9];
+#pragma unroll
+    for (int dz = -1; dz <= 1; ++dz)
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int k = slot(dz, dx);
+            const bool in = iz + dz >= 0 && iz + dz < nz && ix + dx >= 0 && ix + dx < nx;
+            v[k] = in ? C[(long long)(8 - k) * N + i + (long long)dz * nx + dx] : cmake(0.0, 0.0);
+        }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) CT[(long long)k * N + i] = v[k];
+}
+
 // 1-D profile builders (host).  MiniZephyr: minizephyr.py:98-118,126-127 (assignment order kept).
 void mz_profiles(int n, int npml, double h, bool fs_low, bool fs_high, std::vector<double> &dist, std::vector<double> &sgn) {
     dist.assign(n, 0.0);
@@ -325,6 +347,7 @@ int helm_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau
         HIP_TRY(op, hipStreamSynchronize(op->stream));
         helm_pool_free(op->device, d_prof, bytes);
         op->block_zero[0] = false;
+        if (op->transposed) { const int rct = helm_launch_transpose_planes(op); if (rct) return rct; }
     } else {
         if (op->nPML < 2) HELM_FAIL(op, HELM_ERR_ARG, "nPML must be >= 2");
         if (op->nPML > nx || op->nPML > nz) HELM_FAIL(op, HELM_ERR_ARG, "nPML larger than the grid");
@@ -366,5 +389,20 @@ int helm_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau
         helm_pool_free(op->device, d_xi, bytes);
         op->blocks_ready = P.nblk_out;
     }
+    return HELM_OK;
+}
+
+// d_C <- the planes of its transpose (2-D, one block): into a pool buffer of the planes' own size class, which then takes d_C's place.  On op->stream, i.e.
+// behind the assembly it follows (the low-priority set-up stream of helm_assemble included); returns when the planes are complete.
+int helm_launch_transpose_planes(helm_op *op) {
+    if (op->ny > 0 || op->nblocks != 1 || op->nplanes != 9) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "the transposed operator exists for the 2-D single-block system only");
+    const size_t bytes = (size_t)9 * (size_t)op->N * sizeof(cplx);
+    cplx *d_T = (cplx *)helm_pool_alloc(op->device, bytes);
+    if (!d_T) HELM_FAIL(op, HELM_ERR_DEVICE, "hipMalloc of the transposed coefficient planes failed");
+    HELM_LAUNCH(k_transpose_planes, dim3((unsigned)((op->N + 255) / 256)), dim3(256), 0, op->stream, (const cplx *)op->d_C, d_T, op->nz, op->nx);
+    const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(op->stream);
+    if (e1 != hipSuccess || e2 != hipSuccess) { helm_pool_free(op->device, d_T, bytes); HIP_TRY(op, e1); HIP_TRY(op, e2); }
+    helm_pool_free(op->device, op->d_C, bytes);       // (nothing reads the old planes any more: the stream is drained)
+    op->d_C = d_T;
     return HELM_OK;
 }

@@ -254,6 +254,7 @@ extern "C" int helm_assemble(helm_op *op, double freq_re, double freq_im, double
     // quarters of the 604 MB the assembly writes at 1024^2 -- are built when something asks for them (helm_need_all_blocks: a stacked 2N right-hand side,
     // helm_get_diagonals, an apply of another block, the scaled planes of the Krylov paths)
     op->asm_nblk = (op->variant == HELM_EURUS && op->block_zero[2] && !op->block0_only && helm_tuning_now().auto_direct != 0) ? 1 : 4;
+    op->transposed = op->transposed_next;        // (helm_set_transposed: in force from here; assemble.hip leaves the planes of A^T in d_C)
     SetupStream setup_stream(op);
     int rc = op->ny > 0 ? helm3d_launch_assemble(op, freq_re, freq_im, tau, cPML) : helm_launch_assemble(op, freq_re, freq_im, tau, ky, cPML);
     if (rc) return rc;
@@ -268,6 +269,27 @@ extern "C" int helm_assemble(helm_op *op, double freq_re, double freq_im, double
     op->direct_failed = false;
     return HELM_OK;
 }
+
+// The next helm_assemble leaves A^T in the handle (on != 0) or A again (0); what the handle holds until then is unchanged, but what was derived from it
+// -- a factorisation in flight or kept, the scaled planes, the preconditioner -- is dropped as a re-assembly drops it.  2-D MiniZephyr handles (the
+// single-block 9-point system); Eurus and 3-D handles: HELM_ERR_UNSUPPORTED.
+extern "C" int helm_set_transposed(helm_op *op, int on) {
+    helm_tuning_refresh();
+    if (!op) return HELM_ERR_ARG;
+    if (op->variant != HELM_MINIZEPHYR || op->ny > 0) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "helm_set_transposed: the transposed operator exists for 2-D MiniZephyr handles (not Eurus, not 3-D)");
+    const bool want = on != 0;
+    if (want == op->transposed_next) return HELM_OK;
+    HIP_TRY(op, hipSetDevice(op->device));
+    helm_pf_retire(op);
+    op->transposed_next = want;
+    op->scaled_ok = false;
+    if (op->mg || op->mg3) mg_destroy(op);
+    op->mg3_no_keep = false;
+    for (int b = 0; b < 4; ++b) { nd_free(op->direct[b]); op->direct[b] = nullptr; }
+    op->direct_failed = false;
+    return HELM_OK;
+}
+extern "C" int helm_get_transposed(const helm_op *op) { return op ? (op->transposed ? 1 : 0) : HELM_ERR_ARG; }
 
 int helm_need_all_blocks(helm_op *op) {
     if (op->variant != HELM_EURUS || op->block0_only || op->ny > 0 || !op->assembled || op->blocks_ready >= op->nblocks) return HELM_OK;

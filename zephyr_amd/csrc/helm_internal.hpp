@@ -151,6 +151,8 @@ struct helm_op {
     cplx *d_S = nullptr;      // coupled Eurus system: the four blocks scaled by the inverse 2-norm of their system row (36N), on demand
     double *d_rs = nullptr;   // 2N inverse row norms of the 2N x 2N system
     bool assembled = false;
+    bool transposed = false;      // d_C holds the planes of A^T (assemble.hip k_transpose_planes): every consumer of d_C then works on A^T
+    bool transposed_next = false; // what helm_set_transposed asked for: in force from the next helm_assemble
     int asm_nblk = 4, blocks_ready = 0;   // Eurus: blocks the next assembly writes (1: M1 only -- the block-triangular N-row solve needs nothing else) / blocks d_C holds now
     bool scaled_ok = false;       // d_Cs / d_dinv hold the current operator (made on demand: only the Krylov paths need them)
     bool block_zero[4] = {false, false, false, false};   // block is identically zero (e.g. Eurus M3 isotropic)
@@ -289,6 +291,7 @@ int mg3_retreat(helm_op *op, int batch);                   // rebuild as the sta
 
 // ---- launchers implemented in assemble.hip ----------------------------------------------------
 int helm_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau, double ky, double cPML);
+int helm_launch_transpose_planes(helm_op *op);   // d_C (one 2-D block) <- the planes of its transpose, out of place through a pool buffer, on op->stream
 
 // ---- launchers implemented in kernels.hip -----------------------------------------------------
 // epilogues of the fused stencil kernel

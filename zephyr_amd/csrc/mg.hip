@@ -346,6 +346,7 @@ int assemble_child(helm_op *parent, helm_op *child, const std::vector<cplx> &c, 
                    double tau, double cpml) {
     int rc = helm_set_stream(child, parent->stream);
     if (rc) return rc;
+    child->transposed_next = parent->transposed;      // (the levels of a transposed operator's preconditioner are transposed too: it approximates A^-T)
     rc = helm_set_model(child, (const double *)c.data(), rho.data(), th.empty() ? nullptr : th.data(), ep.empty() ? nullptr : ep.data(),
                         de.empty() ? nullptr : de.data());
     if (rc) return rc;

@@ -208,8 +208,13 @@ __global__ __launch_bounds__(256) void k_nd_build_front(const NdDev *nodes, int 
 // 32-wide block is by absolute size, so the gradual row scaling of the PML does cost accuracy and belongs in the estimate.)
 // (The max-entry norm was tried first in round 3: for a near-singular front F11^-1 ~ u v^T / sigma with u, v spread over all unknowns, and max |entry|
 // underestimates the norm by the front's size.  Over the front's own s x s unknowns: the identity that pads a smaller front is not part of it.)
+// tr (a transposed handle, helm_set_transposed): the front of A^T is the transpose of the front of A, and the identity rows of A are columns e_j of A^T -- a
+// boundary ROW of A^T has its unit diagonal beside small off-diagonal entries, so the rule above would not know it and every boundary front would be flagged
+// again.  Such a column is eliminated as exactly as the row was (x_j appears in equation j only).  With tr the estimate is formed of M^T: rows and columns
+// change places in both launches (column sums before, lone COLUMNS weighted, max over columns of sum_j |F11^-1|_ji w_j after), which is term for term the
+// estimate the plain handle forms of the same front.  One lane per column walking down the rows: every load is contiguous across the wave.
 template <int AFTER>
-__global__ __launch_bounds__(256) void k_front_cond(const cplx *M0, int ld, long long stride, const NdDev *nodes, double *out, double *rows, int smax, int nf) {
+__global__ __launch_bounds__(256) void k_front_cond(const cplx *M0, int ld, long long stride, const NdDev *nodes, double *out, double *rows, int smax, int nf, int tr) {
     __shared__ double red[4];
     __shared__ double dsh[LUS_NMAX];
     __shared__ unsigned char lone[LUS_NMAX];
@@ -218,6 +223,21 @@ __global__ __launch_bounds__(256) void k_front_cond(const cplx *M0, int ld, long
     const int n = nodes[blockIdx.x / nf].s;              // (nf > 1: batch index = front * nf + frequency)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     double best = 0.0;
+    if (tr) {
+        const int j = threadIdx.x;                         // (n <= LUS_NMAX < 256: a lane per column)
+        if (j < n) {
+            double v = 0.0, off = 0.0;
+            for (int i = 0; i < n; ++i) {
+                const cplx a = M[(long long)i * ld + j];
+                const double m = fabs(a.x) + fabs(a.y);
+                v += AFTER ? m * w[i] : m;
+                if (!AFTER && i != j) off += m;
+            }
+            if (!AFTER) { dsh[j] = v; lone[j] = off == 0.0; }
+            best = v;
+        }
+        if (AFTER) for (int o = 32; o > 0; o >>= 1) best = fmax(best, __shfl_down(best, o));
+    } else
     for (int i = wv; i < n; i += 4) {                      // a wave per row: coalesced along the row
         double v = 0.0, off = 0.0;
         for (int j = lane; j < n; j += 64) {
@@ -729,11 +749,11 @@ int factor_group_set(helm_op *op, const FacSet &S, size_t gi, cplx *arenaF, cplx
     double *est_rows = watch ? est + est_rows_off(P, nf) : nullptr;
     if (watch) for (int b0 = 0; b0 < nbatch; b0 += 65535 / nf * nf)
         HELM_LAUNCH(k_front_cond<0>, dim3(std::min(65535 / nf * nf, nbatch - b0)), dim3(256), 0, st, Finv + (long long)b0 * s1, nmax, s1, d_nodes + g.first + b0 / nf, est + b0,
-                           est_rows + (long long)b0 * g.smax, g.smax, nf);
+                           est_rows + (long long)b0 * g.smax, g.smax, nf, op->transposed ? 1 : 0);
     invert(op, Finv, nmax, s1, g.smax, nbatch, work, s11, P.dof, 0);      // F11 -> F11^-1 where it stays
     if (watch) for (int b0 = 0; b0 < nbatch; b0 += 65535 / nf * nf)
         HELM_LAUNCH(k_front_cond<1>, dim3(std::min(65535 / nf * nf, nbatch - b0)), dim3(256), 0, st, Finv + (long long)b0 * s1, nmax, s1, d_nodes + g.first + b0 / nf, est + nbatch + b0,
-                           est_rows + (long long)b0 * g.smax, g.smax, nf);
+                           est_rows + (long long)b0 * g.smax, g.smax, nf, op->transposed ? 1 : 0);
     if (watch) for (int k = 0; k < nf; ++k) { const int rcf = flag_group(op, S.f[k], gi, est, S.rtol[k]); if (rcf) return rcf; }      // (the lists travel while the products below run)
     if (g.mmax > 0) {
         // G21 = F21 F11^-1 ; F22 -= G21 F12

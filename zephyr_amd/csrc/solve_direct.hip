@@ -508,7 +508,7 @@ extern "C" int helm_prefactor_many(helm_op **ops, int n) {
     bool together = n >= 2 && n <= ND_NF_MAX && helm_tuning_now().nd_many != 0;
     for (int k = 0; k < n && together; ++k) {
         helm_op *op = ops[k];
-        if (!direct_path_ok(op) || op->direct[0] || op->pf_pending || op->device != ops[0]->device || op->nz != ops[0]->nz || op->nx != ops[0]->nx || op->variant != ops[0]->variant) together = false;
+        if (!direct_path_ok(op) || op->direct[0] || op->pf_pending || op->device != ops[0]->device || op->nz != ops[0]->nz || op->nx != ops[0]->nx || op->variant != ops[0]->variant || op->transposed != ops[0]->transposed) together = false;
         for (int j = 0; j < k; ++j) if (ops[j] == op) together = false;
     }
     if (together) return pf_enqueue(ops, n);

@@ -323,6 +323,47 @@ extern "C" int helm_energy_accumulate_c64_device(helm_op *op, const void *dU32, 
     return launched(op);
 }
 
+// R[s ldr + i] = conj(W[i] U[s ldu + i]): the right-hand sides of the Born data (HelmBaseProblem.JvecBorn), W = v (.) gradientScaler.  k_energy's pattern:
+// one lane per cell in a grid-stride loop over at most HELM_ENERGY_MAX_BLOCKS workgroups, W[i] read once, HELM_ENERGY_UNROLL columns loaded before the first
+// product.  A stream of nsrc N reads against nsrc N 16-byte writes.  Each component is two products and one sum (contracted or not: at most three roundings of
+// terms bounded by |Re W||Re u| + |Im W||Im u|, cross terms for the imaginary part); the conjugation is exact.  No atomics: the same bits on every run.
+template <class F>
+__global__ __launch_bounds__(256) void k_virtual_sources(F U, int nsrc, long long ldu, const cplx *__restrict__ W, cplx *__restrict__ R, long long ldr, long long N) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        const cplx w = W[i];
+        int s = 0;
+        for (; s + HELM_ENERGY_UNROLL <= nsrc; s += HELM_ENERGY_UNROLL) {
+            typename F::raw x[HELM_ENERGY_UNROLL];
+#pragma unroll
+            for (int j = 0; j < HELM_ENERGY_UNROLL; ++j) x[j] = U.load((long long)(s + j) * ldu + i);
+#pragma unroll
+            for (int j = 0; j < HELM_ENERGY_UNROLL; ++j) R[(long long)(s + j) * ldr + i] = cconj(cmul(w, U.value(x[j], s + j)));
+        }
+        for (; s < nsrc; ++s) R[(long long)s * ldr + i] = cconj(cmul(w, U.value(U.load((long long)s * ldu + i), s)));
+    }
+}
+
+// R[s][i] = conj(W[i] U[s][i]) for s < nsrc, i < N (the handle's grid): U [nsrc][ldu] complex128, W N complex128, R [nsrc][ldr] complex128, ldu, ldr >= N.  R must
+// not overlap U or W.  Returns when R is complete.
+extern "C" int helm_virtual_sources_device(helm_op *op, const void *dU, int nsrc, long long ldu, const void *dW, void *dR, long long ldr) {
+    helm_tuning_refresh();
+    if (!op || !dU || !dW || !dR || nsrc < 1 || ldu < op->N || ldr < op->N || dU == dR || dW == dR) return HELM_ERR_ARG;
+    if ((((uintptr_t)dU) | ((uintptr_t)dW) | ((uintptr_t)dR)) & 15) return HELM_ERR_ARG;       // (16-byte loads and stores)
+    HIP_TRY(op, hipSetDevice(op->device));
+    HELM_LAUNCH(k_virtual_sources<FieldC128>, dim3(energy_blocks(op)), dim3(256), 0, op->stream, FieldC128{(const cplx *)dU}, nsrc, ldu, (const cplx *)dW, (cplx *)dR, ldr, op->N);
+    return launched(op);
+}
+
+extern "C" int helm_virtual_sources_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ldu, const void *dW, void *dR, long long ldr) {
+    helm_tuning_refresh();
+    if (!op || !dU32 || !dExp || !dW || !dR || nsrc < 1 || ldu < op->N || ldr < op->N || dU32 == dR || dW == dR) return HELM_ERR_ARG;
+    if ((((uintptr_t)dU32) & 7) || (((uintptr_t)dExp) & 3) || ((((uintptr_t)dW) | ((uintptr_t)dR)) & 15)) return HELM_ERR_ARG;       // (8-byte loads of U32)
+    HIP_TRY(op, hipSetDevice(op->device));
+    HELM_LAUNCH(k_virtual_sources<FieldC64>, dim3(energy_blocks(op)), dim3(256), 0, op->stream, FieldC64{(const cplxf32 *)dU32, (const int *)dExp}, nsrc, ldu, (const cplx *)dW,
+                (cplx *)dR, ldr, op->N);
+    return launched(op);
+}
+
 // receiver sampling: sum_k val[k] U[s][col[k]] over the entries k of sparse row r + s * row_stride (one thread per (r, s), fixed order).
 // row_stride = 0: one receiver array for every source; row_stride >= nrec: source s has rows [s * row_stride, s * row_stride + nrec) of its own (an array
 // that moves with the source, the per-source matrices stacked into one CSR).  ACC = false: out[r][s] = the sum, alpha / beta / beta0 unused (no product

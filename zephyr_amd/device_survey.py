@@ -428,10 +428,44 @@ def dpredFromFields(prob, F):
     return data
 
 
-def gradientFromFields(prob, F, qb, resid):
+def _factorBytes(op):
+    """What the direct factors of one 2-D operator of op's grid take in device memory, from the elimination-tree plan (host only): per front the inverse of
+    its s x s pivot block and the two s x m coupling blocks, 16 B per entry.  A 2.5-D composite keeps one set per ky unless it releases them as it goes."""
+    import ctypes
+    lib = _lib.load()
+    nz, nx, leaf = int(op.nz), int(op.nx), int(_lib.tuning().nd_leaf)
+    n = lib.helm_direct_plan(nz, nx, leaf, None, 0)
+    if n <= 0:
+        return 0
+    plan = np.zeros((n, 12), dtype=np.int32)
+    if lib.helm_direct_plan(nz, nx, leaf, plan.ctypes.data_as(ctypes.c_void_p), n) != n:
+        return 0
+    sm = plan[:, 6].astype(np.int64), plan[:, 7].astype(np.int64)
+    one = int(16 * np.sum(sm[0] * (sm[0] + 2 * sm[1])))
+    subs = getattr(op, 'subProblems', None)
+    return one * (len(subs) if subs is not None and not getattr(op, 'kyRelease', False) else 1)
+
+
+def _checkSecondFactorsFit(items):
+    """MemoryError unless every GPU has room for what a pass through the TRANSPOSED operators adds to a resident forward pass: their factors -- the factors of
+    A and of A^T are held side by side -- and the item's U and R"""
+    import torch
+    from .fieldstore import check_fits
+    need, work, seen = {}, {}, set()
+    for _, op, _, c0, c1 in items:
+        if id(op) not in seen and not op.factors and str(getattr(op, 'method', 'auto')).lower() in ('auto', 'direct'):
+            need[op.device] = need.get(op.device, 0) + _factorBytes(op)
+        seen.add(id(op))
+        work[op.device] = max(work.get(op.device, 0), 2 * (c1 - c0) * int(op.nrow) * 16)
+    check_fits({d: need.get(d, 0) + work[d] for d in work}, {d: torch.cuda.mem_get_info(d)[0] for d in work})
+
+
+def gradientFromFields(prob, F, qb, resid, system=None):
     """The u-given branch of Jtvec (problem.py:154-162) with the forward fields read from the store: per item only the k back-sources are made and solved
     (nsrc columns per frequency, not 2 nsrc), scaler * sum_s uF (.) uB goes into the GPU's partial gradient, and the real part of the sum is returned.
-    qb None: the back-sources of a moving receiver array, made on the device from `resid` (nrec, nsrc, nfreq)."""
+    qb None: the back-sources of a moving receiver array, made on the device from `resid` (nrec, nsrc, nfreq).  system: the wrapper whose operators
+    back-propagate (default prob.system; prob.adjointSystem for Jtvec(adjoint='transpose') -- the same devices and replicas, so every item still finds
+    its slice on its own GPU)."""
     import torch
     F.checkCurrent(prob)
     sv = prob.survey
@@ -443,7 +477,9 @@ def gradientFromFields(prob, F, qb, resid):
     if qb is None:
         for ifreq in F.ownedFreqs:
             sv.adjointPlan(ifreq)
-    devs, items = _storedItems(prob.system, F)
+    devs, items = _storedItems(prob.system if system is None else system, F)
+    if system is not None:
+        _checkSecondFactorsFit(items)
     add = _addOnNativeGrid(prob, scale)
 
     def one(ws, op, ifreq, c0, c1):
@@ -466,6 +502,49 @@ def gradientFromFields(prob, F, qb, resid):
         if finish is not None:
             finish()
     return _sumPartials(prob, [ws.G for ws in runOnDevices(devs, items, one) if ws.G is not None]).real
+
+
+def bornFromFields(prob, F, v):
+    """prob.JvecBorn(u=F): Born data (nrec, nsrc, nfreq) of the model perturbation v (N,) from forward fields already in HBM.  Per stored item
+    W = v (.) gradientScaler(f) scaleTerm is made on the item's GPU (v and the model go up once per worker), the virtual-source kernel writes
+    conj(W (.) slice) -- the store holds the unscaled solves, hence the scaleTerm in W -- the forward operator solves the k columns, and the samples
+    through the CONJUGATED receiver CSR (row stride 0 for a fixed array, nrec for one that moves with the source) come down: nrec x k values per item."""
+    F.checkCurrent(prob)
+    sv = prob.survey
+    nsrc, nrec = sv.nsrc, sv.nrec
+    scale = F.scale
+    data = np.zeros((nrec, nsrc, sv.nfreq), dtype=np.complex128)
+    if not F.items:
+        return data
+    stride = nrec if sv.mode != 'fixed' else 0
+    Rms = {gk: Rm.conj() for gk, Rm in _receiverMatrices(sv, F.ownedFreqs).items()}
+    plain_scaler = prob._plainGradientScaler()
+    v = np.ascontiguousarray(v, dtype=np.complex128)
+    host_w = None if plain_scaler else {ifreq: v * np.asarray(prob.gradientScaler(ifreq)).ravel() * scale for ifreq in F.ownedFreqs}
+    devs, items = _storedItems(prob.system, F)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        dev = ws.device
+        sl, ex = F.slice(ifreq, c0)
+        gk = sv._gridKey(ifreq)
+        csr = _csrOnDevice(ws, Rms[gk], ('conj', gk), nrec, stride, c0)
+        if plain_scaler:
+            cm = op.c
+            inv = ws.cached(('inv_c3', id(cm)), lambda: _inverseCube(cm, dev), keep=cm)
+            vd = ws.cached(('born_v', id(v)), lambda: _lib.to_device(v, dev, np.complex128), keep=v)
+            omega = 2 * np.pi * sv.freqs[ifreq]
+            W = inv * vd * complex(-(omega ** 2) * scale)
+        else:
+            W = ws.cached(('born_w', ifreq, id(v)), lambda: _lib.to_device(host_w[ifreq], dev, np.complex128), keep=v)
+        U, R, out = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni), ws.buffer('out', (nrec, k))
+        _lib.wait_torch_stream(dev)
+        op.virtualSourcesDevice(sl.data_ptr(), k, W.data_ptr(), R.data_ptr(), d_exp=None if ex is None else ex.data_ptr(), rows=Ni)
+        op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+        op.sampleDevice(U.data_ptr(), k, csr, out.data_ptr())
+        data[:, c0:c1, ifreq] = scale * _lib.from_device(out)
+    runOnDevices(devs, items, one)
+    return data
 
 
 # ---- illumination / diagonal pseudo-Hessian ---------------------------------------------------------------------------------------------------

@@ -47,7 +47,10 @@ class BaseDiscretization(BaseModelDependent):
         'batch':          (False,    '_batch',     np.int64),
         'checkEvery':     (False,    '_checkEvery', np.int64),
         'device':         (False,    '_device',    np.int64),
+        'transposed':     (False,    None,         bool),       # the operator is A^T: `obj * rhs` -> conj(A^-T (premul * rhs)) (helm_set_transposed)
     }
+
+    TRANSPOSABLE = False       # classes whose device operator has a transposed assembly (the 2-D MiniZephyr family)
 
     # ---- model properties -----------------------------------------------------------------
     @property
@@ -79,6 +82,19 @@ class BaseDiscretization(BaseModelDependent):
         else:
             self._rho = 310. * self.c.real ** 0.25
         return self._rho
+
+    @property
+    def transposed(self):
+        """config key (default False): the device operator is assembled as A^T, so that `self * rhs` is conj(A^-T (premul * rhs)) -- what back-propagates a
+        residual exactly when A is not symmetric (HelmBaseProblem.Jtvec(adjoint='transpose')).  The 2-D MiniZephyr family only."""
+        return bool(self.__dict__.get('_transposed', False))
+
+    @transposed.setter
+    def transposed(self, value):
+        if value and not self.TRANSPOSABLE:
+            raise NotImplementedError('%s has no transposed operator: helm_set_transposed serves 2-D MiniZephyr handles (not Eurus, not the 3-D operator)'
+                                      % (type(self).__name__,))
+        self._transposed = bool(value)
 
     # ---- solver controls -------------------------------------------------------------------
     @property
@@ -124,6 +140,8 @@ class BaseDiscretization(BaseModelDependent):
             try:
                 c, rho, theta, eps, delta = self._model_arrays()
                 _lib.check(lib.helm_set_model(h, _lib.ptr(c), _lib.ptr(rho), _lib.ptr(theta), _lib.ptr(eps), _lib.ptr(delta)), h)
+                if self.transposed:
+                    _lib.check(lib.helm_set_transposed(h, 1), h)
                 f = complex(self.freq)
                 _lib.check(lib.helm_assemble(h, f.real, f.imag, float(self.tau), float(ky), float(cpml)), h)
             except Exception:
@@ -300,6 +318,17 @@ class BaseDiscretization(BaseModelDependent):
                                                              ctypes.c_void_p(d_e)), self.handle)
             return
         _lib.check(lib.helm_energy_accumulate_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), rows, float(alpha), w, ctypes.c_void_p(d_e)), self.handle)
+
+    def virtualSourcesDevice(self, d_u, nsrc, d_w, d_r, d_exp=None, rows=None):
+        """R[s] = conj(W (.) U[s]) on the device, the right-hand sides of HelmBaseProblem.JvecBorn: d_u [nsrc][rows] complex128 (d_exp given: a complex64 store
+        with those column exponents), d_w nrow complex128, d_r [nsrc][rows] complex128.  All device pointers; returns when R is complete."""
+        lib = _lib.load()
+        rows = int(self.nrow if rows is None else rows)
+        if d_exp is not None:
+            _lib.check(lib.helm_virtual_sources_c64_device(self.handle, ctypes.c_void_p(d_u), ctypes.c_void_p(d_exp), int(nsrc), rows, ctypes.c_void_p(d_w),
+                                                           ctypes.c_void_p(d_r), rows), self.handle)
+            return
+        _lib.check(lib.helm_virtual_sources_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), rows, ctypes.c_void_p(d_w), ctypes.c_void_p(d_r), rows), self.handle)
 
     def packDevice(self, d_u, nsrc, d_out, d_exp, rows=None):
         """The complex64 store of the wavefields d_u ([nsrc][rows] complex128): d_out [nsrc][rows] complex64 values x * 2^-e_s, d_exp the nsrc int32 column

@@ -13,6 +13,7 @@ class MiniZephyr(BaseDiscretization):
     minizephyr.py:40-298 run in the HIP kernel `k_assemble_mz`."""
 
     VARIANT = _lib.HELM_MINIZEPHYR
+    TRANSPOSABLE = True
 
     initMap = {
         'nPML':           (False,    '_nPML',      np.int64),
@@ -72,6 +73,7 @@ class MiniZephyr25D(BaseDiscretization, DiscretizationWrapper):
     }
 
     maskKeys = ['nky', 'Disc', 'parallel', 'kyOnDevice', 'kyRelease']
+    TRANSPOSABLE = True        # (`transposed` stays in the config the ky sub-problems are built from: every A_ky is transposed)
 
     @property
     def Disc(self):
@@ -211,6 +213,10 @@ class MiniZephyr25D(BaseDiscretization, DiscretizationWrapper):
 
     def packDevice(self, d_u, nsrc, d_out, d_exp, rows=None):
         self._liveSub().packDevice(d_u, nsrc, d_out, d_exp, rows=rows)
+
+    def virtualSourcesDevice(self, d_u, nsrc, d_w, d_r, d_exp=None, rows=None):
+        'virtual sources from wavefields that are the ky SUM already'
+        self._liveSub().virtualSourcesDevice(d_u, nsrc, d_w, d_r, d_exp=d_exp, rows=rows)
 
     def _kyLoop(self, each):
         'each(k, sub) for k = 0 .. nky-1 in the order of ky_schedule, the factorisations of the next group enqueued while the current one is being solved'

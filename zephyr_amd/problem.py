@@ -51,7 +51,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
     }
 
     surveyPair = HelmBaseSurvey
-    cacheItems = ['_system']
+    cacheItems = ['_system', '_adjointSystem']
 
     def __init__(self, systemConfig, *args, **kwargs):
         BaseSCCache.__init__(self, systemConfig, *args, **kwargs)
@@ -87,9 +87,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
 
     def clearCache(self):
         self._modelStamp = self.__dict__.get('_modelStamp', 0) + 1        # (what a DeviceFields remembers: fields of an earlier model are refused)
-        sysw = self.__dict__.get('_system', None)
-        if sysw is not None:
-            del sysw.factors
+        for name in ('_system', '_adjointSystem'):
+            sysw = self.__dict__.get(name, None)
+            if sysw is not None:
+                del sysw.factors
         BaseSCCache.clearCache(self)
 
     @property
@@ -97,6 +98,25 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if getattr(self, '_system', None) is None:
             self._system = self.SystemWrapper(self.systemConfig)
         return self._system
+
+    @property
+    def adjointSystem(self):
+        """The system wrapper of the TRANSPOSED operators: the class of `system`, built from the same systemConfig plus `transposed=True` when first asked for
+        -- the same frequencies on the same devices, the same replicas for split sources.  `sub * q` there is conj(A_f^-T (premul q)), what
+        Jtvec(adjoint='transpose') back-propagates through.  It goes with the problem's cache on a model change, and `del prob.factors` releases it too.
+        While both wrappers are in use the factors of A_f and of A_f^T are resident side by side: twice the device memory of `system` alone.
+        2-D MiniZephyr / MiniZephyrHD / MiniZephyr25D on one grid; Eurus, the 3-D operator and the multiscale wrappers raise NotImplementedError."""
+        if getattr(self, '_adjointSystem', None) is None:
+            from .distributors import MultiGridMultiFreq
+            cls = type(self.system)
+            if issubclass(cls, MultiGridMultiFreq) or isinstance(self.survey, HelmMultiGridSurvey):
+                raise NotImplementedError('the transposed operator serves single-grid problems: a multiscale pairing has no exact-adjoint route')
+            cfg = dict(self.systemConfig)
+            cfg['transposed'] = True
+            adj = cls(cfg)
+            adj.subProblems                                # (Eurus / 3-D refuse here, not in the middle of a product)
+            self._adjointSystem = adj
+        return self._adjointSystem
 
     # ---- sharding --------------------------------------------------------------------------------------
     @property
@@ -114,10 +134,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         the ranks that own none are waiting in).'''
         return bool(getattr(self, '_shard', True)) and parallel.rank_and_size()[1] > 1
 
-    def _solveOwned(self, rhs_list):
-        'generator of (ifreq, scaleTerm * sub * rhs) over the owned frequencies'
+    def _solveOwned(self, rhs_list, sysw=None):
+        'generator of (ifreq, scaleTerm * sub * rhs) over the owned frequencies; sysw: the wrapper to solve with (default `system`; `adjointSystem` for A^-T)'
         owned = self.ownedFreqs
-        sysw = self.system
+        sysw = self.system if sysw is None else sysw
         if len(owned) == self.survey.nfreq and getattr(sysw, 'parallel', False) and hasattr(sysw, 'devices'):
             # every frequency is this process's: the wrapper's own dispatch (all visible GPUs, prepare-ahead) does the loop
             rl = list(rhs_list) if isinstance(rhs_list, (list, tuple)) else rhs_list
@@ -191,7 +211,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         """Data perturbation for a model perturbation v (problem.py:87-122): one virtual source
         `v * (-c^3/omega^2)` per frequency is solved, and dpert[:, :, f] is the outer product of the
         receiver and source samplings of that field.  Fixed receiver arrays only: the reference's
-        relative-geometry branch multiplies mismatched shapes (problem.py:117-120)."""
+        relative-geometry branch multiplies mismatched shapes (problem.py:117-120).
+
+        This is the reference's one-column outer-product approximation and stays as it is; it is NOT the adjoint of Jtvec.  The Born data that
+        pair with Jtvec(adjoint='transpose') exactly are `JvecBorn`."""
         if not self.ispaired:
             raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
         if v is None:
@@ -213,7 +236,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         return dpert.ravel()
 
     # ---- gradient ----------------------------------------------------------------------------------------
-    def Jtvec(self, m=None, v=None, u=None):
+    def Jtvec(self, m=None, v=None, u=None, adjoint='reciprocity'):
         """FWI gradient g = sum_f scaler_f sum_s uF (.) uB  (problem.py:124-164).
 
         u is None: "mux" branch -- forward and back-propagated sources are stacked column-wise and
@@ -221,16 +244,28 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         u given (list of forward fields per frequency): only the back-propagation is solved and
         the real part is returned.  u a DeviceFields (fieldsDevice): the same with the forward fields
         read where they were solved, in HBM.
+
+        adjoint='reciprocity' (default): the back-propagation runs through the forward factors, as in the reference.  That is the adjoint of the
+        modelling operator only if A is complex-symmetric, which the 9-point MiniZephyr operator is not (PML and density scale its rows).
+        adjoint='transpose': the back-propagation runs through A^-T (`adjointSystem`),
+            g = Re sum_f w_f (.) sum_s uF_s (.) (scaleTerm S_f^T R_s^T r_s),   S_f^T q = conj(A_f^-T premul q),  w_f = gradientScaler(f),
+        always real float64 (N,) -- there is no mux branch, forward and back solves use different factors -- and the exact adjoint of `JvecBorn` under
+        <a, b> = Re sum conj(a) b.  u a DeviceFields: on the device; u None with the device path: fieldsDevice() internally, released afterwards;
+        u a list of host arrays, or no device path: numpy.  Fixed and moving receiver arrays; multiscale surveys raise NotImplementedError.
         """
         if not self.ispaired:
             raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
         if v is None:
             raise Exception('Actually, Jtvec requires a residual vector')
+        if adjoint not in ('reciprocity', 'transpose'):
+            raise ValueError('adjoint is %r: \'reciprocity\' or \'transpose\'' % (adjoint,))
         self.updateModel(m)
         sv = self.survey
         nsrc = sv.nsrc
         resid = np.asarray(v).reshape((sv.nrec, sv.nsrc, sv.nfreq))
         owned = self.ownedFreqs
+        if adjoint == 'transpose':
+            return self._JtvecTranspose(resid, u)
         if isinstance(u, DeviceFields):
             # forward fields left in HBM by fieldsDevice(): only the back-propagation is solved, on the store's own items
             u.checkCurrent(self)
@@ -255,6 +290,115 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if self._sharded:
             g = parallel.allreduce_sum(g)
         return g if u is None else g.real
+
+    # ---- exact adjoint, Born data, Gauss-Newton product ----------------------------------------------------
+    def _refuseMultiscale(self, what):
+        if isinstance(self.survey, HelmMultiGridSurvey):
+            raise NotImplementedError('%s serves single-grid surveys: the transposed operator and the stored forward fields live on one grid' % (what,))
+
+    def _forwardFields(self, u):
+        """what the exact-adjoint routes read the forward fields from: a DeviceFields as it is (checked), a list of host arrays as a list, None -> a DeviceFields
+        solved now where the device path serves (the caller releases it), else a host list with the owned frequencies' fields (None elsewhere).
+        Returns (fields, made_here)."""
+        if isinstance(u, DeviceFields):
+            u.checkCurrent(self)
+            return u, False
+        if u is not None:
+            return list(u), False
+        if self._deviceGradientAvailable():
+            return self.fieldsDevice(), True
+        uF = [None] * self.survey.nfreq
+        pps = self.survey.postProcessors
+        for ifreq, uf in self._solveOwned(self.survey.getSources()):
+            uF[ifreq] = pps[ifreq](uf)
+        return uF, False
+
+    def _JtvecTranspose(self, resid, u):
+        "Jtvec(adjoint='transpose') once the model is current and `resid` is (nrec, nsrc, nfreq)"
+        self._refuseMultiscale("Jtvec(adjoint='transpose')")
+        sv = self.survey
+        adj = self.adjointSystem
+        F, mine = self._forwardFields(u)
+        if isinstance(F, DeviceFields):
+            try:
+                return device_survey.gradientFromFields(self, F, sv.getResidualSources(resid) if sv.mode == 'fixed' else None, resid, system=adj)
+            finally:
+                if mine:
+                    F.release()
+        qb = sv.getResidualSources(resid)
+        g = np.zeros(self.nrow, dtype=np.complex128)
+        for ifreq, uB in self._solveOwned(qb, adj):
+            g += self.gradientScaler(ifreq) * (np.asarray(F[ifreq]) * uB).sum(axis=1)
+        if self._sharded:
+            g = parallel.allreduce_sum(g)
+        return g.real
+
+    def JvecBorn(self, m=None, v=None, u=None):
+        """Born data of the model perturbation v from the forward fields, the ravel of (nrec, nsrc, nfreq) complex128:
+
+            dd[:, s, f] = conj(R_s) . scaleTerm S_f( conj(v (.) w_f (.) uF_s) ),   S_f q = conj(A_f^-1 premul q),  w_f = gradientScaler(f),  uF_s = scaleTerm S_f qf_s
+
+        one virtual source per SOURCE and frequency.  It is the exact adjoint of Jtvec(adjoint='transpose'): <JvecBorn v, r> = <v, Jtvec(r)> under
+        <a, b> = Re sum conj(a) b, to solver accuracy.  (`Jvec` is the reference's one-column outer-product approximation, kept as it is; it has no such
+        property.)  Only the forward factors are used -- those fieldsDevice has just made.  u a DeviceFields: per stored item the virtual sources are
+        made from the slice on the device, solved there and sampled through the conjugated receiver CSR; nrec x k samples come down per item.  u None
+        with the device path: fieldsDevice() internally, released afterwards.  u a list of host arrays, or no device path: numpy.  Sharded ranks end
+        in one all-reduce.  Multiscale surveys raise NotImplementedError."""
+        if not self.ispaired:
+            raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
+        if v is None:
+            raise Exception('Actually, JvecBorn requires a perturbation vector')
+        self.updateModel(m)
+        self._refuseMultiscale('JvecBorn')
+        sv = self.survey
+        pert = np.asarray(v).reshape((self.nrow,))
+        F, mine = self._forwardFields(u)
+        if isinstance(F, DeviceFields):
+            try:
+                data = device_survey.bornFromFields(self, F, pert)
+            finally:
+                if mine:
+                    F.release()
+        else:
+            data = np.zeros((sv.nrec, sv.nsrc, sv.nfreq), dtype=np.complex128)
+            owned = self.ownedFreqs
+            qv = [np.conj((pert * np.asarray(self.gradientScaler(i)).ravel())[:, None] * np.asarray(F[i])) if i in owned else None for i in range(sv.nfreq)]
+            for ifreq, uB in self._solveOwned(qv):
+                uB = np.asarray(uB)
+                if sv.mode == 'fixed':
+                    data[:, :, ifreq] = sv.rVec(0, ifreq).conj() * uB
+                else:
+                    for isrc in range(sv.nsrc):
+                        data[:, isrc, ifreq] = sv.rVec(isrc, ifreq).conj() * uB[:, isrc]
+        if self._sharded:
+            data = parallel.allreduce_sum(data)
+        return data.ravel()
+
+    def Hvec(self, m=None, v=None, u=None, weights=None):
+        """Gauss-Newton Hessian times v: Jtvec(JvecBorn(v) (.) weights, adjoint='transpose'), float64 (N,).  Symmetric and positive semi-definite as an
+        operator on real vectors, because the two halves are exact adjoints.  weights: optional, real, non-negative, the shape (or ravel) of the data.
+        Both halves read the same forward fields: two solves of nsrc columns per frequency, no forward re-solve; with u None the fields are solved once
+        (into HBM where the device path serves) for both halves.  Needs the factors of A and of A^T side by side (see `adjointSystem`)."""
+        if not self.ispaired:
+            raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
+        if v is None:
+            raise Exception('Actually, Hvec requires a vector')
+        self.updateModel(m)
+        self._refuseMultiscale('Hvec')
+        if weights is not None:
+            weights = np.asarray(weights)
+            if np.iscomplexobj(weights) or weights.size != self.survey.nD or not np.all(weights >= 0):
+                raise ValueError('weights are real, non-negative and of the size of the data (%d)' % (self.survey.nD,))
+            weights = weights.astype(np.float64).ravel()
+        F, mine = self._forwardFields(u)
+        try:
+            d = self.JvecBorn(None, v, u=F)
+            if weights is not None:
+                d = d * weights
+            return self.Jtvec(None, d, u=F, adjoint='transpose')
+        finally:
+            if mine and isinstance(F, DeviceFields):
+                F.release()
 
     # ---- illumination / diagonal pseudo-Hessian ------------------------------------------------------------
     def illumination(self, m=None, u=None, kind='pseudoHessian', side='source', perFreq=False):
@@ -350,6 +494,9 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
     @factors.deleter
     def factors(self):
         del self.system.factors
+        adj = self.__dict__.get('_adjointSystem', None)
+        if adj is not None:
+            del adj.factors
 
 
 class Helm2DProblem(HelmBaseProblem):
