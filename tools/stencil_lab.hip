@@ -1,7 +1,7 @@
 // Kernel lab (development tool, not part of the library): times variants of the batched 9-point
 // complex128 stencil apply on the GPU box and checks them against a naive reference.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -o tools/stencil_lab tools/stencil_lab.hip && tools/stencil_lab [n] [B]
-#include "../zephyr_amd/csrc/kernels.hip"
+#include "../zephyr_amd/csrc/stencil.hip"
 #include <vector>
 #include <random>
 #include <cstdio>

@@ -7,6 +7,9 @@
 // One thread per grid point; everything is elementwise on (c, rho) with clamped ("edge"
 // padded) neighbour reads, so the kernel is a coalesced streaming pass: it runs once per
 // frequency and is not on the per-iteration path.
+//
+// Also here: what is derived from the planes or the model once per operator -- the Jacobi-scaled planes (k_scale_planes), the
+// row-equilibrated coupled Eurus system (k_rowscale_system) and Gardner's density (k_gardner_rho).
 #include "helm_internal.hpp"
 
 namespace {
@@ -307,6 +310,62 @@ void mz_profiles(int n, int npml, double h, bool fs_low, bool fs_high, std::vect
     if (!fs_low) for (int k = 0; k < lo_len; ++k) sgn[k] = 1.0;
 }
 
+// ---- what the solvers derive from the assembled planes and the model -------------------------------------
+// Jacobi scaling: Cs = planes divided by the centre plane, dinv = 1 / centre plane
+__global__ __launch_bounds__(256) void k_scale_planes(const cplx *__restrict__ C, cplx *__restrict__ Cs,
+                                                      cplx *__restrict__ dinv, long long N, int nblocks, double floor_frac,
+                                                      int nplanes, int centre) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    for (int m = 0; m < nblocks; ++m) {
+        const cplx *Cm = C + (long long)m * nplanes * N;
+        cplx *Sm = Cs + (long long)m * nplanes * N;
+        cplx d = Cm[(long long)centre * N + i];
+        const bool zero = (d.x == 0.0 && d.y == 0.0);
+        if (floor_frac > 0.0 && !zero) {
+            // smoother safeguard on multigrid levels: where the diagonal nearly cancels (k h ~ 2: mass term
+            // against the Laplacian) keep its phase but not less than floor_frac of the row's absolute sum
+            double rows = 0.0;
+            for (int k = 0; k < nplanes; ++k) rows += sqrt(cabs2(Cm[(long long)k * N + i]));
+            const double ad = sqrt(cabs2(d));
+            if (ad < floor_frac * rows) d = cscale(d, floor_frac * rows / ad);
+        }
+        const cplx di = zero ? cmake(0.0, 0.0) : crecip(d);
+        dinv[(long long)m * N + i] = di;
+        for (int k = 0; k < nplanes; ++k) Sm[(long long)k * N + i] = (k == centre) ? cmake(1.0, 0.0) : cmul(Cm[(long long)k * N + i], di);
+    }
+}
+
+// Row equilibration of the coupled two-field Eurus system [[M1, M2], [M3, M4]]: every system row is divided by its
+// 2-norm (the diagonal of M4 nearly vanishes where eps ~ delta, so Jacobi scaling is useless there).
+__global__ __launch_bounds__(256) void k_rowscale_system(const cplx *__restrict__ C, cplx *__restrict__ S, double *__restrict__ rs, long long N) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+#pragma unroll
+    for (int row = 0; row < 2; ++row) {
+        double n2 = 0.0;
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) n2 += cabs2(C[((long long)(2 * row + blk) * 9 + k) * N + i]);
+        const double inv = n2 > 0.0 ? 1.0 / sqrt(n2) : 0.0;
+        rs[(long long)row * N + i] = inv;
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk)
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                const long long idx = ((long long)(2 * row + blk) * 9 + k) * N + i;
+                S[idx] = cscale(C[idx], inv);
+            }
+    }
+}
+
+// Gardner's relation, the reference's density default: rho = 310 Re(c)^0.25 (discretization.py:70)
+__global__ __launch_bounds__(256) void k_gardner_rho(const cplx *__restrict__ c, double *__restrict__ rho, long long n) {
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
+        rho[i] = 310.0 * pow(c[i].x, 0.25);
+}
+
 }  // namespace
 
 int helm_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau, double ky, double cPML) {
@@ -404,5 +463,26 @@ int helm_launch_transpose_planes(helm_op *op) {
     if (e1 != hipSuccess || e2 != hipSuccess) { helm_pool_free(op->device, d_T, bytes); HIP_TRY(op, e1); HIP_TRY(op, e2); }
     helm_pool_free(op->device, op->d_C, bytes);       // (nothing reads the old planes any more: the stream is drained)
     op->d_C = d_T;
+    return HELM_OK;
+}
+
+int helm_launch_scale_planes(helm_op *op) {
+    const int blocks = (int)((op->N + 255) / 256);
+    HELM_LAUNCH(k_scale_planes, dim3(blocks), dim3(256), 0, op->stream, op->d_C, op->d_Cs, op->d_dinv, op->N, op->nblocks, op->diag_floor, op->nplanes, op->centre);
+    HIP_TRY(op, hipGetLastError());
+    return HELM_OK;
+}
+
+int helm_launch_rowscaled_system(helm_op *op) {
+    if (!op->d_S) HIP_TRY(op, hipMalloc(&op->d_S, (size_t)36 * op->N * sizeof(cplx)));
+    if (!op->d_rs) HIP_TRY(op, hipMalloc(&op->d_rs, (size_t)2 * op->N * sizeof(double)));
+    HELM_LAUNCH(k_rowscale_system, dim3((unsigned)((op->N + 255) / 256)), dim3(256), 0, op->stream, (const cplx *)op->d_C, op->d_S, op->d_rs, op->N);
+    HIP_TRY(op, hipGetLastError());
+    return HELM_OK;
+}
+
+int helm_launch_gardner_rho(helm_op *op) {
+    HELM_LAUNCH(k_gardner_rho, dim3(vec_blocks(op->N)), dim3(256), 0, op->stream, (const cplx *)op->d_c, op->d_rho, op->N);
+    HIP_TRY(op, hipGetLastError());
     return HELM_OK;
 }

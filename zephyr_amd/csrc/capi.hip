@@ -455,7 +455,7 @@ int solve_block(helm_op *op, int block, const cplx *dRHS, long long rhs_ld, long
                 const bool cj = dUconj != nullptr;
                 for (int j = 0; j < k; ++j) {
                     info[bad[j]] = ki[j];
-                    if (cj) helm_launch_finish_ex(op, tX, N, (long long)j * N, dUconj + (long long)bad[j] * N, N, 0, 1);
+                    if (cj) helm_launch_finish(op, tX, N, (long long)j * N, dUconj + (long long)bad[j] * N, N, 0, 1);
                     else hipMemcpyAsync(dXout + (long long)bad[j] * N, tX + (long long)j * N, colb, hipMemcpyDeviceToDevice, op->stream);
                 }
                 release();
@@ -593,8 +593,8 @@ extern "C" int helm_solve_device(helm_op *op, const void *dRHS, void *dU, int nr
         int rc = solve_block(op, 0, (const cplx *)dRHS_use, rows, 0, premul, nullptr, dW, nrhs, o, info, 1, rows);
         if (rc >= 0) {
             result = rc;
-            rc = helm_launch_finish_ex(op, dW, 2 * N, 0, (cplx *)dU_use, rows, 0, nrhs);
-            if (!rc && stacked) rc = helm_launch_finish_ex(op, dW, 2 * N, N, (cplx *)dU_use, rows, N, nrhs);
+            rc = helm_launch_finish(op, dW, 2 * N, 0, (cplx *)dU_use, rows, 0, nrhs);
+            if (!rc && stacked) rc = helm_launch_finish(op, dW, 2 * N, N, (cplx *)dU_use, rows, N, nrhs);
             if (!rc && hipStreamSynchronize(op->stream) != hipSuccess) rc = HELM_ERR_DEVICE;
         }
         hipFree(dW);
@@ -607,7 +607,7 @@ extern "C" int helm_solve_device(helm_op *op, const void *dRHS, void *dU, int nr
         if (rc < 0) { cleanup(); return rc; }
         result = rc;
         if (!wrote_u) {
-            rc = helm_launch_finish(op, dX, (cplx *)dU_use, rows, nrhs, 0);
+            rc = helm_launch_finish(op, dX, N, 0, (cplx *)dU_use, rows, 0, nrhs);
             if (rc) { cleanup(); return rc; }
         }
     } else {
@@ -626,8 +626,8 @@ extern "C" int helm_solve_device(helm_op *op, const void *dRHS, void *dU, int nr
             if (!rc) rc = solve_block(op, 0, (const cplx *)dRHS_use, rows, 0, premul, dT, dX, nrhs, o, info);
             if (rc >= 0) {
                 result = std::max(result, rc);
-                rc = helm_launch_finish(op, dX, (cplx *)dU_use, rows, nrhs, 0);
-                if (!rc) rc = helm_launch_finish(op, dV, (cplx *)dU_use, rows, nrhs, N);
+                rc = helm_launch_finish(op, dX, N, 0, (cplx *)dU_use, rows, 0, nrhs);
+                if (!rc) rc = helm_launch_finish(op, dV, N, 0, (cplx *)dU_use, rows, N, nrhs);
             }
         }
         hipFree(dV); hipFree(dT);

@@ -115,12 +115,6 @@ struct Stencil3Params {
     int npart;               // partial sums per right-hand side and quantity the caller's reduction reads (>= the workgroups of this launch: the rest is zeroed)
 };
 
-__device__ inline double wave_sum3(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    return v;
-}
-
 __device__ inline int xcd_swizzle3(int bid, int nblk) {
     const int q = nblk / HELM_NXCD, rem = nblk % HELM_NXCD;
     const int x = bid % HELM_NXCD, k = bid / HELM_NXCD;
@@ -284,7 +278,7 @@ __device__ __forceinline__ void stencil3_body(const Stencil3Params &q) {
         if (EPI != EPI_NONE && EPI != EPI_JACOBI) {
             const int wave = tid >> 6;
 #pragma unroll
-            for (int qq = 0; qq < 4; ++qq) dsum[qq] = wave_sum3(dsum[qq]);
+            for (int qq = 0; qq < 4; ++qq) dsum[qq] = wave_sum(dsum[qq]);
             if (lane == 0) { red[wave * 4 + 0] = dsum[0]; red[wave * 4 + 1] = dsum[1]; red[wave * 4 + 2] = dsum[2]; red[wave * 4 + 3] = dsum[3]; }
             __syncthreads();
             if (tid == 0) {

@@ -95,6 +95,40 @@ struct RhsScal {
 
 enum { ST_ACTIVE = 0, ST_CONVERGED = 1, ST_BREAKDOWN = 2, ST_FROZEN = 3, ST_PARKED = 4 };
 
+// ---- reductions and grid sizes (the stencil epilogues, the Krylov updates and the shared vector kernels) ----
+__device__ inline double wave_sum(double v) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    return v;
+}
+
+// Reduce NQ doubles per thread over a 256-thread block; result valid in thread 0.
+template <int NQ>
+__device__ inline void block_sum(double (&v)[NQ], double *smem /* >= 4*NQ doubles */) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int q = 0; q < NQ; ++q) v[q] = wave_sum(v[q]);
+    if (lane == 0) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) smem[wave * NQ + q] = v[q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) v[q] = (smem[q] + smem[NQ + q]) + (smem[2 * NQ + q] + smem[3 * NQ + q]);
+    }
+    __syncthreads();
+}
+
+__device__ inline bool rhs_active(const RhsScal *scal, int b) { return scal == nullptr || scal[b].status == ST_ACTIVE; }
+
+// workgroups of 256 lanes for a grid-stride loop over N points
+inline int vec_blocks(long long N) {
+    long long nb = (N + 255) / 256;
+    if (nb > 1024) nb = 1024;
+    return (int)nb;
+}
+
 // ---- the handle ---------------------------------------------------------------------------
 struct helm_op {
     int device = 0, variant = 0, nz = 0, nx = 0, nPML = 10;
@@ -292,8 +326,11 @@ int mg3_retreat(helm_op *op, int batch);                   // rebuild as the sta
 // ---- launchers implemented in assemble.hip ----------------------------------------------------
 int helm_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau, double ky, double cPML);
 int helm_launch_transpose_planes(helm_op *op);   // d_C (one 2-D block) <- the planes of its transpose, out of place through a pool buffer, on op->stream
+int helm_launch_scale_planes(helm_op *op);       // d_Cs, d_dinv from d_C
+int helm_launch_rowscaled_system(helm_op *op);   // d_S, d_rs: the coupled Eurus system, every row divided by its 2-norm
+int helm_launch_gardner_rho(helm_op *op);        // d_rho = 310 Re(d_c)^0.25
 
-// ---- launchers implemented in kernels.hip -----------------------------------------------------
+// ---- the stencil apply (stencil.hip) -----------------------------------------------------------
 // epilogues of the fused stencil kernel
 enum { EPI_NONE = 0,      // y = A x
        EPI_DOT_W = 1,     // + partial (w, y)                      [BiCGSTAB (r0, v)]
@@ -328,45 +365,26 @@ struct ApplyArgs {
     int x32 = 0, w32 = 0, y32 = 0;  // (3-D) X / W / Y hold complex64 (the multigrid cycle's finest-level vectors, mg3d.hip); the arithmetic stays fp64
 };
 int helm_launch_apply(helm_op *op, const ApplyArgs &a);
+int helm_apply_num_blocks(const helm_op *op);
+int helm_stencil_tile_rows();     // rows of the 64-wide stencil tile (4 * STENCIL_P)
 
 // ---- 3-D operator (helm3d.hip) -------------------------------------------------------------------
 int helm3d_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau, double cPML);
 int helm3d_launch_apply(helm_op *op, const ApplyArgs &a, hipEvent_t e0, hipEvent_t e1);
 int helm3d_apply_num_blocks(const helm_op *op);
 
-int helm_apply_num_blocks(const helm_op *op);
-int helm_stencil_tile_rows();     // rows of the 64-wide stencil tile (4 * STENCIL_P)
-
-int helm_launch_scale_planes(helm_op *op);   // d_Cs, d_dinv from d_C
-
-struct VecPtrs {   // all [nrhs][N] complex, stride N
-    cplx *x, *r, *r0, *p, *v, *s, *t;
-};
-// BiCGSTAB
-int helm_launch_bicg_init(helm_op *op, int block, const cplx *dRHS, long long rhs_ld, cplx premul, const cplx *sub, VecPtrs w, int nrhs, double rtol);
-int helm_launch_bicg_p(helm_op *op, VecPtrs w, int nrhs);
-int helm_launch_bicg_s(helm_op *op, VecPtrs w, int nrhs);
-int helm_launch_bicg_xr(helm_op *op, VecPtrs w, const cplx *xp, const cplx *xs, int nrhs);   // x += alpha xp + omega xs ; r = s - omega t
-int helm_launch_fin(helm_op *op, int which, int nrhs, int nblk_part);
-enum { FIN_BICG_INIT = 0, FIN_ALPHA = 1, FIN_OMEGA = 2, FIN_RHO = 3, FIN_RESTART = 4,
-       FIN_CG_INIT = 5, FIN_CG_ALPHA = 6, FIN_CG_RR = 7, FIN_CG_BETA = 8, FIN_NORM = 9,
-       FIN_NORM2 = 10 /* aux[b] = slot 0, aux[nrhs + b] = slot 1 */ };
-int helm_vec_num_blocks(const helm_op *op);
-// CGNR
-int helm_launch_cg_xr(helm_op *op, VecPtrs w, int nrhs);      // x += alpha p ; r -= alpha w(v) ; (r,r)
-int helm_launch_cg_p(helm_op *op, VecPtrs w, int nrhs, int first);   // p = z(s) + beta p
-// misc
-int helm_launch_finish(helm_op *op, const cplx *x, cplx *dU, long long u_ld, int nrhs, long long row_off);   // U = conj(x)
-int helm_launch_finish_ex(helm_op *op, const cplx *x, long long x_ld, long long x_off, cplx *dU, long long u_ld, long long row_off, int nrhs);
-int helm_launch_prep_rhs_ex(helm_op *op, const cplx *dRHS, long long rhs_ld, long long row_off, cplx premul, const cplx *scale,
-                            cplx *out, long long out_ld, long long out_off, int nrhs);
-int helm_launch_rowscaled_system(helm_op *op);    // d_S, d_rs
-int helm_launch_prep_rhs_rs(helm_op *op, const cplx *dRHS, long long rhs_ld, long long row_off, cplx premul, const double *rs,
-                            cplx *out, long long out_ld, long long out_off, int nrhs);
-int helm_launch_prep_rhs(helm_op *op, const cplx *dRHS, long long rhs_ld, long long row_off, cplx premul, const cplx *sub, cplx *out, int nrhs); // out = premul*rhs - sub
+// ---- vector kernels shared by the solve drivers (vector.hip) -----------------------------------
+int helm_vec_num_blocks(const helm_op *op);     // workgroups (= partial sums per right-hand side) of a launch over the Krylov vectors
+// out[b*out_ld + out_off + i] = scale (.) (premul * rhs[b*rhs_ld + row_off + i] - sub[b*N + i]), i < N; sub may be null; the scale is none,
+// complex (scale) or real (rs)
+int helm_launch_prep_rhs(helm_op *op, const cplx *dRHS, long long rhs_ld, long long row_off, cplx premul, const cplx *sub, const cplx *scale, const double *rs,
+                         cplx *out, long long out_ld, long long out_off, int nrhs);
+int helm_launch_finish(helm_op *op, const cplx *x, long long x_ld, long long x_off, cplx *dU, long long u_ld, long long row_off, int nrhs);   // U = conj(x), N rows
+int helm_launch_norm2(helm_op *op, const cplx *a, int nrhs);                                 // partial (a, a) of vectors of length Nv into d_part
 int helm_launch_rowscale_inplace(helm_op *op, cplx *v, const double *rs, long long NV, int nrhs);
 int helm_launch_abs(helm_op *op, const cplx *in, cplx *out, long long n, double sign);      // out = sign |in|
-int helm_launch_gardner_rho(helm_op *op);     // d_rho = 310 Re(d_c)^0.25
+
+// ---- the model (capi.hip) ------------------------------------------------------------------------
 int helm_ensure_host_model(helm_op *op);      // h_c, h_rho, ... (downloaded from the device on first use)
 int helm_adopt_model_device(helm_op *dst, const cplx *d_c, const double *d_rho);     // model of a multigrid level from device arrays (capi.hip)
 

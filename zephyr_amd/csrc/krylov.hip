@@ -1,5 +1,6 @@
 // Host-side Krylov drivers of libhelm: BiCGSTAB on the Jacobi-scaled or multigrid-preconditioned system, CGNR as the safety net and for the
-// coupled TTI system.
+// coupled TTI system, with the kernels that only they launch: the fused vector updates (k_bicg_*, k_cg_*) and k_fin, the single-workgroup
+// deterministic reduction of the partial sums that also advances the scalar recurrences.
 //
 // The drivers only enqueue kernels: all vectors and all scalar recurrences stay on the device;
 // the host looks at the per-RHS status records every `check_every` iterations.
@@ -41,9 +42,283 @@ int ensure_part(helm_op *op, int nrhs) {
     return HELM_OK;
 }
 
-// ---- Krylov drivers ---------------------------------------------------------------------------
+// ---- vector updates (grid.x over points with a grid-stride loop, grid.y = rhs) -----------------
 namespace {
 
+struct VecPtrs {   // all [nrhs][Nv] complex, stride Nv
+    cplx *x, *r, *r0, *p, *v, *s, *t;
+};
+
+// BiCGSTAB / CGNR start: x = 0, r = r0 = bbar, p = v = 0, partial (r, r)
+__global__ __launch_bounds__(256) void k_krylov_init(const cplx *__restrict__ bbar, VecPtrs w, long long N,
+                                                     double *__restrict__ part, int nblk) {
+    __shared__ double red[4];
+    const int b = blockIdx.y;
+    double s[1] = {0.0};
+    const cplx zero = cmake(0.0, 0.0);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        const long long g = (long long)b * N + i;
+        const cplx v = bbar[g];
+        w.x[g] = zero; w.r[g] = v; w.r0[g] = v; w.p[g] = zero; w.v[g] = zero;
+        s[0] += cabs2(v);
+    }
+    block_sum<1>(s, red);
+    if (threadIdx.x == 0) part[((long long)b * 4) * nblk + blockIdx.x] = s[0];
+}
+
+// p = r + beta (p - omega v)
+__global__ __launch_bounds__(256) void k_bicg_p(VecPtrs w, long long N, const RhsScal *__restrict__ scal) {
+    const int b = blockIdx.y;
+    if (scal[b].status != ST_ACTIVE) return;
+    const cplx beta = cmake(scal[b].beta_re, scal[b].beta_im), omega = cmake(scal[b].omega_re, scal[b].omega_im);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        const long long g = (long long)b * N + i;
+        const cplx r = w.r[g], p = w.p[g], v = w.v[g];
+        cplx tmp = csub(p, cmul(omega, v));
+        w.p[g] = cadd(r, cmul(beta, tmp));
+    }
+}
+
+// s = r - alpha v
+__global__ __launch_bounds__(256) void k_bicg_s(VecPtrs w, long long N, const RhsScal *__restrict__ scal) {
+    const int b = blockIdx.y;
+    if (scal[b].status != ST_ACTIVE) return;
+    const cplx alpha = cmake(scal[b].alpha_re, scal[b].alpha_im);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        const long long g = (long long)b * N + i;
+        w.s[g] = csub(w.r[g], cmul(alpha, w.v[g]));
+    }
+}
+
+// x += alpha p + omega s ; r = s - omega t ; partials (r0, r), (r, r)
+__global__ __launch_bounds__(256) void k_bicg_xr(VecPtrs w, const cplx *__restrict__ xp, const cplx *__restrict__ xs, long long N,
+                                                 const RhsScal *__restrict__ scal, double *__restrict__ part, int nblk) {
+    __shared__ double red[12];
+    const int b = blockIdx.y;
+    if (scal[b].status != ST_ACTIVE) return;
+    const cplx alpha = cmake(scal[b].alpha_re, scal[b].alpha_im), omega = cmake(scal[b].omega_re, scal[b].omega_im);
+    double s[3] = {0.0, 0.0, 0.0};
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        const long long g = (long long)b * N + i;
+        const cplx sv = w.s[g], tv = w.t[g], pv = xp[g];
+        const cplx sx = (xs == w.s) ? sv : xs[g];
+        cplx xv = w.x[g];
+        cfma(xv, alpha, pv);
+        cfma(xv, omega, sx);
+        w.x[g] = xv;
+        const cplx rv = csub(sv, cmul(omega, tv));
+        w.r[g] = rv;
+        const cplx r0 = w.r0[g];
+        s[0] += r0.x * rv.x + r0.y * rv.y;
+        s[1] += r0.x * rv.y - r0.y * rv.x;
+        s[2] += cabs2(rv);
+    }
+    block_sum<3>(s, red);
+    if (threadIdx.x == 0) {
+        double *pp = part + ((long long)b * 4) * nblk + blockIdx.x;
+        pp[0] = s[0]; pp[(long long)nblk] = s[1]; pp[2LL * nblk] = s[2];
+    }
+}
+
+// r0 = r, p = v = 0 for right-hand sides being (re)started (status == ST_ACTIVE after FIN_RESTART
+// is decided by `mask[b]`)
+__global__ __launch_bounds__(256) void k_restart_copy(VecPtrs w, long long N, const int *__restrict__ mask) {
+    const int b = blockIdx.y;
+    if (!mask[b]) return;
+    const cplx zero = cmake(0.0, 0.0);
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        const long long g = (long long)b * N + i;
+        w.r0[g] = w.r[g]; w.p[g] = zero; w.v[g] = zero;
+    }
+}
+
+// CGNR: x += alpha p ; r -= alpha w(v) ; partial (r, r)
+__global__ __launch_bounds__(256) void k_cg_xr(VecPtrs w, long long N, const RhsScal *__restrict__ scal,
+                                               double *__restrict__ part, int nblk) {
+    __shared__ double red[4];
+    const int b = blockIdx.y;
+    if (scal[b].status != ST_ACTIVE) return;
+    const double alpha = scal[b].alpha_re;
+    double s[1] = {0.0};
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        const long long g = (long long)b * N + i;
+        const cplx pv = w.p[g], wv = w.v[g];
+        cplx xv = w.x[g], rv = w.r[g];
+        xv.x += alpha * pv.x; xv.y += alpha * pv.y;
+        rv.x -= alpha * wv.x; rv.y -= alpha * wv.y;
+        w.x[g] = xv; w.r[g] = rv;
+        s[0] += cabs2(rv);
+    }
+    block_sum<1>(s, red);
+    if (threadIdx.x == 0) part[((long long)b * 4) * nblk + blockIdx.x] = s[0];
+}
+
+// CGNR: p = z(s) + beta p
+__global__ __launch_bounds__(256) void k_cg_p(VecPtrs w, long long N, const RhsScal *__restrict__ scal, int first) {
+    const int b = blockIdx.y;
+    if (scal[b].status != ST_ACTIVE) return;
+    const double beta = first ? 0.0 : scal[b].beta_re;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < N; i += (long long)gridDim.x * blockDim.x) {
+        const long long g = (long long)b * N + i;
+        const cplx z = w.s[g];
+        cplx p = first ? cmake(0.0, 0.0) : w.p[g];
+        w.p[g] = cmake(z.x + beta * p.x, z.y + beta * p.y);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
+// finalize: one workgroup per right-hand side sums the per-workgroup partials in a fixed order
+// (bitwise reproducible) and advances the scalar recurrences.
+// ------------------------------------------------------------------------------------------
+__device__ inline void fin_sum(const double *part, int b, int nblk, double (&out)[4], double *smem) {
+    double v[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int i = threadIdx.x; i < nblk; i += blockDim.x) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) v[q] += part[((long long)b * 4 + q) * nblk + i];
+    }
+    block_sum<4>(v, smem);
+    __shared__ double bc[4];
+    if (threadIdx.x == 0) { bc[0] = v[0]; bc[1] = v[1]; bc[2] = v[2]; bc[3] = v[3]; }
+    __syncthreads();
+    out[0] = bc[0]; out[1] = bc[1]; out[2] = bc[2]; out[3] = bc[3];
+}
+
+struct FinParams {
+    RhsScal *scal;
+    const double *part;
+    int nblk;
+    int which;
+    double rtol;
+    const int *mask;    // FIN_RESTART: which RHS to touch
+    double *aux;        // FIN_NORM: aux[b] = sum
+};
+
+__device__ inline bool finite2(cplx a) { return isfinite(a.x) && isfinite(a.y); }
+
+__global__ __launch_bounds__(256) void k_fin(FinParams f) {
+    __shared__ double smem[16];
+    const int b = blockIdx.x;
+    RhsScal *S = f.scal ? f.scal + b : nullptr;
+    if (f.which == FIN_NORM || f.which == FIN_NORM2) {
+        double v[4];
+        fin_sum(f.part, b, f.nblk, v, smem);
+        if (threadIdx.x == 0) { f.aux[b] = v[0]; if (f.which == FIN_NORM2) f.aux[gridDim.x + b] = v[1]; }
+        return;
+    }
+    if (f.which == FIN_RESTART) {
+        if (!f.mask[b]) {   // right-hand sides parked while others restart resume where they were
+            if (threadIdx.x == 0 && S->status == ST_PARKED) S->status = ST_ACTIVE;
+            return;
+        }
+    }
+    else if (f.which != FIN_BICG_INIT && S->status != ST_ACTIVE) return;
+    double v[4];
+    fin_sum(f.part, b, f.nblk, v, smem);
+    if (threadIdx.x != 0) return;
+
+    switch (f.which) {
+    case FIN_BICG_INIT: {           // v[0] = (b, b) of the scaled system
+        S->bb = v[0]; S->rr = v[0];
+        S->rho_re = v[0]; S->rho_im = 0.0;
+        S->alpha_re = 1.0; S->alpha_im = 0.0; S->omega_re = 1.0; S->omega_im = 0.0;
+        S->beta_re = 0.0; S->beta_im = 0.0;
+        S->tol2 = f.rtol * f.rtol;
+        S->iters = 0;
+        S->pad0 = 0;                // restarts
+        S->pad1 = 0;
+        S->status = (v[0] == 0.0 || !isfinite(v[0])) ? ST_CONVERGED : ST_ACTIVE;
+        break;
+    }
+    case FIN_RESTART: {             // v[0] = (r, r) of the recomputed true residual; r0 := r
+        S->rr = v[0];
+        S->rho_re = v[0]; S->rho_im = 0.0;
+        S->alpha_re = 1.0; S->alpha_im = 0.0; S->omega_re = 1.0; S->omega_im = 0.0;
+        S->beta_re = 0.0; S->beta_im = 0.0;
+        S->pad0 += 1;
+        S->status = (v[0] <= S->tol2 * S->bb) ? ST_CONVERGED : ST_ACTIVE;
+        break;
+    }
+    case FIN_ALPHA: {               // sigma = (r0, v); alpha = rho / sigma
+        const cplx sigma = cmake(v[0], v[1]);
+        const cplx rho = cmake(S->rho_re, S->rho_im);
+        const cplx alpha = cdiv(rho, sigma);
+        if (cabs2(sigma) == 0.0 || !finite2(alpha)) { S->status = ST_BREAKDOWN; break; }
+        S->alpha_re = alpha.x; S->alpha_im = alpha.y;
+        break;
+    }
+    case FIN_OMEGA: {               // omega = (t, s) / (t, t)
+        const double tt = v[2];
+        cplx omega = cmake(0.0, 0.0);
+        if (tt > 0.0) omega = cmake(v[0] / tt, v[1] / tt);
+        if (!finite2(omega)) { S->status = ST_BREAKDOWN; break; }
+        S->omega_re = omega.x; S->omega_im = omega.y;
+        break;
+    }
+    case FIN_RHO: {                 // rho' = (r0, r); rr = (r, r); beta = (rho'/rho)(alpha/omega)
+        const cplx rhon = cmake(v[0], v[1]);
+        const double rr = v[2];
+        S->iters += 1;
+        S->rr = rr;
+        if (!isfinite(rr) || !finite2(rhon)) { S->status = ST_BREAKDOWN; break; }
+        if (rr <= S->tol2 * S->bb) { S->status = ST_CONVERGED; break; }
+        const cplx rho = cmake(S->rho_re, S->rho_im);
+        const cplx alpha = cmake(S->alpha_re, S->alpha_im), omega = cmake(S->omega_re, S->omega_im);
+        if (cabs2(omega) == 0.0 || cabs2(rho) == 0.0 || cabs2(rhon) == 0.0) { S->status = ST_BREAKDOWN; break; }
+        const cplx beta = cmul(cdiv(rhon, rho), cdiv(alpha, omega));
+        if (!finite2(beta)) { S->status = ST_BREAKDOWN; break; }
+        S->beta_re = beta.x; S->beta_im = beta.y;
+        S->rho_re = rhon.x; S->rho_im = rhon.y;
+        break;
+    }
+    case FIN_CG_INIT: {             // v[0] = (z, z)
+        S->rho_re = v[0]; S->rho_im = 0.0;
+        if (v[0] == 0.0) S->status = ST_CONVERGED;
+        break;
+    }
+    case FIN_CG_ALPHA: {            // v[0] = (w, w); alpha = gamma / (w, w)
+        if (v[0] == 0.0 || !isfinite(v[0])) { S->status = ST_BREAKDOWN; break; }
+        S->alpha_re = S->rho_re / v[0]; S->alpha_im = 0.0;
+        break;
+    }
+    case FIN_CG_RR: {               // v[0] = (r, r)
+        S->iters += 1;
+        S->rr = v[0];
+        if (!isfinite(v[0])) { S->status = ST_BREAKDOWN; break; }
+        if (v[0] <= S->tol2 * S->bb) S->status = ST_CONVERGED;
+        break;
+    }
+    case FIN_CG_BETA: {             // v[0] = (z, z) new
+        if (S->rho_re == 0.0) { S->status = ST_BREAKDOWN; break; }
+        S->beta_re = v[0] / S->rho_re; S->beta_im = 0.0;
+        S->rho_re = v[0];
+        break;
+    }
+    default: break;
+    }
+}
+
+void launch_fin(helm_op *op, int which, int nrhs, int nblk_part, const int *mask, double *aux, double rtol) {
+    FinParams f; f.scal = op->d_scal; f.part = (const double *)op->d_part; f.nblk = nblk_part; f.which = which; f.rtol = rtol; f.mask = mask; f.aux = aux;
+    HELM_LAUNCH(k_fin, dim3(nrhs), dim3(256), 0, op->stream, f);
+}
+
+// workgroups x right-hand sides of a vector update
+dim3 vec_grid(const helm_op *op, int nrhs) { return dim3(vec_blocks(op->Nv), nrhs); }
+
+// x = 0, r = r0 = bvec, p = v = 0 and the scalar records, for a system whose right-hand side is already formed
+int launch_krylov_init(helm_op *op, const cplx *bvec, VecPtrs w, int nrhs, double rtol) {
+    const dim3 grid = vec_grid(op, nrhs);
+    HELM_LAUNCH(k_krylov_init, grid, dim3(256), 0, op->stream, bvec, w, op->Nv, (double *)op->d_part, (int)grid.x);
+    launch_fin(op, FIN_BICG_INIT, nrhs, grid.x, nullptr, nullptr, rtol);
+    HIP_TRY(op, hipGetLastError());
+    return HELM_OK;
+}
+
+void launch_cg_p(helm_op *op, VecPtrs w, int nrhs, int first) {      // p = z(s) + beta p
+    HELM_LAUNCH(k_cg_p, vec_grid(op, nrhs), dim3(256), 0, op->stream, w, op->Nv, (const RhsScal *)op->d_scal, first);
+}
+
+// ---- Krylov drivers ---------------------------------------------------------------------------
 struct Batch {
     int nrhs;
     VecPtrs w;
@@ -86,6 +361,12 @@ ApplyArgs batch_apply(helm_op *op, const Batch &B, const cplx *X, cplx *Y, const
 }  // namespace
 
 // (solve_internal.hpp)
+int helm_launch_fin_ex(helm_op *op, int which, int nrhs, int nblk_part, const int *mask, double *aux) {
+    launch_fin(op, which, nrhs, nblk_part, mask, aux, 0.0);
+    return HELM_OK;
+}
+
+// (solve_internal.hpp)
 int launch_sys2_apply(helm_op *op, bool raw, int adjoint, const cplx *X, cplx *Y, const cplx *W, int nrhs, int epi, const RhsScal *scal, const cplx *planes_override) {
     const long long N = op->N;
     const int nblk = helm_apply_num_blocks(op);
@@ -126,7 +407,7 @@ int restart_masked(helm_op *op, int block, Batch &B) {
     HIP_TRY(op, hipMemcpyAsync(B.d_mask, B.h_mask, n * sizeof(int), hipMemcpyHostToDevice, op->stream));
     rc = launch_batch_apply(op, B, B.w.x, B.w.r, B.bbar, EPI_RESID);
     if (rc) return rc;
-    helm_launch_restart_copy_mask(op, B.w, n, B.d_mask);
+    HELM_LAUNCH(k_restart_copy, vec_grid(op, n), dim3(256), 0, op->stream, B.w, op->Nv, (const int *)B.d_mask);
     helm_launch_fin_ex(op, FIN_RESTART, n, B.nba, B.d_mask, nullptr);
     HIP_TRY(op, hipGetLastError());
     return HELM_OK;
@@ -135,6 +416,8 @@ int restart_masked(helm_op *op, int block, Batch &B) {
 int run_bicgstab(helm_op *op, int block, Batch &B, int maxit, int check_every, int max_restarts, std::vector<int> &restarts) {
     const int n = B.nrhs;
     const int nba = B.nba, nbv = helm_vec_num_blocks(op);
+    const dim3 vgrid = vec_grid(op, n);
+    const RhsScal *scal = op->d_scal;
     int it_done = 0;
     while (true) {
         int rc = download_scal(op, n);
@@ -166,13 +449,13 @@ int run_bicgstab(helm_op *op, int block, Batch &B, int maxit, int check_every, i
         op->active_hint = nactive;
         const int chunk = std::max(1, std::min(check_every, maxit - min_iters));
         for (int k = 0; k < chunk; ++k) {
-            helm_launch_bicg_p(op, B.w, n);
+            HELM_LAUNCH(k_bicg_p, vgrid, dim3(256), 0, op->stream, B.w, op->Nv, scal);
             const cplx *pin = B.w.p, *sin = B.w.s;
             if (B.pre) { rc = mg_apply(op, B.w.p, B.phat, n, op->d_scal); if (rc) return rc; pin = B.phat; }
             rc = launch_batch_apply(op, B, pin, B.w.v, B.w.r0, EPI_DOT_W);
             if (rc) return rc;
-            helm_launch_fin(op, FIN_ALPHA, n, nba);
-            helm_launch_bicg_s(op, B.w, n);
+            helm_launch_fin_ex(op, FIN_ALPHA, n, nba);
+            HELM_LAUNCH(k_bicg_s, vgrid, dim3(256), 0, op->stream, B.w, op->Nv, scal);
             if (B.pre) {
                 rc = mg_apply(op, B.w.s, B.shat, n, op->d_scal); if (rc) return rc; sin = B.shat;
                 rc = launch_batch_apply(op, B, sin, B.w.t, B.w.s, EPI_DOT_WY);
@@ -180,9 +463,9 @@ int run_bicgstab(helm_op *op, int block, Batch &B, int maxit, int check_every, i
                 rc = launch_batch_apply(op, B, sin, B.w.t, nullptr, EPI_DOT_XY);
             }
             if (rc) return rc;
-            helm_launch_fin(op, FIN_OMEGA, n, nba);
-            helm_launch_bicg_xr(op, B.w, pin, sin, n);
-            helm_launch_fin(op, FIN_RHO, n, nbv);
+            helm_launch_fin_ex(op, FIN_OMEGA, n, nba);
+            HELM_LAUNCH(k_bicg_xr, vgrid, dim3(256), 0, op->stream, B.w, pin, sin, op->Nv, scal, (double *)op->d_part, nbv);      // x += alpha pin + omega sin ; r = s - omega t
+            helm_launch_fin_ex(op, FIN_RHO, n, nbv);
         }
         HIP_TRY(op, hipGetLastError());
         it_done += chunk;
@@ -209,11 +492,11 @@ int run_cgnr(helm_op *op, int block, Batch &B, int maxit, int check_every) {
     };
     rc = cg_apply(B.w.x, B.w.r, B.bscaled, 0, EPI_RESID);
     if (rc) return rc;
-    helm_launch_fin(op, FIN_CG_RR, n, nba);            // rr (and convergence check); iters becomes 1
+    helm_launch_fin_ex(op, FIN_CG_RR, n, nba);            // rr (and convergence check); iters becomes 1
     rc = cg_apply(B.w.r, B.w.s, nullptr, 1, EPI_DOT_YY);   // z = A^H r
     if (rc) return rc;
-    helm_launch_fin(op, FIN_CG_INIT, n, nba);
-    helm_launch_cg_p(op, B.w, n, 1);
+    helm_launch_fin_ex(op, FIN_CG_INIT, n, nba);
+    launch_cg_p(op, B.w, n, 1);
     while (true) {
         rc = download_scal(op, n);
         if (rc) return rc;
@@ -232,13 +515,13 @@ int run_cgnr(helm_op *op, int block, Batch &B, int maxit, int check_every) {
         for (int k = 0; k < chunk; ++k) {
             rc = cg_apply(B.w.p, B.w.v, nullptr, 0, EPI_DOT_YY);   // w = A p
             if (rc) return rc;
-            helm_launch_fin(op, FIN_CG_ALPHA, n, nba);
-            helm_launch_cg_xr(op, B.w, n);
-            helm_launch_fin(op, FIN_CG_RR, n, nbv);
+            helm_launch_fin_ex(op, FIN_CG_ALPHA, n, nba);
+            HELM_LAUNCH(k_cg_xr, vec_grid(op, n), dim3(256), 0, op->stream, B.w, op->Nv, (const RhsScal *)op->d_scal, (double *)op->d_part, nbv);
+            helm_launch_fin_ex(op, FIN_CG_RR, n, nbv);
             rc = cg_apply(B.w.r, B.w.s, nullptr, 1, EPI_DOT_YY); // z = A^H r
             if (rc) return rc;
-            helm_launch_fin(op, FIN_CG_BETA, n, nba);
-            helm_launch_cg_p(op, B.w, n, 0);
+            helm_launch_fin_ex(op, FIN_CG_BETA, n, nba);
+            launch_cg_p(op, B.w, n, 0);
         }
         HIP_TRY(op, hipGetLastError());
     }
@@ -319,29 +602,31 @@ int solve_block_krylov(helm_op *op, int block, const cplx *dRHS, long long rhs_l
             HIP_TRY(op, hipMemsetAsync(qprime, 0, (size_t)n * NV * sizeof(cplx), op->stream));
             HIP_TRY(op, hipMemsetAsync(B.bscaled, 0, (size_t)n * NV * sizeof(cplx), op->stream));
             for (int half = 0; half < (rows_in == 2 * N ? 2 : 1); ++half) {
-                rc = helm_launch_prep_rhs_ex(op, rhs_b, rhs_ld, half * N, premul, nullptr, qprime, NV, half * N, n);
+                rc = helm_launch_prep_rhs(op, rhs_b, rhs_ld, half * N, premul, nullptr, nullptr, nullptr, qprime, NV, half * N, n);
                 if (rc) return rc;
-                rc = helm_launch_prep_rhs_rs(op, rhs_b, rhs_ld, half * N, premul, op->d_rs + half * N, B.bscaled, NV, half * N, n);
+                rc = helm_launch_prep_rhs(op, rhs_b, rhs_ld, half * N, premul, nullptr, nullptr, op->d_rs + half * N, B.bscaled, NV, half * N, n);
                 if (rc) return rc;
             }
         } else {
-            rc = helm_launch_prep_rhs(op, rhs_b, rhs_ld, row_off, premul, sub_b, qprime, n);
+            rc = helm_launch_prep_rhs(op, rhs_b, rhs_ld, row_off, premul, sub_b, nullptr, nullptr, qprime, N, 0, n);
             if (rc) return rc;
         }
         helm_launch_norm2(op, qprime, n);
         helm_launch_fin_ex(op, FIN_NORM, n, helm_vec_num_blocks(op), nullptr, B.d_aux + n);
         // scaled system start
         if (sys2) {
-            rc = helm_launch_krylov_init(op, B.bscaled, B.w, n, o.rtol * 0.5);
+            rc = launch_krylov_init(op, B.bscaled, B.w, n, o.rtol * 0.5);
             if (rc) return rc;
         } else {
             VecPtrs w = B.w;
-            w.t = B.bscaled;   // init writes the scaled right-hand side through w.t
+            w.t = B.bscaled;   // prep writes the scaled right-hand side D^-1 q' through w.t; the init reads it there and leaves t alone
             // NB: row offset is applied by giving prep a shifted base pointer
-            rc = helm_launch_bicg_init(op, block, rhs_b + row_off, rhs_ld, premul, sub_b, w, n, o.rtol * 0.5);
+            rc = helm_launch_prep_rhs(op, rhs_b + row_off, rhs_ld, 0, premul, sub_b, op->d_dinv + (long long)block * N, nullptr, w.t, N, 0, n);
+            if (rc) return rc;
+            rc = launch_krylov_init(op, w.t, w, n, o.rtol * 0.5);
             if (rc) return rc;
             if (use_mg) {      // iterate on the unscaled system A (M^-1 y) = q'
-                rc = helm_launch_krylov_init(op, qprime, B.w, n, o.rtol * 0.9);
+                rc = launch_krylov_init(op, qprime, B.w, n, o.rtol * 0.9);
                 if (rc) return rc;
             }
         }

@@ -243,13 +243,13 @@ int direct_batch_sys2(DirectCall &c, int first, int n) {
     const cplx *rhs_b = c.dRHS + (long long)first * c.rhs_ld;
     HIP_TRY(op, hipMemsetAsync(q, 0, (size_t)n * NV * sizeof(cplx), op->stream));
     for (int half = 0; half < (c.rows_in == 2 * N ? 2 : 1); ++half) {
-        rc = helm_launch_prep_rhs_ex(op, rhs_b, c.rhs_ld, half * N, c.premul, nullptr, q, NV, half * N, n);
+        rc = helm_launch_prep_rhs(op, rhs_b, c.rhs_ld, half * N, c.premul, nullptr, nullptr, nullptr, q, NV, half * N, n);
         if (rc) return rc;
     }
     helm_launch_norm2(op, q, n);
     helm_launch_fin_ex(op, FIN_NORM, n, helm_vec_num_blocks(op), nullptr, d_aux + n);
     for (int half = 0; half < 2; ++half) {
-        rc = helm_launch_prep_rhs_rs(op, q, NV, half * N, cmake(1.0, 0.0), op->d_rs + half * N, x, NV, half * N, n);
+        rc = helm_launch_prep_rhs(op, q, NV, half * N, cmake(1.0, 0.0), nullptr, nullptr, op->d_rs + half * N, x, NV, half * N, n);
         if (rc) return rc;
     }
     rc = nd_solve(op, f, x, x, n, nws);

@@ -6,12 +6,6 @@
 #include "direct.hpp"
 #include <cstdlib>
 
-// launchers from kernels.hip not in the shared header
-int helm_launch_fin_ex(helm_op *op, int which, int nrhs, int nblk_part, const int *mask, double *aux);
-int helm_launch_restart_copy_mask(helm_op *op, VecPtrs w, int nrhs, const int *mask);
-int helm_launch_norm2(helm_op *op, const cplx *a, int nrhs);
-int helm_launch_krylov_init(helm_op *op, const cplx *bvec, VecPtrs w, int nrhs, double rtol);
-
 // fault-injection and branch-forcing hooks of the test-suite: honoured only when the process runs with HELM_TESTING=1 (read per call: the tests flip them)
 inline int testing_hook(const char *name) {
     const char *t = getenv("HELM_TESTING"), *v = getenv(name);
@@ -71,6 +65,12 @@ int solve_block_direct(helm_op *op, int block, const cplx *dRHS, long long rhs_l
                        const helm_solve_opts &o, helm_solve_info *info, int sys2 = 0, long long rows_in = 0, cplx *dUconj = nullptr);
 
 // ---- Krylov drivers (krylov.hip) ----------------------------------------------------------------
+// k_fin: one workgroup per right-hand side sums the partials of the launch before it in a fixed order and advances that right-hand side's scalar
+// record.  The direct path and the residual test hook use it for the plain sums: FIN_NORM (aux[b] = sum) and FIN_NORM2.
+enum { FIN_BICG_INIT = 0, FIN_ALPHA = 1, FIN_OMEGA = 2, FIN_RHO = 3, FIN_RESTART = 4,
+       FIN_CG_INIT = 5, FIN_CG_ALPHA = 6, FIN_CG_RR = 7, FIN_CG_BETA = 8, FIN_NORM = 9,
+       FIN_NORM2 = 10 /* aux[b] = slot 0, aux[nrhs + b] = slot 1 */ };
+int helm_launch_fin_ex(helm_op *op, int which, int nrhs, int nblk_part, const int *mask = nullptr, double *aux = nullptr);
 // Apply of the coupled Eurus system [[M1, M2], [M3, M4]] (or its conjugate transpose) to vectors [u; v] of length 2N:
 // four stencil launches, the second of each output half accumulating into the first and carrying the fused epilogue.
 // raw = unscaled planes (true residual), otherwise the row-equilibrated system d_S.
