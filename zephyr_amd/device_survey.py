@@ -9,7 +9,20 @@ The same loop serves forward fields that outlive a call (`fieldstore.DeviceField
 `dpredFromFields` samples the store and `gradientFromFields` images against it, both over the items the store recorded.  `illumination` and
 `illuminationFromFields` (last section) are the same two loops again with the energy kernel in the place of the imaging kernel and a float64 partial.
 
-Three rules hold everywhere below.
+The eight pipelines, one row each.  Every row is a body of its own made of the shared item steps of the next section.
+
+    pipeline                items                what fills R                        columns solved   what consumes U                       what comes down
+    dpred                   dealt                source columns                      k                sampleDevice (2.5-D: sampleSumDevice) nrec x k samples per item
+    fields                  dealt, then stored   source columns                      k                the store's slice (complex64: pack)   nothing
+    dpredFromFields         stored               --                                  0                -- (sampleDevice reads the slice)     nrec x k samples per item
+    bornFromFields          stored               virtual sources conj(W (.) slice)   k                sampleDevice, conjugated receivers    nrec x k samples per item
+    gradient                dealt                [qf | qb]                           2k               imaging kernel, uF and uB from U      one partial G per worker
+    gradientFromFields      stored               qb                                  k                imaging kernel, uF from the slice     one partial G per worker
+    illumination            dealt                source or receiver columns          k                energy kernel                         one partial H per worker
+    illuminationFromFields  stored               --                                  0                -- (energy kernel reads the slice)    one partial H per worker
+
+Three rules hold everywhere below.  The shared steps carry them, so that a new pipeline inherits them with the steps it calls, and
+tests/test_gpu_pipeline_order.py holds the order of library calls and waits of every item against a recorded one.
 
 * Stream hand-over.  The library runs on its own streams.  Every torch operation whose result a library call reads (an upload, an element-wise
   product, `zero_()`, `fill_()`, a fresh tensor the library writes) is followed by `_lib.wait_torch_stream(dev)` before that call.
@@ -57,11 +70,16 @@ class Workspace(object):
 
 
 # ---- dealing and running the items -------------------------------------------------------------------------------------------------------------
+def _workerDevices(sysw):
+    "the GPUs the workers of a system wrapper run on, in worker order (a wrapper without a parallel mode: the GPU of its first operator)"
+    return list(sysw.devices) if hasattr(sysw, 'devices') else [sysw.subProblems[0].device]
+
+
 def deviceItems(sysw, owned, ncols):
     """Work items (worker, operator, ifreq, c0, c1) for the owned frequencies: frequency-major over the system wrapper's devices (a GPU keeps the operators
     of its frequencies); with fewer frequencies than GPUs the `ncols` source columns of a frequency are split over the spare ones."""
     subs = sysw.subProblems
-    devs = list(sysw.devices) if hasattr(sysw, 'devices') else [subs[0].device]
+    devs = _workerDevices(sysw)
     nw = len(devs)
     split = max(1, nw // max(1, len(owned))) if hasattr(sysw, '_replica') else 1
     split = min(split, max(1, ncols))
@@ -141,25 +159,81 @@ def _planOnDevice(ws, sv, ifreq):
     return ws.cached(('plan', sv._gridKey(ifreq)), upload)
 
 
-def _fillMuxDevice(ws, sv, op, qf_i, qb_i, resid, ifreq, c0, c1, d_R, rows):
-    """d_R ([2k][rows], k = c1 - c0) = [qf | qb] of the sources c0 .. c1-1 of frequency ifreq.  qb_i given (fixed array): both halves as sparse triplets.
-    qb_i None (the array moves with the source): the qf half from triplets, the qb half by the gather of the survey's adjoint plan from the item's
-    residual samples resid[:, c0:c1, ifreq] -- 16 nrec k bytes up instead of ~81 entries of 28 B per sample, and no sparse products on the host."""
-    k = c1 - c0
-    if qb_i is not None:
-        op.rhsFromSparseDevice(_muxTriplets((qf_i, qb_i), c0, c1, rows), d_R)
+def _fillMuxDevice(ws, sv, op, qf_i, qb, resid, ifreq, c0, c1, d_R, rows):
+    """d_R ([2k][rows], k = c1 - c0) = [qf | qb] of the sources c0 .. c1-1 of frequency ifreq.  qb given (fixed array): both halves as sparse triplets in
+    one upload.  qb None (the array moves with the source): the qf half from triplets, the qb half by `_backSources`."""
+    if qb is not None:
+        op.rhsFromSparseDevice(_muxTriplets((qf_i, qb[ifreq]), c0, c1, rows), d_R)
         return
     op.rhsFromSparseDevice(_muxTriplets((qf_i,), c0, c1, rows), d_R)
+    _backSources(ws, sv, op, None, resid, ifreq, c0, c1, d_R + (c1 - c0) * rows * 16, rows)
+
+
+# ---- the item steps the pipelines share ----------------------------------------------------------------------------------------------------------
+# A step may enqueue torch work (uploads, element-wise products, zero_(), fresh tensors) and does not wait for it: the item body issues the
+# _lib.wait_torch_stream between its steps and the first library call that reads their results.  A step that itself calls the library on what it
+# has just uploaded (`_backSources` for a moving array; rhsFromSparseDevice inside `_expandColumns`) waits before that call.  What a step needs from
+# the survey's caches has a half that runs on the calling thread, before the workers start: `_prepareBackSources`, and the set-up of `_sampling`.
+
+def _ofFrequency(q, ifreq):
+    "the column matrix of frequency ifreq: `q` is one matrix per frequency (a multiscale survey), or one for all of them"
+    return q[ifreq] if isinstance(q, (list, tuple)) else q
+
+
+def _expandColumns(op, q, ifreq, c0, c1, R):
+    "R ([c1 - c0][rows]) = columns c0 .. c1-1 of the frequency's sparse column matrix, expanded on the item's GPU: only the entries cross PCIe"
+    op.rhsFromSparseDevice(sp.csc_matrix(_ofFrequency(q, ifreq))[:, c0:c1], R.data_ptr())
+
+
+def _prepareBackSources(sv, qb, freqs):
+    "calling-thread half of `_backSources`: the survey's adjoint plans of a moving array (the survey caches them; a fixed array brings its qb)"
+    if qb is None:
+        for ifreq in freqs:
+            sv.adjointPlan(ifreq)
+
+
+def _backSources(ws, sv, op, qb, resid, ifreq, c0, c1, d_R, rows):
+    """d_R ([k][rows], k = c1 - c0) = the back-sources R_s^T resid[:, s, ifreq] of the sources c0 .. c1-1.  qb given (fixed array): the host-built
+    sparse matrix as triplets.  qb None (the array moves with the source): the gather of the survey's adjoint plan from the item's residual samples
+    resid[:, c0:c1, ifreq] -- 16 nrec k bytes up instead of ~81 entries of 28 B per sample, and no sparse products on the host."""
+    if qb is not None:
+        op.rhsFromSparseDevice(_muxTriplets((qb[ifreq],), c0, c1, rows), d_R)
+        return
     plan = _planOnDevice(ws, sv, ifreq)
     panel = _lib.to_device(resid[:, c0:c1, ifreq], ws.device, np.complex128)       # (nrec, k), one contiguous panel
     _lib.wait_torch_stream(ws.device)
-    op.rhsFromSamplesDevice(panel.data_ptr(), k, plan, c0, c1, d_R + k * rows * 16, rows=rows)
+    op.rhsFromSamplesDevice(panel.data_ptr(), c1 - c0, plan, c0, c1, d_R, rows=rows)
 
 
 def _inverseCube(c, dev):
     '1 / c^3 on `dev` from one upload of the model array c'
     cd = _lib.to_device(np.asarray(c).ravel(), dev, np.complex128)
     return 1.0 / (cd * cd * cd)
+
+
+def _cachedInverseCube(ws, cm):
+    "1 / c^3 of the model array cm, made once per worker (the id stays this array's while the entry lives: it keeps the array)"
+    return ws.cached(('inv_c3', id(cm)), lambda: _inverseCube(cm, ws.device), keep=cm)
+
+
+def _partial(ws, name, shape, dtype):
+    "the worker's partial result ws.<name> ('G': gradient, 'H': illumination), zeroed on first use"
+    import torch
+    if getattr(ws, name) is None:
+        setattr(ws, name, torch.zeros(shape, dtype=dtype, device=ws.device))
+    return getattr(ws, name)
+
+
+def _checkItemsFit(items, held, work):
+    """MemoryError unless every GPU has room for what its items leave there, the sum of held(op, c0, c1) bytes, beside the largest working set
+    work(op, c0, c1) of an item there"""
+    import torch
+    from .fieldstore import check_fits
+    need, peak = {}, {}
+    for _, op, _, c0, c1 in items:
+        need[op.device] = need.get(op.device, 0) + held(op, c0, c1)
+        peak[op.device] = max(peak.get(op.device, 0), work(op, c0, c1))
+    check_fits({d: need[d] + peak[d] for d in need}, {d: torch.cuda.mem_get_info(d)[0] for d in need})
 
 
 # ---- the two ways an item's imaging sum reaches G ----------------------------------------------------------------------------------------------
@@ -177,10 +251,8 @@ def _addOnNativeGrid(prob, scale):
         if plain_scaler:
             # -(omega^2 / c^3) scale^2 on the GPU from one upload of the model per worker: on the host the complex power and division of problem.py:74-81 cost
             # 6 ms per frequency at 512^2 (numpy), in the thread whose only other job is to keep the solve stream fed
-            cm = op.c
-            inv = ws.cached(('inv_c3', id(cm)), lambda: _inverseCube(cm, dev), keep=cm)          # (the id stays this array's while the worker lives)
             omega = 2 * np.pi * sv.freqs[ifreq]
-            scaler = inv * complex(-(omega ** 2) * scale * scale)
+            scaler = _cachedInverseCube(ws, op.c) * complex(-(omega ** 2) * scale * scale)
         else:
             scaler = _lib.to_device(prob.gradientScaler(ifreq) * scale * scale, dev, np.complex128)
         return scaler, ws.G, None
@@ -227,21 +299,17 @@ def gradient(prob, qb, owned, resid):
     scale = complex(prob.system.scaleTerm)
     qf = sv.getSources()
     if not owned:
-        g = np.zeros(N, dtype=np.complex128)
-        return parallel.allreduce_sum(g) if prob._sharded else g
-    if qb is None:
-        for ifreq in owned:
-            sv.adjointPlan(ifreq)
+        return _sumPartials(prob, [])
+    _prepareBackSources(sv, qb, owned)
     devs, items = deviceItems(prob.system, owned, nsrc)
     add = _addUpscaled(prob, scale) if isinstance(sv, HelmMultiGridSurvey) else _addOnNativeGrid(prob, scale)
 
     def one(ws, op, ifreq, c0, c1):
         k, Ni = c1 - c0, int(op.nrow)
-        if ws.G is None:
-            ws.G = torch.zeros(N, dtype=torch.complex128, device=ws.device)
+        _partial(ws, 'G', N, torch.complex128)
         U, R = ws.buffer('U', 2 * k * Ni), ws.buffer('R', 2 * k * Ni)
         # [qf | qb] of the item's sources: sparse triplets (or residual samples) up, dense on the device
-        _fillMuxDevice(ws, sv, op, qf[ifreq] if isinstance(qf, (list, tuple)) else qf, None if qb is None else qb[ifreq], resid, ifreq, c0, c1, R.data_ptr(), Ni)
+        _fillMuxDevice(ws, sv, op, _ofFrequency(qf, ifreq), qb, resid, ifreq, c0, c1, R.data_ptr(), Ni)
         scaler, target, finish = add(ws, op, ifreq, Ni)
         _lib.wait_torch_stream(ws.device)                # (covers the torch work the adding step has just enqueued -- scaler product, zero_(), fill_(): keep it between the two)
         op.solveDevice(R.data_ptr(), U.data_ptr(), 2 * k, Ni)
@@ -252,7 +320,8 @@ def gradient(prob, qb, owned, resid):
 
 
 def _sumPartials(prob, parts):
-    "the gradient from the workers' partial gradients: summed on the host, then ONE all-reduce over ranks when the frequencies are sharded"
+    """the gradient from the workers' partial gradients: summed on the host, then ONE all-reduce over ranks when the frequencies are sharded (no partial:
+    a rank that owns no frequency brings zeros to that all-reduce)"""
     import torch
     N = prob.nrow
     if len(parts) == 1:
@@ -295,38 +364,59 @@ def _csrOnDevice(ws, Rm, gk, nrec, stride, c0):
     return csr
 
 
+def _sampling(prob, freqs, scale, conj=False):
+    """What the three routes that end in receiver samples share: (data, stage, sample).  `data` is the (nrec, nsrc, nfreq) result, zeros; the receiver
+    matrices of the frequencies `freqs` are made here, on the calling thread (conj: their conjugates, for Born data).  One receiver CSR per grid key
+    (None: the one grid of a single-grid survey).  A receiver array that moves with the source is sampled through the survey's stacked CSR, source s from
+    its own rows s * nrec .. (row stride nrec); a fixed one through the one matrix (stride 0).
+
+    stage(ws, ifreq, c0, c1) -> (csr, out): the item's torch work, the CSR on the worker's GPU (uploaded once per worker and grid key) and the (nrec, k)
+    buffer the samples go to.  It comes BEFORE the item's wait_torch_stream, which is why sampling is handed out in two halves.
+    sample(op, ifreq, c0, c1, staged, d_u, d_exp): sampleDevice of the k wavefields at d_u (d_exp: the column exponents of a complex64 store, or None)
+    and data[:, c0:c1, ifreq] = scale * samples.  d_u None: the item has put its samples into `out` itself (the 2.5-D sum of dpred)."""
+    sv = prob.survey
+    nrec = sv.nrec
+    data = np.zeros((nrec, sv.nsrc, sv.nfreq), dtype=np.complex128)
+    stride = nrec if sv.mode != 'fixed' else 0
+    Rms = _receiverMatrices(sv, freqs)
+    if conj:
+        Rms = {gk: Rm.conj() for gk, Rm in Rms.items()}
+
+    def stage(ws, ifreq, c0, c1):
+        gk = sv._gridKey(ifreq)
+        return _csrOnDevice(ws, Rms[gk], ('conj', gk) if conj else gk, nrec, stride, c0), ws.buffer('out', (nrec, c1 - c0))
+
+    def sample(op, ifreq, c0, c1, staged, d_u, d_exp=None):
+        csr, out = staged
+        if d_u is not None:
+            op.sampleDevice(d_u, c1 - c0, csr, out.data_ptr(), d_exp=d_exp)      # (returns when the samples are there: helm_sample_device waits for its own stream)
+        data[:, c0:c1, ifreq] = scale * _lib.from_device(out)          # (disjoint slices per item: no two workers write the same entries)
+    return data, stage, sample
+
+
 def dpred(prob, owned):
     """Predicted data (nrec, nsrc, nfreq) with the wavefields kept in HBM: per work item (frequency, source batch) the sparse sources are expanded on the
-    item's GPU and solved there on the frequency's own grid, and only the receiver samples R u (nrec x sources) come back.  One receiver CSR per grid
-    key (None: the one grid of a single-grid survey).  A receiver array that moves with the source is sampled through the survey's stacked CSR, source
-    s from its own rows s * nrec .. (row stride nrec); a fixed one through the one matrix (stride 0)."""
+    item's GPU and solved there on the frequency's own grid, and only the receiver samples R u (nrec x sources) come back."""
     sv = prob.survey
-    nsrc, nrec = sv.nsrc, sv.nrec
-    scale = complex(prob.system.scaleTerm)
-    data = np.zeros((nrec, nsrc, sv.nfreq), dtype=np.complex128)
+    data, stage, sample = _sampling(prob, owned, complex(prob.system.scaleTerm))
     if not owned:
         return data
-    moving = sv.mode != 'fixed'
-    stride = nrec if moving else 0
-    Rms = _receiverMatrices(sv, owned)
     qf = sv.getSources()
-    devs, items = deviceItems(prob.system, owned, nsrc)
+    devs, items = deviceItems(prob.system, owned, sv.nsrc)
 
     def one(ws, op, ifreq, c0, c1):
         k, Ni = c1 - c0, int(op.nrow)
-        summed = hasattr(op, 'sampleSumDevice')           # a composite (2.5-D ky sum): its samples are accumulated per ky, it keeps its own wavefield scratch
-        gk = sv._gridKey(ifreq)
-        csr = _csrOnDevice(ws, Rms[gk], gk, nrec, stride, c0)
-        R, out = ws.buffer('R', k * Ni), ws.buffer('out', (nrec, k))
-        q = qf[ifreq] if isinstance(qf, (list, tuple)) else qf
-        op.rhsFromSparseDevice(sp.csc_matrix(q)[:, c0:c1], R.data_ptr())
-        if summed:
-            op.sampleSumDevice(R.data_ptr(), k, csr, out.data_ptr(), rows=Ni)      # (sampling is linear: the N x k sum over ky is never formed)
+        staged = stage(ws, ifreq, c0, c1)
+        R = ws.buffer('R', k * Ni)
+        _expandColumns(op, qf, ifreq, c0, c1, R)         # (its own wait covers what `stage` has enqueued)
+        if hasattr(op, 'sampleSumDevice'):               # a composite (2.5-D ky sum): its samples are accumulated per ky, it keeps its own wavefield scratch
+            op.sampleSumDevice(R.data_ptr(), k, staged[0], staged[1].data_ptr(), rows=Ni)      # (sampling is linear: the N x k sum over ky is never formed)
+            d_u = None
         else:
             U = ws.buffer('U', k * Ni)
             op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
-            op.sampleDevice(U.data_ptr(), k, csr, out.data_ptr())      # (returns when the samples are there: helm_sample_device waits for its own stream)
-        data[:, c0:c1, ifreq] = scale * _lib.from_device(out)          # (disjoint slices per item: no two workers write the same entries)
+            d_u = U.data_ptr()
+        sample(op, ifreq, c0, c1, staged, d_u)
     runOnDevices(devs, items, one)
     return data
 
@@ -337,21 +427,20 @@ def dpred(prob, owned):
 
 def _storedItems(sysw, F):
     "(devs, items) as runOnDevices takes them from the items a store recorded: the frequency's own operator for its first batch, the system's replica j for batch j"
-    devs = list(sysw.devices) if hasattr(sysw, 'devices') else [sysw.subProblems[0].device]
     batch, items = {}, []
     for w, dev, ifreq, c0, c1 in F.items:
         j = batch.get(ifreq, 0)
         batch[ifreq] = j + 1
         op = sysw.subProblems[ifreq] if j == 0 else sysw._replica(ifreq, j, dev)
         items.append((w, op, ifreq, c0, c1))
-    return devs, items
+    return _workerDevices(sysw), items
 
 
 def fields(prob, owned, dtype='complex128'):
     """The forward wavefields of the owned frequencies solved into a DeviceFields: per work item the sparse sources are expanded on the item's GPU and
     solved straight into the item's slice of the store (complex128), or into the workspace and packed into it (complex64).  Nothing comes down."""
     import torch
-    from .fieldstore import DeviceFields, DTYPES, check_fits
+    from .fieldstore import DeviceFields, DTYPES
     from .survey import HelmMultiGridSurvey
     sv = prob.survey
     if isinstance(sv, HelmMultiGridSurvey):
@@ -369,12 +458,8 @@ def fields(prob, owned, dtype='complex128'):
     packed = dtype == 'complex64'
     esize = 8 if packed else 16
     # what every GPU has to hold: its slices (and exponents), and the largest working set of an item there (R; U as well when the store is packed)
-    need, work = {}, {}
-    for _, op, _, c0, c1 in items:
-        k, Ni = c1 - c0, int(op.nrow)
-        need[op.device] = need.get(op.device, 0) + k * Ni * esize + (4 * k if packed else 0)
-        work[op.device] = max(work.get(op.device, 0), k * Ni * 16 * (2 if packed else 1))
-    check_fits({d: need[d] + work[d] for d in need}, {d: torch.cuda.mem_get_info(d)[0] for d in need})
+    _checkItemsFit(items, held=lambda op, c0, c1: (c1 - c0) * (int(op.nrow) * esize + (4 if packed else 0)),
+                   work=lambda op, c0, c1: (c1 - c0) * int(op.nrow) * 16 * (2 if packed else 1))
     tdtype = torch.complex64 if packed else torch.complex128
     slices = [torch.empty((c1 - c0, int(op.nrow)), dtype=tdtype, device=torch.device('cuda', op.device)) for _, op, _, c0, c1 in items]
     exps = [torch.empty(c1 - c0, dtype=torch.int32, device=sl.device) for sl, (_, _, _, c0, c1) in zip(slices, items)] if packed else None
@@ -384,8 +469,7 @@ def fields(prob, owned, dtype='complex128'):
         k, Ni = c1 - c0, int(op.nrow)
         sl, ex = F.slice(ifreq, c0)
         R = ws.buffer('R', k * Ni)
-        q = qf[ifreq] if isinstance(qf, (list, tuple)) else qf
-        op.rhsFromSparseDevice(sp.csc_matrix(q)[:, c0:c1], R.data_ptr())
+        _expandColumns(op, qf, ifreq, c0, c1, R)
         _lib.wait_torch_stream(ws.device)
         if not packed:
             op.solveDevice(R.data_ptr(), sl.data_ptr(), k, Ni)           # (no copy: the solve's output IS the slice)
@@ -405,25 +489,15 @@ def dpredFromFields(prob, F):
     """Predicted data (nrec, nsrc, nfreq) from forward fields already in HBM: no solve, every item samples its slice of the store (row stride 0 for a fixed
     array, nrec for one that moves with the source) and only the receiver samples come back."""
     F.checkCurrent(prob)
-    sv = prob.survey
-    nsrc, nrec = sv.nsrc, sv.nrec
-    scale = F.scale
-    data = np.zeros((nrec, nsrc, sv.nfreq), dtype=np.complex128)
+    data, stage, sample = _sampling(prob, F.ownedFreqs, F.scale)
     if not F.items:
         return data
-    stride = nrec if sv.mode != 'fixed' else 0
-    Rms = _receiverMatrices(sv, F.ownedFreqs)
     devs, items = _storedItems(prob.system, F)
 
     def one(ws, op, ifreq, c0, c1):
-        k = c1 - c0
-        sl, ex = F.slice(ifreq, c0)
-        gk = sv._gridKey(ifreq)
-        csr = _csrOnDevice(ws, Rms[gk], gk, nrec, stride, c0)
-        out = ws.buffer('out', (nrec, k))
+        staged = stage(ws, ifreq, c0, c1)
         _lib.wait_torch_stream(ws.device)
-        op.sampleDevice(sl.data_ptr(), k, csr, out.data_ptr(), d_exp=None if ex is None else ex.data_ptr())
-        data[:, c0:c1, ifreq] = scale * _lib.from_device(out)
+        sample(op, ifreq, c0, c1, staged, *F.pointers(ifreq, c0))
     runOnDevices(devs, items, one, factor=False)
     return data
 
@@ -449,15 +523,14 @@ def _factorBytes(op):
 def _checkSecondFactorsFit(items):
     """MemoryError unless every GPU has room for what a pass through the TRANSPOSED operators adds to a resident forward pass: their factors -- the factors of
     A and of A^T are held side by side -- and the item's U and R"""
-    import torch
-    from .fieldstore import check_fits
-    need, work, seen = {}, {}, set()
-    for _, op, _, c0, c1 in items:
-        if id(op) not in seen and not op.factors and str(getattr(op, 'method', 'auto')).lower() in ('auto', 'direct'):
-            need[op.device] = need.get(op.device, 0) + _factorBytes(op)
+    seen = set()
+
+    def factors(op, c0, c1):
+        'the factors an operator has yet to make, counted with its first item'
+        first = id(op) not in seen
         seen.add(id(op))
-        work[op.device] = max(work.get(op.device, 0), 2 * (c1 - c0) * int(op.nrow) * 16)
-    check_fits({d: need.get(d, 0) + work[d] for d in work}, {d: torch.cuda.mem_get_info(d)[0] for d in work})
+        return _factorBytes(op) if first and not op.factors and str(getattr(op, 'method', 'auto')).lower() in ('auto', 'direct') else 0
+    _checkItemsFit(items, held=factors, work=lambda op, c0, c1: 2 * (c1 - c0) * int(op.nrow) * 16)
 
 
 def gradientFromFields(prob, F, qb, resid, system=None):
@@ -472,11 +545,8 @@ def gradientFromFields(prob, F, qb, resid, system=None):
     N = prob.nrow
     scale = F.scale
     if not F.items:
-        g = np.zeros(N, dtype=np.complex128)
-        return (parallel.allreduce_sum(g) if prob._sharded else g).real
-    if qb is None:
-        for ifreq in F.ownedFreqs:
-            sv.adjointPlan(ifreq)
+        return _sumPartials(prob, []).real
+    _prepareBackSources(sv, qb, F.ownedFreqs)
     devs, items = _storedItems(prob.system if system is None else system, F)
     if system is not None:
         _checkSecondFactorsFit(items)
@@ -484,21 +554,14 @@ def gradientFromFields(prob, F, qb, resid, system=None):
 
     def one(ws, op, ifreq, c0, c1):
         k, Ni = c1 - c0, int(op.nrow)
-        sl, ex = F.slice(ifreq, c0)
-        if ws.G is None:
-            ws.G = torch.zeros(N, dtype=torch.complex128, device=ws.device)
+        d_uF, d_exp = F.pointers(ifreq, c0)
+        _partial(ws, 'G', N, torch.complex128)
         U, R = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
-        if qb is not None:
-            op.rhsFromSparseDevice(_muxTriplets((qb[ifreq],), c0, c1, Ni), R.data_ptr())
-        else:
-            plan = _planOnDevice(ws, sv, ifreq)
-            panel = _lib.to_device(resid[:, c0:c1, ifreq], ws.device, np.complex128)
-            _lib.wait_torch_stream(ws.device)
-            op.rhsFromSamplesDevice(panel.data_ptr(), k, plan, c0, c1, R.data_ptr(), rows=Ni)
+        _backSources(ws, sv, op, qb, resid, ifreq, c0, c1, R.data_ptr(), Ni)
         scaler, target, finish = add(ws, op, ifreq, Ni)
         _lib.wait_torch_stream(ws.device)
         op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
-        op.imagingAccumulateDevice(sl.data_ptr(), U.data_ptr(), k, scaler.data_ptr(), target.data_ptr(), d_exp=None if ex is None else ex.data_ptr())
+        op.imagingAccumulateDevice(d_uF, U.data_ptr(), k, scaler.data_ptr(), target.data_ptr(), d_exp=d_exp)
         if finish is not None:
             finish()
     return _sumPartials(prob, [ws.G for ws in runOnDevices(devs, items, one) if ws.G is not None]).real
@@ -511,13 +574,10 @@ def bornFromFields(prob, F, v):
     through the CONJUGATED receiver CSR (row stride 0 for a fixed array, nrec for one that moves with the source) come down: nrec x k values per item."""
     F.checkCurrent(prob)
     sv = prob.survey
-    nsrc, nrec = sv.nsrc, sv.nrec
     scale = F.scale
-    data = np.zeros((nrec, nsrc, sv.nfreq), dtype=np.complex128)
+    data, stage, sample = _sampling(prob, F.ownedFreqs, scale, conj=True)
     if not F.items:
         return data
-    stride = nrec if sv.mode != 'fixed' else 0
-    Rms = {gk: Rm.conj() for gk, Rm in _receiverMatrices(sv, F.ownedFreqs).items()}
     plain_scaler = prob._plainGradientScaler()
     v = np.ascontiguousarray(v, dtype=np.complex128)
     host_w = None if plain_scaler else {ifreq: v * np.asarray(prob.gradientScaler(ifreq)).ravel() * scale for ifreq in F.ownedFreqs}
@@ -526,23 +586,20 @@ def bornFromFields(prob, F, v):
     def one(ws, op, ifreq, c0, c1):
         k, Ni = c1 - c0, int(op.nrow)
         dev = ws.device
-        sl, ex = F.slice(ifreq, c0)
-        gk = sv._gridKey(ifreq)
-        csr = _csrOnDevice(ws, Rms[gk], ('conj', gk), nrec, stride, c0)
+        d_uF, d_exp = F.pointers(ifreq, c0)
+        staged = stage(ws, ifreq, c0, c1)
         if plain_scaler:
-            cm = op.c
-            inv = ws.cached(('inv_c3', id(cm)), lambda: _inverseCube(cm, dev), keep=cm)
+            inv = _cachedInverseCube(ws, op.c)
             vd = ws.cached(('born_v', id(v)), lambda: _lib.to_device(v, dev, np.complex128), keep=v)
             omega = 2 * np.pi * sv.freqs[ifreq]
             W = inv * vd * complex(-(omega ** 2) * scale)
         else:
             W = ws.cached(('born_w', ifreq, id(v)), lambda: _lib.to_device(host_w[ifreq], dev, np.complex128), keep=v)
-        U, R, out = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni), ws.buffer('out', (nrec, k))
+        U, R = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
         _lib.wait_torch_stream(dev)
-        op.virtualSourcesDevice(sl.data_ptr(), k, W.data_ptr(), R.data_ptr(), d_exp=None if ex is None else ex.data_ptr(), rows=Ni)
+        op.virtualSourcesDevice(d_uF, k, W.data_ptr(), R.data_ptr(), d_exp=d_exp, rows=Ni)
         op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
-        op.sampleDevice(U.data_ptr(), k, csr, out.data_ptr())
-        data[:, c0:c1, ifreq] = scale * _lib.from_device(out)
+        sample(op, ifreq, c0, c1, staged, U.data_ptr())
     runOnDevices(devs, items, one)
     return data
 
@@ -553,11 +610,11 @@ def bornFromFields(prob, F, v):
 # the worker's float64 partial `ws.H`; the store and the workspace hold the unscaled solves, so |scaleTerm|^2 is part of alpha.
 
 def _energyWeight(prob, kind, scale, freqs):
-    """step(ws, op, ifreq) -> (alpha, W): what an item's energy kernel multiplies its sum by, alpha a float and W a float64 device tensor or None.
-    'energy': |scale|^2 and no array.  'pseudoHessian': |gradientScaler|^2 |scale|^2 = omega^4 / |c|^6 |scale|^2 -- with the problem's own scaler
-    W = |1 / c^3|^2 is made once per worker from the cached inv_c3 of _addOnNativeGrid and omega^4 |scale|^2 goes into alpha (no torch work per item);
-    otherwise |prob.gradientScaler(ifreq)|^2 is made here, on the calling thread, and uploaded once per worker and frequency.  A step may enqueue torch work;
-    the item body issues the wait_torch_stream."""
+    """step(ws, op, ifreq) -> (alpha, d_w): what an item's energy kernel multiplies its sum by, alpha a float and d_w the device address of a float64
+    array the worker's cache keeps, or None.  'energy': |scale|^2 and no array.  'pseudoHessian': |gradientScaler|^2 |scale|^2 = omega^4 / |c|^6 |scale|^2
+    -- with the problem's own scaler W = |1 / c^3|^2 is made once per worker from the cached inv_c3 of _addOnNativeGrid and omega^4 |scale|^2 goes into
+    alpha (no torch work per item); otherwise |prob.gradientScaler(ifreq)|^2 is made here, on the calling thread, and uploaded once per worker and
+    frequency.  A step may enqueue torch work; the item body issues the wait_torch_stream."""
     a2 = scale.real * scale.real + scale.imag * scale.imag
     if kind == 'energy':
         return lambda ws, op, ifreq: (a2, None)
@@ -565,10 +622,10 @@ def _energyWeight(prob, kind, scale, freqs):
     if prob._plainGradientScaler():
         def step(ws, op, ifreq):
             cm = op.c
-            inv = ws.cached(('inv_c3', id(cm)), lambda: _inverseCube(cm, ws.device), keep=cm)
+            inv = _cachedInverseCube(ws, cm)
             W = ws.cached(('abs2_inv_c3', id(cm)), lambda: inv.real * inv.real + inv.imag * inv.imag, keep=cm)
             omega = 2 * np.pi * sv.freqs[ifreq]
-            return (omega ** 4) * a2, W
+            return (omega ** 4) * a2, W.data_ptr()
         return step
     host = {}
     for ifreq in freqs:
@@ -576,16 +633,15 @@ def _energyWeight(prob, kind, scale, freqs):
         host[ifreq] = np.square(w.real) + np.square(w.imag)
 
     def step(ws, op, ifreq):
-        return a2, ws.cached(('abs2_scaler', ifreq), lambda: _lib.to_device(host[ifreq], ws.device, np.float64))
+        return a2, ws.cached(('abs2_scaler', ifreq), lambda: _lib.to_device(host[ifreq], ws.device, np.float64)).data_ptr()
     return step
 
 
 def _energyRow(ws, shape, ifreq):
     "device pointer of the row of the worker's partial illumination that frequency ifreq adds to (the partial zeroed on first use)"
     import torch
-    if ws.H is None:
-        ws.H = torch.zeros(shape, dtype=torch.float64, device=ws.device)
-    return ws.H.data_ptr() + (ifreq * shape[1] * 8 if len(shape) == 2 else 0)
+    H = _partial(ws, 'H', shape, torch.float64)
+    return H.data_ptr() + (ifreq * shape[1] * 8 if len(shape) == 2 else 0)
 
 
 def _sumEnergyPartials(prob, parts, shape):
@@ -619,12 +675,11 @@ def illumination(prob, owned, kind, side, perFreq):
         k, Ni = c1 - c0, int(op.nrow)
         row = _energyRow(ws, shape, ifreq)
         U, R = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
-        qi = q[ifreq] if isinstance(q, (list, tuple)) else q
-        op.rhsFromSparseDevice(sp.csc_matrix(qi)[:, c0:c1], R.data_ptr())
-        alpha, W = weight(ws, op, ifreq)
+        _expandColumns(op, q, ifreq, c0, c1, R)
+        alpha, d_w = weight(ws, op, ifreq)
         _lib.wait_torch_stream(ws.device)                # (covers the zeroed partial and the weight: keep it between the torch work and the library calls)
         op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
-        op.energyAccumulateDevice(U.data_ptr(), k, alpha, None if W is None else W.data_ptr(), row, rows=Ni)
+        op.energyAccumulateDevice(U.data_ptr(), k, alpha, d_w, row, rows=Ni)
     return _sumEnergyPartials(prob, [ws.H for ws in runOnDevices(devs, items, one) if ws.H is not None], shape)
 
 
@@ -642,9 +697,9 @@ def illuminationFromFields(prob, F, kind, perFreq):
 
     def one(ws, op, ifreq, c0, c1):
         k, Ni = c1 - c0, int(op.nrow)
-        sl, ex = F.slice(ifreq, c0)
+        d_uF, d_exp = F.pointers(ifreq, c0)
         row = _energyRow(ws, shape, ifreq)
-        alpha, W = weight(ws, op, ifreq)
+        alpha, d_w = weight(ws, op, ifreq)
         _lib.wait_torch_stream(ws.device)
-        op.energyAccumulateDevice(sl.data_ptr(), k, alpha, None if W is None else W.data_ptr(), row, d_exp=None if ex is None else ex.data_ptr(), rows=Ni)
+        op.energyAccumulateDevice(d_uF, k, alpha, d_w, row, d_exp=d_exp, rows=Ni)
     return _sumEnergyPartials(prob, [ws.H for ws in runOnDevices(devs, items, one, factor=False) if ws.H is not None], shape)

@@ -99,6 +99,11 @@ class DeviceFields(object):
         '(tensor, exponents or None) of the item that starts at source c0 of frequency ifreq'
         return self._store[(ifreq, c0)]
 
+    def pointers(self, ifreq, c0):
+        '(d_u, d_exp) of that item as the kernels take them: the device address of its slice, and of its column exponents or None (complex128)'
+        sl, ex = self._store[(ifreq, c0)]
+        return sl.data_ptr(), None if ex is None else ex.data_ptr()
+
     def __getitem__(self, ifreq):
         'the (N, nsrc) complex128 array prob.fields()[ifreq] would be: downloaded, scaled by scaleTerm'
         ifreq = int(ifreq)

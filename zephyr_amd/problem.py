@@ -16,6 +16,8 @@ per-worker buffers, partial gradients) live in `zephyr_amd.device_survey`; `_dpr
 forward wavefields in HBM (`zephyr_amd.fieldstore.DeviceFields`) for `survey.dpred(m, u=F)` and `Jtvec(m, v, u=F)`.  `illumination` (no counterpart in the
 reference) returns the source- or receiver-side illumination or the diagonal pseudo-Hessian from those fields, what a gradient is preconditioned with.
 """
+import contextlib
+
 import numpy as np
 import scipy.sparse as sp
 
@@ -67,6 +69,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
     @property
     def ispaired(self):
         return self.survey is not None
+
+    def _requirePaired(self):
+        if not self.ispaired:
+            raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
 
     # ---- model -----------------------------------------------------------------------------------------
     def updateModel(self, m, loneKey='c'):
@@ -173,16 +179,14 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
     # ---- forward -----------------------------------------------------------------------------------------
     def lazyFields(self, m=None):
         'generator of forward wavefields (N, nsrc) for the owned frequencies, in frequency order (problem.py:166-179)'
-        if not self.ispaired:
-            raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
+        self._requirePaired()
         self.updateModel(m)
         qf = self.survey.getSources()
         return (u for _, u in self._solveOwned(qf))
 
     def fields(self, m=None):
         'list of forward wavefields for ALL frequencies on this rank (no sharding), on the native grid (problem.py:181-191: post-processed)'
-        if not self.ispaired:
-            raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
+        self._requirePaired()
         self.updateModel(m)
         qf = self.survey.getSources()
         return [pp(u) for u, pp in zip(self.system * qf, self.survey.postProcessors)]
@@ -197,8 +201,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         `Jtvec(m, v, u=F)`, which then solve nsrc columns per frequency between them and the back-propagation instead of re-solving the forward fields.
         `F[ifreq]` downloads what `fields()[ifreq]` would be.  Single-grid surveys (2-D, and 2.5-D with the ky sum on the device); without the device
         path (no GPU, hostGradient, a host ky reduction) this raises and `fields()` is the route."""
-        if not self.ispaired:
-            raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
+        self._requirePaired()
         self.updateModel(m)
         if isinstance(self.survey, HelmMultiGridSurvey):
             return device_survey.fields(self, [], self.fieldsDtype)            # (raises NotImplementedError with the reason)
@@ -215,8 +218,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
 
         This is the reference's one-column outer-product approximation and stays as it is; it is NOT the adjoint of Jtvec.  The Born data that
         pair with Jtvec(adjoint='transpose') exactly are `JvecBorn`."""
-        if not self.ispaired:
-            raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
+        self._requirePaired()
         if v is None:
             raise Exception('Actually, Jvec requires a perturbation vector')
         self.updateModel(m)
@@ -253,8 +255,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         <a, b> = Re sum conj(a) b.  u a DeviceFields: on the device; u None with the device path: fieldsDevice() internally, released afterwards;
         u a list of host arrays, or no device path: numpy.  Fixed and moving receiver arrays; multiscale surveys raise NotImplementedError.
         """
-        if not self.ispaired:
-            raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
+        self._requirePaired()
         if v is None:
             raise Exception('Actually, Jtvec requires a residual vector')
         if adjoint not in ('reciprocity', 'transpose'):
@@ -269,11 +270,9 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if isinstance(u, DeviceFields):
             # forward fields left in HBM by fieldsDevice(): only the back-propagation is solved, on the store's own items
             u.checkCurrent(self)
-            return device_survey.gradientFromFields(self, u, sv.getResidualSources(resid) if sv.mode == 'fixed' else None, resid)
+            return device_survey.gradientFromFields(self, u, self._deviceBackSources(resid), resid)
         if u is None and self._deviceGradientAvailable():
-            # a fixed array keeps its host-built back-sources (sparse, sent up as triplets); those of an array that moves with the source are made on the
-            # device from the residual samples (helm_rhs_from_samples_device): qb = None
-            return self._JtvecDevice(sv.getResidualSources(resid) if sv.mode == 'fixed' else None, owned, resid)
+            return self._JtvecDevice(self._deviceBackSources(resid), owned, resid)
         qb = sv.getResidualSources(resid)
         g = np.zeros(self.nrow, dtype=np.complex128)
         if u is None:
@@ -296,39 +295,45 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if isinstance(self.survey, HelmMultiGridSurvey):
             raise NotImplementedError('%s serves single-grid surveys: the transposed operator and the stored forward fields live on one grid' % (what,))
 
+    @contextlib.contextmanager
     def _forwardFields(self, u):
-        """what the exact-adjoint routes read the forward fields from: a DeviceFields as it is (checked), a list of host arrays as a list, None -> a DeviceFields
-        solved now where the device path serves (the caller releases it), else a host list with the owned frequencies' fields (None elsewhere).
-        Returns (fields, made_here)."""
+        """`with self._forwardFields(u) as F`: what the exact-adjoint routes read the forward fields from -- a DeviceFields as it is (checked), a list of host
+        arrays as a list, None -> a DeviceFields solved now where the device path serves, released when the block is left whatever happened in it, else a
+        host list with the owned frequencies' fields (None elsewhere)."""
         if isinstance(u, DeviceFields):
             u.checkCurrent(self)
-            return u, False
-        if u is not None:
-            return list(u), False
-        if self._deviceGradientAvailable():
-            return self.fieldsDevice(), True
-        uF = [None] * self.survey.nfreq
-        pps = self.survey.postProcessors
-        for ifreq, uf in self._solveOwned(self.survey.getSources()):
-            uF[ifreq] = pps[ifreq](uf)
-        return uF, False
+            yield u
+        elif u is not None:
+            yield list(u)
+        elif self._deviceGradientAvailable():
+            F = self.fieldsDevice()
+            try:
+                yield F
+            finally:
+                F.release()
+        else:
+            uF = [None] * self.survey.nfreq
+            pps = self.survey.postProcessors
+            for ifreq, uf in self._solveOwned(self.survey.getSources()):
+                uF[ifreq] = pps[ifreq](uf)
+            yield uF
+
+    def _deviceBackSources(self, resid):
+        """the back-sources as the device pipelines take them: a fixed array keeps its host-built ones (sparse, sent up as triplets); those of an array that
+        moves with the source are made on the device from the residual samples (helm_rhs_from_samples_device): None"""
+        sv = self.survey
+        return sv.getResidualSources(resid) if sv.mode == 'fixed' else None
 
     def _JtvecTranspose(self, resid, u):
         "Jtvec(adjoint='transpose') once the model is current and `resid` is (nrec, nsrc, nfreq)"
         self._refuseMultiscale("Jtvec(adjoint='transpose')")
-        sv = self.survey
         adj = self.adjointSystem
-        F, mine = self._forwardFields(u)
-        if isinstance(F, DeviceFields):
-            try:
-                return device_survey.gradientFromFields(self, F, sv.getResidualSources(resid) if sv.mode == 'fixed' else None, resid, system=adj)
-            finally:
-                if mine:
-                    F.release()
-        qb = sv.getResidualSources(resid)
-        g = np.zeros(self.nrow, dtype=np.complex128)
-        for ifreq, uB in self._solveOwned(qb, adj):
-            g += self.gradientScaler(ifreq) * (np.asarray(F[ifreq]) * uB).sum(axis=1)
+        with self._forwardFields(u) as F:
+            if isinstance(F, DeviceFields):
+                return device_survey.gradientFromFields(self, F, self._deviceBackSources(resid), resid, system=adj)
+            g = np.zeros(self.nrow, dtype=np.complex128)
+            for ifreq, uB in self._solveOwned(self.survey.getResidualSources(resid), adj):
+                g += self.gradientScaler(ifreq) * (np.asarray(F[ifreq]) * uB).sum(axis=1)
         if self._sharded:
             g = parallel.allreduce_sum(g)
         return g.real
@@ -344,32 +349,27 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         made from the slice on the device, solved there and sampled through the conjugated receiver CSR; nrec x k samples come down per item.  u None
         with the device path: fieldsDevice() internally, released afterwards.  u a list of host arrays, or no device path: numpy.  Sharded ranks end
         in one all-reduce.  Multiscale surveys raise NotImplementedError."""
-        if not self.ispaired:
-            raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
+        self._requirePaired()
         if v is None:
             raise Exception('Actually, JvecBorn requires a perturbation vector')
         self.updateModel(m)
         self._refuseMultiscale('JvecBorn')
         sv = self.survey
         pert = np.asarray(v).reshape((self.nrow,))
-        F, mine = self._forwardFields(u)
-        if isinstance(F, DeviceFields):
-            try:
+        with self._forwardFields(u) as F:
+            if isinstance(F, DeviceFields):
                 data = device_survey.bornFromFields(self, F, pert)
-            finally:
-                if mine:
-                    F.release()
-        else:
-            data = np.zeros((sv.nrec, sv.nsrc, sv.nfreq), dtype=np.complex128)
-            owned = self.ownedFreqs
-            qv = [np.conj((pert * np.asarray(self.gradientScaler(i)).ravel())[:, None] * np.asarray(F[i])) if i in owned else None for i in range(sv.nfreq)]
-            for ifreq, uB in self._solveOwned(qv):
-                uB = np.asarray(uB)
-                if sv.mode == 'fixed':
-                    data[:, :, ifreq] = sv.rVec(0, ifreq).conj() * uB
-                else:
-                    for isrc in range(sv.nsrc):
-                        data[:, isrc, ifreq] = sv.rVec(isrc, ifreq).conj() * uB[:, isrc]
+            else:
+                data = np.zeros((sv.nrec, sv.nsrc, sv.nfreq), dtype=np.complex128)
+                owned = self.ownedFreqs
+                qv = [np.conj((pert * np.asarray(self.gradientScaler(i)).ravel())[:, None] * np.asarray(F[i])) if i in owned else None for i in range(sv.nfreq)]
+                for ifreq, uB in self._solveOwned(qv):
+                    uB = np.asarray(uB)
+                    if sv.mode == 'fixed':
+                        data[:, :, ifreq] = sv.rVec(0, ifreq).conj() * uB
+                    else:
+                        for isrc in range(sv.nsrc):
+                            data[:, isrc, ifreq] = sv.rVec(isrc, ifreq).conj() * uB[:, isrc]
         if self._sharded:
             data = parallel.allreduce_sum(data)
         return data.ravel()
@@ -379,8 +379,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         operator on real vectors, because the two halves are exact adjoints.  weights: optional, real, non-negative, the shape (or ravel) of the data.
         Both halves read the same forward fields: two solves of nsrc columns per frequency, no forward re-solve; with u None the fields are solved once
         (into HBM where the device path serves) for both halves.  Needs the factors of A and of A^T side by side (see `adjointSystem`)."""
-        if not self.ispaired:
-            raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
+        self._requirePaired()
         if v is None:
             raise Exception('Actually, Hvec requires a vector')
         self.updateModel(m)
@@ -390,15 +389,11 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             if np.iscomplexobj(weights) or weights.size != self.survey.nD or not np.all(weights >= 0):
                 raise ValueError('weights are real, non-negative and of the size of the data (%d)' % (self.survey.nD,))
             weights = weights.astype(np.float64).ravel()
-        F, mine = self._forwardFields(u)
-        try:
+        with self._forwardFields(u) as F:
             d = self.JvecBorn(None, v, u=F)
             if weights is not None:
                 d = d * weights
             return self.Jtvec(None, d, u=F, adjoint='transpose')
-        finally:
-            if mine and isinstance(F, DeviceFields):
-                F.release()
 
     # ---- illumination / diagonal pseudo-Hessian ------------------------------------------------------------
     def illumination(self, m=None, u=None, kind='pseudoHessian', side='source', perFreq=False):
@@ -415,8 +410,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         u a DeviceFields (fieldsDevice): no solve, the store is read where it lies.  u None with the device path on a single-grid survey: the fields are
         solved into HBM, accumulated there and dropped; only the result comes down.  Otherwise (u a list of host arrays, no GPU, hostGradient, a host ky
         reduction, a multiscale survey): numpy on the host."""
-        if not self.ispaired:
-            raise Exception('%s instance is not paired to a survey' % (self.__class__.__name__,))
+        self._requirePaired()
         if kind not in ('energy', 'pseudoHessian'):
             raise ValueError('kind is %r: \'energy\' or \'pseudoHessian\'' % (kind,))
         if side not in ('source', 'receiver'):
