@@ -28,6 +28,8 @@
  *   helm_set_transposed            <- (no counterpart) the handle holds A^T: HelmBaseProblem.Jtvec(adjoint='transpose') back-propagates through A^-T
  *   helm_virtual_sources_device,
  *   helm_virtual_sources_c64_device <- (no counterpart) HelmBaseProblem.JvecBorn: conj(W (.) u_s), the right-hand sides of Born data
+ *   helm_virtual_sources_op[_c64]_device,
+ *   helm_imaging_op_accumulate[_c64]_device <- (no counterpart) the same two with linearisation='operator': the mass stencil of the assembled operator fused in
  *   helm_axpby_device,
  *   helm_sample_accumulate_device  <- MiniZephyr25D.__mul__: the sum over ky sub-problems
  *                                     (`reduce(np.add, ...)`, scaled)     minizephyr.py:435-460
@@ -271,6 +273,29 @@ int helm_energy_accumulate_device(helm_op *op, const void *dU, int nsrc, long lo
  * overlapping pointer: HELM_ERR_ARG.  All device pointers; returns when R is complete. */
 int helm_virtual_sources_device(helm_op *op, const void *dU, int nsrc, long long ldu, const void *dW, void *dR, long long ldr);
 int helm_virtual_sources_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ldu, const void *dW, void *dR, long long ldr);
+
+/* --- the exact Frechet derivative of MiniZephyr (HelmBaseProblem.JvecBorn / Jtvec with linearisation='operator') -------------------------------
+ * MiniZephyr carries the velocity as K = (omega_d^2 / c^2 - ky^2) / rho of the neighbouring cell, spread over the nine slots by the mass weights, and its boundary
+ * rows are +-identity: (dA) u = mask_int (.) M0(dK (.) u), M0 the constant 9-point stencil with weights 0.6248 (centre), 0.09381 (edges), 1.297e-6 (corners) on the
+ * handle's nz x nx grid (cells outside contribute nothing), mask_int zero on the four boundary lines.
+ *
+ * R[s ldr + i] = coef mask_int[i] M0(W (.) X[s])[i], X[s] = U[s] or (conj != 0) conj(U[s]), s < nsrc, i < N.  U: nsrc columns of ldu >= N complex128 values (or, _c64,
+ * complex64 values with the int32 column exponents dExp of helm_pack_c64_device); W: N complex128; R: nsrc columns of ldr >= N complex128, not overlapping U or
+ * W; 16-byte aligned (U32: 8, dExp: 4).
+ *
+ * G[i] += W[i] sum_{s<nsrc} UF[s ldf + i] M0(mask_int (.) UB[s])[i]: the imaging sum with the stencil (M0^T mask_int = M0 mask_int) applied to the back-propagated
+ * columns UB (nsrc columns of ldb >= N complex128) on the fly; UF as U above; W, G: N complex128, G not overlapping the others.
+ *
+ * Plain fp64 in an order the code fixes (per cell: centre, the four edges, the four corners; s ascending), no atomics: the same bits on every run.  2-D MiniZephyr
+ * handles; Eurus and 3-D handles: HELM_ERR_UNSUPPORTED.  Null pointers, nsrc < 1, a leading dimension < N, a misaligned or overlapping pointer: HELM_ERR_ARG.  All
+ * device pointers; each call returns when its result is complete. */
+int helm_virtual_sources_op_device(helm_op *op, const void *dU, int nsrc, long long ldu, const void *dW, double coef_re, double coef_im, int conj, void *dR,
+                                   long long ldr);
+int helm_virtual_sources_op_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ldu, const void *dW, double coef_re, double coef_im,
+                                       int conj, void *dR, long long ldr);
+int helm_imaging_op_accumulate_device(helm_op *op, const void *dUF, long long ldf, const void *dUB, long long ldb, int nsrc, const void *dW, void *dG);
+int helm_imaging_op_accumulate_c64_device(helm_op *op, const void *dUF32, const void *dExp, long long ldf, const void *dUB, long long ldb, int nsrc, const void *dW,
+                                          void *dG);
 
 /* --- device-resident callers: sparse sources in, receiver samples out ---------------------------------- */
 /* Dense right-hand sides from the COO triplets of the reference's sparse source matrix (survey.py:162-169,

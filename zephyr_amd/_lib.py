@@ -108,6 +108,14 @@ _SIGNATURES = {
                                                    ctypes.c_longlong]),
     'helm_virtual_sources_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p,
                                                        ctypes.c_void_p, ctypes.c_longlong]),
+    'helm_virtual_sources_op_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_double,
+                                                      ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong]),
+    'helm_virtual_sources_op_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p,
+                                                          ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong]),
+    'helm_imaging_op_accumulate_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                                         ctypes.c_void_p, ctypes.c_void_p]),
+    'helm_imaging_op_accumulate_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                                             ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
     'helm_num_blocks': (ctypes.c_int, [ctypes.c_void_p]),
     'helm_num_points': (ctypes.c_longlong, [ctypes.c_void_p]),
     'helm_get_diagonals': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),

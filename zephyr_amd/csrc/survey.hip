@@ -1,6 +1,6 @@
 // What a survey runs on the device besides the solves: right-hand sides from sparse sources and from residual samples, receiver sampling, the imaging
-// condition, illumination (energy), axpby, and the optional complex64 store of forward wavefields.  Each kernel stands beside the C entry point that
-// launches it.
+// condition, illumination (energy), axpby, the optional complex64 store of forward wavefields, and (last section) the mass stencil of the exact Frechet
+// derivative fused into the virtual sources and the imaging sum.  Each kernel stands beside the C entry point that launches it.
 //
 // The complex64 store (zephyr_amd/fieldstore.py, config key fieldsDtype='complex64'): a wavefield column s is kept as
 // complex64 values x * 2^-e_s with ONE power-of-two scale per column, e_s the binary exponent of the column's largest component
@@ -230,6 +230,9 @@ struct FieldC128 {
     const cplx *__restrict__ u;
     __device__ __forceinline__ raw load(long long i) const { return u[i]; }
     __device__ __forceinline__ cplx value(raw x, int) const { return x; }
+    // value() in two steps, for a loop that reads one column many times: scale(s) once, scaled(x, scale) per element
+    __device__ __forceinline__ double scale(int) const { return 1.0; }
+    __device__ __forceinline__ cplx scaled(raw x, double) const { return x; }
 };
 struct FieldC64 {
     typedef cplxf32 raw;
@@ -238,6 +241,8 @@ struct FieldC64 {
     __device__ __forceinline__ raw load(long long i) const { return u[i]; }
     // each component is scaled in fp64 (exact: 2^(2 e_s) alone would overflow where the field does not)
     __device__ __forceinline__ cplx value(raw x, int s) const { const double sc = pow2(exps[s]); return cmake((double)x.x * sc, (double)x.y * sc); }
+    __device__ __forceinline__ double scale(int s) const { return pow2(exps[s]); }
+    __device__ __forceinline__ cplx scaled(raw x, double sc) const { return cmake((double)x.x * sc, (double)x.y * sc); }
 };
 
 // G[i] += scaler[i] * sum_s UF[s][i] * UB[s][i]      (problem.py:152)
@@ -433,4 +438,248 @@ extern "C" int helm_sample_rows_c64_device(helm_op *op, const void *dU32, const 
     HIP_TRY(op, hipSetDevice(op->device));
     return launch_sample<FieldC64, true>(op, FieldC64{(const cplxf32 *)dU32, (const int *)dExp}, nsrc, ld, d_rowptr, d_col, d_val, nrec, row_stride,
                                          cmake(alpha_re, alpha_im), cmake(beta_re, beta_im), d_out);
+}
+
+// ------------------------------------------------------------------------------------------
+// the exact Frechet derivative of MiniZephyr: the mass stencil fused into the virtual sources and into the imaging sum
+// ------------------------------------------------------------------------------------------
+// MiniZephyr carries the velocity as K = (omega_d^2 / c^2 - ky^2) / rho of the NEIGHBOURING cell, spread over the nine slots of a row by the mass weights
+// (assemble.hip: centre cc, edges dc, corners ec), and its four boundary lines are +-identity rows.  So (dA) u = mask_int (.) M0(dK (.) u): M0 the constant
+// 9-point stencil of those weights (cells outside the grid contribute nothing), mask_int zero on the boundary lines.  HelmBaseProblem.JvecBorn /
+// Jtvec(linearisation='operator') need M0 applied to k columns on the way to the solver (k_virtual_sources_op) and, transposed -- M0^T mask_int = M0 mask_int,
+// the weights are symmetric -- to the back-propagated columns inside the imaging sum (k_imaging_op).
+//
+// Both kernels walk the grid the same way.  A wave takes a tile of OP_TILE_X output cells along x, one lane per cell, plus one halo lane at either end (lanes 0 and
+// 63 load and never store), and OP_ROWS output rows, which it walks down with a rolling window of three rows per column held in registers: per row and column
+// the value t of the lane's own cell and h = t(x - 1) + t(x + 1), fetched from the neighbouring lanes (no LDS, no barrier: waves run independently).  Row z is
+//     mc t(z) + md ((t(z-1) + t(z+1)) + h(z)) + me (h(z-1) + h(z+1))
+// OP_UNROLL columns are walked together, and the loads of the next row are issued before the arithmetic of the current one.  A field element is loaded once per
+// kernel except for the halo: one lane in 32 and two rows in OP_ROWS + 2 are loaded by two waves (neighbours in the grid, hence in flight together).
+// The order of every sum is fixed by the code: the same bits on every run.
+constexpr double MZ_MC = 0.6248, MZ_MD = 0.09381, MZ_ME = 0.000001297;      // (assemble.hip cc, dc, ec)
+constexpr int OP_TILE_X = 62;       // output cells per wave along x
+constexpr int OP_ROWS = 32;         // output rows per wave
+constexpr int OP_UNROLL = 4;        // columns walked together
+
+struct MassRow { cplx t, h; };
+
+// t(x - 1) + t(x + 1) from the neighbouring lanes.  Lane 0 and lane 63 get their own value for the missing neighbour: they are halo lanes, whose h is never used.
+__device__ __forceinline__ cplx lane_neighbours(cplx t) {
+    const double lx = __shfl_up(t.x, 1, 64), ly = __shfl_up(t.y, 1, 64), rx = __shfl_down(t.x, 1, 64), ry = __shfl_down(t.y, 1, 64);
+    return cmake(lx + rx, ly + ry);
+}
+__device__ __forceinline__ cplx mass_row(const MassRow &up, const MassRow &mid, const MassRow &dn) {
+    const cplx e = cmake((up.t.x + dn.t.x) + mid.h.x, (up.t.y + dn.t.y) + mid.h.y);
+    const cplx c = cmake(up.h.x + dn.h.x, up.h.y + dn.h.y);
+    return cmake(MZ_MC * mid.t.x + MZ_MD * e.x + MZ_ME * c.x, MZ_MC * mid.t.y + MZ_MD * e.y + MZ_ME * c.y);
+}
+
+// where a wave works: its tile and rows from the flat job index (x tiles fastest), its lane's cell
+struct OpJob {
+    int x, z0, z1; bool live, xin, store;
+    __device__ __forceinline__ OpJob(int nz, int nx) {
+        const int lane = threadIdx.x & 63;
+        const int ntx = (nx + OP_TILE_X - 1) / OP_TILE_X, nzc = (nz + OP_ROWS - 1) / OP_ROWS;
+        const long long job = (long long)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+        live = job < (long long)ntx * nzc;
+        const int tile = live ? (int)(job % ntx) : 0, chunk = live ? (int)(job / ntx) : 0;
+        x = tile * OP_TILE_X + lane - 1;
+        z0 = chunk * OP_ROWS;
+        z1 = min(z0 + OP_ROWS, nz);
+        xin = x >= 0 && x < nx;
+        store = lane >= 1 && lane <= OP_TILE_X && x < nx;
+    }
+};
+static dim3 op_grid(const helm_op *op, int groups) {
+    const long long jobs = (long long)((op->nx + OP_TILE_X - 1) / OP_TILE_X) * ((op->nz + OP_ROWS - 1) / OP_ROWS);
+    return dim3((unsigned)((jobs + 3) / 4), (unsigned)groups);
+}
+
+// R[s ldr + i] = coef mask_int[i] M0(W (.) (CONJ ? conj(U[s]) : U[s]))[i] for the nsrc columns, i over the nz x nx grid.  grid.y: groups of OP_UNROLL columns.
+// Per cell and column 16 (8: complex64 store) bytes read and 16 written; W is read once per group of columns (16 B per cell against 4 x 32).
+template <class F, bool CONJ>
+__global__ __launch_bounds__(256) void k_virtual_sources_op(F U, int nsrc, long long ldu, const cplx *__restrict__ W, cplx coef, cplx *__restrict__ R, long long ldr,
+                                                            int nz, int nx) {
+    const OpJob job(nz, nx);
+    if (!job.live) return;                                  // (a whole wave: the lane exchanges below stay complete)
+    const int s0 = blockIdx.y * OP_UNROLL, ncol = min(OP_UNROLL, nsrc - s0);
+    const int x = job.x;
+    typename F::raw raw[OP_UNROLL];
+    cplx w;
+    MassRow up[OP_UNROLL], mid[OP_UNROLL], dn[OP_UNROLL];
+    double sc[OP_UNROLL];                                   // (the columns' scales, read once: not a dependent load per row)
+#pragma unroll
+    for (int j = 0; j < OP_UNROLL; ++j) sc[j] = U.scale(s0 + min(j, ncol - 1));
+
+    // the loads of row z (nothing outside the grid); the products and the neighbour exchange of what was loaded
+    auto fetch = [&](int z) {
+        const bool in = job.xin && z >= 0 && z < nz;
+        const long long i = (long long)z * nx + x;
+        w = in ? W[i] : cmake(0.0, 0.0);
+#pragma unroll
+        for (int j = 0; j < OP_UNROLL; ++j) raw[j] = (in && j < ncol) ? U.load((long long)(s0 + j) * ldu + i) : typename F::raw{};
+    };
+    auto make = [&](MassRow *row) {
+#pragma unroll
+        for (int j = 0; j < OP_UNROLL; ++j) {
+            cplx u = U.scaled(raw[j], sc[j]);
+            if (CONJ) u = cconj(u);
+            row[j].t = cmul(w, u);
+            row[j].h = lane_neighbours(row[j].t);
+        }
+    };
+    fetch(job.z0 - 1); make(up);
+    fetch(job.z0); make(mid);
+    fetch(job.z0 + 1);
+    for (int z = job.z0; z < job.z1; ++z) {
+        make(dn);
+        if (z + 1 < job.z1) fetch(z + 2);                  // (wave-uniform)
+        const bool inside = z >= 1 && z <= nz - 2 && x >= 1 && x <= nx - 2;
+        if (job.store) {
+            const long long i = (long long)z * nx + x;
+#pragma unroll
+            for (int j = 0; j < OP_UNROLL; ++j)
+                if (j < ncol) R[(long long)(s0 + j) * ldr + i] = inside ? cmul(coef, mass_row(up[j], mid[j], dn[j])) : cmake(0.0, 0.0);
+        }
+#pragma unroll
+        for (int j = 0; j < OP_UNROLL; ++j) { up[j] = mid[j]; mid[j] = dn[j]; }
+    }
+}
+
+static int virtual_sources_op_args(helm_op *op, const void *dU, int nsrc, long long ldu, const void *dW, void *dR, long long ldr) {
+    if (!op || !dU || !dW || !dR || nsrc < 1 || nsrc > 65535 * OP_UNROLL || ldu < op->N || ldr < op->N || dU == dR || dW == dR) return HELM_ERR_ARG;
+    if (op->variant != HELM_MINIZEPHYR || op->ny > 0) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "the mass stencil of the exact derivative is that of the 2-D MiniZephyr operator");
+    return HELM_OK;
+}
+
+// R[s][i] = coef mask_int[i] M0(W (.) U[s])[i] (conj != 0: M0(W (.) conj(U[s]))) for s < nsrc, i < N (the handle's nz x nx grid): U [nsrc][ldu] complex128, W N
+// complex128, R [nsrc][ldr] complex128, ldu, ldr >= N.  R must not overlap U or W.  Returns when R is complete.
+extern "C" int helm_virtual_sources_op_device(helm_op *op, const void *dU, int nsrc, long long ldu, const void *dW, double coef_re, double coef_im, int conj,
+                                              void *dR, long long ldr) {
+    helm_tuning_refresh();
+    if (int rc = virtual_sources_op_args(op, dU, nsrc, ldu, dW, dR, ldr)) return rc;
+    if ((((uintptr_t)dU) | ((uintptr_t)dW) | ((uintptr_t)dR)) & 15) return HELM_ERR_ARG;       // (16-byte loads and stores)
+    HIP_TRY(op, hipSetDevice(op->device));
+    const dim3 grid = op_grid(op, (nsrc + OP_UNROLL - 1) / OP_UNROLL);
+    const FieldC128 U{(const cplx *)dU};
+    if (conj) HELM_LAUNCH((k_virtual_sources_op<FieldC128, true>), grid, dim3(256), 0, op->stream, U, nsrc, ldu, (const cplx *)dW, cmake(coef_re, coef_im), (cplx *)dR, ldr, op->nz, op->nx);
+    else HELM_LAUNCH((k_virtual_sources_op<FieldC128, false>), grid, dim3(256), 0, op->stream, U, nsrc, ldu, (const cplx *)dW, cmake(coef_re, coef_im), (cplx *)dR, ldr, op->nz, op->nx);
+    return launched(op);
+}
+
+extern "C" int helm_virtual_sources_op_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ldu, const void *dW, double coef_re, double coef_im,
+                                                  int conj, void *dR, long long ldr) {
+    helm_tuning_refresh();
+    if (int rc = virtual_sources_op_args(op, dU32, nsrc, ldu, dW, dR, ldr)) return rc;
+    if (!dExp || (((uintptr_t)dU32) & 7) || (((uintptr_t)dExp) & 3) || ((((uintptr_t)dW) | ((uintptr_t)dR)) & 15)) return HELM_ERR_ARG;       // (8-byte loads of U32)
+    HIP_TRY(op, hipSetDevice(op->device));
+    const dim3 grid = op_grid(op, (nsrc + OP_UNROLL - 1) / OP_UNROLL);
+    const FieldC64 U{(const cplxf32 *)dU32, (const int *)dExp};
+    if (conj) HELM_LAUNCH((k_virtual_sources_op<FieldC64, true>), grid, dim3(256), 0, op->stream, U, nsrc, ldu, (const cplx *)dW, cmake(coef_re, coef_im), (cplx *)dR, ldr, op->nz, op->nx);
+    else HELM_LAUNCH((k_virtual_sources_op<FieldC64, false>), grid, dim3(256), 0, op->stream, U, nsrc, ldu, (const cplx *)dW, cmake(coef_re, coef_im), (cplx *)dR, ldr, op->nz, op->nx);
+    return launched(op);
+}
+
+// G[i] += W[i] sum_s UF[s ldf + i] M0(mask_int (.) UB[s])[i]: the stencil on the back-propagated field inside the imaging sum, no intermediate array.  A workgroup
+// of IMG_WAVES waves owns a tile of OP_TILE_X x IMG_ROWS cells of G.  The columns go to its waves in groups of OP_UNROLL, group g to wave g mod IMG_WAVES; a wave walks
+// the tile's rows once per group (the walk of the header comment) and keeps its sum per cell in an LDS slice of its own.  After one barrier wave r adds the slices
+// of row r in wave order and then W (.) sum to G: one writer per cell and a fixed order, so no atomics and the same bits on every run.
+// Per cell and column 16 (8: complex64 store) bytes of UF and 16 of UB, the latter times (1 + 2 / IMG_ROWS) (1 + 2 / OP_TILE_X) for the halo; W and G once per cell.
+// Rows are short because the columns of a tile are spread over the waves of ONE workgroup: with a wave per 32 rows and every column, 512^2 cells gave 144 waves
+// to 1024 SIMDs and the kernel ran at 0.7 TB/s.
+constexpr int IMG_ROWS = 8;         // output rows per workgroup
+constexpr int IMG_WAVES = 8;        // waves per workgroup: 64 KB of LDS
+static_assert(IMG_ROWS <= IMG_WAVES, "wave r finishes row r");
+
+template <class F>
+__global__ __launch_bounds__(64 * IMG_WAVES) void k_imaging_op(F UF, long long ldf, const cplx *__restrict__ UB, long long ldb, int nsrc, const cplx *__restrict__ W,
+                                                               cplx *__restrict__ G, int nz, int nx) {
+    __shared__ cplx part[IMG_WAVES][IMG_ROWS][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ntx = (nx + OP_TILE_X - 1) / OP_TILE_X;
+    const int x = (int)(blockIdx.x % ntx) * OP_TILE_X + lane - 1, z0 = (int)(blockIdx.x / ntx) * IMG_ROWS;
+    const bool store = lane >= 1 && lane <= OP_TILE_X && x < nx;
+    cplx rawb[OP_UNROLL];
+    MassRow up[OP_UNROLL], mid[OP_UNROLL], dn[OP_UNROLL];
+    const int ngroups = (nsrc + OP_UNROLL - 1) / OP_UNROLL;
+    for (int g = wave; g < ngroups; g += IMG_WAVES) {          // (wave-uniform: the lane exchanges stay complete)
+        const int s0 = g * OP_UNROLL, ncol = min(OP_UNROLL, nsrc - s0);
+        double sc[OP_UNROLL];                               // (the columns' scales, read once per group: not a dependent load per row)
+#pragma unroll
+        for (int j = 0; j < OP_UNROLL; ++j) sc[j] = UF.scale(s0 + min(j, ncol - 1));
+        // the loads of row z of UB with mask_int applied: nothing outside the grid, nothing from its boundary lines
+        auto fetch = [&](int z) {
+            const bool in = z >= 1 && z <= nz - 2 && x >= 1 && x <= nx - 2;
+            const long long i = (long long)z * nx + x;
+#pragma unroll
+            for (int j = 0; j < OP_UNROLL; ++j) rawb[j] = (in && j < ncol) ? UB[(long long)(s0 + j) * ldb + i] : cmake(0.0, 0.0);
+        };
+        auto make = [&](MassRow *row) {
+#pragma unroll
+            for (int j = 0; j < OP_UNROLL; ++j) { row[j].t = rawb[j]; row[j].h = lane_neighbours(rawb[j]); }
+        };
+        fetch(z0 - 1); make(up);
+        fetch(z0); make(mid);
+        fetch(z0 + 1);
+#pragma unroll 1
+        for (int r = 0; r < IMG_ROWS; ++r) {
+            const int z = z0 + r;
+            make(dn);
+            if (r + 1 < IMG_ROWS) fetch(z + 2);
+            cplx acc = cmake(0.0, 0.0);
+            if (store && z < nz) {
+                const long long i = (long long)z * nx + x;
+                typename F::raw rawf[OP_UNROLL];
+#pragma unroll
+                for (int j = 0; j < OP_UNROLL; ++j) rawf[j] = j < ncol ? UF.load((long long)(s0 + j) * ldf + i) : typename F::raw{};
+#pragma unroll
+                for (int j = 0; j < OP_UNROLL; ++j)
+                    if (j < ncol) cfma(acc, UF.scaled(rawf[j], sc[j]), mass_row(up[j], mid[j], dn[j]));
+            }
+            part[wave][r][lane] = g == wave ? acc : cadd(part[wave][r][lane], acc);      // (the wave's own slice: no other wave touches it before the barrier)
+#pragma unroll
+            for (int j = 0; j < OP_UNROLL; ++j) { up[j] = mid[j]; mid[j] = dn[j]; }
+        }
+    }
+    __syncthreads();
+    if (wave < IMG_ROWS && store && z0 + wave < nz) {
+        cplx sum = part[0][wave][lane];                          // (nsrc >= 1: wave 0 has a group)
+        for (int w = 1; w < min(IMG_WAVES, ngroups); ++w) sum = cadd(sum, part[w][wave][lane]);
+        const long long i = (long long)(z0 + wave) * nx + x;
+        cplx gv = G[i];
+        cfma(gv, W[i], sum);
+        G[i] = gv;
+    }
+}
+static dim3 imaging_op_grid(const helm_op *op) {
+    return dim3((unsigned)(((op->nx + OP_TILE_X - 1) / OP_TILE_X) * ((op->nz + IMG_ROWS - 1) / IMG_ROWS)));
+}
+
+static int imaging_op_args(helm_op *op, const void *dUF, long long ldf, const void *dUB, long long ldb, int nsrc, const void *dW, void *dG) {
+    if (!op || !dUF || !dUB || !dW || !dG || nsrc < 1 || ldf < op->N || ldb < op->N || dUF == dG || dUB == dG || dW == dG) return HELM_ERR_ARG;
+    if (op->variant != HELM_MINIZEPHYR || op->ny > 0) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "the mass stencil of the exact derivative is that of the 2-D MiniZephyr operator");
+    return HELM_OK;
+}
+
+// G[i] += W[i] sum_s UF[s][i] M0(mask_int (.) UB[s])[i] for i < N: UF [nsrc][ldf], UB [nsrc][ldb], W and G N complex128.  G must not overlap the others.  Returns when G
+// is complete.
+extern "C" int helm_imaging_op_accumulate_device(helm_op *op, const void *dUF, long long ldf, const void *dUB, long long ldb, int nsrc, const void *dW, void *dG) {
+    helm_tuning_refresh();
+    if (int rc = imaging_op_args(op, dUF, ldf, dUB, ldb, nsrc, dW, dG)) return rc;
+    if ((((uintptr_t)dUF) | ((uintptr_t)dUB) | ((uintptr_t)dW) | ((uintptr_t)dG)) & 15) return HELM_ERR_ARG;
+    HIP_TRY(op, hipSetDevice(op->device));
+    HELM_LAUNCH(k_imaging_op<FieldC128>, imaging_op_grid(op), dim3(64 * IMG_WAVES), 0, op->stream, FieldC128{(const cplx *)dUF}, ldf, (const cplx *)dUB, ldb, nsrc, (const cplx *)dW,
+                (cplx *)dG, op->nz, op->nx);
+    return launched(op);
+}
+
+extern "C" int helm_imaging_op_accumulate_c64_device(helm_op *op, const void *dUF32, const void *dExp, long long ldf, const void *dUB, long long ldb, int nsrc,
+                                                     const void *dW, void *dG) {
+    helm_tuning_refresh();
+    if (int rc = imaging_op_args(op, dUF32, ldf, dUB, ldb, nsrc, dW, dG)) return rc;
+    if (!dExp || (((uintptr_t)dUF32) & 7) || (((uintptr_t)dExp) & 3) || ((((uintptr_t)dUB) | ((uintptr_t)dW) | ((uintptr_t)dG)) & 15)) return HELM_ERR_ARG;
+    HIP_TRY(op, hipSetDevice(op->device));
+    HELM_LAUNCH(k_imaging_op<FieldC64>, imaging_op_grid(op), dim3(64 * IMG_WAVES), 0, op->stream, FieldC64{(const cplxf32 *)dUF32, (const int *)dExp}, ldf, (const cplx *)dUB, ldb, nsrc,
+                (const cplx *)dW, (cplx *)dG, op->nz, op->nx);
+    return launched(op);
 }

@@ -16,8 +16,10 @@ The eight pipelines, one row each.  Every row is a body of its own made of the s
     fields                  dealt, then stored   source columns                      k                the store's slice (complex64: pack)   nothing
     dpredFromFields         stored               --                                  0                -- (sampleDevice reads the slice)     nrec x k samples per item
     bornFromFields          stored               virtual sources conj(W (.) slice)   k                sampleDevice, conjugated receivers    nrec x k samples per item
+      linearisation='operator'                   coef mask M0(W (.) conj(slice))     k                sampleDevice, receivers as they are   nrec x k samples per item
     gradient                dealt                [qf | qb]                           2k               imaging kernel, uF and uB from U      one partial G per worker
     gradientFromFields      stored               qb                                  k                imaging kernel, uF from the slice     one partial G per worker
+      linearisation='operator'                   qb of R^H r                         k                imaging kernel with the mass stencil  one partial G per worker
     illumination            dealt                source or receiver columns          k                energy kernel                         one partial H per worker
     illuminationFromFields  stored               --                                  0                -- (energy kernel reads the slice)    one partial H per worker
 
@@ -216,6 +218,14 @@ def _cachedInverseCube(ws, cm):
     return ws.cached(('inv_c3', id(cm)), lambda: _inverseCube(cm, ws.device), keep=cm)
 
 
+def _cachedInverseC3Rho(ws, op):
+    """1 / (c^3 rho) of the operator's model, made once per worker: the cached 1 / c^3 and one upload of rho -- the per-cell factor of
+    d K / d c = -2 omega_d^2 / (c^3 rho), what linearisation='operator' weighs with"""
+    cm, rho = op.c, op.rho
+    inv = _cachedInverseCube(ws, cm)
+    return ws.cached(('inv_c3_rho', id(cm), id(rho)), lambda: inv / _lib.to_device(np.asarray(rho, dtype=np.float64).ravel(), ws.device, np.float64), keep=(cm, rho))
+
+
 def _partial(ws, name, shape, dtype):
     "the worker's partial result ws.<name> ('G': gradient, 'H': illumination), zeroed on first use"
     import torch
@@ -256,6 +266,18 @@ def _addOnNativeGrid(prob, scale):
         else:
             scaler = _lib.to_device(prob.gradientScaler(ifreq) * scale * scale, dev, np.complex128)
         return scaler, ws.G, None
+    return step
+
+
+def _addOperator(prob, scale):
+    """linearisation='operator' on the gradient's grid: the adding step hands out W = 2 scale conj(omega_d^2 / premul) / (conj(c)^3 rho), the weight of
+    k_imaging_op (G += W (.) sum_s U_s (.) M0(mask_int (.) uB_s), U_s and uB_s the unscaled solves: the scaleTerm enters once)"""
+    import torch
+    from .frechet import dampedOmega
+
+    def step(ws, op, ifreq, Ni):
+        om = dampedOmega(op)
+        return torch.conj(_cachedInverseC3Rho(ws, op)).resolve_conj() * complex(2.0 * scale * np.conj(om * om / complex(op.premul))), ws.G, None
     return step
 
 
@@ -533,12 +555,13 @@ def _checkSecondFactorsFit(items):
     _checkItemsFit(items, held=factors, work=lambda op, c0, c1: 2 * (c1 - c0) * int(op.nrow) * 16)
 
 
-def gradientFromFields(prob, F, qb, resid, system=None):
+def gradientFromFields(prob, F, qb, resid, system=None, linearisation='scaler'):
     """The u-given branch of Jtvec (problem.py:154-162) with the forward fields read from the store: per item only the k back-sources are made and solved
     (nsrc columns per frequency, not 2 nsrc), scaler * sum_s uF (.) uB goes into the GPU's partial gradient, and the real part of the sum is returned.
     qb None: the back-sources of a moving receiver array, made on the device from `resid` (nrec, nsrc, nfreq).  system: the wrapper whose operators
     back-propagate (default prob.system; prob.adjointSystem for Jtvec(adjoint='transpose') -- the same devices and replicas, so every item still finds
-    its slice on its own GPU)."""
+    its slice on its own GPU).  linearisation='operator' (with the transposed system, qb / resid those of R_s^H r): the same items, calls and waits with the
+    weight of `_addOperator` and k_imaging_op, the mass stencil on the back-propagated columns fused into the imaging sum."""
     import torch
     F.checkCurrent(prob)
     sv = prob.survey
@@ -550,7 +573,8 @@ def gradientFromFields(prob, F, qb, resid, system=None):
     devs, items = _storedItems(prob.system if system is None else system, F)
     if system is not None:
         _checkSecondFactorsFit(items)
-    add = _addOnNativeGrid(prob, scale)
+    exact = linearisation == 'operator'
+    add = _addOperator(prob, scale) if exact else _addOnNativeGrid(prob, scale)
 
     def one(ws, op, ifreq, c0, c1):
         k, Ni = c1 - c0, int(op.nrow)
@@ -561,17 +585,23 @@ def gradientFromFields(prob, F, qb, resid, system=None):
         scaler, target, finish = add(ws, op, ifreq, Ni)
         _lib.wait_torch_stream(ws.device)
         op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
-        op.imagingAccumulateDevice(d_uF, U.data_ptr(), k, scaler.data_ptr(), target.data_ptr(), d_exp=d_exp)
+        if exact:
+            op.imagingOpAccumulateDevice(d_uF, U.data_ptr(), k, scaler.data_ptr(), target.data_ptr(), d_exp=d_exp, rows=Ni)
+        else:
+            op.imagingAccumulateDevice(d_uF, U.data_ptr(), k, scaler.data_ptr(), target.data_ptr(), d_exp=d_exp)
         if finish is not None:
             finish()
     return _sumPartials(prob, [ws.G for ws in runOnDevices(devs, items, one) if ws.G is not None]).real
 
 
-def bornFromFields(prob, F, v):
+def bornFromFields(prob, F, v, linearisation='scaler'):
     """prob.JvecBorn(u=F): Born data (nrec, nsrc, nfreq) of the model perturbation v (N,) from forward fields already in HBM.  Per stored item
     W = v (.) gradientScaler(f) scaleTerm is made on the item's GPU (v and the model go up once per worker), the virtual-source kernel writes
     conj(W (.) slice) -- the store holds the unscaled solves, hence the scaleTerm in W -- the forward operator solves the k columns, and the samples
-    through the CONJUGATED receiver CSR (row stride 0 for a fixed array, nrec for one that moves with the source) come down: nrec x k values per item."""
+    through the CONJUGATED receiver CSR (row stride 0 for a fixed array, nrec for one that moves with the source) come down: nrec x k values per item.
+    linearisation='operator': `_bornOperatorFromFields`."""
+    if linearisation == 'operator':
+        return _bornOperatorFromFields(prob, F, v)
     F.checkCurrent(prob)
     sv = prob.survey
     scale = F.scale
@@ -598,6 +628,36 @@ def bornFromFields(prob, F, v):
         U, R = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
         _lib.wait_torch_stream(dev)
         op.virtualSourcesDevice(d_uF, k, W.data_ptr(), R.data_ptr(), d_exp=d_exp, rows=Ni)
+        op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+        sample(op, ifreq, c0, c1, staged, U.data_ptr())
+    runOnDevices(devs, items, one)
+    return data
+
+
+def _bornOperatorFromFields(prob, F, v):
+    """prob.JvecBorn(u=F, linearisation='operator'): the derivative of dpred along v.  The items, calls and waits of `bornFromFields` with
+    W = dK = -2 omega_d^2 v / (c^3 rho) (the cached 1 / c^3, one upload of rho and of v per worker), k_virtual_sources_op in the place of
+    k_virtual_sources -- R = -(1 / premul) mask_int (.) M0(W (.) conj(slice)), the slice being conj(u^) unscaled -- and the receiver CSR as it is, not
+    conjugated; the scaleTerm multiplies the samples."""
+    from .frechet import dampedOmega
+    F.checkCurrent(prob)
+    data, stage, sample = _sampling(prob, F.ownedFreqs, F.scale)
+    if not F.items:
+        return data
+    v = np.ascontiguousarray(v, dtype=np.complex128)
+    devs, items = _storedItems(prob.system, F)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        dev = ws.device
+        d_uF, d_exp = F.pointers(ifreq, c0)
+        staged = stage(ws, ifreq, c0, c1)
+        vd = ws.cached(('born_v', id(v)), lambda: _lib.to_device(v, dev, np.complex128), keep=v)
+        om = dampedOmega(op)
+        W = _cachedInverseC3Rho(ws, op) * vd * complex(-2.0 * om * om)
+        U, R = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
+        _lib.wait_torch_stream(dev)
+        op.virtualSourcesOpDevice(d_uF, k, W.data_ptr(), -1.0 / complex(op.premul), R.data_ptr(), conj=True, d_exp=d_exp, rows=Ni)
         op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
         sample(op, ifreq, c0, c1, staged, U.data_ptr())
     runOnDevices(devs, items, one)

@@ -330,6 +330,31 @@ class BaseDiscretization(BaseModelDependent):
             return
         _lib.check(lib.helm_virtual_sources_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), rows, ctypes.c_void_p(d_w), ctypes.c_void_p(d_r), rows), self.handle)
 
+    def virtualSourcesOpDevice(self, d_u, nsrc, d_w, coef, d_r, conj=True, d_exp=None, rows=None):
+        """R[s] = coef mask_int (.) M0(W (.) conj-or-not(U[s])) on the device, the right-hand sides of JvecBorn(linearisation='operator'): the mass stencil of
+        the assembled 2-D MiniZephyr operator applied to W (.) U[s], boundary lines zeroed.  Arguments as for virtualSourcesDevice; coef a complex number."""
+        lib = _lib.load()
+        rows = int(self.nrow if rows is None else rows)
+        coef = complex(coef)
+        if d_exp is not None:
+            _lib.check(lib.helm_virtual_sources_op_c64_device(self.handle, ctypes.c_void_p(d_u), ctypes.c_void_p(d_exp), int(nsrc), rows, ctypes.c_void_p(d_w),
+                                                              coef.real, coef.imag, 1 if conj else 0, ctypes.c_void_p(d_r), rows), self.handle)
+            return
+        _lib.check(lib.helm_virtual_sources_op_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), rows, ctypes.c_void_p(d_w), coef.real, coef.imag,
+                                                      1 if conj else 0, ctypes.c_void_p(d_r), rows), self.handle)
+
+    def imagingOpAccumulateDevice(self, d_uf, d_ub, nsrc, d_w, d_g, d_exp=None, rows=None):
+        """G += W (.) sum_s UF[s] (.) M0(mask_int (.) UB[s]) on the device, the imaging sum of Jtvec(linearisation='operator').  Arguments as for
+        imagingAccumulateDevice, both fields [nsrc][rows]."""
+        lib = _lib.load()
+        rows = int(self.nrow if rows is None else rows)
+        if d_exp is not None:
+            _lib.check(lib.helm_imaging_op_accumulate_c64_device(self.handle, ctypes.c_void_p(d_uf), ctypes.c_void_p(d_exp), rows, ctypes.c_void_p(d_ub), rows,
+                                                                 int(nsrc), ctypes.c_void_p(d_w), ctypes.c_void_p(d_g)), self.handle)
+            return
+        _lib.check(lib.helm_imaging_op_accumulate_device(self.handle, ctypes.c_void_p(d_uf), rows, ctypes.c_void_p(d_ub), rows, int(nsrc),
+                                                         ctypes.c_void_p(d_w), ctypes.c_void_p(d_g)), self.handle)
+
     def packDevice(self, d_u, nsrc, d_out, d_exp, rows=None):
         """The complex64 store of the wavefields d_u ([nsrc][rows] complex128): d_out [nsrc][rows] complex64 values x * 2^-e_s, d_exp the nsrc int32 column
         exponents e_s (fieldstore.pack_reference states the format).  All device pointers; returns when both are complete."""

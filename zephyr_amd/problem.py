@@ -29,6 +29,7 @@ from . import parallel
 from . import device_survey
 from . import _lib
 from .fieldstore import DeviceFields
+from .frechet import MZ_MASS, maskInterior, massStencil, operatorWeight      # noqa: F401 (what linearisation='operator' is made of)
 
 EPS = 1e-15
 
@@ -238,7 +239,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         return dpert.ravel()
 
     # ---- gradient ----------------------------------------------------------------------------------------
-    def Jtvec(self, m=None, v=None, u=None, adjoint='reciprocity'):
+    def Jtvec(self, m=None, v=None, u=None, adjoint='reciprocity', linearisation='scaler'):
         """FWI gradient g = sum_f scaler_f sum_s uF (.) uB  (problem.py:124-164).
 
         u is None: "mux" branch -- forward and back-propagated sources are stacked column-wise and
@@ -254,19 +255,30 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         always real float64 (N,) -- there is no mux branch, forward and back solves use different factors -- and the exact adjoint of `JvecBorn` under
         <a, b> = Re sum conj(a) b.  u a DeviceFields: on the device; u None with the device path: fieldsDevice() internally, released afterwards;
         u a list of host arrays, or no device path: numpy.  Fixed and moving receiver arrays; multiscale surveys raise NotImplementedError.
+
+        linearisation='scaler' (default): the weight is the reference's gradientScaler w_f = -omega^2 / c^3, the reference's convention.  That is NOT the
+        derivative of `dpred`: the assembled operator carries c as K = (omega_d^2 / c^2 - ky^2) / rho spread over nine slots by the mass weights, with
+        identity boundary rows, so this g is a rho-dependent rescaling of the gradient (and of the opposite sign).
+        linearisation='operator' (needs adjoint='transpose'): g = J^T v with J the derivative of `dpred` (see `JvecBorn`), the gradient of
+        1/2 ||dpred - dobs||^2 for v = dpred - dobs,
+            g = Re sum_f W_f (.) sum_s U_s (.) M0(mask_int (.) uB_s),   W_f = 2 scaleTerm conj(omega_d^2 / premul) / (c^3 rho),
+        U_s the unscaled forward solve and uB_s = conj(A_f^-T premul R_s^H v_s).  `_requireOperatorLinearisation` lists what it serves.
         """
         self._requirePaired()
         if v is None:
             raise Exception('Actually, Jtvec requires a residual vector')
         if adjoint not in ('reciprocity', 'transpose'):
             raise ValueError('adjoint is %r: \'reciprocity\' or \'transpose\'' % (adjoint,))
+        self._checkLinearisation(linearisation)
+        if linearisation == 'operator' and adjoint != 'transpose':
+            raise ValueError('linearisation=\'operator\' needs adjoint=\'transpose\': the exact derivative back-propagates through A^-T')
         self.updateModel(m)
         sv = self.survey
         nsrc = sv.nsrc
         resid = np.asarray(v).reshape((sv.nrec, sv.nsrc, sv.nfreq))
         owned = self.ownedFreqs
         if adjoint == 'transpose':
-            return self._JtvecTranspose(resid, u)
+            return self._JtvecTranspose(resid, u, linearisation)
         if isinstance(u, DeviceFields):
             # forward fields left in HBM by fieldsDevice(): only the back-propagation is solved, on the store's own items
             u.checkCurrent(self)
@@ -294,6 +306,45 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
     def _refuseMultiscale(self, what):
         if isinstance(self.survey, HelmMultiGridSurvey):
             raise NotImplementedError('%s serves single-grid surveys: the transposed operator and the stored forward fields live on one grid' % (what,))
+
+    @staticmethod
+    def _checkLinearisation(linearisation):
+        if linearisation not in ('scaler', 'operator'):
+            raise ValueError('linearisation is %r: \'scaler\' or \'operator\'' % (linearisation,))
+
+    def _requireOperatorLinearisation(self, what):
+        """linearisation='operator' serves Helm2DProblem with MiniZephyr / MiniZephyrHD on a single grid and an explicit density: everything else is refused
+        here with the reason"""
+        from .minizephyr import MiniZephyr
+        from .discretization import DiscretizationWrapper
+        self._refuseMultiscale(what)
+        if isinstance(self.system, ViscoMultiFreq):
+            raise NotImplementedError('%s does not serve visco problems: the chain factor of the complex velocity with respect to c and Q is not built' % (what,))
+        sub = self.system.subProblems[0] if self.system.subProblems else None
+        if sub is not None and isinstance(sub, DiscretizationWrapper):
+            raise NotImplementedError('%s does not serve the 2.5-D composite: the stored fields are the ky SUM, the exact derivative needs the fields per ky' % (what,))
+        if sub is not None and not (isinstance(sub, MiniZephyr) and getattr(sub, 'ny', None) is None):
+            raise NotImplementedError('%s serves the 2-D MiniZephyr operators: %s assembles its mass term differently' % (what, type(sub).__name__))
+        if 'rho' not in self.systemConfig or self.systemConfig['rho'] is None:
+            raise NotImplementedError('%s needs an explicit `rho` in the config: without one the Gardner density follows c, and its sensitivity is not built' % (what,))
+
+    def _hermitianResidual(self, resid):
+        """resid' with R_s^T resid'_s = R_s^H resid_s, for the device pipelines (which build R_s^T r): a receiver matrix is diag(srTerms) R0 with R0 the real
+        columns of the source generator, so resid' = resid (.) conj(srTerms) / srTerms per receiver (0 where the term is 0: that row of R is zero).  A
+        generator with complex columns has no such form and is refused."""
+        sv = self.survey
+        t = np.asarray(sv.srTerms, dtype=np.complex128).ravel()
+        if not np.any(t.imag):
+            return resid
+        Rm = sp.csr_matrix(sv.rVec(0, 0))
+        rows = np.repeat(np.arange(Rm.shape[0]), np.diff(Rm.indptr))
+        base = Rm.data * np.conj(t[rows])
+        if np.any(np.abs(base.imag) > 1e-12 * np.abs(base)):
+            raise NotImplementedError("linearisation='operator' on the device needs a source generator with real receiver columns (complex receiver terms are served)")
+        nz = t != 0
+        ph = np.zeros_like(t)
+        ph[nz] = np.conj(t[nz]) / t[nz]
+        return resid * ph[:, None, None]
 
     @contextlib.contextmanager
     def _forwardFields(self, u):
@@ -324,21 +375,36 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         sv = self.survey
         return sv.getResidualSources(resid) if sv.mode == 'fixed' else None
 
-    def _JtvecTranspose(self, resid, u):
+    def _JtvecTranspose(self, resid, u, linearisation='scaler'):
         "Jtvec(adjoint='transpose') once the model is current and `resid` is (nrec, nsrc, nfreq)"
         self._refuseMultiscale("Jtvec(adjoint='transpose')")
+        exact = linearisation == 'operator'
+        if exact:
+            self._requireOperatorLinearisation("Jtvec(linearisation='operator')")
         adj = self.adjointSystem
         with self._forwardFields(u) as F:
             if isinstance(F, DeviceFields):
-                return device_survey.gradientFromFields(self, F, self._deviceBackSources(resid), resid, system=adj)
+                if exact:
+                    resid = self._hermitianResidual(resid)
+                return device_survey.gradientFromFields(self, F, self._deviceBackSources(resid), resid, system=adj, linearisation=linearisation)
             g = np.zeros(self.nrow, dtype=np.complex128)
-            for ifreq, uB in self._solveOwned(self.survey.getResidualSources(resid), adj):
-                g += self.gradientScaler(ifreq) * (np.asarray(F[ifreq]) * uB).sum(axis=1)
+            if exact:
+                # the back-sources are R_s^H r_s = conj(R_s^T conj(r_s)); the solves come back scaled (scaleTerm uB), the host fields are scaleTerm U: one
+                # scaleTerm of the product stays in the weight, the other is divided out
+                st = complex(self.system.scaleTerm)
+                qb = [q.conj() for q in self.survey.getResidualSources(np.conj(resid))]
+                for ifreq, uB in self._solveOwned(qb, adj):
+                    op = self.system.subProblems[ifreq]
+                    w = -np.conj(operatorWeight(op)) / (st * np.conj(complex(op.premul)))
+                    g += w * (np.asarray(F[ifreq]) * massStencil(maskInterior(np.asarray(uB), op.nz, op.nx), op.nz, op.nx)).sum(axis=1)
+            else:
+                for ifreq, uB in self._solveOwned(self.survey.getResidualSources(resid), adj):
+                    g += self.gradientScaler(ifreq) * (np.asarray(F[ifreq]) * uB).sum(axis=1)
         if self._sharded:
             g = parallel.allreduce_sum(g)
         return g.real
 
-    def JvecBorn(self, m=None, v=None, u=None):
+    def JvecBorn(self, m=None, v=None, u=None, linearisation='scaler'):
         """Born data of the model perturbation v from the forward fields, the ravel of (nrec, nsrc, nfreq) complex128:
 
             dd[:, s, f] = conj(R_s) . scaleTerm S_f( conj(v (.) w_f (.) uF_s) ),   S_f q = conj(A_f^-1 premul q),  w_f = gradientScaler(f),  uF_s = scaleTerm S_f qf_s
@@ -348,52 +414,80 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         property.)  Only the forward factors are used -- those fieldsDevice has just made.  u a DeviceFields: per stored item the virtual sources are
         made from the slice on the device, solved there and sampled through the conjugated receiver CSR; nrec x k samples come down per item.  u None
         with the device path: fieldsDevice() internally, released afterwards.  u a list of host arrays, or no device path: numpy.  Sharded ranks end
-        in one all-reduce.  Multiscale surveys raise NotImplementedError."""
+        in one all-reduce.  Multiscale surveys raise NotImplementedError.
+
+        linearisation='scaler' (default) is the above: the reference's convention, delta A ~ diag(v (.) w_f).  It is NOT the derivative of `dpred`.
+        linearisation='operator': the derivative of `dpred`, d/dh dpred(m + h v) at h = 0, from what the operator is assembled from:
+
+            dd[:, s, f] = R_s . scaleTerm conj(-A_f^-1 delta A u^_s),   delta A u^ = mask_int (.) M0(delta K (.) u^),   delta K = -2 omega_d^2 v / (c^3 rho)
+
+        u^_s = A_f^-1 premul qf_s (the conjugate of the unscaled forward solve), M0 the constant 9-point stencil of the mass weights (centre 0.6248, edges
+        0.09381, corners 1.297e-6), mask_int zero on the four boundary lines (their rows are +-identity), omega_d = 2 pi f - i / tau.  v is real.  It is
+        the exact adjoint of Jtvec(adjoint='transpose', linearisation='operator').  The dependence of the PML stretch on c is left out: the derivative is
+        exact for perturbations that vanish in the absorbing layers (inside them it is the mass-term part only).  `_requireOperatorLinearisation` lists
+        what it serves."""
         self._requirePaired()
         if v is None:
             raise Exception('Actually, JvecBorn requires a perturbation vector')
+        self._checkLinearisation(linearisation)
         self.updateModel(m)
         self._refuseMultiscale('JvecBorn')
+        exact = linearisation == 'operator'
+        if exact:
+            self._requireOperatorLinearisation("JvecBorn(linearisation='operator')")
         sv = self.survey
         pert = np.asarray(v).reshape((self.nrow,))
         with self._forwardFields(u) as F:
             if isinstance(F, DeviceFields):
-                data = device_survey.bornFromFields(self, F, pert)
+                data = device_survey.bornFromFields(self, F, pert, linearisation=linearisation)
             else:
                 data = np.zeros((sv.nrec, sv.nsrc, sv.nfreq), dtype=np.complex128)
                 owned = self.ownedFreqs
-                qv = [np.conj((pert * np.asarray(self.gradientScaler(i)).ravel())[:, None] * np.asarray(F[i])) if i in owned else None for i in range(sv.nfreq)]
+                if exact:
+                    # F[i] = scaleTerm conj(u^): the scaleTerm is divided out of the virtual source and comes back with the solve (_solveOwned scales)
+                    st = complex(self.system.scaleTerm)
+                    subs = self.system.subProblems
+                    qv = [massStencil((operatorWeight(subs[i]) * pert)[:, None] * np.conj(np.asarray(F[i]) / st), subs[i].nz, subs[i].nx, mask=True)
+                          / -complex(subs[i].premul) if i in owned else None for i in range(sv.nfreq)]
+                else:
+                    qv = [np.conj((pert * np.asarray(self.gradientScaler(i)).ravel())[:, None] * np.asarray(F[i])) if i in owned else None for i in range(sv.nfreq)]
                 for ifreq, uB in self._solveOwned(qv):
                     uB = np.asarray(uB)
                     if sv.mode == 'fixed':
-                        data[:, :, ifreq] = sv.rVec(0, ifreq).conj() * uB
+                        Rm = sv.rVec(0, ifreq)
+                        data[:, :, ifreq] = (Rm if exact else Rm.conj()) * uB
                     else:
                         for isrc in range(sv.nsrc):
-                            data[:, isrc, ifreq] = sv.rVec(isrc, ifreq).conj() * uB[:, isrc]
+                            Rm = sv.rVec(isrc, ifreq)
+                            data[:, isrc, ifreq] = (Rm if exact else Rm.conj()) * uB[:, isrc]
         if self._sharded:
             data = parallel.allreduce_sum(data)
         return data.ravel()
 
-    def Hvec(self, m=None, v=None, u=None, weights=None):
+    def Hvec(self, m=None, v=None, u=None, weights=None, linearisation='scaler'):
         """Gauss-Newton Hessian times v: Jtvec(JvecBorn(v) (.) weights, adjoint='transpose'), float64 (N,).  Symmetric and positive semi-definite as an
         operator on real vectors, because the two halves are exact adjoints.  weights: optional, real, non-negative, the shape (or ravel) of the data.
         Both halves read the same forward fields: two solves of nsrc columns per frequency, no forward re-solve; with u None the fields are solved once
-        (into HBM where the device path serves) for both halves.  Needs the factors of A and of A^T side by side (see `adjointSystem`)."""
+        (into HBM where the device path serves) for both halves.  Needs the factors of A and of A^T side by side (see `adjointSystem`).
+        linearisation: handed to both halves; with 'operator' this is the Gauss-Newton Hessian of 1/2 ||dpred - dobs||^2 (with 'scaler' it is not)."""
         self._requirePaired()
         if v is None:
             raise Exception('Actually, Hvec requires a vector')
+        self._checkLinearisation(linearisation)
         self.updateModel(m)
         self._refuseMultiscale('Hvec')
+        if linearisation == 'operator':
+            self._requireOperatorLinearisation("Hvec(linearisation='operator')")       # (before the fields are solved for both halves)
         if weights is not None:
             weights = np.asarray(weights)
             if np.iscomplexobj(weights) or weights.size != self.survey.nD or not np.all(weights >= 0):
                 raise ValueError('weights are real, non-negative and of the size of the data (%d)' % (self.survey.nD,))
             weights = weights.astype(np.float64).ravel()
         with self._forwardFields(u) as F:
-            d = self.JvecBorn(None, v, u=F)
+            d = self.JvecBorn(None, v, u=F, linearisation=linearisation)
             if weights is not None:
                 d = d * weights
-            return self.Jtvec(None, d, u=F, adjoint='transpose')
+            return self.Jtvec(None, d, u=F, adjoint='transpose', linearisation=linearisation)
 
     # ---- illumination / diagonal pseudo-Hessian ------------------------------------------------------------
     def illumination(self, m=None, u=None, kind='pseudoHessian', side='source', perFreq=False):
