@@ -297,6 +297,32 @@ int helm_imaging_op_accumulate_device(helm_op *op, const void *dUF, long long ld
 int helm_imaging_op_accumulate_c64_device(helm_op *op, const void *dUF32, const void *dExp, long long ldf, const void *dUB, long long ldb, int nsrc, const void *dW,
                                           void *dG);
 
+/* --- the exact density derivative of MiniZephyr (HelmBaseProblem.JvecBorn / Jtvec with linearisation='operator', parameter='rho') ---------------
+ * Every interior row of MiniZephyr is linear and homogeneous in the buoyancy field b = 1 / rho; its boundary rows are +-identity.  L maps a real field db (N) to
+ * the nine planes dC[k][i], k = 3 (dz + 1) + (dx + 1), of d A / d b along db: the assembly's formulas on db, boundary rows zero, for the c, the PML and the frequency
+ * of the operator the handle holds (HELM_ERR_STATE before the first helm_assemble).
+ *
+ * helm_buoyancy_planes_device:  dC = L[db].  db: N float64; dC: 9 N complex128.
+ * helm_stencil_sources_device:  R[s ldr + i] = coef sum_k C[k][i] X[s][i + off_k], X[s] = U[s] or (conj != 0) conj(U[s]); cells outside the grid contribute
+ *     nothing.  U: nsrc columns of ldu >= N complex128 (or, _c64, complex64 values with the int32 column exponents dExp of helm_pack_c64_device); C: 9 N
+ *     complex128; R: nsrc columns of ldr >= N complex128.
+ * helm_lag_imaging_accumulate_device:  P[k][i] += sum_{s<nsrc} UB[s ldb + i] UF[s ldf + i + off_k] for the interior cells i; the boundary lines of P are left
+ *     as they are.  UF as U above; UB: nsrc columns of ldb >= N complex128; P: 9 N complex128.
+ * helm_buoyancy_adjoint_device:  G[j] += w sum_{k, i} L_{(k, i), j} P[k][i] (conj != 0: conj(L)), the plain transpose of L; the boundary rows of P are not read.
+ *     G: N complex128.
+ *
+ * Plain fp64 in an order the code fixes, no atomics: the same bits on every run.  An output must not overlap an input.  2-D MiniZephyr handles; Eurus and 3-D
+ * handles: HELM_ERR_UNSUPPORTED.  Null pointers, nsrc < 1, a leading dimension < N, a grid below 3 x 3, a misaligned (16 bytes; U32: 8, dExp: 4, db: 8) or
+ * overlapping pointer: HELM_ERR_ARG.  All device pointers; each call returns when its result is complete. */
+int helm_buoyancy_planes_device(helm_op *op, const void *dDb, void *dC);
+int helm_stencil_sources_device(helm_op *op, const void *dU, int nsrc, long long ldu, const void *dC, double coef_re, double coef_im, int conj, void *dR,
+                                long long ldr);
+int helm_stencil_sources_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ldu, const void *dC, double coef_re, double coef_im,
+                                    int conj, void *dR, long long ldr);
+int helm_lag_imaging_accumulate_device(helm_op *op, const void *dUF, long long ldf, const void *dUB, long long ldb, int nsrc, void *dP);
+int helm_lag_imaging_accumulate_c64_device(helm_op *op, const void *dUF32, const void *dExp, long long ldf, const void *dUB, long long ldb, int nsrc, void *dP);
+int helm_buoyancy_adjoint_device(helm_op *op, const void *dP, double w_re, double w_im, int conj, void *dG);
+
 /* --- device-resident callers: sparse sources in, receiver samples out ---------------------------------- */
 /* Dense right-hand sides from the COO triplets of the reference's sparse source matrix (survey.py:162-169,
  * source.py:213-317): R (nrhs x rows, zeroed by the call), R[col[k]][row[k]] = val[k]; no duplicate entries.

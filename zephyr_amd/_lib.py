@@ -116,6 +116,16 @@ _SIGNATURES = {
                                                          ctypes.c_void_p, ctypes.c_void_p]),
     'helm_imaging_op_accumulate_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
                                                              ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'helm_buoyancy_planes_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'helm_stencil_sources_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_double,
+                                                   ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong]),
+    'helm_stencil_sources_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p,
+                                                       ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong]),
+    'helm_lag_imaging_accumulate_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                                          ctypes.c_void_p]),
+    'helm_lag_imaging_accumulate_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                                              ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]),
+    'helm_buoyancy_adjoint_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
     'helm_num_blocks': (ctypes.c_int, [ctypes.c_void_p]),
     'helm_num_points': (ctypes.c_longlong, [ctypes.c_void_p]),
     'helm_get_diagonals': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),

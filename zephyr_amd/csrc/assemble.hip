@@ -11,19 +11,12 @@
 // Also here: what is derived from the planes or the model once per operator -- the Jacobi-scaled planes (k_scale_planes), the
 // row-equilibrated coupled Eurus system (k_rowscale_system) and Gardner's density (k_gardner_rho).
 #include "helm_internal.hpp"
+#include "mz_row.hpp"
 
 namespace {
 
 __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-__host__ __device__ inline int slot(int dz, int dx) { return 3 * (dz + 1) + (dx + 1); }
-
-struct MzParams {
-    int nz, nx;
-    double dx, dz, aky;
-    cplx om;          // damped angular frequency
-    double fx, fz;    // PML factors 3 ln(1/1e-3) / (2 L^3)
-    int fs0, fs1, fs2, fs3;
-};
+__host__ __device__ inline int slot(int dz, int dx) { return mz_slot(dz, dx); }
 
 // MiniZephyr: minizephyr.py:98-133 (PML), :169-202 (buoyancy / K), :219-243 (star), :269-298 (edges)
 __global__ __launch_bounds__(256) void k_assemble_mz(MzParams P, const cplx *__restrict__ c,
@@ -36,23 +29,8 @@ __global__ __launch_bounds__(256) void k_assemble_mz(MzParams P, const cplx *__r
     if (i >= N) return;
     const int iz = (int)(i / P.nx), ix = (int)(i % P.nx);
 
-    const double ac = 0.5461, bc = 0.4539, cc = 0.6248, dc = 0.09381, ec = 0.000001297;
-    const double dxx = P.dx * P.dx, dzz = P.dz * P.dz, dxz = (dxx + dzz) / 2.0, dd = sqrt(dxz);
-    const cplx iom = cmake(-P.om.y, P.om.x);          // 1j * om
-    const cplx om2 = cmul(P.om, P.om);
-    const double aky2 = P.aky * P.aky;
-
-    const cplx c0 = c[i];
-    // PML stretch factors from the local (unpadded) velocity
-    const double dX = distx[ix], dZ = distz[iz];
-    cplx denx = cadd(cscale(cscale(c0, P.fx), dX * dX), iom);
-    cplx r1x = cdiv(iom, denx);
-    cplx X = cmul(r1x, r1x);
-    cplx px = cdiv(cmul(cscale(X, sgnx[ix]), cscale(cscale(c0, 2.0 * P.fx), dX)), denx);
-    cplx denz = cadd(cscale(cscale(c0, P.fz), dZ * dZ), iom);
-    cplx r1z = cdiv(iom, denz);
-    cplx Z = cmul(r1z, r1z);
-    cplx pz = cdiv(cmul(cscale(Z, sgnz[iz]), cscale(cscale(c0, 2.0 * P.fz), dZ)), denz);
+    // PML stretch factors from the local (unpadded) velocity (mz_row.hpp: the buoyancy derivative of survey.hip takes the same)
+    const MzRow row = mz_row_factors(P, c[i], distx[ix], sgnx[ix], distz[iz], sgnz[iz]);
 
     // neighbour properties with edge padding
     double bn[9];
@@ -67,53 +45,12 @@ __global__ __launch_bounds__(256) void k_assemble_mz(MzParams P, const cplx *__r
             const double r = rho[j];
             const cplx cj = c[j];
             bn[slot(sz, sx)] = (b0 + 1.0 / r) / 2.0;
-            cplx k = cdiv(om2, cmul(cj, cj));
-            k.x -= aky2;
+            const cplx k = mz_kappa(P, cj);
             Kn[slot(sz, sx)] = cmake(k.x / r, k.y / r);
         }
 
     cplx out[9];
-    const cplx ZpX = cadd(Z, X), ZmX = csub(Z, X), XmZ = csub(X, Z);
-    // corners
-#pragma unroll
-    for (int sz = -1; sz <= 1; sz += 2)
-#pragma unroll
-        for (int sx = -1; sx <= 1; sx += 2) {
-            const int k = slot(sz, sx);
-            cplx t = cadd(cscale(ZpX, 1.0 / (4 * dxz)),
-                          cscale(cadd(cscale(pz, (double)sz), cscale(px, (double)sx)), 1.0 / (4 * dd)));
-            out[k] = cadd(cscale(Kn[k], ec), cscale(t, bc * bn[k]));
-        }
-    // vertical neighbours
-#pragma unroll
-    for (int sz = -1; sz <= 1; sz += 2) {
-        const int k = slot(sz, 0);
-        cplx t1 = cscale(cadd(cscale(Z, 1.0 / P.dz), cscale(pz, sz / 2.0)), ac * bn[k] / P.dz);
-        cplx t2 = cscale(ZmX, bc * (bn[slot(sz, 1)] + bn[slot(sz, -1)]) / (4 * dxz));
-        out[k] = cadd(cscale(Kn[k], dc), cadd(t1, t2));
-    }
-    // horizontal neighbours
-#pragma unroll
-    for (int sx = -1; sx <= 1; sx += 2) {
-        const int k = slot(0, sx);
-        cplx t1 = cscale(cadd(cscale(X, 1.0 / P.dx), cscale(px, sx / 2.0)), ac * bn[k] / P.dx);
-        cplx t2 = cscale(XmZ, bc * (bn[slot(1, sx)] + bn[slot(-1, sx)]) / (4 * dxz));
-        out[k] = cadd(cscale(Kn[k], dc), cadd(t1, t2));
-    }
-    // centre
-    {
-        const double bW = bn[slot(0, -1)], bE = bn[slot(0, 1)], bS = bn[slot(-1, 0)], bNn = bn[slot(1, 0)];
-        const double bSW = bn[slot(-1, -1)], bNE = bn[slot(1, 1)], bSE = bn[slot(-1, 1)], bNW = bn[slot(1, -1)];
-        cplx a1 = cscale(px, (bW - bE) / (2 * P.dx));
-        cplx a2 = cscale(pz, (bS - bNn) / (2 * P.dz));
-        cplx a3 = cscale(X, (bW + bE) / dxx);
-        cplx a4 = cscale(Z, (bS + bNn) / dzz);
-        cplx aterm = csub(csub(cadd(a1, a2), a3), a4);
-        cplx b1 = cscale(cadd(cscale(cadd(px, pz), (bSW - bNE)), cscale(csub(pz, px), (bSE - bNW))), 1.0 / (4 * dd));
-        cplx b2 = cscale(cadd(X, Z), (bSW + bNE + bNW + bSE) / (4 * dxz));
-        cplx bterm = csub(b1, b2);
-        out[4] = cadd(cscale(Kn[4], cc), cadd(cscale(aterm, ac), cscale(bterm, bc)));
-    }
+    mz_star(P, row, bn, Kn, out);
 
     // boundary rows: +/- identity, write order left, right, iz=0, iz=nz-1 (later wins)
     int edge = -1;
@@ -368,13 +305,35 @@ __global__ __launch_bounds__(256) void k_gardner_rho(const cplx *__restrict__ c,
 
 }  // namespace
 
-int helm_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau, double ky, double cPML) {
-    const int nz = op->nz, nx = op->nx;
-    const long long N = op->N;
-    // omega~ = 2 pi f - i / tau      (discretization.py:38-41)
+// MzParams of a handle's grid and PML at a frequency: what k_assemble_mz is launched with
+static MzParams mz_params_at(const helm_op *op, cplx om, double ky) {
+    MzParams P;
+    P.nz = op->nz; P.nx = op->nx; P.dx = op->dx; P.dz = op->dz; P.aky = 2.0 * M_PI * ky; P.om = om;
+    const double lx = op->dx * (op->nPML - 1), lz = op->dz * (op->nPML - 1);
+    P.fx = op->pml_scale * 3.0 * log(1.0 / 1e-3) / (2.0 * lx * lx * lx);
+    P.fz = op->pml_scale * 3.0 * log(1.0 / 1e-3) / (2.0 * lz * lz * lz);
+    P.fs0 = op->fs[0]; P.fs1 = op->fs[1]; P.fs2 = op->fs[2]; P.fs3 = op->fs[3]; P.npml = op->nPML;
+    return P;
+}
+// omega~ = 2 pi f - i / tau      (discretization.py:38-41)
+static cplx mz_damped_omega(double freq_re, double freq_im, double tau) {
     const double twopi = 2.0 * M_PI;
     cplx om = cmake(twopi * freq_re, twopi * freq_im);
     if (std::isfinite(tau) && tau != 0.0) om.y -= 1.0 / tau;
+    return om;
+}
+
+// MzParams of the operator the handle holds, from the arguments its last assembly recorded
+int helm_mz_params(const helm_op *op, MzParams *P) {
+    if (!op || !P || op->variant != HELM_MINIZEPHYR || op->ny > 0 || !op->assembled || op->nPML < 2) return HELM_ERR_ARG;
+    *P = mz_params_at(op, mz_damped_omega(op->a_freq_re, op->a_freq_im, op->a_tau), op->a_ky);
+    return HELM_OK;
+}
+
+int helm_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau, double ky, double cPML) {
+    const int nz = op->nz, nx = op->nx;
+    const long long N = op->N;
+    const cplx om = mz_damped_omega(freq_re, freq_im, tau);
     const int threads = 256;
     const int blocks = (int)((N + threads - 1) / threads);
 
@@ -394,12 +353,7 @@ int helm_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau
         std::copy(distz.begin(), distz.end(), h.begin() + 2 * nx);
         std::copy(sgnz.begin(), sgnz.end(), h.begin() + 2 * nx + nz);
         HIP_TRY(op, hipMemcpyAsync(d_prof, h.data(), bytes, hipMemcpyHostToDevice, op->stream));
-        MzParams P;
-        P.nz = nz; P.nx = nx; P.dx = op->dx; P.dz = op->dz; P.aky = twopi * ky; P.om = om;
-        const double lx = op->dx * (op->nPML - 1), lz = op->dz * (op->nPML - 1);
-        P.fx = op->pml_scale * 3.0 * log(1.0 / 1e-3) / (2.0 * lx * lx * lx);
-        P.fz = op->pml_scale * 3.0 * log(1.0 / 1e-3) / (2.0 * lz * lz * lz);
-        P.fs0 = op->fs[0]; P.fs1 = op->fs[1]; P.fs2 = op->fs[2]; P.fs3 = op->fs[3];
+        const MzParams P = mz_params_at(op, om, ky);
         HELM_LAUNCH(k_assemble_mz, dim3(blocks), dim3(threads), 0, op->stream, P, op->d_c, op->d_rho,
                            d_prof, d_prof + nx, d_prof + 2 * nx, d_prof + 2 * nx + nz, op->d_C);
         HIP_TRY(op, hipGetLastError());

@@ -1,0 +1,101 @@
+// The row factors of the 2-D MiniZephyr operator, shared by its assembly (assemble.hip k_assemble_mz) and by the buoyancy derivative (survey.hip
+// k_buoyancy_planes / k_buoyancy_adjoint): what a row takes from the velocity of its own cell and from the PML alone.
+#pragma once
+#include "helm_internal.hpp"
+
+struct MzParams {
+    int nz, nx;
+    double dx, dz, aky;
+    cplx om;          // damped angular frequency
+    double fx, fz;    // PML factors 3 ln(1/1e-3) / (2 L^3)
+    int fs0, fs1, fs2, fs3;
+    int npml;         // (the profiles made in place by mz_profile_at; k_assemble_mz reads the uploaded ones)
+};
+
+// the weights of the 9-point star (minizephyr.py:205-209): stiffness a, b; mass centre c, edge d, corner e
+constexpr double MZ_WA = 0.5461, MZ_WB = 0.4539, MZ_WC = 0.6248, MZ_WD = 0.09381, MZ_WE = 0.000001297;
+
+// PML stretch factors of a row from the local (unpadded) velocity c0 and the profiles at its cell (minizephyr.py:98-133)
+struct MzRow { cplx X, Z, px, pz; };
+__device__ __forceinline__ MzRow mz_row_factors(const MzParams &P, cplx c0, double dX, double sX, double dZ, double sZ) {
+    const cplx iom = cmake(-P.om.y, P.om.x);          // 1j * om
+    MzRow r;
+    cplx denx = cadd(cscale(cscale(c0, P.fx), dX * dX), iom);
+    cplx r1x = cdiv(iom, denx);
+    r.X = cmul(r1x, r1x);
+    r.px = cdiv(cmul(cscale(r.X, sX), cscale(cscale(c0, 2.0 * P.fx), dX)), denx);
+    cplx denz = cadd(cscale(cscale(c0, P.fz), dZ * dZ), iom);
+    cplx r1z = cdiv(iom, denz);
+    r.Z = cmul(r1z, r1z);
+    r.pz = cdiv(cmul(cscale(r.Z, sZ), cscale(cscale(c0, 2.0 * P.fz), dZ)), denz);
+    return r;
+}
+
+// kappa = omega_d^2 / c^2 - ky^2 of a cell: K = kappa / rho
+__device__ __forceinline__ cplx mz_kappa(const MzParams &P, cplx cj) {
+    cplx k = cdiv(cmul(P.om, P.om), cmul(cj, cj));
+    k.x -= P.aky * P.aky;
+    return k;
+}
+
+__host__ __device__ inline int mz_slot(int dz, int dx) { return 3 * (dz + 1) + (dx + 1); }
+
+// The nine coefficients of a row (minizephyr.py:219-243) from its factors, the averaged buoyancies bn[k] = (b_i + b_(i+k)) / 2 and the mass terms
+// Kn[k] = kappa b of the neighbouring cells: linear and homogeneous in (bn, Kn), hence in the buoyancy field.  The assembly calls it with b = 1 / rho, the
+// buoyancy derivative with a perturbation of b.
+__device__ __forceinline__ void mz_star(const MzParams &P, const MzRow &row, const double (&bn)[9], const cplx (&Kn)[9], cplx (&out)[9]) {
+    const double ac = MZ_WA, bc = MZ_WB, cc = MZ_WC, dc = MZ_WD, ec = MZ_WE;
+    const double dxx = P.dx * P.dx, dzz = P.dz * P.dz, dxz = (dxx + dzz) / 2.0, dd = sqrt(dxz);
+    const cplx X = row.X, Z = row.Z, px = row.px, pz = row.pz;
+    const cplx ZpX = cadd(Z, X), ZmX = csub(Z, X), XmZ = csub(X, Z);
+    // corners
+#pragma unroll
+    for (int sz = -1; sz <= 1; sz += 2)
+#pragma unroll
+        for (int sx = -1; sx <= 1; sx += 2) {
+            const int k = mz_slot(sz, sx);
+            cplx t = cadd(cscale(ZpX, 1.0 / (4 * dxz)),
+                          cscale(cadd(cscale(pz, (double)sz), cscale(px, (double)sx)), 1.0 / (4 * dd)));
+            out[k] = cadd(cscale(Kn[k], ec), cscale(t, bc * bn[k]));
+        }
+    // vertical neighbours
+#pragma unroll
+    for (int sz = -1; sz <= 1; sz += 2) {
+        const int k = mz_slot(sz, 0);
+        cplx t1 = cscale(cadd(cscale(Z, 1.0 / P.dz), cscale(pz, sz / 2.0)), ac * bn[k] / P.dz);
+        cplx t2 = cscale(ZmX, bc * (bn[mz_slot(sz, 1)] + bn[mz_slot(sz, -1)]) / (4 * dxz));
+        out[k] = cadd(cscale(Kn[k], dc), cadd(t1, t2));
+    }
+    // horizontal neighbours
+#pragma unroll
+    for (int sx = -1; sx <= 1; sx += 2) {
+        const int k = mz_slot(0, sx);
+        cplx t1 = cscale(cadd(cscale(X, 1.0 / P.dx), cscale(px, sx / 2.0)), ac * bn[k] / P.dx);
+        cplx t2 = cscale(XmZ, bc * (bn[mz_slot(1, sx)] + bn[mz_slot(-1, sx)]) / (4 * dxz));
+        out[k] = cadd(cscale(Kn[k], dc), cadd(t1, t2));
+    }
+    // centre
+    {
+        const double bW = bn[mz_slot(0, -1)], bE = bn[mz_slot(0, 1)], bS = bn[mz_slot(-1, 0)], bNn = bn[mz_slot(1, 0)];
+        const double bSW = bn[mz_slot(-1, -1)], bNE = bn[mz_slot(1, 1)], bSE = bn[mz_slot(-1, 1)], bNW = bn[mz_slot(1, -1)];
+        cplx a1 = cscale(px, (bW - bE) / (2 * P.dx));
+        cplx a2 = cscale(pz, (bS - bNn) / (2 * P.dz));
+        cplx a3 = cscale(X, (bW + bE) / dxx);
+        cplx a4 = cscale(Z, (bS + bNn) / dzz);
+        cplx aterm = csub(csub(cadd(a1, a2), a3), a4);
+        cplx b1 = cscale(cadd(cscale(cadd(px, pz), (bSW - bNE)), cscale(csub(pz, px), (bSE - bNW))), 1.0 / (4 * dd));
+        cplx b2 = cscale(cadd(X, Z), (bSW + bNE + bNW + bSE) / (4 * dxz));
+        cplx bterm = csub(b1, b2);
+        out[4] = cadd(cscale(Kn[4], cc), cadd(cscale(aterm, ac), cscale(bterm, bc)));
+    }
+}
+
+// entry k of the 1-D PML distance and sign profiles along an axis of n cells: what mz_profiles (assemble.hip) tabulates, the same products
+__device__ __forceinline__ void mz_profile_at(int n, int npml, double h, int fs_low, int fs_high, int k, double &dist, double &sgn) {
+    const int hi = n - npml > 0 ? n - npml : 0;
+    dist = k >= hi ? (double)(k - (n - npml) + 1) * h : (k < npml ? (double)(npml - k) * h : 0.0);
+    sgn = (k < npml && !fs_low) ? 1.0 : ((k >= hi && !fs_high) ? -1.0 : 0.0);
+}
+
+// the parameters of the operator a handle holds, from what its last assembly recorded (assemble.hip)
+int helm_mz_params(const helm_op *op, MzParams *P);

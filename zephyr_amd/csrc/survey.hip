@@ -1,6 +1,7 @@
 // What a survey runs on the device besides the solves: right-hand sides from sparse sources and from residual samples, receiver sampling, the imaging
-// condition, illumination (energy), axpby, the optional complex64 store of forward wavefields, and (last section) the mass stencil of the exact Frechet
-// derivative fused into the virtual sources and the imaging sum.  Each kernel stands beside the C entry point that launches it.
+// condition, illumination (energy), axpby, the optional complex64 store of forward wavefields, the mass stencil of the exact Frechet derivative fused into
+// the virtual sources and the imaging sum, and (last section) the exact density derivative: the buoyancy map, its stencil on stored columns, the nine lag
+// products and its transpose.  Each kernel stands beside the C entry point that launches it.
 //
 // The complex64 store (zephyr_amd/fieldstore.py, config key fieldsDtype='complex64'): a wavefield column s is kept as
 // complex64 values x * 2^-e_s with ONE power-of-two scale per column, e_s the binary exponent of the column's largest component
@@ -10,6 +11,7 @@
 // forward field (FieldC128 / FieldC64 below): the complex64 entry points give the complex128 sum of the unpacked field term for term because it is the
 // same loop.
 #include "helm_internal.hpp"
+#include "mz_row.hpp"
 #include <algorithm>
 
 // what every entry point here ends on: the launch error, then the stream drained (the result is complete when the call returns)
@@ -681,5 +683,381 @@ extern "C" int helm_imaging_op_accumulate_c64_device(helm_op *op, const void *dU
     HIP_TRY(op, hipSetDevice(op->device));
     HELM_LAUNCH(k_imaging_op<FieldC64>, imaging_op_grid(op), dim3(64 * IMG_WAVES), 0, op->stream, FieldC64{(const cplxf32 *)dUF32, (const int *)dExp}, ldf, (const cplx *)dUB, ldb, nsrc,
                 (const cplx *)dW, (cplx *)dG, op->nz, op->nx);
+    return launched(op);
+}
+
+// ------------------------------------------------------------------------------------------
+// the exact density derivative of MiniZephyr: the buoyancy map L, its stencil on stored columns, the nine lag products and L^T
+// ------------------------------------------------------------------------------------------
+// Every interior row of MiniZephyr is a linear, homogeneous function of the buoyancy field b = 1 / rho (mz_row.hpp mz_star: the mass terms carry
+// kappa b of the neighbouring cell, kappa = omega_d^2 / c^2 - ky^2; every stiffness term is a row factor -- X, Z, px, pz of the row's own cell, which depend
+// on c and the PML only -- times an average (b_i + b_(i+o)) / 2), and the four boundary lines are +-identity.  So the derivative of A along a perturbation
+// db of the buoyancy is the nine planes dC = L[db], the assembly's own formulas evaluated on db with the boundary rows zero, and
+//     (dA) u = sum_k dC_k (.) shift_k(u)                                  (k_buoyancy_planes, then k_stencil_sources on the stored columns)
+//     sum_s z_s^T (dA) u_s = sum_k sum_i dC_k[i] P_k[i],   P_k[i] = sum_s z_s[i] u_s[i + off_k]     (k_lag_imaging: nine model-sized planes)
+//     g_b = L^T P                                                         (k_buoyancy_adjoint: a gather over the 3 x 3 rows around a cell)
+// HelmBaseProblem.JvecBorn / Jtvec(linearisation='operator', parameter='rho') put these together (device_survey.py); db = -v / rho^2 and g_rho = -g_b / rho^2
+// are the caller's.  Planes are [9][N] with the slot order of the operator, k = 3 (dz + 1) + (dx + 1).
+
+static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+    const uintptr_t pa = (uintptr_t)a, pb = (uintptr_t)b;
+    return pa < pb + nb && pb < pa + na;
+}
+static int mz_handle_args(helm_op *op, const char *what) {
+    if (op->variant != HELM_MINIZEPHYR || op->ny > 0) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "%s: the buoyancy derivative is that of the 2-D MiniZephyr operator", what);
+    return HELM_OK;
+}
+
+__device__ __forceinline__ MzRow mz_row_at(const MzParams &P, const cplx *__restrict__ c, int iz, int ix) {
+    double dX, sX, dZ, sZ;
+    mz_profile_at(P.nx, P.npml, P.dx, P.fs3, P.fs1, ix, dX, sX);
+    mz_profile_at(P.nz, P.npml, P.dz, P.fs0, P.fs2, iz, dZ, sZ);
+    return mz_row_factors(P, c[(long long)iz * P.nx + ix], dX, sX, dZ, sZ);
+}
+
+// dC = L[db]: one lane per cell, the assembly's star (mz_star) on the perturbation.  An interior row reads only cells inside the grid, so there is no padding.
+__global__ __launch_bounds__(256) void k_buoyancy_planes(MzParams P, const cplx *__restrict__ c, const double *__restrict__ db, cplx *__restrict__ C) {
+    const long long N = (long long)P.nz * P.nx;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const int iz = (int)(i / P.nx), ix = (int)(i % P.nx);
+    cplx out[9];
+    if (iz == 0 || iz == P.nz - 1 || ix == 0 || ix == P.nx - 1) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) out[k] = cmake(0.0, 0.0);
+    } else {
+        const MzRow row = mz_row_at(P, c, iz, ix);
+        double bn[9];
+        cplx Kn[9];
+        const double b0 = db[i];
+#pragma unroll
+        for (int sz = -1; sz <= 1; ++sz)
+#pragma unroll
+            for (int sx = -1; sx <= 1; ++sx) {
+                const long long j = i + (long long)sz * P.nx + sx;
+                const double bj = db[j];
+                const cplx k = mz_kappa(P, c[j]);
+                bn[mz_slot(sz, sx)] = (b0 + bj) / 2.0;
+                Kn[mz_slot(sz, sx)] = cmake(k.x * bj, k.y * bj);
+            }
+        mz_star(P, row, bn, Kn, out);
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) C[(long long)k * N + i] = out[k];
+}
+
+// dC[9][N] = L[db] for the operator the handle holds (its c, PML and the frequency of its last assembly): db N float64, dC 9 N complex128, boundary rows zero.
+// Returns when dC is complete.
+extern "C" int helm_buoyancy_planes_device(helm_op *op, const void *dDb, void *dC) {
+    helm_tuning_refresh();
+    if (!op || !dDb || !dC) return HELM_ERR_ARG;
+    if (int rc = mz_handle_args(op, "helm_buoyancy_planes_device")) return rc;
+    if (op->nz < 3 || op->nx < 3 || (((uintptr_t)dDb) & 7) || (((uintptr_t)dC) & 15)) return HELM_ERR_ARG;
+    if (ranges_overlap(dDb, (size_t)op->N * 8, dC, (size_t)op->N * 9 * sizeof(cplx))) return HELM_ERR_ARG;
+    MzParams P;
+    if (helm_mz_params(op, &P)) HELM_FAIL(op, HELM_ERR_STATE, "helm_buoyancy_planes_device: the handle holds no assembled operator");
+    HIP_TRY(op, hipSetDevice(op->device));
+    HELM_LAUNCH(k_buoyancy_planes, dim3((unsigned)((op->N + 255) / 256)), dim3(256), 0, op->stream, P, (const cplx *)op->d_c, (const double *)dDb, (cplx *)dC);
+    return launched(op);
+}
+
+// R[s ldr + i] = coef sum_k C_k[i] (CONJ ? conj(U[s]) : U[s])[i + off_k] for the nsrc columns, cells outside the grid contributing nothing: the walk of
+// k_virtual_sources_op (a tile of OP_TILE_X cells and OP_ROWS rows per wave, OP_UNROLL columns together, a rolling window of three rows in registers), with
+// the left and right neighbours kept apart because their coefficients differ.  The nine planes are read once per group of columns: per cell and column 16 (8)
+// bytes read and 16 written, plus 144 / OP_UNROLL.  The sum runs k = 0 .. 8: the same bits on every run.
+struct LagRow { cplx t, l, r; };
+__device__ __forceinline__ void lane_left_right(cplx t, cplx &l, cplx &r) {
+    l = cmake(__shfl_up(t.x, 1, 64), __shfl_up(t.y, 1, 64));          // (lane 0 and lane 63 are halo lanes: their l / r are never used)
+    r = cmake(__shfl_down(t.x, 1, 64), __shfl_down(t.y, 1, 64));
+}
+
+template <class F, bool CONJ>
+__global__ __launch_bounds__(256) void k_stencil_sources(F U, int nsrc, long long ldu, const cplx *__restrict__ C, cplx coef, cplx *__restrict__ R, long long ldr,
+                                                         int nz, int nx) {
+    const OpJob job(nz, nx);
+    if (!job.live) return;                                  // (a whole wave: the lane exchanges below stay complete)
+    const long long N = (long long)nz * nx;
+    const int s0 = blockIdx.y * OP_UNROLL, ncol = min(OP_UNROLL, nsrc - s0);
+    const int x = job.x;
+    typename F::raw raw[OP_UNROLL];
+    LagRow up[OP_UNROLL], mid[OP_UNROLL], dn[OP_UNROLL];
+    double sc[OP_UNROLL];
+#pragma unroll
+    for (int j = 0; j < OP_UNROLL; ++j) sc[j] = U.scale(s0 + min(j, ncol - 1));
+    auto fetch = [&](int z) {
+        const bool in = job.xin && z >= 0 && z < nz;
+        const long long i = (long long)z * nx + x;
+#pragma unroll
+        for (int j = 0; j < OP_UNROLL; ++j) raw[j] = (in && j < ncol) ? U.load((long long)(s0 + j) * ldu + i) : typename F::raw{};
+    };
+    auto make = [&](LagRow *row) {
+#pragma unroll
+        for (int j = 0; j < OP_UNROLL; ++j) {
+            cplx u = U.scaled(raw[j], sc[j]);
+            if (CONJ) u = cconj(u);
+            row[j].t = u;
+            lane_left_right(u, row[j].l, row[j].r);
+        }
+    };
+    fetch(job.z0 - 1); make(up);
+    fetch(job.z0); make(mid);
+    fetch(job.z0 + 1);
+    for (int z = job.z0; z < job.z1; ++z) {
+        make(dn);
+        if (z + 1 < job.z1) fetch(z + 2);                  // (wave-uniform)
+        if (job.store) {
+            const long long i = (long long)z * nx + x;
+            cplx ck[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) ck[k] = C[(long long)k * N + i];
+#pragma unroll
+            for (int j = 0; j < OP_UNROLL; ++j)
+                if (j < ncol) {
+                    cplx acc = cmake(0.0, 0.0);
+                    cfma(acc, ck[0], up[j].l); cfma(acc, ck[1], up[j].t); cfma(acc, ck[2], up[j].r);
+                    cfma(acc, ck[3], mid[j].l); cfma(acc, ck[4], mid[j].t); cfma(acc, ck[5], mid[j].r);
+                    cfma(acc, ck[6], dn[j].l); cfma(acc, ck[7], dn[j].t); cfma(acc, ck[8], dn[j].r);
+                    R[(long long)(s0 + j) * ldr + i] = cmul(coef, acc);
+                }
+        }
+#pragma unroll
+        for (int j = 0; j < OP_UNROLL; ++j) { up[j] = mid[j]; mid[j] = dn[j]; }
+    }
+}
+
+static int stencil_sources_args(helm_op *op, const void *dU, size_t esize, int nsrc, long long ldu, const void *dC, void *dR, long long ldr) {
+    if (!op || !dU || !dC || !dR || nsrc < 1 || nsrc > 65535 * OP_UNROLL || ldu < op->N || ldr < op->N) return HELM_ERR_ARG;
+    if (int rc = mz_handle_args(op, "helm_stencil_sources_device")) return rc;
+    const size_t rbytes = (size_t)nsrc * ldr * sizeof(cplx);
+    if (ranges_overlap(dU, (size_t)nsrc * ldu * esize, dR, rbytes) || ranges_overlap(dC, (size_t)op->N * 9 * sizeof(cplx), dR, rbytes)) return HELM_ERR_ARG;
+    return HELM_OK;
+}
+
+// R[s][i] = coef sum_k C_k[i] U[s][i + off_k] (conj != 0: conj(U[s])) for s < nsrc, i < N (the handle's nz x nx grid): U [nsrc][ldu] complex128, C [9][N]
+// complex128 (helm_buoyancy_planes_device), R [nsrc][ldr] complex128, ldu, ldr >= N.  R must not overlap U or C.  Returns when R is complete.
+extern "C" int helm_stencil_sources_device(helm_op *op, const void *dU, int nsrc, long long ldu, const void *dC, double coef_re, double coef_im, int conj,
+                                           void *dR, long long ldr) {
+    helm_tuning_refresh();
+    if (int rc = stencil_sources_args(op, dU, sizeof(cplx), nsrc, ldu, dC, dR, ldr)) return rc;
+    if ((((uintptr_t)dU) | ((uintptr_t)dC) | ((uintptr_t)dR)) & 15) return HELM_ERR_ARG;       // (16-byte loads and stores)
+    HIP_TRY(op, hipSetDevice(op->device));
+    const dim3 grid = op_grid(op, (nsrc + OP_UNROLL - 1) / OP_UNROLL);
+    const FieldC128 U{(const cplx *)dU};
+    if (conj) HELM_LAUNCH((k_stencil_sources<FieldC128, true>), grid, dim3(256), 0, op->stream, U, nsrc, ldu, (const cplx *)dC, cmake(coef_re, coef_im), (cplx *)dR, ldr, op->nz, op->nx);
+    else HELM_LAUNCH((k_stencil_sources<FieldC128, false>), grid, dim3(256), 0, op->stream, U, nsrc, ldu, (const cplx *)dC, cmake(coef_re, coef_im), (cplx *)dR, ldr, op->nz, op->nx);
+    return launched(op);
+}
+
+extern "C" int helm_stencil_sources_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ldu, const void *dC, double coef_re, double coef_im,
+                                               int conj, void *dR, long long ldr) {
+    helm_tuning_refresh();
+    if (int rc = stencil_sources_args(op, dU32, sizeof(cplxf32), nsrc, ldu, dC, dR, ldr)) return rc;
+    if (!dExp || (((uintptr_t)dU32) & 7) || (((uintptr_t)dExp) & 3) || ((((uintptr_t)dC) | ((uintptr_t)dR)) & 15)) return HELM_ERR_ARG;       // (8-byte loads of U32)
+    HIP_TRY(op, hipSetDevice(op->device));
+    const dim3 grid = op_grid(op, (nsrc + OP_UNROLL - 1) / OP_UNROLL);
+    const FieldC64 U{(const cplxf32 *)dU32, (const int *)dExp};
+    if (conj) HELM_LAUNCH((k_stencil_sources<FieldC64, true>), grid, dim3(256), 0, op->stream, U, nsrc, ldu, (const cplx *)dC, cmake(coef_re, coef_im), (cplx *)dR, ldr, op->nz, op->nx);
+    else HELM_LAUNCH((k_stencil_sources<FieldC64, false>), grid, dim3(256), 0, op->stream, U, nsrc, ldu, (const cplx *)dC, cmake(coef_re, coef_im), (cplx *)dR, ldr, op->nz, op->nx);
+    return launched(op);
+}
+
+// P_k[i] += sum_s UB[s ldb + i] UF[s ldf + i + off_k] for the nine lags k and the interior cells i (the boundary lines of P are left as they are: the rows of
+// dC are zero there; an interior cell has every neighbour inside the grid).  A workgroup of LAG_WAVES waves owns a tile of OP_TILE_X x LAG_ROWS cells.  Column s
+// goes to wave s mod LAG_WAVES, which keeps the 9 LAG_ROWS sums of its lane's cells in REGISTERS over all its columns: per column it loads the LAG_ROWS + 2 rows
+// of UF and the LAG_ROWS rows of UB at once (ten 16-byte loads in flight per lane), gets the left and right neighbours of UF from the adjacent lanes and
+// does 9 LAG_ROWS complex FMAs.  Then the waves add their sums into ONE LDS tile in wave order (36 KiB; nine accumulators per cell and wave side by side, the
+// scheme of k_imaging_op, would be 9 x 64 KiB), and wave r adds row r to P: one writer per entry, a fixed order, no atomics -- the same bits on every run.
+// Per cell and column 16 B of UB and 16 (8) B of UF, the latter times (1 + 2 / LAG_ROWS)(1 + 2 / OP_TILE_X) for the halo, which neighbouring workgroups read at the
+// same time; the nine planes of P once per call.
+constexpr int LAG_ROWS = 4;         // output rows per workgroup: 72 accumulator doubles per lane
+constexpr int LAG_WAVES = 4;        // waves per workgroup
+static_assert(LAG_ROWS <= LAG_WAVES, "wave r finishes row r");
+
+template <class F>
+__global__ __launch_bounds__(64 * LAG_WAVES) void k_lag_imaging(F UF, long long ldf, const cplx *__restrict__ UB, long long ldb, int nsrc, cplx *__restrict__ P,
+                                                                int nz, int nx) {
+    __shared__ cplx part[LAG_ROWS][9][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ntx = (nx + OP_TILE_X - 1) / OP_TILE_X;
+    const int x = (int)(blockIdx.x % ntx) * OP_TILE_X + lane - 1, z0 = (int)(blockIdx.x / ntx) * LAG_ROWS;
+    const bool xin = x >= 0 && x < nx;
+    const bool store = lane >= 1 && lane <= OP_TILE_X && x >= 1 && x <= nx - 2;
+    const long long N = (long long)nz * nx;
+    cplx acc[LAG_ROWS][9];
+#pragma unroll
+    for (int r = 0; r < LAG_ROWS; ++r)
+#pragma unroll
+        for (int k = 0; k < 9; ++k) acc[r][k] = cmake(0.0, 0.0);
+    for (int s = wave; s < nsrc; s += LAG_WAVES) {             // (wave-uniform: the lane exchanges stay complete)
+        const double sc = UF.scale(s);
+        typename F::raw rf[LAG_ROWS + 2];
+        cplx rb[LAG_ROWS];
+#pragma unroll
+        for (int r = 0; r < LAG_ROWS + 2; ++r) {
+            const int z = z0 - 1 + r;
+            rf[r] = (xin && z >= 0 && z < nz) ? UF.load((long long)s * ldf + (long long)z * nx + x) : typename F::raw{};
+        }
+#pragma unroll
+        for (int r = 0; r < LAG_ROWS; ++r) {
+            const int z = z0 + r;
+            rb[r] = (store && z >= 1 && z <= nz - 2) ? UB[(long long)s * ldb + (long long)z * nx + x] : cmake(0.0, 0.0);      // (zero off the interior: nothing is added there)
+        }
+#pragma unroll
+        for (int wr = 0; wr < LAG_ROWS + 2; ++wr) {            // row z0 - 1 + wr of UF serves the output rows wr - 2 (dz = +1), wr - 1 (dz = 0) and wr (dz = -1)
+            LagRow w;
+            w.t = UF.scaled(rf[wr], sc);
+            lane_left_right(w.t, w.l, w.r);
+#pragma unroll
+            for (int dz = -1; dz <= 1; ++dz) {
+                const int r = wr - 1 - dz;
+                if (r >= 0 && r < LAG_ROWS) {
+                    cfma(acc[r][3 * (dz + 1) + 0], rb[r], w.l);
+                    cfma(acc[r][3 * (dz + 1) + 1], rb[r], w.t);
+                    cfma(acc[r][3 * (dz + 1) + 2], rb[r], w.r);
+                }
+            }
+        }
+    }
+    for (int w = 0; w < LAG_WAVES; ++w) {
+        if (wave == w) {
+#pragma unroll
+            for (int r = 0; r < LAG_ROWS; ++r)
+#pragma unroll
+                for (int k = 0; k < 9; ++k) part[r][k][lane] = w == 0 ? acc[r][k] : cadd(part[r][k][lane], acc[r][k]);
+        }
+        __syncthreads();
+    }
+    if (wave < LAG_ROWS) {
+        const int z = z0 + wave;
+        if (store && z >= 1 && z <= nz - 2) {
+            const long long i = (long long)z * nx + x;
+#pragma unroll
+            for (int k = 0; k < 9; ++k) {
+                cplx *p = P + (long long)k * N + i;
+                *p = cadd(*p, part[wave][k][lane]);
+            }
+        }
+    }
+}
+static dim3 lag_grid(const helm_op *op) {
+    return dim3((unsigned)(((op->nx + OP_TILE_X - 1) / OP_TILE_X) * ((op->nz + LAG_ROWS - 1) / LAG_ROWS)));
+}
+
+static int lag_imaging_args(helm_op *op, const void *dUF, size_t esize, long long ldf, const void *dUB, long long ldb, int nsrc, void *dP) {
+    if (!op || !dUF || !dUB || !dP || nsrc < 1 || ldf < op->N || ldb < op->N) return HELM_ERR_ARG;
+    if (int rc = mz_handle_args(op, "helm_lag_imaging_accumulate_device")) return rc;
+    const size_t pbytes = (size_t)op->N * 9 * sizeof(cplx);
+    if (ranges_overlap(dUF, (size_t)nsrc * ldf * esize, dP, pbytes) || ranges_overlap(dUB, (size_t)nsrc * ldb * sizeof(cplx), dP, pbytes)) return HELM_ERR_ARG;
+    return HELM_OK;
+}
+
+// P[k][i] += sum_s UB[s][i] UF[s][i + off_k] for k < 9 and the interior cells i of the handle's grid: UF [nsrc][ldf], UB [nsrc][ldb], P [9][N] complex128.  P must
+// not overlap the fields.  Returns when P is complete.
+extern "C" int helm_lag_imaging_accumulate_device(helm_op *op, const void *dUF, long long ldf, const void *dUB, long long ldb, int nsrc, void *dP) {
+    helm_tuning_refresh();
+    if (int rc = lag_imaging_args(op, dUF, sizeof(cplx), ldf, dUB, ldb, nsrc, dP)) return rc;
+    if ((((uintptr_t)dUF) | ((uintptr_t)dUB) | ((uintptr_t)dP)) & 15) return HELM_ERR_ARG;
+    HIP_TRY(op, hipSetDevice(op->device));
+    HELM_LAUNCH(k_lag_imaging<FieldC128>, lag_grid(op), dim3(64 * LAG_WAVES), 0, op->stream, FieldC128{(const cplx *)dUF}, ldf, (const cplx *)dUB, ldb, nsrc, (cplx *)dP,
+                op->nz, op->nx);
+    return launched(op);
+}
+
+extern "C" int helm_lag_imaging_accumulate_c64_device(helm_op *op, const void *dUF32, const void *dExp, long long ldf, const void *dUB, long long ldb, int nsrc, void *dP) {
+    helm_tuning_refresh();
+    if (int rc = lag_imaging_args(op, dUF32, sizeof(cplxf32), ldf, dUB, ldb, nsrc, dP)) return rc;
+    if (!dExp || (((uintptr_t)dUF32) & 7) || (((uintptr_t)dExp) & 3) || ((((uintptr_t)dUB) | ((uintptr_t)dP)) & 15)) return HELM_ERR_ARG;
+    HIP_TRY(op, hipSetDevice(op->device));
+    HELM_LAUNCH(k_lag_imaging<FieldC64>, lag_grid(op), dim3(64 * LAG_WAVES), 0, op->stream, FieldC64{(const cplxf32 *)dUF32, (const int *)dExp}, ldf, (const cplx *)dUB, ldb, nsrc,
+                (cplx *)dP, op->nz, op->nx);
+    return launched(op);
+}
+
+// G[j] += w sum_(k, i) L_((k, i), j) P_k[i] (CONJ: conj(L)): the transpose of k_buoyancy_planes as a gather, one lane per cell j over the interior rows i = j - o of
+// the 3 x 3 block around it.  Row i holds b_j three ways: kappa_j b_j times the mass weight in the plane of the lag o; (b_i + b_j) / 2 in the average of that
+// lag; and, for i = j, b_i / 2 in all eight averages.  With T the row's own stiffness factors (mz_star: corners tc, verticals tv, horizontals th, the cross
+// term tzx) the coefficient of the average of lag o is
+//     Q_o = T_o (P_o - P_4)  [+ tzx (P_(sz, 0) - P_(0, sx)) for a corner o = (sz, sx)]
+// (the centre plane takes every average with the opposite sign: the stiffness rows sum to zero).  One writer per cell, a fixed order.
+struct MzStiff { cplx tv[2], th[2], tc[2][2], tzx; };
+template <bool CONJ>
+__device__ __forceinline__ MzStiff mz_stiffness(const MzParams &P, MzRow row) {
+    if (CONJ) { row.X = cconj(row.X); row.Z = cconj(row.Z); row.px = cconj(row.px); row.pz = cconj(row.pz); }
+    const double dxx = P.dx * P.dx, dzz = P.dz * P.dz, dxz = (dxx + dzz) / 2.0, dd = sqrt(dxz);
+    MzStiff t;
+    const cplx ZpX = cscale(cadd(row.Z, row.X), 1.0 / (4 * dxz));
+#pragma unroll
+    for (int a = 0; a < 2; ++a) {
+        const double sg = a ? 1.0 : -1.0;
+        t.tv[a] = cscale(cadd(cscale(row.Z, 1.0 / P.dz), cscale(row.pz, sg / 2.0)), MZ_WA / P.dz);
+        t.th[a] = cscale(cadd(cscale(row.X, 1.0 / P.dx), cscale(row.px, sg / 2.0)), MZ_WA / P.dx);
+#pragma unroll
+        for (int b = 0; b < 2; ++b) {
+            const double sx = b ? 1.0 : -1.0;
+            t.tc[a][b] = cscale(cadd(ZpX, cscale(cadd(cscale(row.pz, sg), cscale(row.px, sx)), 1.0 / (4 * dd))), MZ_WB);
+        }
+    }
+    t.tzx = cscale(csub(row.Z, row.X), MZ_WB / (4 * dxz));
+    return t;
+}
+// Q_o of row i for the lag o = (sz, sx) != (0, 0)
+__device__ __forceinline__ cplx lag_coefficient(const MzStiff &t, const cplx *__restrict__ Pl, long long N, long long i, int sz, int sx) {
+    const cplx d = csub(Pl[(long long)mz_slot(sz, sx) * N + i], Pl[4 * N + i]);
+    if (sz == 0) return cmul(t.th[(sx + 1) / 2], d);
+    if (sx == 0) return cmul(t.tv[(sz + 1) / 2], d);
+    cplx q = cmul(t.tc[(sz + 1) / 2][(sx + 1) / 2], d);
+    cfma(q, t.tzx, csub(Pl[(long long)mz_slot(sz, 0) * N + i], Pl[(long long)mz_slot(0, sx) * N + i]));
+    return q;
+}
+
+template <bool CONJ>
+__global__ __launch_bounds__(256) void k_buoyancy_adjoint(MzParams P, const cplx *__restrict__ c, const cplx *__restrict__ Pl, cplx w, cplx *__restrict__ G) {
+    const long long N = (long long)P.nz * P.nx;
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    const int jz = (int)(j / P.nx), jx = (int)(j % P.nx);
+    cplx mass = cmake(0.0, 0.0), avg = cmake(0.0, 0.0);
+#pragma unroll
+    for (int sz = -1; sz <= 1; ++sz)
+#pragma unroll
+        for (int sx = -1; sx <= 1; ++sx) {
+            const int iz = jz - sz, ix = jx - sx;                 // row i sees cell j at the lag (sz, sx)
+            if (iz < 1 || iz > P.nz - 2 || ix < 1 || ix > P.nx - 2) continue;
+            const long long i = (long long)iz * P.nx + ix;
+            const MzStiff t = mz_stiffness<CONJ>(P, mz_row_at(P, c, iz, ix));
+            const double m = (sz == 0 && sx == 0) ? MZ_WC : ((sz == 0 || sx == 0) ? MZ_WD : MZ_WE);
+            const cplx p = Pl[(long long)mz_slot(sz, sx) * N + i];
+            mass.x += m * p.x; mass.y += m * p.y;
+            if (sz == 0 && sx == 0) {
+#pragma unroll
+                for (int oz = -1; oz <= 1; ++oz)
+#pragma unroll
+                    for (int ox = -1; ox <= 1; ++ox)
+                        if (oz != 0 || ox != 0) avg = cadd(avg, lag_coefficient(t, Pl, N, i, oz, ox));
+            } else avg = cadd(avg, lag_coefficient(t, Pl, N, i, sz, sx));
+        }
+    cplx kap = mz_kappa(P, c[j]);
+    if (CONJ) kap = cconj(kap);
+    cplx sum = cscale(avg, 0.5);
+    cfma(sum, kap, mass);
+    cplx g = G[j];
+    cfma(g, w, sum);
+    G[j] = g;
+}
+
+// G[j] += w sum_(k, i) L_((k, i), j) P_k[i] for j < N (conj != 0: the conjugated coefficients), L the map of helm_buoyancy_planes_device for the operator the
+// handle holds: P [9][N] complex128 (its boundary rows are not read), G N complex128.  G must not overlap P.  Returns when G is complete.
+extern "C" int helm_buoyancy_adjoint_device(helm_op *op, const void *dP, double w_re, double w_im, int conj, void *dG) {
+    helm_tuning_refresh();
+    if (!op || !dP || !dG) return HELM_ERR_ARG;
+    if (int rc = mz_handle_args(op, "helm_buoyancy_adjoint_device")) return rc;
+    if (op->nz < 3 || op->nx < 3 || ((((uintptr_t)dP) | ((uintptr_t)dG)) & 15)) return HELM_ERR_ARG;
+    if (ranges_overlap(dP, (size_t)op->N * 9 * sizeof(cplx), dG, (size_t)op->N * sizeof(cplx))) return HELM_ERR_ARG;
+    MzParams P;
+    if (helm_mz_params(op, &P)) HELM_FAIL(op, HELM_ERR_STATE, "helm_buoyancy_adjoint_device: the handle holds no assembled operator");
+    HIP_TRY(op, hipSetDevice(op->device));
+    const dim3 grid((unsigned)((op->N + 255) / 256));
+    if (conj) HELM_LAUNCH(k_buoyancy_adjoint<true>, grid, dim3(256), 0, op->stream, P, (const cplx *)op->d_c, (const cplx *)dP, cmake(w_re, w_im), (cplx *)dG);
+    else HELM_LAUNCH(k_buoyancy_adjoint<false>, grid, dim3(256), 0, op->stream, P, (const cplx *)op->d_c, (const cplx *)dP, cmake(w_re, w_im), (cplx *)dG);
     return launched(op);
 }

@@ -17,9 +17,11 @@ The eight pipelines, one row each.  Every row is a body of its own made of the s
     dpredFromFields         stored               --                                  0                -- (sampleDevice reads the slice)     nrec x k samples per item
     bornFromFields          stored               virtual sources conj(W (.) slice)   k                sampleDevice, conjugated receivers    nrec x k samples per item
       linearisation='operator'                   coef mask M0(W (.) conj(slice))     k                sampleDevice, receivers as they are   nrec x k samples per item
+      parameter='rho'                            coef sum_k L[db]_k shift_k(conj(slice)) k            sampleDevice, receivers as they are   nrec x k samples per item
     gradient                dealt                [qf | qb]                           2k               imaging kernel, uF and uB from U      one partial G per worker
     gradientFromFields      stored               qb                                  k                imaging kernel, uF from the slice     one partial G per worker
       linearisation='operator'                   qb of R^H r                         k                imaging kernel with the mass stencil  one partial G per worker
+      parameter='rho'                            qb of R^H r                         k                lag imaging into P, then L^T P        one partial G per worker
     illumination            dealt                source or receiver columns          k                energy kernel                         one partial H per worker
     illuminationFromFields  stored               --                                  0                -- (energy kernel reads the slice)    one partial H per worker
 
@@ -542,9 +544,9 @@ def _factorBytes(op):
     return one * (len(subs) if subs is not None and not getattr(op, 'kyRelease', False) else 1)
 
 
-def _checkSecondFactorsFit(items):
+def _checkSecondFactorsFit(items, planes=0):
     """MemoryError unless every GPU has room for what a pass through the TRANSPOSED operators adds to a resident forward pass: their factors -- the factors of
-    A and of A^T are held side by side -- and the item's U and R"""
+    A and of A^T are held side by side -- and the item's U and R (planes: and that many model-sized complex128 planes, the lag products of parameter='rho')"""
     seen = set()
 
     def factors(op, c0, c1):
@@ -552,17 +554,20 @@ def _checkSecondFactorsFit(items):
         first = id(op) not in seen
         seen.add(id(op))
         return _factorBytes(op) if first and not op.factors and str(getattr(op, 'method', 'auto')).lower() in ('auto', 'direct') else 0
-    _checkItemsFit(items, held=factors, work=lambda op, c0, c1: 2 * (c1 - c0) * int(op.nrow) * 16)
+    _checkItemsFit(items, held=factors, work=lambda op, c0, c1: (2 * (c1 - c0) + planes) * int(op.nrow) * 16)
 
 
-def gradientFromFields(prob, F, qb, resid, system=None, linearisation='scaler'):
+def gradientFromFields(prob, F, qb, resid, system=None, linearisation='scaler', parameter='c'):
     """The u-given branch of Jtvec (problem.py:154-162) with the forward fields read from the store: per item only the k back-sources are made and solved
     (nsrc columns per frequency, not 2 nsrc), scaler * sum_s uF (.) uB goes into the GPU's partial gradient, and the real part of the sum is returned.
     qb None: the back-sources of a moving receiver array, made on the device from `resid` (nrec, nsrc, nfreq).  system: the wrapper whose operators
     back-propagate (default prob.system; prob.adjointSystem for Jtvec(adjoint='transpose') -- the same devices and replicas, so every item still finds
     its slice on its own GPU).  linearisation='operator' (with the transposed system, qb / resid those of R_s^H r): the same items, calls and waits with the
-    weight of `_addOperator` and k_imaging_op, the mass stencil on the back-propagated columns fused into the imaging sum."""
+    weight of `_addOperator` and k_imaging_op, the mass stencil on the back-propagated columns fused into the imaging sum.  parameter='rho': the gradient
+    with respect to the BUOYANCY, `_gradientDensityFromFields` (the caller applies d b / d rho)."""
     import torch
+    if parameter == 'rho':
+        return _gradientDensityFromFields(prob, F, qb, resid, system)
     F.checkCurrent(prob)
     sv = prob.survey
     N = prob.nrow
@@ -594,12 +599,14 @@ def gradientFromFields(prob, F, qb, resid, system=None, linearisation='scaler'):
     return _sumPartials(prob, [ws.G for ws in runOnDevices(devs, items, one) if ws.G is not None]).real
 
 
-def bornFromFields(prob, F, v, linearisation='scaler'):
+def bornFromFields(prob, F, v, linearisation='scaler', parameter='c'):
     """prob.JvecBorn(u=F): Born data (nrec, nsrc, nfreq) of the model perturbation v (N,) from forward fields already in HBM.  Per stored item
     W = v (.) gradientScaler(f) scaleTerm is made on the item's GPU (v and the model go up once per worker), the virtual-source kernel writes
     conj(W (.) slice) -- the store holds the unscaled solves, hence the scaleTerm in W -- the forward operator solves the k columns, and the samples
     through the CONJUGATED receiver CSR (row stride 0 for a fixed array, nrec for one that moves with the source) come down: nrec x k values per item.
-    linearisation='operator': `_bornOperatorFromFields`."""
+    linearisation='operator': `_bornOperatorFromFields`; with parameter='rho' (v the BUOYANCY perturbation -v_rho / rho^2): `_bornDensityFromFields`."""
+    if parameter == 'rho':
+        return _bornDensityFromFields(prob, F, v)
     if linearisation == 'operator':
         return _bornOperatorFromFields(prob, F, v)
     F.checkCurrent(prob)
@@ -662,6 +669,64 @@ def _bornOperatorFromFields(prob, F, v):
         sample(op, ifreq, c0, c1, staged, U.data_ptr())
     runOnDevices(devs, items, one)
     return data
+
+
+def _bornDensityFromFields(prob, F, db):
+    """prob.JvecBorn(u=F, linearisation='operator', parameter='rho'): the derivative of dpred along the buoyancy perturbation db (N,) float64.  The items,
+    calls and waits of `_bornOperatorFromFields` with the virtual-source step in two calls: k_buoyancy_planes makes the nine planes L_f[db] of the item's
+    frequency in the workspace (db goes up once per worker), k_stencil_sources writes R = -(1 / premul) sum_k L_f[db]_k (.) shift_k(conj(slice))."""
+    F.checkCurrent(prob)
+    data, stage, sample = _sampling(prob, F.ownedFreqs, F.scale)
+    if not F.items:
+        return data
+    db = np.ascontiguousarray(db, dtype=np.float64)
+    devs, items = _storedItems(prob.system, F)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        dev = ws.device
+        d_uF, d_exp = F.pointers(ifreq, c0)
+        staged = stage(ws, ifreq, c0, c1)
+        dbd = ws.cached(('born_db', id(db)), lambda: _lib.to_device(db, dev, np.float64), keep=db)
+        U, R, C = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni), ws.buffer('planes', 9 * Ni)
+        _lib.wait_torch_stream(dev)
+        op.buoyancyPlanesDevice(dbd.data_ptr(), C.data_ptr())
+        op.stencilSourcesDevice(d_uF, k, C.data_ptr(), -1.0 / complex(op.premul), R.data_ptr(), conj=True, d_exp=d_exp, rows=Ni)
+        op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+        sample(op, ifreq, c0, c1, staged, U.data_ptr())
+    runOnDevices(devs, items, one)
+    return data
+
+
+def _gradientDensityFromFields(prob, F, qb, resid, system):
+    """prob.Jtvec(u=F, adjoint='transpose', linearisation='operator', parameter='rho') up to d b / d rho: the gradient with respect to the buoyancy, float64
+    (N,).  The items and shared steps of `gradientFromFields` (qb / resid those of R_s^H r, `system` the transposed operators) with the imaging step in two
+    calls: k_lag_imaging adds P_k = sum_s uB_s (.) shift_k(slice_s) of the item's columns to nine planes of the workspace, zeroed per item, and
+    k_buoyancy_adjoint adds -(scaleTerm / conj(premul)) conj(L_f)^T P to the worker's partial G -- the slice and the solves are the conjugates of u^ and z,
+    so the coefficients of L are conjugated, not the fields, and the real part is taken at the end."""
+    import torch
+    F.checkCurrent(prob)
+    sv = prob.survey
+    N = prob.nrow
+    scale = F.scale
+    if not F.items:
+        return _sumPartials(prob, []).real
+    _prepareBackSources(sv, qb, F.ownedFreqs)
+    devs, items = _storedItems(prob.system if system is None else system, F)
+    _checkSecondFactorsFit(items, planes=9)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        d_uF, d_exp = F.pointers(ifreq, c0)
+        G = _partial(ws, 'G', N, torch.complex128)
+        U, R, P = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni), ws.buffer('lags', 9 * Ni)
+        _backSources(ws, sv, op, qb, resid, ifreq, c0, c1, R.data_ptr(), Ni)
+        P.zero_()
+        _lib.wait_torch_stream(ws.device)
+        op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+        op.lagImagingAccumulateDevice(d_uF, U.data_ptr(), k, P.data_ptr(), d_exp=d_exp, rows=Ni)
+        op.buoyancyAdjointDevice(P.data_ptr(), -scale / np.conj(complex(op.premul)), G.data_ptr(), conj=True)
+    return _sumPartials(prob, [ws.G for ws in runOnDevices(devs, items, one) if ws.G is not None]).real
 
 
 # ---- illumination / diagonal pseudo-Hessian ---------------------------------------------------------------------------------------------------

@@ -355,6 +355,41 @@ class BaseDiscretization(BaseModelDependent):
         _lib.check(lib.helm_imaging_op_accumulate_device(self.handle, ctypes.c_void_p(d_uf), rows, ctypes.c_void_p(d_ub), rows, int(nsrc),
                                                          ctypes.c_void_p(d_w), ctypes.c_void_p(d_g)), self.handle)
 
+    def buoyancyPlanesDevice(self, d_db, d_c):
+        """dC = L[db] on the device: the nine planes (9 nrow complex128 at d_c, boundary rows zero) of d A / d b along the buoyancy perturbation db (nrow
+        float64 at d_db) for the operator this object holds -- frechet.buoyancyPlanes.  2-D MiniZephyr operators."""
+        _lib.check(_lib.load().helm_buoyancy_planes_device(self.handle, ctypes.c_void_p(d_db), ctypes.c_void_p(d_c)), self.handle)
+
+    def stencilSourcesDevice(self, d_u, nsrc, d_c, coef, d_r, conj=True, d_exp=None, rows=None):
+        """R[s] = coef sum_k C_k (.) shift_k(conj-or-not(U[s])) on the device, the right-hand sides of JvecBorn(linearisation='operator', parameter='rho'):
+        d_c the nine planes of buoyancyPlanesDevice; the other arguments as for virtualSourcesOpDevice."""
+        lib = _lib.load()
+        rows = int(self.nrow if rows is None else rows)
+        coef = complex(coef)
+        if d_exp is not None:
+            _lib.check(lib.helm_stencil_sources_c64_device(self.handle, ctypes.c_void_p(d_u), ctypes.c_void_p(d_exp), int(nsrc), rows, ctypes.c_void_p(d_c),
+                                                           coef.real, coef.imag, 1 if conj else 0, ctypes.c_void_p(d_r), rows), self.handle)
+            return
+        _lib.check(lib.helm_stencil_sources_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), rows, ctypes.c_void_p(d_c), coef.real, coef.imag,
+                                                   1 if conj else 0, ctypes.c_void_p(d_r), rows), self.handle)
+
+    def lagImagingAccumulateDevice(self, d_uf, d_ub, nsrc, d_p, d_exp=None, rows=None):
+        """P_k += sum_s UB[s] (.) shift_k(UF[s]) on the device for the nine lags k, interior cells only: the per-source half of
+        Jtvec(linearisation='operator', parameter='rho').  d_p: 9 nrow complex128; the fields as for imagingOpAccumulateDevice."""
+        lib = _lib.load()
+        rows = int(self.nrow if rows is None else rows)
+        if d_exp is not None:
+            _lib.check(lib.helm_lag_imaging_accumulate_c64_device(self.handle, ctypes.c_void_p(d_uf), ctypes.c_void_p(d_exp), rows, ctypes.c_void_p(d_ub), rows,
+                                                                  int(nsrc), ctypes.c_void_p(d_p)), self.handle)
+            return
+        _lib.check(lib.helm_lag_imaging_accumulate_device(self.handle, ctypes.c_void_p(d_uf), rows, ctypes.c_void_p(d_ub), rows, int(nsrc),
+                                                          ctypes.c_void_p(d_p)), self.handle)
+
+    def buoyancyAdjointDevice(self, d_p, w, d_g, conj=False):
+        "G += w L^T P (conj: conj(L)^T P) on the device, frechet.buoyancyAdjoint: d_p 9 nrow complex128, d_g nrow complex128, w a complex number"
+        w = complex(w)
+        _lib.check(_lib.load().helm_buoyancy_adjoint_device(self.handle, ctypes.c_void_p(d_p), w.real, w.imag, 1 if conj else 0, ctypes.c_void_p(d_g)), self.handle)
+
     def packDevice(self, d_u, nsrc, d_out, d_exp, rows=None):
         """The complex64 store of the wavefields d_u ([nsrc][rows] complex128): d_out [nsrc][rows] complex64 values x * 2^-e_s, d_exp the nsrc int32 column
         exponents e_s (fieldstore.pack_reference states the format).  All device pointers; returns when both are complete."""

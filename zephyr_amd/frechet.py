@@ -5,7 +5,7 @@ row by the mass weights, and overwrites its boundary rows by +-identity, so
     (dA) u = mask_int (.) M0(dK (.) u),      dK = -2 omega_d^2 v / (c^3 rho)
 
 The host routes of problem.py evaluate this here; the device routes (device_survey.py) take the scalars from here and run the stencil in
-k_virtual_sources_op / k_imaging_op (csrc/survey.hip)."""
+k_virtual_sources_op / k_imaging_op (csrc/survey.hip).  The second half of the module is the derivative with respect to the density (parameter='rho')."""
 import numpy as np
 
 
@@ -44,3 +44,191 @@ def operatorWeight(op):
     om = dampedOmega(op)
     c = np.asarray(op.c, dtype=np.complex128).ravel()
     return -2.0 * om * om / (c * c * c * np.asarray(op.rho, dtype=np.float64).ravel())
+
+
+# ---- the density derivative: every interior row of MiniZephyr is linear in the buoyancy b = 1 / rho ---------------------------------------------
+# Written out from the assembly (minizephyr.py:90-243; csrc/mz_row.hpp mz_star).  With kappa = omega_d^2 / c^2 - (2 pi ky)^2 of a cell, the row factors
+# X, Z, px, pz of the row's own cell (c and the PML only) and the averages a_o = (b_i + b_(i+o)) / 2 over the eight lags o = (sz, sx), row i is
+#     corner   o:  e kappa b (i+o) + tc_o a_o                                tc_o = B ((Z + X) / (4 dxz) + (sz pz + sx px) / (4 dd))
+#     vertical o:  d kappa b (i+o) + tv_o a_o + tzx (a_(sz,1) + a_(sz,-1))   tv_o = A (Z / dz + sz pz / 2) / dz,   tzx = B (Z - X) / (4 dxz)
+#     horizontal:  d kappa b (i+o) + th_o a_o - tzx (a_(1,sx) + a_(-1,sx))   th_o = A (X / dx + sx px / 2) / dx
+#     centre:      c kappa b (i)   - sum_o t_o a_o                           (the stiffness rows sum to zero)
+# and the four boundary lines are +-identity whatever b is.  L : db -> the nine planes of d A / d b along db (`buoyancyPlanes`), L^T its plain transpose
+# (`buoyancyAdjoint`).  The device kernels k_buoyancy_planes / k_buoyancy_adjoint (csrc/survey.hip) are these two; an interior row reads only cells inside
+# the grid, so the edge padding of the assembly never enters.
+MZ_STIFF = (0.5461, 0.4539)                   # the stiffness weights A, B of the rotated and the plain star (minizephyr.py:205-206)
+LAGS = [(sz, sx) for sz in (-1, 0, 1) for sx in (-1, 0, 1)]      # slot k = 3 (sz + 1) + (sx + 1): plane k multiplies u(iz + sz, ix + sx)
+
+
+def _real(dtype):
+    return np.longdouble if np.dtype(dtype) == np.dtype(np.clongdouble) else np.float64
+
+
+def _profile(n, npml, h, fs_low, fs_high):
+    'the 1-D PML distance and sign profiles along an axis (minizephyr.py:98-118,126-127; the assignment order kept)'
+    dist, sgn = np.zeros(n), np.zeros(n)
+    dist[:npml] = np.arange(npml, 0, -1) * h
+    dist[-npml:] = np.arange(1, npml + 1, 1) * h
+    if not fs_high:
+        sgn[-npml:] = -1.0
+    if not fs_low:
+        sgn[:npml] = 1.0
+    return dist, sgn
+
+
+def rowFactors(op, dtype=np.complex128):
+    """(X, Z, px, pz, kappa) of a 2-D MiniZephyr operator, each (nz, nx): the PML stretch factors of a row from the velocity of its own cell, and
+    kappa = omega_d^2 / c^2 - (2 pi ky)^2 per cell.  dtype np.clongdouble: evaluated in 80-bit arithmetic."""
+    R = _real(dtype)
+    nz, nx, npml = int(op.nz), int(op.nx), int(op.nPML)
+    dx, dz = R(float(op.dx)), R(float(op.dz))
+    c = np.asarray(op.c).astype(dtype).reshape((nz, nx))
+    f = complex(op.freq)
+    om = 2 * R(np.pi) * (R(f.real) + dtype(1j) * R(f.imag))          # (the double pi in either arithmetic: the operator is defined with it)
+    tau = float(op.tau)
+    if np.isfinite(tau) and tau != 0.0:
+        om = om - dtype(1j) / R(tau)
+    iom = dtype(1j) * om
+    fs = tuple(bool(x) for x in op.freeSurf)
+    lx, lz = dx * (npml - 1), dz * (npml - 1)
+    fx, fz = 3 * np.log(R(1000)) / (2 * lx ** 3), 3 * np.log(R(1000)) / (2 * lz ** 3)
+    distx, sgnx = _profile(nx, npml, float(op.dx), fs[3], fs[1])
+    distz, sgnz = _profile(nz, npml, float(op.dz), fs[0], fs[2])
+    distx, sgnx, distz, sgnz = distx.astype(R)[None, :], sgnx.astype(R)[None, :], distz.astype(R)[:, None], sgnz.astype(R)[:, None]
+    denx = fx * c * distx ** 2 + iom
+    X = (iom / denx) ** 2
+    px = sgnx * X * (2 * fx * c * distx) / denx
+    denz = fz * c * distz ** 2 + iom
+    Z = (iom / denz) ** 2
+    pz = sgnz * Z * (2 * fz * c * distz) / denz
+    aky = 2 * R(np.pi) * R(float(op.ky))
+    kappa = om * om / (c * c) - aky * aky
+    return X + 0 * c, Z + 0 * c, px + 0 * c, pz + 0 * c, kappa
+
+
+def _stiffness(op, rf, magnitude=False):
+    """{lag: t_o} (nz, nx) and tzx of the header comment from the row factors.  magnitude: every term by its modulus, every difference a sum -- what bounds
+    the rounding of the evaluation per component."""
+    X, Z, px, pz = rf[:4]
+    if magnitude:
+        X, Z, px, pz = np.abs(X), np.abs(Z), np.abs(px), np.abs(pz)
+    R = X.real.dtype.type
+    A, B = R(MZ_STIFF[0]), R(MZ_STIFF[1])
+    dx, dz = R(float(op.dx)), R(float(op.dz))
+    dxz = (dx * dx + dz * dz) / 2
+    dd = np.sqrt(dxz)
+    s = (lambda v: abs(v)) if magnitude else (lambda v: v)
+    t = {}
+    for sz, sx in LAGS:
+        if sz and sx:
+            t[(sz, sx)] = B * ((Z + X) / (4 * dxz) + (s(sz) * pz + s(sx) * px) / (4 * dd))
+        elif sz:
+            t[(sz, sx)] = A * (Z / dz + s(sz) * pz / 2) / dz
+        elif sx:
+            t[(sz, sx)] = A * (X / dx + s(sx) * px / 2) / dx
+    tzx = B * ((Z + X) if magnitude else (Z - X)) / (4 * dxz)
+    return t, tzx
+
+
+def _at(a, sz, sx):
+    "a(i + o) on the grid, zero where i + o is outside: s[z, x] = a[z + sz, x + sx]"
+    nz, nx = a.shape[:2]
+    out = np.zeros_like(a)
+    out[max(0, -sz):nz - max(0, sz), max(0, -sx):nx - max(0, sx)] = a[max(0, sz):nz - max(0, -sz), max(0, sx):nx - max(0, -sx)]
+    return out
+
+
+def _interiorMask(nz, nx):
+    m = np.zeros((nz, nx), dtype=bool)
+    m[1:-1, 1:-1] = True
+    return m
+
+
+def buoyancyPlanes(op, db, dtype=np.complex128, magnitude=False):
+    """L[db]: the nine planes (9, nz, nx) of d A / d b along the real buoyancy perturbation db (N,), boundary rows zero, for the 2-D MiniZephyr operator `op`
+    (its c, PML, frequency, damping and ky; rho does not enter: A is linear in b).  magnitude: the same sum with every term replaced by its modulus."""
+    nz, nx = int(op.nz), int(op.nx)
+    R = _real(dtype)
+    rf = rowFactors(op, dtype)
+    kappa = np.abs(rf[4]) if magnitude else rf[4]
+    t, tzx = _stiffness(op, rf, magnitude)
+    b = np.asarray(db).astype(R).reshape((nz, nx))
+    if magnitude:
+        b = np.abs(b)
+    a = {o: (b + _at(b, *o)) / 2 for o in LAGS if o != (0, 0)}
+    kb = kappa * b
+    mc, md, me = [R(w) for w in MZ_MASS]
+    sgn = 1 if magnitude else -1
+    C = np.zeros((9, nz, nx), dtype=R if magnitude else dtype)
+    centre = mc * kb
+    for k, (sz, sx) in enumerate(LAGS):
+        if (sz, sx) == (0, 0):
+            continue
+        o = (sz, sx)
+        if sz and sx:
+            C[k] = me * _at(kb, sz, sx) + t[o] * a[o]
+        elif sz:
+            C[k] = md * _at(kb, sz, sx) + t[o] * a[o] + tzx * (a[(sz, 1)] + a[(sz, -1)])
+        else:
+            C[k] = md * _at(kb, sz, sx) + t[o] * a[o] + sgn * tzx * (a[(1, sx)] + a[(-1, sx)])
+        centre = centre + sgn * t[o] * a[o]
+    C[4] = centre
+    C[:, ~_interiorMask(nz, nx)] = 0
+    return C
+
+
+def buoyancyAdjoint(op, P, dtype=np.complex128, magnitude=False, conj=False):
+    """L^T P: (N,) with <L[db], P> = <db, L^T P> under the bilinear pairing sum_k sum_i (no conjugate), P (9, N) or (9, nz, nx) complex; its boundary rows
+    are not read.  conj: conj(L)^T P.  magnitude: the sum of the moduli of the terms."""
+    nz, nx = int(op.nz), int(op.nx)
+    R = _real(dtype)
+    rf = rowFactors(op, dtype)
+    if conj:
+        rf = tuple(np.conj(x) for x in rf)
+    kappa = np.abs(rf[4]) if magnitude else rf[4]
+    t, tzx = _stiffness(op, rf, magnitude)
+    Pl = np.asarray(P).astype(dtype).reshape((9, nz, nx)).copy()
+    Pl[:, ~_interiorMask(nz, nx)] = 0
+    if magnitude:
+        Pl = np.abs(Pl)
+        t = {o: v * _interiorMask(nz, nx) for o, v in t.items()}
+    slot = {o: k for k, o in enumerate(LAGS)}
+    sgn = 1 if magnitude else -1
+    mc, md, me = [R(w) for w in MZ_MASS]
+    mass = mc * Pl[4]
+    avg = np.zeros((nz, nx), dtype=Pl.dtype)
+    for o in LAGS:
+        if o == (0, 0):
+            continue
+        sz, sx = o
+        q = t[o] * (Pl[slot[o]] + sgn * Pl[4])
+        if sz and sx:
+            q = q + tzx * (Pl[slot[(sz, 0)]] + sgn * Pl[slot[(0, sx)]])
+        # row i holds (b_i + b_(i+o)) / 2: half of q stays at i, half goes to j = i + o
+        avg = avg + q / 2 + _at(q, -sz, -sx) / 2
+        mass = mass + (me if sz and sx else md) * _at(Pl[slot[o]], -sz, -sx)
+    return (avg + kappa * mass).ravel()
+
+
+def applyPlanes(C, u, nz, nx):
+    "sum_k C_k (.) u(i + off_k) column by column of u ((N,) or (N, k)), cells outside the grid contributing nothing: (dA) u for the planes C (9, nz, nx)"
+    nz, nx = int(nz), int(nx)
+    a = np.asarray(u).reshape((nz, nx) + np.shape(u)[1:])
+    Cb = np.asarray(C).reshape((9, nz, nx) + (1,) * (a.ndim - 2))
+    out = np.zeros(a.shape, dtype=np.result_type(a.dtype, Cb.dtype))
+    for k, (sz, sx) in enumerate(LAGS):
+        out = out + Cb[k] * _at(a, sz, sx)
+    return out.reshape(np.shape(u))
+
+
+def lagProducts(z, u, nz, nx):
+    """P (9, N): P_k[i] = sum_s z[i, s] u[i + off_k, s] for the nine lags, zero where i is on a boundary line (an interior i has every i + off_k inside the
+    grid).  z, u: (N, nsrc).  sum_s z_s^T (dA) u_s = sum_k sum_i C_k[i] P_k[i] for planes C with zero boundary rows."""
+    nz, nx = int(nz), int(nx)
+    za = np.asarray(z).reshape((nz, nx, -1))
+    ua = np.asarray(u).reshape((nz, nx, -1))
+    inside = _interiorMask(nz, nx)
+    P = np.zeros((9, nz, nx), dtype=np.result_type(za.dtype, ua.dtype))
+    for k, (sz, sx) in enumerate(LAGS):
+        P[k] = np.where(inside, (za * _at(ua, sz, sx)).sum(axis=2), 0)
+    return P.reshape((9, nz * nx))

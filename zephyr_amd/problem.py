@@ -30,6 +30,7 @@ from . import device_survey
 from . import _lib
 from .fieldstore import DeviceFields
 from .frechet import MZ_MASS, maskInterior, massStencil, operatorWeight      # noqa: F401 (what linearisation='operator' is made of)
+from .frechet import applyPlanes, buoyancyAdjoint, buoyancyPlanes, lagProducts      # (and what parameter='rho' is made of)
 
 EPS = 1e-15
 
@@ -239,7 +240,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         return dpert.ravel()
 
     # ---- gradient ----------------------------------------------------------------------------------------
-    def Jtvec(self, m=None, v=None, u=None, adjoint='reciprocity', linearisation='scaler'):
+    def Jtvec(self, m=None, v=None, u=None, adjoint='reciprocity', linearisation='scaler', parameter='c'):
         """FWI gradient g = sum_f scaler_f sum_s uF (.) uB  (problem.py:124-164).
 
         u is None: "mux" branch -- forward and back-propagated sources are stacked column-wise and
@@ -263,6 +264,14 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         1/2 ||dpred - dobs||^2 for v = dpred - dobs,
             g = Re sum_f W_f (.) sum_s U_s (.) M0(mask_int (.) uB_s),   W_f = 2 scaleTerm conj(omega_d^2 / premul) / (c^3 rho),
         U_s the unscaled forward solve and uB_s = conj(A_f^-T premul R_s^H v_s).  `_requireOperatorLinearisation` lists what it serves.
+
+        parameter='c' (default): all of the above.  parameter='rho' (needs linearisation='operator', hence adjoint='transpose'): the gradient with
+        respect to the density of the config at fixed c, the exact adjoint of JvecBorn(parameter='rho'), float64 (N,) in density units.  With
+        P_f,k[i] = sum_s z_s[i] u^_s[i + off_k] the nine lag products of the transposed back-propagation z_s = A_f^-T premul R_s^H v_s against the unscaled
+        forward solves (zero where i is on a boundary line), and L_f the linear map from a buoyancy field to the nine planes of the interior rows
+        (frechet.buoyancyPlanes),
+            g_b = Re sum_f -(conj(scaleTerm) / premul) L_f^T P_f,      g_rho = -g_b / rho^2.
+        m stays the velocity.  The same routes as 'c'.
         """
         self._requirePaired()
         if v is None:
@@ -270,6 +279,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if adjoint not in ('reciprocity', 'transpose'):
             raise ValueError('adjoint is %r: \'reciprocity\' or \'transpose\'' % (adjoint,))
         self._checkLinearisation(linearisation)
+        self._checkParameter(parameter, linearisation)
         if linearisation == 'operator' and adjoint != 'transpose':
             raise ValueError('linearisation=\'operator\' needs adjoint=\'transpose\': the exact derivative back-propagates through A^-T')
         self.updateModel(m)
@@ -278,7 +288,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         resid = np.asarray(v).reshape((sv.nrec, sv.nsrc, sv.nfreq))
         owned = self.ownedFreqs
         if adjoint == 'transpose':
-            return self._JtvecTranspose(resid, u, linearisation)
+            return self._JtvecTranspose(resid, u, linearisation, parameter)
         if isinstance(u, DeviceFields):
             # forward fields left in HBM by fieldsDevice(): only the back-propagation is solved, on the store's own items
             u.checkCurrent(self)
@@ -311,6 +321,19 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
     def _checkLinearisation(linearisation):
         if linearisation not in ('scaler', 'operator'):
             raise ValueError('linearisation is %r: \'scaler\' or \'operator\'' % (linearisation,))
+
+    @staticmethod
+    def _checkParameter(parameter, linearisation):
+        "parameter is 'c' or 'rho'; the density has no scaler in the reference, so 'rho' needs linearisation='operator'"
+        if parameter not in ('c', 'rho'):
+            raise ValueError('parameter is %r: \'c\' or \'rho\'' % (parameter,))
+        if parameter == 'rho' and linearisation != 'operator':
+            raise ValueError('parameter=\'rho\' needs linearisation=\'operator\': the reference has no gradient scaler for the density')
+
+    def _buoyancyChain(self):
+        "d b / d rho = -1 / rho^2 per cell, float64 (N,), at the density of the config: b = 1 / rho is what the operator is linear in"
+        rho = np.broadcast_to(np.asarray(self.systemConfig['rho'], dtype=np.float64).ravel(), (self.nrow,))       # (a scalar rho is one value for every cell)
+        return -1.0 / (rho * rho)
 
     def _requireOperatorLinearisation(self, what):
         """linearisation='operator' serves Helm2DProblem with MiniZephyr / MiniZephyrHD on a single grid and an explicit density: everything else is refused
@@ -375,10 +398,11 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         sv = self.survey
         return sv.getResidualSources(resid) if sv.mode == 'fixed' else None
 
-    def _JtvecTranspose(self, resid, u, linearisation='scaler'):
+    def _JtvecTranspose(self, resid, u, linearisation='scaler', parameter='c'):
         "Jtvec(adjoint='transpose') once the model is current and `resid` is (nrec, nsrc, nfreq)"
         self._refuseMultiscale("Jtvec(adjoint='transpose')")
         exact = linearisation == 'operator'
+        density = parameter == 'rho'
         if exact:
             self._requireOperatorLinearisation("Jtvec(linearisation='operator')")
         adj = self.adjointSystem
@@ -386,9 +410,20 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             if isinstance(F, DeviceFields):
                 if exact:
                     resid = self._hermitianResidual(resid)
+                if density:
+                    return self._buoyancyChain() * device_survey.gradientFromFields(self, F, self._deviceBackSources(resid), resid, system=adj, linearisation=linearisation,
+                                                                                    parameter='rho')
                 return device_survey.gradientFromFields(self, F, self._deviceBackSources(resid), resid, system=adj, linearisation=linearisation)
             g = np.zeros(self.nrow, dtype=np.complex128)
-            if exact:
+            if density:
+                # z_s = A^-T premul R_s^H r_s and u^_s from the scaled, conjugated arrays the solves and the host fields are; g_b = Re -(conj(st) / premul) L^T P
+                st = complex(self.system.scaleTerm)
+                qb = [q.conj() for q in self.survey.getResidualSources(np.conj(resid))]
+                for ifreq, uB in self._solveOwned(qb, adj):
+                    op = self.system.subProblems[ifreq]
+                    P = lagProducts(np.conj(np.asarray(uB) / st), np.conj(np.asarray(F[ifreq]) / st), op.nz, op.nx)
+                    g += (-np.conj(st) / complex(op.premul)) * buoyancyAdjoint(op, P)
+            elif exact:
                 # the back-sources are R_s^H r_s = conj(R_s^T conj(r_s)); the solves come back scaled (scaleTerm uB), the host fields are scaleTerm U: one
                 # scaleTerm of the product stays in the weight, the other is divided out
                 st = complex(self.system.scaleTerm)
@@ -402,9 +437,9 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
                     g += self.gradientScaler(ifreq) * (np.asarray(F[ifreq]) * uB).sum(axis=1)
         if self._sharded:
             g = parallel.allreduce_sum(g)
-        return g.real
+        return self._buoyancyChain() * g.real if density else g.real
 
-    def JvecBorn(self, m=None, v=None, u=None, linearisation='scaler'):
+    def JvecBorn(self, m=None, v=None, u=None, linearisation='scaler', parameter='c'):
         """Born data of the model perturbation v from the forward fields, the ravel of (nrec, nsrc, nfreq) complex128:
 
             dd[:, s, f] = conj(R_s) . scaleTerm S_f( conj(v (.) w_f (.) uF_s) ),   S_f q = conj(A_f^-1 premul q),  w_f = gradientScaler(f),  uF_s = scaleTerm S_f qf_s
@@ -425,25 +460,46 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         0.09381, corners 1.297e-6), mask_int zero on the four boundary lines (their rows are +-identity), omega_d = 2 pi f - i / tau.  v is real.  It is
         the exact adjoint of Jtvec(adjoint='transpose', linearisation='operator').  The dependence of the PML stretch on c is left out: the derivative is
         exact for perturbations that vanish in the absorbing layers (inside them it is the mass-term part only).  `_requireOperatorLinearisation` lists
-        what it serves."""
+        what it serves.
+
+        parameter='c' (default): all of the above.  parameter='rho' (needs linearisation='operator'): v is a density perturbation and the result is
+        d/dh dpred(c, rho + h v) at h = 0, at the rho of the config with c held fixed (m stays the velocity).  Every interior row of the operator is linear
+        in the buoyancy b = 1 / rho (mass terms and stiffness averages alike) and the PML stretch does not depend on rho, so nothing is left out: with
+        db = -v / rho^2 and L_f[db] the nine planes of frechet.buoyancyPlanes (boundary rows zero),
+
+            dd[:, s, f] = R_s . scaleTerm conj(-A_f^-1 (delta A) u^_s),   (delta A) u^ = sum_k L_f[db]_k (.) shift_k(u^)
+
+        exact everywhere, the absorbing layers and the boundary lines included.  The exact adjoint of Jtvec(..., parameter='rho'); the same routes."""
         self._requirePaired()
         if v is None:
             raise Exception('Actually, JvecBorn requires a perturbation vector')
         self._checkLinearisation(linearisation)
+        self._checkParameter(parameter, linearisation)
         self.updateModel(m)
         self._refuseMultiscale('JvecBorn')
         exact = linearisation == 'operator'
+        density = parameter == 'rho'
         if exact:
             self._requireOperatorLinearisation("JvecBorn(linearisation='operator')")
         sv = self.survey
         pert = np.asarray(v).reshape((self.nrow,))
+        if density:
+            pert = self._buoyancyChain() * np.asarray(pert, dtype=np.float64)          # (db: the operator is linear in the buoyancy)
         with self._forwardFields(u) as F:
             if isinstance(F, DeviceFields):
-                data = device_survey.bornFromFields(self, F, pert, linearisation=linearisation)
+                if density:
+                    data = device_survey.bornFromFields(self, F, pert, linearisation=linearisation, parameter='rho')
+                else:
+                    data = device_survey.bornFromFields(self, F, pert, linearisation=linearisation)
             else:
                 data = np.zeros((sv.nrec, sv.nsrc, sv.nfreq), dtype=np.complex128)
                 owned = self.ownedFreqs
-                if exact:
+                if density:
+                    st = complex(self.system.scaleTerm)
+                    subs = self.system.subProblems
+                    qv = [applyPlanes(buoyancyPlanes(subs[i], pert), np.conj(np.asarray(F[i]) / st), subs[i].nz, subs[i].nx) / -complex(subs[i].premul)
+                          if i in owned else None for i in range(sv.nfreq)]
+                elif exact:
                     # F[i] = scaleTerm conj(u^): the scaleTerm is divided out of the virtual source and comes back with the solve (_solveOwned scales)
                     st = complex(self.system.scaleTerm)
                     subs = self.system.subProblems
@@ -464,16 +520,21 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             data = parallel.allreduce_sum(data)
         return data.ravel()
 
-    def Hvec(self, m=None, v=None, u=None, weights=None, linearisation='scaler'):
+    def Hvec(self, m=None, v=None, u=None, weights=None, linearisation='scaler', parameter='c'):
         """Gauss-Newton Hessian times v: Jtvec(JvecBorn(v) (.) weights, adjoint='transpose'), float64 (N,).  Symmetric and positive semi-definite as an
         operator on real vectors, because the two halves are exact adjoints.  weights: optional, real, non-negative, the shape (or ravel) of the data.
         Both halves read the same forward fields: two solves of nsrc columns per frequency, no forward re-solve; with u None the fields are solved once
         (into HBM where the device path serves) for both halves.  Needs the factors of A and of A^T side by side (see `adjointSystem`).
-        linearisation: handed to both halves; with 'operator' this is the Gauss-Newton Hessian of 1/2 ||dpred - dobs||^2 (with 'scaler' it is not)."""
+        linearisation: handed to both halves; with 'operator' this is the Gauss-Newton Hessian of 1/2 ||dpred - dobs||^2 (with 'scaler' it is not).
+        parameter: 'c' (default), 'rho', or a pair (input, output) handed to JvecBorn and Jtvec respectively -- ('c', 'rho') takes a velocity perturbation
+        and returns the density block row of the Hessian, the transpose of ('rho', 'c').  Anything with 'rho' needs linearisation='operator'."""
         self._requirePaired()
         if v is None:
             raise Exception('Actually, Hvec requires a vector')
         self._checkLinearisation(linearisation)
+        pin, pout = parameter if isinstance(parameter, (tuple, list)) and len(parameter) == 2 else (parameter, parameter)
+        self._checkParameter(pin, linearisation)
+        self._checkParameter(pout, linearisation)
         self.updateModel(m)
         self._refuseMultiscale('Hvec')
         if linearisation == 'operator':
@@ -484,10 +545,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
                 raise ValueError('weights are real, non-negative and of the size of the data (%d)' % (self.survey.nD,))
             weights = weights.astype(np.float64).ravel()
         with self._forwardFields(u) as F:
-            d = self.JvecBorn(None, v, u=F, linearisation=linearisation)
+            d = self.JvecBorn(None, v, u=F, linearisation=linearisation, parameter=pin)
             if weights is not None:
                 d = d * weights
-            return self.Jtvec(None, d, u=F, adjoint='transpose', linearisation=linearisation)
+            return self.Jtvec(None, d, u=F, adjoint='transpose', linearisation=linearisation, parameter=pout)
 
     # ---- illumination / diagonal pseudo-Hessian ------------------------------------------------------------
     def illumination(self, m=None, u=None, kind='pseudoHessian', side='source', perFreq=False):
