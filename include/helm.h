@@ -498,6 +498,9 @@ typedef struct helm_tuning {
                                                                launching threads need) */
     int    sync_sleep_us;      /* HELM_SYNC_SLEEP_US     0     > 0: a wait of the library polls with a sleep of this many microseconds between two looks instead of the runtime's wait, which keeps a
                                                                CPU busy while it lasts (2.5 CPUs per process in the pipelined bench job): for several processes under a container CPU quota */
+    /* 2-D sparse direct path, continued (new fields join at the end: the layout of the earlier ones stays) */
+    int    nd_fused_sep;       /* HELM_ND_FUSEDSEP       1     separator levels of at most 16 unknowns per front (s + m <= 128) are factored in one kernel per level */
+    int    nd_fused_sep_min;   /* HELM_ND_FUSEDSEP_MIN   512   fewest fronts of a level for which it pays (measured) */
 } helm_tuning;
 int helm_get_tuning(helm_tuning *out);          /* the values in force now (environment applied) */
 int helm_set_tuning(const helm_tuning *t);      /* NULL: defaults + environment again */

@@ -53,7 +53,8 @@ class Tuning(ctypes.Structure):
                 ('auto_mg3', ctypes.c_int), ('prof_ext', ctypes.c_int), ('ws_slots', ctypes.c_int), ('pf_prio', ctypes.c_int),
                 ('mg3_keep', ctypes.c_int), ('mg3_keep_levels', ctypes.c_int), ('mg3_galerkin', ctypes.c_int), ('mg3_depth_model', ctypes.c_int),
                 ('mg3_bt_f32', ctypes.c_int), ('mg3_otf', ctypes.c_int), ('mg3_f32', ctypes.c_int), ('mg3_omega', ctypes.c_double),
-                ('mg3_coarse', ctypes.c_int), ('mg3_nd_leaf', ctypes.c_int), ('mg3_bt_twist', ctypes.c_int), ('mg3_beta', ctypes.c_double), ('sync_spin_ms', ctypes.c_double), ('sync_sleep_us', ctypes.c_int)]
+                ('mg3_coarse', ctypes.c_int), ('mg3_nd_leaf', ctypes.c_int), ('mg3_bt_twist', ctypes.c_int), ('mg3_beta', ctypes.c_double), ('sync_spin_ms', ctypes.c_double), ('sync_sleep_us', ctypes.c_int),
+                ('nd_fused_sep', ctypes.c_int), ('nd_fused_sep_min', ctypes.c_int)]
 
 
 class RuntimeStats(ctypes.Structure):

@@ -705,6 +705,35 @@ int factor_group_set(helm_op *op, const FacSet &S, size_t gi, cplx *arenaF, cplx
     const bool packs = P.dof <= 2 ? (nmax < (1 << 14) && P.nz < 65536 && P.nx < 32768) : (nmax < 65535 && P.nz < 4096 && P.nx < 4096 && P.dof < 128);
     if ((size_t)nmax * sizeof(int2) <= 64 * 1024 && packs)
         schur_gather = !g.leaf && g.mmax > 0 && P.dof == 1;
+    // (wider pivot windows -- 64-wide base blocks for the leaves, the upper levels or the tree top -- were measured in round 2 and do not move the
+    // first-pass residual: it is not a pivoting artefact but near-resonant subdomains, which the NdStable treatment below handles)
+    const int stable_smax = 128;      // larger fronts are left alone: the one-workgroup LU would cost more than the refinement pass it saves, none that large has been seen ill-conditioned
+    // (leaves are not watched: 20-40 typically, below 6e3 in every operator examined, and their level is the one where two more passes over
+    // every front cost something)
+    const bool watch = stable_enabled(P) && !g.leaf && g.mmax > 0 && g.smax <= std::min(stable_smax, LUS_NMAX) && ensure_est(op, f0, std::min(stable_smax, LUS_NMAX)) == HELM_OK;
+    double *est = watch ? f0->d_est : nullptr;
+    double *est_rows = watch ? est + est_rows_off(P, nf) : nullptr;
+    // separator fronts of at most 16 unknowns (the three levels above the leaves at 1024^2): the whole elimination of the level in one kernel
+    // (k_sep_factor_small, nd_leaf.hip; HELM_ND_FUSEDSEP=0: the batched path below).  Like the leaf kernel it is a chain of latencies per front, which
+    // thousands of fronts in flight hide and a few hundred do not: HELM_ND_FUSEDSEP_MIN.
+    // (the kernel addresses the coefficient planes by 32-bit byte offsets: nine planes of 16-byte entries below 4 GB)
+    if (schur_gather && tune.nd_fused_sep && g.smax <= 16 && nmax <= 128 && g.cnt >= tune.nd_fused_sep_min && (long long)nbatch <= 0x7fffffffLL &&
+        (long long)P.nz * P.nx * 9 * (long long)sizeof(cplx) < (1LL << 32)) {
+        NdPlanesSet ps; for (int k = 0; k < ND_NF_MAX; ++k) ps.p[k] = S.planes[k < nf ? k : 0];
+        {
+            // booked with the products (mode 7): the two products' flops; every entry of the front gathered once (F11, F12, F21: three terms at most, about
+            // half of the ring x ring block has a child's entry), the factors, G21 and the Schur complement written once
+            const double sm = (double)g.smax * g.mmax, mm = (double)g.mmax * g.mmax;
+            const bool ext = op && op->profiling && tune.prof_ext != 0;
+            ExtArm arm(op, ext, 8.0 * (sm * g.smax + mm * g.smax) * nbatch, 16.0 * (2.0 * (double)g.smax * nmax + 2.0 * sm + 1.5 * mm) * nbatch, g.mmax, g.mmax, g.smax, nbatch, 7);
+            launch_sep_factor_small(st, g.smax, nbatch, d_nodes, g.first, arenaF, f0->d_fac, G21, ps, P.nz, P.nx, nf, est, est_rows, (long long)nbatch, op->transposed ? 1 : 0);
+        }
+        if (watch) for (int k = 0; k < nf; ++k) { const int rcf = flag_group(op, S.f[k], gi, est, S.rtol[k]); if (rcf) return rcf; }
+        for (int k = 0; k < nf; ++k)
+            S.f[k]->flops += (double)g.cnt * 8.0 * (2.0 * g.smax * g.smax * g.smax + (double)g.smax * g.smax * g.mmax + (double)g.smax * g.mmax * g.mmax);
+        if (watch) for (int k = 0; k < nf; ++k) { const int rcs = stabilise_group(op, S.f[k], gi, arenaF, work, S.planes[k], est); if (rcs) return rcs; }
+        return HELM_OK;
+    }
     if ((size_t)nmax * sizeof(int2) <= 64 * 1024 && packs) {      // (its row table must fit the 64 KB of LDS a launch gets by default: larger fronts take the unfused path)
         // rows per workgroup: whole fronts while there are thousands of them, a few rows each for the handful of big ones at the top
         const int want = std::max(1, 2048 / g.cnt);
@@ -739,14 +768,6 @@ int factor_group_set(helm_op *op, const FacSet &S, size_t gi, cplx *arenaF, cplx
                 }
         }
     }
-    // (wider pivot windows -- 64-wide base blocks for the leaves, the upper levels or the tree top -- were measured in round 2 and do not move the
-    // first-pass residual: it is not a pivoting artefact but near-resonant subdomains, which the NdStable treatment below handles)
-    const int stable_smax = 128;      // larger fronts are left alone: the one-workgroup LU would cost more than the refinement pass it saves, none that large has been seen ill-conditioned
-    // (leaves are not watched: 20-40 typically, below 6e3 in every operator examined, and their level is the one where two more passes over
-    // every front cost something)
-    const bool watch = stable_enabled(P) && !g.leaf && g.mmax > 0 && g.smax <= std::min(stable_smax, LUS_NMAX) && ensure_est(op, f0, std::min(stable_smax, LUS_NMAX)) == HELM_OK;
-    double *est = watch ? f0->d_est : nullptr;
-    double *est_rows = watch ? est + est_rows_off(P, nf) : nullptr;
     if (watch) for (int b0 = 0; b0 < nbatch; b0 += 65535 / nf * nf)
         HELM_LAUNCH(k_front_cond<0>, dim3(std::min(65535 / nf * nf, nbatch - b0)), dim3(256), 0, st, Finv + (long long)b0 * s1, nmax, s1, d_nodes + g.first + b0 / nf, est + b0,
                            est_rows + (long long)b0 * g.smax, g.smax, nf, op->transposed ? 1 : 0);

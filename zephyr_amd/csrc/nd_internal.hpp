@@ -237,6 +237,9 @@ void launch_zgemm3_la(hipStream_t st, bool latency_tile, int nb, int M, int Nn, 
 // the leaf level of the factorisation in one kernel (+ the pivoted re-elimination of the leaves it flags)
 void launch_leaf_factor(hipStream_t st, int smax, int nb, const NdDev *d_nodes, int first, cplx *arenaF, cplx *fac, cplx *g21b, const cplx *planes, int nz, int nx, int *flags, int dbg,
                         int nf = 1, int kf = 0);
+// a level of small separator fronts (smax <= 16, smax + mmax <= 128) eliminated in one kernel: gather, condition estimates, inverse, G21, Schur complement
+void launch_sep_factor_small(hipStream_t st, int smax, int nb, const NdDev *d_nodes, int first, cplx *arenaF, cplx *fac, cplx *g21b, const NdPlanesSet &ps, int nz, int nx, int nf,
+                             double *est, double *est_rows, long long nbatch_all, int tr);
 // ---- nd_factor.hip ----
 struct FacSet { int nf = 1; NdFactor *f[ND_NF_MAX] = {nullptr, nullptr, nullptr, nullptr}; const cplx *planes[ND_NF_MAX] = {nullptr, nullptr, nullptr, nullptr}; double rtol[ND_NF_MAX] = {0, 0, 0, 0}; };
 int factor_prologue(helm_op *op, int block, NdFactor *f, const cplx *planes_in, const cplx **planes);

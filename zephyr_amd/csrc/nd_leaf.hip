@@ -1,5 +1,6 @@
-// Direct solver, leaf level of the factorisation in one kernel.
+// Direct solver, the bottom of the factorisation in one kernel per level: the leaves, and the small separator fronts just above them.
 #include "nd_internal.hpp"
+#include "nd_gj32w.hpp"
 
 namespace {
 
@@ -285,7 +286,291 @@ __global__ __launch_bounds__(256) void k_leaf_factor_pivoted(const NdDev *nodes,
     }
 }
 
+// ---- the small separator levels of the factorisation in one kernel each ------------------------------------------------------------------------
+// The three levels above the leaves (8 or 16 separator cells, rings of 48-96 at 1024^2) went through seven launches apiece -- build, two condition
+// estimates, the one-wave inverse, two products with an inner dimension of 8 or 16 -- each of which filled the chip and moved the front through HBM
+// again.  Here a workgroup of four waves takes one (front, frequency) from the coefficient planes and the children's Schur complements to its
+// factors and its own Schur complement:
+//   1. [F11 | F12] (smax rows of smax + mmax) is gathered into LDS with k_nd_build_front's maps, sum order and padding, every load of a pass issued
+//      before the first is used (a term that is not there loads its base's first element and is zeroed when it is used: no load is branched around);
+//   2. the condition estimates of a watched group are formed of the block in LDS exactly as k_front_cond<0> / <1> form them of the one in HBM;
+//   3. wave 0 inverts F11 in registers (gj32w_core) while the other waves gather their first 16 ring rows of F21 -- as matrix-core operands, straight
+//      into registers: F21 never exists as a block;
+//   4. both products run TRANSPOSED on the matrix cores, G21^T = F11^-T F21^T and S^T = C^T - F12^T G21^T, 16 ring rows per wave at a time: the
+//      accumulator layout of the first (lane: ring row l & 15, k = (l >> 4) + 4 q) is the B-operand layout of the second, register q = k group q,
+//      so G21 goes from one product to the next without leaving the registers.  Term by term these are the products of zgemm3_body -- the same
+//      four real instructions per k group in the same order on accumulators kept apart, the two factors of every multiplication exchanged;
+//   5. [F11^-1 | F12], G21 and S are stored where the batched path leaves them; [F21 | .] of the arena is not written (nobody reads it: the parent
+//      takes S, and the re-elimination of a flagged front builds the whole front again from the children).
+// SP: smax padded to the matrix cores' k groups (8 or 16).  LDS: 16 (SP = 8) or 32 KB of front, the inverse once more in fragment order (2 / 4 KB), 4 KB of tables:
+// 22 / 40 KB, four workgroups per compute unit; 115 registers, four waves per SIMD.  Variants measured and not kept: HISTORY.md.
+static __device__ cplx g_sep_zero[4];        // stands in for the Schur complement of a child that is not there
+
+// k_front_cond<AFTER> (nd_factor.hip) of an n x n block held in LDS: the same sums in the same order, so that the lists of flagged fronts come out the same
+template <int AFTER>
+__device__ __forceinline__ void sep_cond(const cplx *M, int ld, int n, int tr, double *dsh, unsigned char *lone, double *wsh, double *red, double *out, double *wglob, int tid) {
+    const int lane = tid & 63, wv = tid >> 6;
+    double best = 0.0;
+    if (tr) {
+        const int j = tid;
+        if (j < n) {
+            double v = 0.0, off = 0.0;
+            for (int i = 0; i < n; ++i) {
+                const cplx a = M[i * ld + j];
+                const double m = fabs(a.x) + fabs(a.y);
+                v += AFTER ? m * wsh[i] : m;
+                if (!AFTER && i != j) off += m;
+            }
+            if (!AFTER) { dsh[j] = v; lone[j] = off == 0.0; }
+            best = v;
+        }
+        if (AFTER) for (int o = 32; o > 0; o >>= 1) best = fmax(best, __shfl_down(best, o));
+    } else
+    for (int i = wv; i < n; i += 4) {
+        double v = 0.0, off = 0.0;
+        for (int j = lane; j < n; j += 64) {
+            const cplx a = M[i * ld + j];
+            const double m = fabs(a.x) + fabs(a.y);
+            v += AFTER ? m * wsh[j] : m;
+            if (!AFTER && j != i) off += m;
+        }
+        for (int o = 32; o > 0; o >>= 1) { v += __shfl_down(v, o); if (!AFTER) off += __shfl_down(off, o); }
+        v = __shfl(v, 0);
+        if (!AFTER && lane == 0) { dsh[i] = v; lone[i] = off == 0.0; }
+        best = fmax(best, v);
+    }
+    if (!AFTER) {
+        __syncthreads();
+        double a = 0.0, any = 0.0;
+        for (int i = 0; i < n; ++i) { any = fmax(any, dsh[i]); if (!lone[i]) a = fmax(a, dsh[i]); }
+        if (!(a > 0.0)) a = any > 0.0 ? any : 1.0;
+        if (tid < n) { const double w = lone[tid] ? dsh[tid] / a : 1.0; wsh[tid] = w; wglob[tid] = w; }
+        if (tid == 0) *out = a;
+        __syncthreads();
+        return;
+    }
+    if (lane == 0) red[wv] = best;
+    __syncthreads();
+    if (tid == 0) *out = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+
+template <int SP>
+__global__ __launch_bounds__(256, 4) void k_sep_factor_small(const NdDev *nodes, int first, cplx *arenaF, cplx *fac, cplx *g21base, NdPlanesSet pset, int nz, int nx, int nf,
+                                                             double *est, double *est_rows, long long nbatch, int tr) {
+    constexpr int KG = SP / 4;
+    __shared__ cplx FS[SP * 128];            // [F11 | F12], rows of smax + mmax <= 128: the image of the front's slot in the factor storage
+    __shared__ int4 finfo[128];              // per padded front row: cell (z, x; z = -1: padding), position on child 0's / child 1's ring (-1: not there)
+    __shared__ Gj32w GS;
+    __shared__ cplx FI[KG * 64];             // F11^-1 once more, in the order the first product reads it: lane l of k group g at g * 64 + l (zero on the padding)
+    __shared__ double dsh[16], wsh[16], red[4];
+    __shared__ unsigned char lone[16];
+    const long long b = blockIdx.x;          // batch index = front * nf + frequency
+    const int front = (int)(b / nf), kf = (int)(b - (long long)front * nf);
+    const cplx *planes = pset.p[kf];
+    const NdDev n = nodes[first + front];
+    const int smax = n.smax, mmax = n.mmax, nmax = smax + mmax;
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, lr = lane & 15, lq = lane >> 4;      // (wave: uniform, in a scalar register)
+    const long long N = (long long)nz * nx;
+    const int ns = n.s;
+    // per padded front row: its cell, then its position on each child's ring (the children's records one after the other: three records at once do not fit
+    // the scalar registers; a thread looks after the same rows in every pass, so no barrier between them)
+    for (int r = tid; r < nmax; r += 256) {
+        int a = -1;
+        if (r < n.s) a = r;
+        else if (r >= smax && r - smax < n.m) a = n.s + r - smax;
+        int4 e = make_int4(-1, 0, -1, -1);
+        if (a >= 0) nd_cell(n, a, e.x, e.y);
+        finfo[r] = e;
+    }
+    const cplx *S0 = g_sep_zero, *S1 = g_sep_zero;           // the children's Schur complements (this frequency's), row lengths ld0 / ld1
+    int ld0 = 0, ld1 = 0;
+    #pragma unroll
+    for (int slot = 0; slot < 2; ++slot) {
+        if (n.kid[slot] < 0) continue;
+        const NdDev c = nodes[n.kid[slot]];
+        const int ldc = c.smax + c.mmax;
+        const cplx *Sc = arenaF + (long long)nf * c.foff + (long long)kf * c.mmax * ldc + c.smax;
+        if (slot == 0) { S0 = Sc; ld0 = ldc; } else { S1 = Sc; ld1 = ldc; }
+        for (int r = tid; r < nmax; r += 256) {
+            const int4 e = finfo[r];
+            if (e.x < 0) continue;
+            const int la = nd_local(c, nz, nx, e.x, e.y);
+            if (la >= c.s) { if (slot == 0) finfo[r].z = la - c.s; else finfo[r].w = la - c.s; }
+        }
+    }
+    const long long finv_off = n.finv_off, foff = n.foff;
+    __syncthreads();
+    // The three terms of front entry (r, c) -- stencil coefficient, child 0's and child 1's Schur-complement entry, summed in that order (k_nd_build_front) -- as
+    // byte offsets from three bases that sit in scalar registers (the planes, the children's blocks; 32 bits: the caller checks that the planes stay below 4 GB).
+    // A term that is not there loads its base's first element and is set to zero when it is used (mask bit t: term t is there; bit 3: an identity entry of the
+    // padding): no load is branched around, so that all loads of a pass are in flight together.
+    auto addr = [&](int r, int c, bool ok, unsigned (&o)[3]) -> unsigned {
+        o[0] = 0u; o[1] = 0u; o[2] = 0u;
+        if (!ok) return 0u;
+        const int4 ia = finfo[r], ib = finfo[c];
+        if (ia.x < 0 || ib.x < 0) return (r == c && r < smax) ? 8u : 0u;
+        unsigned m = 0u;
+        if (r < smax || c < smax) {              // ring x ring entries belong to an ancestor
+            const int dz = ib.x - ia.x, dx = ib.y - ia.y;
+            if (dz >= -1 && dz <= 1 && dx >= -1 && dx <= 1) { o[0] = (unsigned)(((dz + 1) * 3 + dx + 1) * (int)N + ia.x * nx + ia.y) * 16u; m |= 1u; }
+        }
+        if (ia.z >= 0 && ib.z >= 0) { o[1] = (unsigned)(ia.z * ld0 + ib.z) * 16u; m |= 2u; }
+        if (ia.w >= 0 && ib.w >= 0) { o[2] = (unsigned)(ia.w * ld1 + ib.w) * 16u; m |= 4u; }
+        return m;
+    };
+    auto at = [](const cplx *base, unsigned off) -> cplx { return *reinterpret_cast<const cplx *>(reinterpret_cast<const char *>(base) + off); };
+    auto entry = [](unsigned m, cplx v0, cplx v1, cplx v2) -> cplx {
+        const cplx z = cmake(0.0, 0.0);
+        return (m & 8u) ? cmake(1.0, 0.0) : cadd(cadd((m & 1u) ? v0 : z, (m & 2u) ? v1 : z), (m & 4u) ? v2 : z);
+    };
+    // ---- 1. [F11 | F12] into LDS, four entries (twelve loads) per thread in flight
+    const int tot = smax * nmax;
+    for (int e0 = 0; e0 < tot; e0 += 1024) {
+        unsigned o[4][3], m[4];
+        #pragma unroll
+        for (int u = 0; u < 4; ++u) { const int e = e0 + u * 256 + tid; const int r = e / nmax; m[u] = addr(r, e - r * nmax, e < tot, o[u]); }
+        cplx v[4][3];
+        #pragma unroll
+        for (int u = 0; u < 4; ++u) { v[u][0] = at(planes, o[u][0]); v[u][1] = at(S0, o[u][1]); v[u][2] = at(S1, o[u][2]); }
+        #pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int e = e0 + u * 256 + tid;
+            if (e < tot) FS[e] = entry(m[u], v[u][0], v[u][1], v[u][2]);
+        }
+    }
+    __syncthreads();
+    // ---- 2. condition estimate, before the inversion
+    if (est) sep_cond<0>(FS, nmax, ns, tr, dsh, lone, wsh, red, est + b, est_rows + b * smax, tid);
+    // 16 ring rows of F21 as the B operand of the transposed first product: lane (lq, lr) holds F21[16 rb + lr][4 g + lq], g = 0 .. KG - 1
+    auto gather_f21 = [&](int rb, int lr, int lq, cplx (&f)[KG]) {
+        unsigned o[KG][3], m[KG];
+        const int rr = 16 * rb + lr;
+        #pragma unroll
+        for (int g = 0; g < KG; ++g) { const int j = 4 * g + lq; m[g] = addr(smax + rr, j, rr < mmax && j < smax, o[g]); }
+        cplx v[KG][3];
+        #pragma unroll
+        for (int g = 0; g < KG; ++g) { v[g][0] = at(planes, o[g][0]); v[g][1] = at(S0, o[g][1]); v[g][2] = at(S1, o[g][2]); }
+        #pragma unroll
+        for (int g = 0; g < KG; ++g) f[g] = entry(m[g], v[g][0], v[g][1], v[g][2]);
+    };
+    // ---- 3. F11 -> F11^-1 in place (wave 0, as k_gj32w_inverse does it); the other waves fetch their first block of F21 meanwhile
+    if (wave == 0) {
+        const int r = lane & 31, h = lane >> 5;
+        cplx a[16];
+        #pragma unroll
+        for (int c = 0; c < 16; ++c) {
+            const int j = 16 * h + c;
+            const bool in = r < smax && j < smax;
+            const cplx v = FS[in ? r * nmax + j : 0];
+            a[c] = in ? v : cmake(r == j ? 1.0 : 0.0, 0.0);
+        }
+        gj32w_core(a, GS, smax, r, h);
+        // inv[i][sigma(kcol)] = R[sigma(i)][kcol]: this lane holds storage row r = sigma(i), i.e. output row i = sinv[r]
+        if (r < smax) {
+            const int i = GS.sinv[r] & 31;
+            #pragma unroll
+            for (int c = 0; c < 16; ++c) {
+                const int kcol = 16 * h + c;
+                const int col = GS.sigma[kcol & 31] & 31;
+                if (kcol < smax && i < smax && col < smax) FS[i * nmax + col] = a[c];
+            }
+        }
+    }
+    __syncthreads();
+    if (est) sep_cond<1>(FS, nmax, ns, tr, dsh, lone, wsh, red, est + nbatch + b, est_rows + b * smax, tid);
+    // ---- 5a. [F11^-1 | F12] where the passes look for it
+    {
+        cplx *Fout = fac + (long long)nf * finv_off + (long long)kf * smax * nmax;
+        for (int e = tid; e < tot; e += 256) Fout[e] = FS[e];
+        for (int e = tid; e < KG * 64; e += 256) {
+            const int j = 4 * (e >> 6) + ((e & 63) >> 4), k = e & 15;
+            const bool in = j < smax && k < smax;
+            const cplx v = FS[in ? j * nmax + k : 0];                                 // F11^-1[j][k]
+            FI[e] = in ? v : cmake(0.0, 0.0);
+        }
+    }
+    __syncthreads();
+    // ---- 4. the two products, 16 ring rows per wave at a time
+    cplx *G21 = g21base + b * mmax * smax;
+    cplx *S = arenaF + (long long)nf * foff + (long long)kf * mmax * nmax + smax;
+    const int nblk = (mmax + 15) >> 4;
+    const cplx mone = cmake(-1.0, 0.0);
+    for (int rb = wave; rb < nblk; rb += 4) {
+        cplx f21[KG];
+        gather_f21(rb, lr, lq, f21);
+        const int rr = 16 * rb + lr;                                                   // this lane's ring row in both accumulators
+        const bool rok = rr < mmax;
+        // G21^T = F11^-T F21^T: lane holds G21[rr][lq + 4 q] in (gr[q], gi[q])
+        v4f64 gr = (v4f64){0, 0, 0, 0}, gi = (v4f64){0, 0, 0, 0};
+        #pragma unroll
+        for (int g = 0; g < KG; ++g) {
+            const cplx fv = FI[g * 64 + lane];                                      // F11^-1[4 g + lq][k = lr]
+            const cplx a = f21[g];
+            gr = __builtin_amdgcn_mfma_f64_16x16x4f64(fv.x, a.x, gr, 0, 0, 0);
+            gi = __builtin_amdgcn_mfma_f64_16x16x4f64(fv.y, a.x, gi, 0, 0, 0);
+            gr = __builtin_amdgcn_mfma_f64_16x16x4f64(fv.y, -a.y, gr, 0, 0, 0);
+            gi = __builtin_amdgcn_mfma_f64_16x16x4f64(fv.x, a.y, gi, 0, 0, 0);
+        }
+        #pragma unroll
+        for (int q = 0; q < KG; ++q) {
+            const int k = lq + 4 * q;
+            if (rok && k < smax) G21[(long long)rr * smax + k] = cmake(gr[q], gi[q]);
+        }
+        const int4 er = finfo[smax + (rok ? rr : 0)];
+        // the children's entries of S[rr][16 cb + lq + 4 q], q = 0 .. 3: eight loads, none waited for here.  A masked entry loads the block's first element and is
+        // set to zero when it is used (bit q / 4 + q of the mask: child 0 / 1 has the entry) -- no branch around a load, and every address is the child's base in
+        // scalar registers plus a 32-bit offset
+        auto load_cv = [&](int cb, cplx (&c0)[4], cplx (&c1)[4]) -> unsigned {
+            unsigned mask = 0;
+            #pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = 16 * cb + lq + 4 * q;
+                const bool ok = rok && c < mmax;
+                const int4 ec = finfo[smax + (ok ? c : 0)];
+                const bool ok0 = ok && er.z >= 0 && ec.z >= 0, ok1 = ok && er.w >= 0 && ec.w >= 0;
+                const unsigned o0 = ok0 ? (unsigned)(er.z * ld0 + ec.z) * 16u : 0u, o1 = ok1 ? (unsigned)(er.w * ld1 + ec.w) * 16u : 0u;
+                c0[q] = at(S0, o0);
+                c1[q] = at(S1, o1);
+                mask |= (ok0 ? 1u : 0u) << q | (ok1 ? 16u : 0u) << q;
+            }
+            return mask;
+        };
+        for (int cb = 0; cb < nblk; ++cb) {
+            cplx nx0[4], nx1[4];
+            const unsigned nmask = load_cv(cb, nx0, nx1);
+            v4f64 sr = (v4f64){0, 0, 0, 0}, si = (v4f64){0, 0, 0, 0};
+            #pragma unroll
+            for (int g = 0; g < KG; ++g) {
+                const int k = 4 * g + lq, cc = 16 * cb + lr;
+                const bool in = k < smax && cc < mmax;
+                cplx fb = FS[in ? k * nmax + smax + cc : 0];                         // F12[k][cc]
+                if (!in) fb = cmake(0.0, 0.0);
+                const double ar = gr[g], ai = gi[g];                                // G21[rr][4 g + lq]
+                sr = __builtin_amdgcn_mfma_f64_16x16x4f64(fb.x, ar, sr, 0, 0, 0);
+                si = __builtin_amdgcn_mfma_f64_16x16x4f64(fb.y, ar, si, 0, 0, 0);
+                sr = __builtin_amdgcn_mfma_f64_16x16x4f64(fb.y, -ai, sr, 0, 0, 0);
+                si = __builtin_amdgcn_mfma_f64_16x16x4f64(fb.x, ai, si, 0, 0, 0);
+            }
+            #pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int c = 16 * cb + lq + 4 * q;
+                const cplx cv = cadd((nmask >> q) & 1u ? nx0[q] : cmake(0.0, 0.0), (nmask >> (4 + q)) & 1u ? nx1[q] : cmake(0.0, 0.0));
+                if (rok && c < mmax) S[(long long)rr * nmax + c] = cadd(cv, cmul(mone, cmake(sr[q], si[q])));
+            }
+        }
+    }
+}
+
 }  // namespace
+
+// the whole elimination of nbatch = fronts x frequencies small separator fronts of one level (smax <= 16, smax + mmax <= 128, one unknown per cell);
+// est / est_rows: where k_front_cond would leave the condition estimates of a watched group (null: not watched), nbatch_all: the group's batch (the
+// second estimate lies that far behind the first), tr: a transposed handle
+void launch_sep_factor_small(hipStream_t st, int smax, int nb, const NdDev *d_nodes, int first, cplx *arenaF, cplx *fac, cplx *g21b, const NdPlanesSet &ps, int nz, int nx, int nf,
+                             double *est, double *est_rows, long long nbatch_all, int tr) {
+    if (smax <= 8) ZG_LAUNCH(k_sep_factor_small<8>, dim3(nb), d_nodes, first, arenaF, fac, g21b, ps, nz, nx, nf, est, est_rows, nbatch_all, tr);
+    else ZG_LAUNCH(k_sep_factor_small<16>, dim3(nb), d_nodes, first, arenaF, fac, g21b, ps, nz, nx, nf, est, est_rows, nbatch_all, tr);
+}
 
 // (nf, kf: frequency kf of a set of nf -- fac / arenaF / g21b are the SET's bases, the kernels place this frequency's slots among the interleaved ones)
 void launch_leaf_factor(hipStream_t st, int smax, int nb, const NdDev *d_nodes, int first, cplx *arenaF, cplx *fac, cplx *g21b, const cplx *planes, int nz, int nx, int *flags, int dbg,

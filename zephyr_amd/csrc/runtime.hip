@@ -229,6 +229,7 @@ static void tuning_clamp(helm_tuning &t) {
     if (!(t.sync_spin_ms >= 0)) t.sync_spin_ms = 0.0;
     t.sync_spin_ms = std::min(t.sync_spin_ms, 60000.0);
     t.sync_sleep_us = std::min(100000, std::max(0, t.sync_sleep_us));
+    t.nd_fused_sep_min = std::max(1, t.nd_fused_sep_min);
 }
 static helm_tuning tuning_from_env() {
     helm_tuning t;
@@ -267,6 +268,8 @@ static helm_tuning tuning_from_env() {
     t.mg3_beta = tune_d("HELM_MG3_BETA", 0.0);
     t.sync_spin_ms = tune_d("HELM_SYNC_SPIN_MS", 0.0);
     t.sync_sleep_us = helm_env_int("HELM_SYNC_SLEEP_US", 0);
+    t.nd_fused_sep = helm_env_int("HELM_ND_FUSEDSEP", 1);
+    t.nd_fused_sep_min = helm_env_int("HELM_ND_FUSEDSEP_MIN", 512);
     tuning_clamp(t);
     return t;
 }
