@@ -323,6 +323,21 @@ int helm_lag_imaging_accumulate_device(helm_op *op, const void *dUF, long long l
 int helm_lag_imaging_accumulate_c64_device(helm_op *op, const void *dUF32, const void *dExp, long long ldf, const void *dUB, long long ldb, int nsrc, void *dP);
 int helm_buoyancy_adjoint_device(helm_op *op, const void *dP, double w_re, double w_im, int conj, void *dG);
 
+/* --- the total velocity derivative of MiniZephyr (HelmBaseProblem.JvecBorn / Jtvec with linearisation='full') -------------------------------------
+ * A row is star(row_i, bn, Kn): the stretch factors row_i are functions of c_i, the mass terms Kn_k = kappa_j b_j of c_j, the averaged buoyancies bn of b = 1 / rho.
+ * V maps a real field dc (N) to the nine planes of d A / d c along dc at the density the handle assembled with (the model's, or the Gardner default
+ * 310 Re(c)^0.25 made by helm_set_model): star(dc_i d row_i / dc, bn[b], (d kappa_j / dc) b_j dc_j), boundary rows zero -- the mass term and the PML stretch.
+ *
+ * helm_velocity_planes_device:  dC = V[dc] + L[db] (dDb NULL: V[dc] alone).  db is the buoyancy perturbation that goes with dc where the density follows c
+ *     (-0.25 b / Re(c) dc for the Gardner default; the caller's), L the map of helm_buoyancy_planes_device.  dc, db: N float64; dC: 9 N complex128.
+ * helm_velocity_adjoint_device:  G[j] += w sum_{k, i} V_{(k, i), j} P[k][i] (conj != 0: conj(V)), the plain transpose of V; the boundary rows of P are not read.
+ *     P: 9 N complex128; G: N complex128.  (The transpose of the L[db] part is helm_buoyancy_adjoint_device, times d b / d c.)
+ *
+ * The same rules as above: plain fp64 in a fixed order, one writer per entry; HELM_ERR_STATE before the first helm_assemble; Eurus, 3-D and ny > 0 handles
+ * HELM_ERR_UNSUPPORTED; null (other than dDb), misaligned (16 bytes; dc, db: 8) or overlapping pointers and grids below 3 x 3 HELM_ERR_ARG. */
+int helm_velocity_planes_device(helm_op *op, const void *dDc, const void *dDb, void *dC);
+int helm_velocity_adjoint_device(helm_op *op, const void *dP, double w_re, double w_im, int conj, void *dG);
+
 /* --- device-resident callers: sparse sources in, receiver samples out ---------------------------------- */
 /* Dense right-hand sides from the COO triplets of the reference's sparse source matrix (survey.py:162-169,
  * source.py:213-317): R (nrhs x rows, zeroed by the call), R[col[k]][row[k]] = val[k]; no duplicate entries.

@@ -127,6 +127,8 @@ _SIGNATURES = {
     'helm_lag_imaging_accumulate_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
                                                               ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]),
     'helm_buoyancy_adjoint_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
+    'helm_velocity_planes_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'helm_velocity_adjoint_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_void_p]),
     'helm_num_blocks': (ctypes.c_int, [ctypes.c_void_p]),
     'helm_num_points': (ctypes.c_longlong, [ctypes.c_void_p]),
     'helm_get_diagonals': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),

@@ -1,5 +1,6 @@
 // The row factors of the 2-D MiniZephyr operator, shared by its assembly (assemble.hip k_assemble_mz) and by the buoyancy derivative (survey.hip
-// k_buoyancy_planes / k_buoyancy_adjoint): what a row takes from the velocity of its own cell and from the PML alone.
+// k_buoyancy_planes / k_buoyancy_adjoint): what a row takes from the velocity of its own cell and from the PML alone.  Their derivatives with respect to that
+// velocity (mz_row_factors_dc, mz_kappa_dc) serve the total velocity derivative (survey.hip k_velocity_planes / k_velocity_adjoint).
 #pragma once
 #include "helm_internal.hpp"
 
@@ -31,11 +32,36 @@ __device__ __forceinline__ MzRow mz_row_factors(const MzParams &P, cplx c0, doub
     return r;
 }
 
+// d (X, px) / dc along one axis (f the PML factor, d the profile distance, s its sign), from the same inputs: with den = f c d^2 + i om, X = (i om / den)^2 and
+// p = s X 2 f c d / den,   dX/dc = -2 X f d^2 / den,   dp/dc = s 2 f d (dX/dc c + X - X c f d^2 / den) / den.  Outside the layers d = 0 and both are zero.
+__device__ __forceinline__ void mz_axis_factors_dc(cplx iom, double f, cplx c0, double d, double s, cplx &dS, cplx &dp) {
+    const double fdd = f * d * d;
+    const cplx den = cadd(cscale(c0, fdd), iom);
+    const cplx r1 = cdiv(iom, den);
+    const cplx S = cmul(r1, r1);
+    dS = cdiv(cscale(S, -2.0 * fdd), den);
+    const cplx Sc = cmul(S, c0);
+    const cplx inner = csub(cadd(cmul(dS, c0), S), cdiv(cscale(Sc, fdd), den));
+    dp = cdiv(cscale(inner, s * 2.0 * f * d), den);
+}
+// d (X, Z, px, pz) / dc of mz_row_factors: the derivative of a row's stretch factors with respect to the velocity of its own cell
+__device__ __forceinline__ MzRow mz_row_factors_dc(const MzParams &P, cplx c0, double dX, double sX, double dZ, double sZ) {
+    const cplx iom = cmake(-P.om.y, P.om.x);          // 1j * om
+    MzRow r;
+    mz_axis_factors_dc(iom, P.fx, c0, dX, sX, r.X, r.px);
+    mz_axis_factors_dc(iom, P.fz, c0, dZ, sZ, r.Z, r.pz);
+    return r;
+}
+
 // kappa = omega_d^2 / c^2 - ky^2 of a cell: K = kappa / rho
 __device__ __forceinline__ cplx mz_kappa(const MzParams &P, cplx cj) {
     cplx k = cdiv(cmul(P.om, P.om), cmul(cj, cj));
     k.x -= P.aky * P.aky;
     return k;
+}
+// d kappa / dc = -2 omega_d^2 / c^3 of a cell
+__device__ __forceinline__ cplx mz_kappa_dc(const MzParams &P, cplx cj) {
+    return cdiv(cscale(cmul(P.om, P.om), -2.0), cmul(cmul(cj, cj), cj));
 }
 
 __host__ __device__ inline int mz_slot(int dz, int dx) { return 3 * (dz + 1) + (dx + 1); }

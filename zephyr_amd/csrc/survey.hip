@@ -1,7 +1,7 @@
 // What a survey runs on the device besides the solves: right-hand sides from sparse sources and from residual samples, receiver sampling, the imaging
 // condition, illumination (energy), axpby, the optional complex64 store of forward wavefields, the mass stencil of the exact Frechet derivative fused into
-// the virtual sources and the imaging sum, and (last section) the exact density derivative: the buoyancy map, its stencil on stored columns, the nine lag
-// products and its transpose.  Each kernel stands beside the C entry point that launches it.
+// the virtual sources and the imaging sum, the exact density derivative: the buoyancy map, its stencil on stored columns, the nine lag products and its
+// transpose, and (last section) the planes of the total velocity derivative and their transpose.  Each kernel stands beside the C entry point that launches it.
 //
 // The complex64 store (zephyr_amd/fieldstore.py, config key fieldsDtype='complex64'): a wavefield column s is kept as
 // complex64 values x * 2^-e_s with ONE power-of-two scale per column, e_s the binary exponent of the column's largest component
@@ -704,7 +704,7 @@ static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
     return pa < pb + nb && pb < pa + na;
 }
 static int mz_handle_args(helm_op *op, const char *what) {
-    if (op->variant != HELM_MINIZEPHYR || op->ny > 0) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "%s: the buoyancy derivative is that of the 2-D MiniZephyr operator", what);
+    if (op->variant != HELM_MINIZEPHYR || op->ny > 0) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "%s: the density and velocity derivatives are those of the 2-D MiniZephyr operator", what);
     return HELM_OK;
 }
 
@@ -1059,5 +1059,149 @@ extern "C" int helm_buoyancy_adjoint_device(helm_op *op, const void *dP, double 
     const dim3 grid((unsigned)((op->N + 255) / 256));
     if (conj) HELM_LAUNCH(k_buoyancy_adjoint<true>, grid, dim3(256), 0, op->stream, P, (const cplx *)op->d_c, (const cplx *)dP, cmake(w_re, w_im), (cplx *)dG);
     else HELM_LAUNCH(k_buoyancy_adjoint<false>, grid, dim3(256), 0, op->stream, P, (const cplx *)op->d_c, (const cplx *)dP, cmake(w_re, w_im), (cplx *)dG);
+    return launched(op);
+}
+
+// ------------------------------------------------------------------------------------------
+// the total velocity derivative of MiniZephyr (linearisation='full'): mass term, PML stretch and the density that follows c
+// ------------------------------------------------------------------------------------------
+// A row is mz_star(row_i, bn, Kn): linear in (row, Kn) for fixed averaged buoyancies bn and linear in (bn, Kn) for a fixed row.  The row factors are functions of
+// c_i, the mass terms Kn_k = kappa_j b_j of c_j (j = i + o_k), so along a real dc the nine planes of dA are
+//     dC_i = mz_star(dc_i d row_i / dc, bn[b], Kn_k = (d kappa_j / dc) b_j dc_j)        (the mass term of k_virtual_sources_op and the stretch it leaves out)
+//          + mz_star(row_i, bn[db], Kn_k = kappa_j db_j)                               (only where the density follows c: db = (d b / d c) dc, the caller's)
+// with b = 1 / rho of the model the handle assembled with, boundary rows zero.  The forward and imaging loops are those of the density derivative
+// (k_stencil_sources, k_lag_imaging); the transpose of the second star is k_buoyancy_adjoint.
+
+__device__ __forceinline__ MzRow mz_row_dc_at(const MzParams &P, const cplx *__restrict__ c, int iz, int ix) {
+    double dX, sX, dZ, sZ;
+    mz_profile_at(P.nx, P.npml, P.dx, P.fs3, P.fs1, ix, dX, sX);
+    mz_profile_at(P.nz, P.npml, P.dz, P.fs0, P.fs2, iz, dZ, sZ);
+    return mz_row_factors_dc(P, c[(long long)iz * P.nx + ix], dX, sX, dZ, sZ);
+}
+
+// dC = V[dc] (+ L[db] when db is given): one lane per cell, the assembly's star once or twice.  An interior row reads only cells inside the grid.
+__global__ __launch_bounds__(256) void k_velocity_planes(MzParams P, const cplx *__restrict__ c, const double *__restrict__ rho, const double *__restrict__ dc,
+                                                         const double *__restrict__ db, cplx *__restrict__ C) {
+    const long long N = (long long)P.nz * P.nx;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const int iz = (int)(i / P.nx), ix = (int)(i % P.nx);
+    cplx out[9];
+    if (iz == 0 || iz == P.nz - 1 || ix == 0 || ix == P.nx - 1) {
+#pragma unroll
+        for (int k = 0; k < 9; ++k) out[k] = cmake(0.0, 0.0);
+    } else {
+        MzRow drow = mz_row_dc_at(P, c, iz, ix);
+        const double v0 = dc[i];
+        drow.X = cscale(drow.X, v0); drow.Z = cscale(drow.Z, v0); drow.px = cscale(drow.px, v0); drow.pz = cscale(drow.pz, v0);
+        double bn[9];
+        cplx Kn[9];
+        const double b0 = 1.0 / rho[i];
+#pragma unroll
+        for (int sz = -1; sz <= 1; ++sz)
+#pragma unroll
+            for (int sx = -1; sx <= 1; ++sx) {
+                const long long j = i + (long long)sz * P.nx + sx;
+                const double bj = 1.0 / rho[j];
+                bn[mz_slot(sz, sx)] = (b0 + bj) / 2.0;
+                Kn[mz_slot(sz, sx)] = cscale(mz_kappa_dc(P, c[j]), bj * dc[j]);
+            }
+        mz_star(P, drow, bn, Kn, out);
+        if (db) {
+            const MzRow row = mz_row_at(P, c, iz, ix);
+            cplx more[9];
+            const double d0 = db[i];
+#pragma unroll
+            for (int sz = -1; sz <= 1; ++sz)
+#pragma unroll
+                for (int sx = -1; sx <= 1; ++sx) {
+                    const long long j = i + (long long)sz * P.nx + sx;
+                    const double dj = db[j];
+                    bn[mz_slot(sz, sx)] = (d0 + dj) / 2.0;
+                    Kn[mz_slot(sz, sx)] = cscale(mz_kappa(P, c[j]), dj);
+                }
+            mz_star(P, row, bn, Kn, more);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) out[k] = cadd(out[k], more[k]);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 9; ++k) C[(long long)k * N + i] = out[k];
+}
+
+// dC[9][N] = V[dc] + (dDb ? L[db] : 0) for the operator the handle holds (its c and rho, PML and the frequency of its last assembly): dc, db N float64 (db may be
+// NULL), dC 9 N complex128, boundary rows zero.  Returns when dC is complete.
+extern "C" int helm_velocity_planes_device(helm_op *op, const void *dDc, const void *dDb, void *dC) {
+    helm_tuning_refresh();
+    if (!op || !dDc || !dC) return HELM_ERR_ARG;
+    if (int rc = mz_handle_args(op, "helm_velocity_planes_device")) return rc;
+    if (op->nz < 3 || op->nx < 3 || ((((uintptr_t)dDc) | ((uintptr_t)dDb)) & 7) || (((uintptr_t)dC) & 15)) return HELM_ERR_ARG;
+    const size_t cbytes = (size_t)op->N * 9 * sizeof(cplx);
+    if (ranges_overlap(dDc, (size_t)op->N * 8, dC, cbytes) || (dDb && ranges_overlap(dDb, (size_t)op->N * 8, dC, cbytes))) return HELM_ERR_ARG;
+    MzParams P;
+    if (helm_mz_params(op, &P)) HELM_FAIL(op, HELM_ERR_STATE, "helm_velocity_planes_device: the handle holds no assembled operator");
+    HIP_TRY(op, hipSetDevice(op->device));
+    HELM_LAUNCH(k_velocity_planes, dim3((unsigned)((op->N + 255) / 256)), dim3(256), 0, op->stream, P, (const cplx *)op->d_c, (const double *)op->d_rho, (const double *)dDc,
+                (const double *)dDb, (cplx *)dC);
+    return launched(op);
+}
+
+// G[j] += w sum_(k, i) V_((k, i), j) P_k[i] (CONJ: conj(V)): the transpose of the first star of k_velocity_planes, one lane per cell j.  The mass part is the
+// gather of k_buoyancy_adjoint over the interior rows i = j - o, times (d kappa_j / dc) b_j.  The stretch part is local to row j: its differentiated stiffness
+// factors dT (mz_stiffness is linear in the row) times the averaged buoyancies a_o = (b_j + b_(j+o)) / 2 and the Q-differences of P at j (lag_coefficient); a
+// boundary row has none.  One writer per cell, a fixed order; the boundary rows of P are not read.
+template <bool CONJ>
+__global__ __launch_bounds__(256) void k_velocity_adjoint(MzParams P, const cplx *__restrict__ c, const double *__restrict__ rho, const cplx *__restrict__ Pl, cplx w,
+                                                          cplx *__restrict__ G) {
+    const long long N = (long long)P.nz * P.nx;
+    const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= N) return;
+    const int jz = (int)(j / P.nx), jx = (int)(j % P.nx);
+    const double bj = 1.0 / rho[j];
+    cplx mass = cmake(0.0, 0.0), stretch = cmake(0.0, 0.0);
+#pragma unroll
+    for (int sz = -1; sz <= 1; ++sz)
+#pragma unroll
+        for (int sx = -1; sx <= 1; ++sx) {
+            const int iz = jz - sz, ix = jx - sx;                 // row i sees cell j at the lag (sz, sx)
+            if (iz < 1 || iz > P.nz - 2 || ix < 1 || ix > P.nx - 2) continue;
+            const double m = (sz == 0 && sx == 0) ? MZ_WC : ((sz == 0 || sx == 0) ? MZ_WD : MZ_WE);
+            const cplx p = Pl[(long long)mz_slot(sz, sx) * N + (long long)iz * P.nx + ix];
+            mass.x += m * p.x; mass.y += m * p.y;
+        }
+    if (jz >= 1 && jz <= P.nz - 2 && jx >= 1 && jx <= P.nx - 2) {
+        const MzStiff dt = mz_stiffness<CONJ>(P, mz_row_dc_at(P, c, jz, jx));
+#pragma unroll
+        for (int oz = -1; oz <= 1; ++oz)
+#pragma unroll
+            for (int ox = -1; ox <= 1; ++ox)
+                if (oz != 0 || ox != 0) {
+                    const double a = (bj + 1.0 / rho[j + (long long)oz * P.nx + ox]) / 2.0;
+                    stretch = cadd(stretch, cscale(lag_coefficient(dt, Pl, N, j, oz, ox), a));
+                }
+    }
+    cplx dk = cscale(mz_kappa_dc(P, c[j]), bj);
+    if (CONJ) dk = cconj(dk);
+    cplx sum = stretch;
+    cfma(sum, dk, mass);
+    cplx g = G[j];
+    cfma(g, w, sum);
+    G[j] = g;
+}
+
+// G[j] += w sum_(k, i) V_((k, i), j) P_k[i] for j < N (conj != 0: the conjugated coefficients), V the map of helm_velocity_planes_device with dDb NULL for the
+// operator the handle holds: P [9][N] complex128 (its boundary rows are not read), G N complex128.  G must not overlap P.  Returns when G is complete.
+extern "C" int helm_velocity_adjoint_device(helm_op *op, const void *dP, double w_re, double w_im, int conj, void *dG) {
+    helm_tuning_refresh();
+    if (!op || !dP || !dG) return HELM_ERR_ARG;
+    if (int rc = mz_handle_args(op, "helm_velocity_adjoint_device")) return rc;
+    if (op->nz < 3 || op->nx < 3 || ((((uintptr_t)dP) | ((uintptr_t)dG)) & 15)) return HELM_ERR_ARG;
+    if (ranges_overlap(dP, (size_t)op->N * 9 * sizeof(cplx), dG, (size_t)op->N * sizeof(cplx))) return HELM_ERR_ARG;
+    MzParams P;
+    if (helm_mz_params(op, &P)) HELM_FAIL(op, HELM_ERR_STATE, "helm_velocity_adjoint_device: the handle holds no assembled operator");
+    HIP_TRY(op, hipSetDevice(op->device));
+    const dim3 grid((unsigned)((op->N + 255) / 256));
+    if (conj) HELM_LAUNCH(k_velocity_adjoint<true>, grid, dim3(256), 0, op->stream, P, (const cplx *)op->d_c, (const double *)op->d_rho, (const cplx *)dP, cmake(w_re, w_im), (cplx *)dG);
+    else HELM_LAUNCH(k_velocity_adjoint<false>, grid, dim3(256), 0, op->stream, P, (const cplx *)op->d_c, (const double *)op->d_rho, (const cplx *)dP, cmake(w_re, w_im), (cplx *)dG);
     return launched(op);
 }

@@ -18,10 +18,13 @@ The eight pipelines, one row each.  Every row is a body of its own made of the s
     bornFromFields          stored               virtual sources conj(W (.) slice)   k                sampleDevice, conjugated receivers    nrec x k samples per item
       linearisation='operator'                   coef mask M0(W (.) conj(slice))     k                sampleDevice, receivers as they are   nrec x k samples per item
       parameter='rho'                            coef sum_k L[db]_k shift_k(conj(slice)) k            sampleDevice, receivers as they are   nrec x k samples per item
+      linearisation='full'                       the same with the planes V[dc] (+ L[db]) k           sampleDevice, receivers as they are   nrec x k samples per item
     gradient                dealt                [qf | qb]                           2k               imaging kernel, uF and uB from U      one partial G per worker
     gradientFromFields      stored               qb                                  k                imaging kernel, uF from the slice     one partial G per worker
       linearisation='operator'                   qb of R^H r                         k                imaging kernel with the mass stencil  one partial G per worker
       parameter='rho'                            qb of R^H r                         k                lag imaging into P, then L^T P        one partial G per worker
+      linearisation='full'                       qb of R^H r                         k                lag imaging into P, then V^T P        one partial G per worker
+                                                                                                      (no `rho`: and L^T P into Gb)         (and one Gb)
     illumination            dealt                source or receiver columns          k                energy kernel                         one partial H per worker
     illuminationFromFields  stored               --                                  0                -- (energy kernel reads the slice)    one partial H per worker
 
@@ -47,11 +50,12 @@ from . import parallel
 
 class Workspace(object):
     """Device memory of one worker on one GPU for one call of dpred / Jtvec: named complex128 buffers whose storage only grows, the constants that
-    are uploaded once (`cached`), the worker's partial gradient `G` and its partial illumination `H`."""
+    are uploaded once (`cached`), the worker's partial gradient `G` (`Gb`: its buoyancy part where the density follows c) and its partial illumination `H`."""
 
     def __init__(self, device):
         self.device = device            # (a torch.device)
         self.G = None                   # (the partial gradient of this worker and GPU: made on first use by the gradient pipeline)
+        self.Gb = None                  # (the partial buoyancy gradient of linearisation='full' without an explicit density: made on first use)
         self.H = None                   # (its partial illumination, float64 (N,) or (nfreq, N): made on first use by the illumination pipeline)
         self._storage = {}
         self._constants = {}
@@ -229,7 +233,7 @@ def _cachedInverseC3Rho(ws, op):
 
 
 def _partial(ws, name, shape, dtype):
-    "the worker's partial result ws.<name> ('G': gradient, 'H': illumination), zeroed on first use"
+    "the worker's partial result ws.<name> ('G': gradient, 'Gb': its buoyancy part, 'H': illumination), zeroed on first use"
     import torch
     if getattr(ws, name) is None:
         setattr(ws, name, torch.zeros(shape, dtype=dtype, device=ws.device))
@@ -557,17 +561,20 @@ def _checkSecondFactorsFit(items, planes=0):
     _checkItemsFit(items, held=factors, work=lambda op, c0, c1: (2 * (c1 - c0) + planes) * int(op.nrow) * 16)
 
 
-def gradientFromFields(prob, F, qb, resid, system=None, linearisation='scaler', parameter='c'):
+def gradientFromFields(prob, F, qb, resid, system=None, linearisation='scaler', parameter='c', chain=None):
     """The u-given branch of Jtvec (problem.py:154-162) with the forward fields read from the store: per item only the k back-sources are made and solved
     (nsrc columns per frequency, not 2 nsrc), scaler * sum_s uF (.) uB goes into the GPU's partial gradient, and the real part of the sum is returned.
     qb None: the back-sources of a moving receiver array, made on the device from `resid` (nrec, nsrc, nfreq).  system: the wrapper whose operators
     back-propagate (default prob.system; prob.adjointSystem for Jtvec(adjoint='transpose') -- the same devices and replicas, so every item still finds
     its slice on its own GPU).  linearisation='operator' (with the transposed system, qb / resid those of R_s^H r): the same items, calls and waits with the
     weight of `_addOperator` and k_imaging_op, the mass stencil on the back-propagated columns fused into the imaging sum.  parameter='rho': the gradient
-    with respect to the BUOYANCY, `_gradientDensityFromFields` (the caller applies d b / d rho)."""
+    with respect to the BUOYANCY, `_gradientPlanesFromFields` (the caller applies d b / d rho).  linearisation='full': the same pipeline with the transpose
+    of the velocity planes; chain (N,) float64, d b / d c where the density follows c, or None."""
     import torch
     if parameter == 'rho':
-        return _gradientDensityFromFields(prob, F, qb, resid, system)
+        return _gradientPlanesFromFields(prob, F, qb, resid, system)
+    if linearisation == 'full':
+        return _gradientPlanesFromFields(prob, F, qb, resid, system, velocity=True, chain=chain)
     F.checkCurrent(prob)
     sv = prob.survey
     N = prob.nrow
@@ -599,14 +606,18 @@ def gradientFromFields(prob, F, qb, resid, system=None, linearisation='scaler', 
     return _sumPartials(prob, [ws.G for ws in runOnDevices(devs, items, one) if ws.G is not None]).real
 
 
-def bornFromFields(prob, F, v, linearisation='scaler', parameter='c'):
+def bornFromFields(prob, F, v, linearisation='scaler', parameter='c', db=None):
     """prob.JvecBorn(u=F): Born data (nrec, nsrc, nfreq) of the model perturbation v (N,) from forward fields already in HBM.  Per stored item
     W = v (.) gradientScaler(f) scaleTerm is made on the item's GPU (v and the model go up once per worker), the virtual-source kernel writes
     conj(W (.) slice) -- the store holds the unscaled solves, hence the scaleTerm in W -- the forward operator solves the k columns, and the samples
     through the CONJUGATED receiver CSR (row stride 0 for a fixed array, nrec for one that moves with the source) come down: nrec x k values per item.
-    linearisation='operator': `_bornOperatorFromFields`; with parameter='rho' (v the BUOYANCY perturbation -v_rho / rho^2): `_bornDensityFromFields`."""
+    linearisation='operator': `_bornOperatorFromFields`; with parameter='rho' (v the BUOYANCY perturbation -v_rho / rho^2): `_bornPlanesFromFields`.
+    linearisation='full': the same pipeline with the velocity planes of v; db (N,) float64 the buoyancy perturbation that goes with v where the density follows
+    c, or None."""
     if parameter == 'rho':
-        return _bornDensityFromFields(prob, F, v)
+        return _bornPlanesFromFields(prob, F, v)
+    if linearisation == 'full':
+        return _bornPlanesFromFields(prob, F, db, dc=v)
     if linearisation == 'operator':
         return _bornOperatorFromFields(prob, F, v)
     F.checkCurrent(prob)
@@ -671,15 +682,19 @@ def _bornOperatorFromFields(prob, F, v):
     return data
 
 
-def _bornDensityFromFields(prob, F, db):
+def _bornPlanesFromFields(prob, F, db, dc=None):
     """prob.JvecBorn(u=F, linearisation='operator', parameter='rho'): the derivative of dpred along the buoyancy perturbation db (N,) float64.  The items,
     calls and waits of `_bornOperatorFromFields` with the virtual-source step in two calls: k_buoyancy_planes makes the nine planes L_f[db] of the item's
-    frequency in the workspace (db goes up once per worker), k_stencil_sources writes R = -(1 / premul) sum_k L_f[db]_k (.) shift_k(conj(slice))."""
+    frequency in the workspace (db goes up once per worker), k_stencil_sources writes R = -(1 / premul) sum_k L_f[db]_k (.) shift_k(conj(slice)).
+    dc given (N,) float64: prob.JvecBorn(u=F, linearisation='full'), the total derivative along the velocity perturbation dc -- the same body with
+    k_velocity_planes in the place of k_buoyancy_planes: the planes V_f[dc] of the mass term and the PML stretch, plus L_f[db] where the density follows c
+    (db = (d b / d c) dc then; None with an explicit density)."""
     F.checkCurrent(prob)
     data, stage, sample = _sampling(prob, F.ownedFreqs, F.scale)
     if not F.items:
         return data
-    db = np.ascontiguousarray(db, dtype=np.float64)
+    db = None if db is None else np.ascontiguousarray(db, dtype=np.float64)
+    dc = None if dc is None else np.ascontiguousarray(dc, dtype=np.float64)
     devs, items = _storedItems(prob.system, F)
 
     def one(ws, op, ifreq, c0, c1):
@@ -687,10 +702,14 @@ def _bornDensityFromFields(prob, F, db):
         dev = ws.device
         d_uF, d_exp = F.pointers(ifreq, c0)
         staged = stage(ws, ifreq, c0, c1)
-        dbd = ws.cached(('born_db', id(db)), lambda: _lib.to_device(db, dev, np.float64), keep=db)
+        dbd = None if db is None else ws.cached(('born_db', id(db)), lambda: _lib.to_device(db, dev, np.float64), keep=db)
+        dcd = None if dc is None else ws.cached(('born_dc', id(dc)), lambda: _lib.to_device(dc, dev, np.float64), keep=dc)
         U, R, C = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni), ws.buffer('planes', 9 * Ni)
         _lib.wait_torch_stream(dev)
-        op.buoyancyPlanesDevice(dbd.data_ptr(), C.data_ptr())
+        if dcd is None:
+            op.buoyancyPlanesDevice(dbd.data_ptr(), C.data_ptr())
+        else:
+            op.velocityPlanesDevice(dcd.data_ptr(), None if dbd is None else dbd.data_ptr(), C.data_ptr())
         op.stencilSourcesDevice(d_uF, k, C.data_ptr(), -1.0 / complex(op.premul), R.data_ptr(), conj=True, d_exp=d_exp, rows=Ni)
         op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
         sample(op, ifreq, c0, c1, staged, U.data_ptr())
@@ -698,19 +717,24 @@ def _bornDensityFromFields(prob, F, db):
     return data
 
 
-def _gradientDensityFromFields(prob, F, qb, resid, system):
+def _gradientPlanesFromFields(prob, F, qb, resid, system, velocity=False, chain=None):
     """prob.Jtvec(u=F, adjoint='transpose', linearisation='operator', parameter='rho') up to d b / d rho: the gradient with respect to the buoyancy, float64
     (N,).  The items and shared steps of `gradientFromFields` (qb / resid those of R_s^H r, `system` the transposed operators) with the imaging step in two
     calls: k_lag_imaging adds P_k = sum_s uB_s (.) shift_k(slice_s) of the item's columns to nine planes of the workspace, zeroed per item, and
     k_buoyancy_adjoint adds -(scaleTerm / conj(premul)) conj(L_f)^T P to the worker's partial G -- the slice and the solves are the conjugates of u^ and z,
-    so the coefficients of L are conjugated, not the fields, and the real part is taken at the end."""
+    so the coefficients of L are conjugated, not the fields, and the real part is taken at the end.
+    velocity: prob.Jtvec(u=F, adjoint='transpose', linearisation='full'), the gradient with respect to the velocity -- the same body with k_velocity_adjoint
+    (conj(V_f)^T P) in the place of k_buoyancy_adjoint.  chain (N,) float64 (the density follows c): k_buoyancy_adjoint as well, into a second partial Gb,
+    which the real d b / d c multiplies once, after the sum over frequencies and workers."""
     import torch
     F.checkCurrent(prob)
     sv = prob.survey
     N = prob.nrow
     scale = F.scale
+    gardner = velocity and chain is not None
     if not F.items:
-        return _sumPartials(prob, []).real
+        g = _sumPartials(prob, []).real
+        return g + chain * _sumPartials(prob, []).real if gardner else g
     _prepareBackSources(sv, qb, F.ownedFreqs)
     devs, items = _storedItems(prob.system if system is None else system, F)
     _checkSecondFactorsFit(items, planes=9)
@@ -719,14 +743,23 @@ def _gradientDensityFromFields(prob, F, qb, resid, system):
         k, Ni = c1 - c0, int(op.nrow)
         d_uF, d_exp = F.pointers(ifreq, c0)
         G = _partial(ws, 'G', N, torch.complex128)
+        Gb = _partial(ws, 'Gb', N, torch.complex128) if gardner else None
         U, R, P = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni), ws.buffer('lags', 9 * Ni)
         _backSources(ws, sv, op, qb, resid, ifreq, c0, c1, R.data_ptr(), Ni)
         P.zero_()
         _lib.wait_torch_stream(ws.device)
         op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
         op.lagImagingAccumulateDevice(d_uF, U.data_ptr(), k, P.data_ptr(), d_exp=d_exp, rows=Ni)
-        op.buoyancyAdjointDevice(P.data_ptr(), -scale / np.conj(complex(op.premul)), G.data_ptr(), conj=True)
-    return _sumPartials(prob, [ws.G for ws in runOnDevices(devs, items, one) if ws.G is not None]).real
+        w = -scale / np.conj(complex(op.premul))
+        if not velocity:
+            op.buoyancyAdjointDevice(P.data_ptr(), w, G.data_ptr(), conj=True)
+        else:
+            op.velocityAdjointDevice(P.data_ptr(), w, G.data_ptr(), conj=True)
+            if gardner:
+                op.buoyancyAdjointDevice(P.data_ptr(), w, Gb.data_ptr(), conj=True)
+    wss = runOnDevices(devs, items, one)
+    g = _sumPartials(prob, [ws.G for ws in wss if ws.G is not None]).real
+    return g + chain * _sumPartials(prob, [ws.Gb for ws in wss if ws.Gb is not None]).real if gardner else g
 
 
 # ---- illumination / diagonal pseudo-Hessian ---------------------------------------------------------------------------------------------------

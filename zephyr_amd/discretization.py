@@ -390,6 +390,18 @@ class BaseDiscretization(BaseModelDependent):
         w = complex(w)
         _lib.check(_lib.load().helm_buoyancy_adjoint_device(self.handle, ctypes.c_void_p(d_p), w.real, w.imag, 1 if conj else 0, ctypes.c_void_p(d_g)), self.handle)
 
+    def velocityPlanesDevice(self, d_dc, d_db, d_c):
+        """dC = V[dc] + L[db] on the device, frechet.velocityPlanes: the nine planes (9 nrow complex128 at d_c, boundary rows zero) of d A / d c along the
+        velocity perturbation dc (nrow float64 at d_dc) at the density this operator assembled with; d_db (nrow float64, or None) the buoyancy perturbation that
+        goes with dc where the density follows c.  2-D MiniZephyr operators."""
+        db = None if d_db is None else ctypes.c_void_p(d_db)
+        _lib.check(_lib.load().helm_velocity_planes_device(self.handle, ctypes.c_void_p(d_dc), db, ctypes.c_void_p(d_c)), self.handle)
+
+    def velocityAdjointDevice(self, d_p, w, d_g, conj=False):
+        "G += w V^T P (conj: conj(V)^T P) on the device, frechet.velocityAdjoint: d_p 9 nrow complex128, d_g nrow complex128, w a complex number"
+        w = complex(w)
+        _lib.check(_lib.load().helm_velocity_adjoint_device(self.handle, ctypes.c_void_p(d_p), w.real, w.imag, 1 if conj else 0, ctypes.c_void_p(d_g)), self.handle)
+
     def packDevice(self, d_u, nsrc, d_out, d_exp, rows=None):
         """The complex64 store of the wavefields d_u ([nsrc][rows] complex128): d_out [nsrc][rows] complex64 values x * 2^-e_s, d_exp the nsrc int32 column
         exponents e_s (fieldstore.pack_reference states the format).  All device pointers; returns when both are complete."""

@@ -5,7 +5,8 @@ row by the mass weights, and overwrites its boundary rows by +-identity, so
     (dA) u = mask_int (.) M0(dK (.) u),      dK = -2 omega_d^2 v / (c^3 rho)
 
 The host routes of problem.py evaluate this here; the device routes (device_survey.py) take the scalars from here and run the stencil in
-k_virtual_sources_op / k_imaging_op (csrc/survey.hip).  The second half of the module is the derivative with respect to the density (parameter='rho')."""
+k_virtual_sources_op / k_imaging_op (csrc/survey.hip).  The second part of the module is the derivative with respect to the density (parameter='rho'), the
+third the total derivative with respect to the velocity (linearisation='full'): the mass term above, the PML stretch and the density that follows c."""
 import numpy as np
 
 
@@ -76,9 +77,9 @@ def _profile(n, npml, h, fs_low, fs_high):
     return dist, sgn
 
 
-def rowFactors(op, dtype=np.complex128):
-    """(X, Z, px, pz, kappa) of a 2-D MiniZephyr operator, each (nz, nx): the PML stretch factors of a row from the velocity of its own cell, and
-    kappa = omega_d^2 / c^2 - (2 pi ky)^2 per cell.  dtype np.clongdouble: evaluated in 80-bit arithmetic."""
+def _pmlAxes(op, dtype):
+    """(c, om, iom, (fx, distx, sgnx), (fz, distz, sgnz)) of a 2-D MiniZephyr operator in the arithmetic of dtype: the velocity (nz, nx), the damped angular
+    frequency and i times it, and per axis the PML factor with the distance and sign profiles broadcast over the grid"""
     R = _real(dtype)
     nz, nx, npml = int(op.nz), int(op.nx), int(op.nPML)
     dx, dz = R(float(op.dx)), R(float(op.dz))
@@ -88,13 +89,19 @@ def rowFactors(op, dtype=np.complex128):
     tau = float(op.tau)
     if np.isfinite(tau) and tau != 0.0:
         om = om - dtype(1j) / R(tau)
-    iom = dtype(1j) * om
     fs = tuple(bool(x) for x in op.freeSurf)
     lx, lz = dx * (npml - 1), dz * (npml - 1)
     fx, fz = 3 * np.log(R(1000)) / (2 * lx ** 3), 3 * np.log(R(1000)) / (2 * lz ** 3)
     distx, sgnx = _profile(nx, npml, float(op.dx), fs[3], fs[1])
     distz, sgnz = _profile(nz, npml, float(op.dz), fs[0], fs[2])
-    distx, sgnx, distz, sgnz = distx.astype(R)[None, :], sgnx.astype(R)[None, :], distz.astype(R)[:, None], sgnz.astype(R)[:, None]
+    return c, om, dtype(1j) * om, (fx, distx.astype(R)[None, :], sgnx.astype(R)[None, :]), (fz, distz.astype(R)[:, None], sgnz.astype(R)[:, None])
+
+
+def rowFactors(op, dtype=np.complex128):
+    """(X, Z, px, pz, kappa) of a 2-D MiniZephyr operator, each (nz, nx): the PML stretch factors of a row from the velocity of its own cell, and
+    kappa = omega_d^2 / c^2 - (2 pi ky)^2 per cell.  dtype np.clongdouble: evaluated in 80-bit arithmetic."""
+    R = _real(dtype)
+    c, om, iom, (fx, distx, sgnx), (fz, distz, sgnz) = _pmlAxes(op, dtype)
     denx = fx * c * distx ** 2 + iom
     X = (iom / denx) ** 2
     px = sgnx * X * (2 * fx * c * distx) / denx
@@ -104,6 +111,35 @@ def rowFactors(op, dtype=np.complex128):
     aky = 2 * R(np.pi) * R(float(op.ky))
     kappa = om * om / (c * c) - aky * aky
     return X + 0 * c, Z + 0 * c, px + 0 * c, pz + 0 * c, kappa
+
+
+def rowFactorsDc(op, dtype=np.complex128, magnitude=False):
+    """d (X, Z, px, pz) / d c of `rowFactors`, each (nz, nx).  Per axis, with den = f c d^2 + i omega_d (f the PML factor, d the profile distance, s its
+    sign), X = (i omega_d / den)^2 and p = s X 2 f c d / den:
+
+        dX / dc = -2 X f d^2 / den,      dp / dc = s 2 f d (dX/dc c / den + X / den - X c f d^2 / den^2)
+
+    Outside the layers d = 0 and all four vanish.  The factors are holomorphic in c: this is the derivative along a real perturbation of a complex c too.
+    magnitude: the moduli, dp / dc as the sum of the moduli of its three terms (they cancel in part) -- what bounds the rounding of the evaluation."""
+    c, _, iom, ax, az = _pmlAxes(op, dtype)
+    out = []
+    for f, d, s in (ax, az):
+        den = f * c * d ** 2 + iom
+        S = (iom / den) ** 2
+        dS = -2 * S * (f * d ** 2) / den
+        terms = (dS * c / den, S / den, -S * c * (f * d ** 2) / den ** 2)
+        if magnitude:
+            dS, dp = np.abs(dS), np.abs(s) * (2 * f * d) * ((np.abs(terms[0]) + np.abs(terms[1])) + np.abs(terms[2]))
+        else:
+            dp = s * (2 * f * d) * ((terms[0] + terms[1]) + terms[2])
+        out.append((dS + 0 * c.real, dp + 0 * c.real) if magnitude else (dS + 0 * c, dp + 0 * c))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+def massWeightDc(op, dtype=np.complex128):
+    "d kappa / d c = -2 omega_d^2 / c^3 per cell (nz, nx), kappa = omega_d^2 / c^2 - (2 pi ky)^2, in the arithmetic of dtype"
+    c, om = _pmlAxes(op, dtype)[:2]
+    return -2 * om * om / (c * c * c)
 
 
 def _stiffness(op, rf, magnitude=False):
@@ -144,19 +180,11 @@ def _interiorMask(nz, nx):
     return m
 
 
-def buoyancyPlanes(op, db, dtype=np.complex128, magnitude=False):
-    """L[db]: the nine planes (9, nz, nx) of d A / d b along the real buoyancy perturbation db (N,), boundary rows zero, for the 2-D MiniZephyr operator `op`
-    (its c, PML, frequency, damping and ky; rho does not enter: A is linear in b).  magnitude: the same sum with every term replaced by its modulus."""
-    nz, nx = int(op.nz), int(op.nx)
-    R = _real(dtype)
-    rf = rowFactors(op, dtype)
-    kappa = np.abs(rf[4]) if magnitude else rf[4]
-    t, tzx = _stiffness(op, rf, magnitude)
-    b = np.asarray(db).astype(R).reshape((nz, nx))
-    if magnitude:
-        b = np.abs(b)
+def _starPlanes(t, tzx, b, kb, R, dtype, magnitude):
+    """the nine planes of the star of the header comment from its stiffness factors (t, tzx), the buoyancy field b (nz, nx) that is averaged and the mass
+    terms kb of the cells; boundary rows zero.  Linear in (t, tzx, kb) for a fixed b and in (b, kb) for fixed factors."""
+    nz, nx = b.shape
     a = {o: (b + _at(b, *o)) / 2 for o in LAGS if o != (0, 0)}
-    kb = kappa * b
     mc, md, me = [R(w) for w in MZ_MASS]
     sgn = 1 if magnitude else -1
     C = np.zeros((9, nz, nx), dtype=R if magnitude else dtype)
@@ -175,6 +203,20 @@ def buoyancyPlanes(op, db, dtype=np.complex128, magnitude=False):
     C[4] = centre
     C[:, ~_interiorMask(nz, nx)] = 0
     return C
+
+
+def buoyancyPlanes(op, db, dtype=np.complex128, magnitude=False):
+    """L[db]: the nine planes (9, nz, nx) of d A / d b along the real buoyancy perturbation db (N,), boundary rows zero, for the 2-D MiniZephyr operator `op`
+    (its c, PML, frequency, damping and ky; rho does not enter: A is linear in b).  magnitude: the same sum with every term replaced by its modulus."""
+    nz, nx = int(op.nz), int(op.nx)
+    R = _real(dtype)
+    rf = rowFactors(op, dtype)
+    kappa = np.abs(rf[4]) if magnitude else rf[4]
+    t, tzx = _stiffness(op, rf, magnitude)
+    b = np.asarray(db).astype(R).reshape((nz, nx))
+    if magnitude:
+        b = np.abs(b)
+    return _starPlanes(t, tzx, b, kappa * b, R, dtype, magnitude)
 
 
 def buoyancyAdjoint(op, P, dtype=np.complex128, magnitude=False, conj=False):
@@ -232,3 +274,69 @@ def lagProducts(z, u, nz, nx):
     for k, (sz, sx) in enumerate(LAGS):
         P[k] = np.where(inside, (za * _at(ua, sz, sx)).sum(axis=2), 0)
     return P.reshape((9, nz * nx))
+
+
+# ---- the total velocity derivative (linearisation='full'): the mass term, the PML stretch and the Gardner density -------------------------------------
+# A row is star(row_i, bn, Kn) (csrc/mz_row.hpp mz_star): linear in (row, Kn) for fixed averaged buoyancies bn, and linear in (bn, Kn) for a fixed row.  The row
+# factors are functions of c_i, the mass terms Kn_k = kappa_j b_j of c_j (j = i + o_k), so along a real dc
+#     dC_i = star(dc_i d row_i / dc, bn[b], Kn_k = (-2 omega_d^2 / c_j^3) b_j dc_j)           the mass term ('operator') and the stretch
+#          + star(row_i, bn[db], Kn_k = kappa_j db_j)                                        only where the density follows c: `buoyancyPlanes` of db
+# with db = gardnerChain(c) dc for the default density rho = 310 Re(c)^0.25.  Boundary rows zero.  `velocityPlanes` is the map, `velocityAdjoint` the plain
+# transpose of its first star (the second one's is `buoyancyAdjoint`); k_velocity_planes / k_velocity_adjoint (csrc/survey.hip) are the device kernels.
+
+def gardnerChain(c):
+    "d b / d c per cell, float64 (N,), of the default density: b = 1 / (310 Re(c)^0.25), so -0.25 b / Re(c)"
+    cr = np.asarray(c).real.astype(np.float64).ravel()
+    return -0.25 / (310. * cr ** 0.25) / cr
+
+
+def _buoyancy(op, R):
+    "b = 1 / rho (nz, nx) at the density the operator is assembled with (its config's, or the Gardner default)"
+    return 1 / np.broadcast_to(np.asarray(op.rho, dtype=np.float64), (int(op.nz), int(op.nx))).astype(R)
+
+
+def velocityPlanes(op, dc, db=None, dtype=np.complex128, magnitude=False):
+    """The nine planes (9, nz, nx) of d A / d c along the real velocity perturbation dc (N,), boundary rows zero, for the 2-D MiniZephyr operator `op`:
+    mass term and PML stretch at the density of the operator.  db (N,): the buoyancy perturbation that goes with dc (gardnerChain(c) dc where the density
+    follows c), whose planes `buoyancyPlanes(op, db)` are added.  magnitude: the same sum with every term replaced by its modulus."""
+    nz, nx = int(op.nz), int(op.nx)
+    R = _real(dtype)
+    v = np.asarray(dc).astype(R).reshape((nz, nx))
+    b = _buoyancy(op, R)
+    drow = [x * v for x in rowFactorsDc(op, dtype, magnitude)]
+    dkb = massWeightDc(op, dtype) * b * v
+    t, tzx = _stiffness(op, drow, magnitude)
+    C = _starPlanes(t, tzx, b, np.abs(dkb) if magnitude else dkb, R, dtype, magnitude)
+    return C if db is None else C + buoyancyPlanes(op, db, dtype, magnitude)
+
+
+def velocityAdjoint(op, P, dtype=np.complex128, magnitude=False, conj=False):
+    """V^T P: (N,) with <velocityPlanes(op, dc), P> = <dc, V^T P> under the bilinear pairing sum_k sum_i (no conjugate), P (9, N) or (9, nz, nx) complex; its
+    boundary rows are not read.  Cell j takes (d kappa_j / dc) b_j times the mass weights from the planes of the rows around it, and from its own row the
+    differentiated stiffness factors times the averaged buoyancies.  conj: conj(V)^T P.  magnitude: the sum of the moduli of the terms."""
+    nz, nx = int(op.nz), int(op.nx)
+    R = _real(dtype)
+    b = _buoyancy(op, R)
+    drow, w = rowFactorsDc(op, dtype, magnitude), massWeightDc(op, dtype) * b
+    if conj:
+        drow, w = tuple(np.conj(x) for x in drow), np.conj(w)
+    t, tzx = _stiffness(op, drow, magnitude)
+    Pl = np.asarray(P).astype(dtype).reshape((9, nz, nx)).copy()
+    Pl[:, ~_interiorMask(nz, nx)] = 0
+    if magnitude:
+        Pl, w = np.abs(Pl), np.abs(w)
+    slot = {o: k for k, o in enumerate(LAGS)}
+    sgn = 1 if magnitude else -1
+    mc, md, me = [R(x) for x in MZ_MASS]
+    mass = mc * Pl[4]
+    stiff = np.zeros((nz, nx), dtype=Pl.dtype)
+    for o in LAGS:
+        if o == (0, 0):
+            continue
+        sz, sx = o
+        q = t[o] * (Pl[slot[o]] + sgn * Pl[4])
+        if sz and sx:
+            q = q + tzx * (Pl[slot[(sz, 0)]] + sgn * Pl[slot[(0, sx)]])
+        stiff = stiff + (b + _at(b, sz, sx)) / 2 * q             # (zero on the boundary lines: the planes are zero there)
+        mass = mass + (me if sz and sx else md) * _at(Pl[slot[o]], -sz, -sx)
+    return (stiff + w * mass).ravel()

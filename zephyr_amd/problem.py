@@ -31,6 +31,7 @@ from . import _lib
 from .fieldstore import DeviceFields
 from .frechet import MZ_MASS, maskInterior, massStencil, operatorWeight      # noqa: F401 (what linearisation='operator' is made of)
 from .frechet import applyPlanes, buoyancyAdjoint, buoyancyPlanes, lagProducts      # (and what parameter='rho' is made of)
+from .frechet import gardnerChain, velocityAdjoint, velocityPlanes                  # (and linearisation='full')
 
 EPS = 1e-15
 
@@ -264,6 +265,9 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         1/2 ||dpred - dobs||^2 for v = dpred - dobs,
             g = Re sum_f W_f (.) sum_s U_s (.) M0(mask_int (.) uB_s),   W_f = 2 scaleTerm conj(omega_d^2 / premul) / (c^3 rho),
         U_s the unscaled forward solve and uB_s = conj(A_f^-T premul R_s^H v_s).  `_requireOperatorLinearisation` lists what it serves.
+        linearisation='full' (needs adjoint='transpose'): the exact adjoint of JvecBorn(linearisation='full'), the gradient with respect to the velocity in
+        every cell -- absorbing layers included, with an explicit or the default density.  With P_f the nine lag products below and V_f the map of
+        frechet.velocityPlanes,  g = Re sum_f -(conj(scaleTerm) / premul) (V_f^T P_f + (d b / d c) (.) L_f^T P_f),  the second term only without `rho`.
 
         parameter='c' (default): all of the above.  parameter='rho' (needs linearisation='operator', hence adjoint='transpose'): the gradient with
         respect to the density of the config at fixed c, the exact adjoint of JvecBorn(parameter='rho'), float64 (N,) in density units.  With
@@ -271,7 +275,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         forward solves (zero where i is on a boundary line), and L_f the linear map from a buoyancy field to the nine planes of the interior rows
         (frechet.buoyancyPlanes),
             g_b = Re sum_f -(conj(scaleTerm) / premul) L_f^T P_f,      g_rho = -g_b / rho^2.
-        m stays the velocity.  The same routes as 'c'.
+        m stays the velocity.  The same routes as 'c'.  With linearisation='full' and an explicit `rho` this is 'operator' under another name; without one
+        the density is not a free parameter and the call raises NotImplementedError.
         """
         self._requirePaired()
         if v is None:
@@ -280,8 +285,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             raise ValueError('adjoint is %r: \'reciprocity\' or \'transpose\'' % (adjoint,))
         self._checkLinearisation(linearisation)
         self._checkParameter(parameter, linearisation)
-        if linearisation == 'operator' and adjoint != 'transpose':
-            raise ValueError('linearisation=\'operator\' needs adjoint=\'transpose\': the exact derivative back-propagates through A^-T')
+        if linearisation in ('operator', 'full') and adjoint != 'transpose':
+            raise ValueError('linearisation=%r needs adjoint=\'transpose\': the exact derivative back-propagates through A^-T' % (linearisation,))
         self.updateModel(m)
         sv = self.survey
         nsrc = sv.nsrc
@@ -319,15 +324,15 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
 
     @staticmethod
     def _checkLinearisation(linearisation):
-        if linearisation not in ('scaler', 'operator'):
-            raise ValueError('linearisation is %r: \'scaler\' or \'operator\'' % (linearisation,))
+        if linearisation not in ('scaler', 'operator', 'full'):
+            raise ValueError('linearisation is %r: \'scaler\', \'operator\' or \'full\'' % (linearisation,))
 
     @staticmethod
     def _checkParameter(parameter, linearisation):
-        "parameter is 'c' or 'rho'; the density has no scaler in the reference, so 'rho' needs linearisation='operator'"
+        "parameter is 'c' or 'rho'; the density has no scaler in the reference, so 'rho' needs linearisation='operator' (or 'full', which is the same there)"
         if parameter not in ('c', 'rho'):
             raise ValueError('parameter is %r: \'c\' or \'rho\'' % (parameter,))
-        if parameter == 'rho' and linearisation != 'operator':
+        if parameter == 'rho' and linearisation not in ('operator', 'full'):
             raise ValueError('parameter=\'rho\' needs linearisation=\'operator\': the reference has no gradient scaler for the density')
 
     def _buoyancyChain(self):
@@ -335,9 +340,21 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         rho = np.broadcast_to(np.asarray(self.systemConfig['rho'], dtype=np.float64).ravel(), (self.nrow,))       # (a scalar rho is one value for every cell)
         return -1.0 / (rho * rho)
 
+    def _hasDensity(self):
+        'the config gives the density: it is a parameter of its own.  Otherwise it follows the velocity, rho = 310 Re(c)^0.25 (Gardner)'
+        return self.systemConfig.get('rho', None) is not None
+
     def _requireOperatorLinearisation(self, what):
         """linearisation='operator' serves Helm2DProblem with MiniZephyr / MiniZephyrHD on a single grid and an explicit density: everything else is refused
         here with the reason"""
+        self._requireFullLinearisation(what)
+        if not self._hasDensity():
+            raise NotImplementedError('%s needs an explicit `rho` in the config: without one the Gardner density follows c, and its sensitivity is not built '
+                                      '(linearisation=\'full\' carries it)' % (what,))
+
+    def _requireFullLinearisation(self, what):
+        """linearisation='full' serves Helm2DProblem with MiniZephyr / MiniZephyrHD on a single grid, with an explicit density or the default one: everything
+        else is refused here with the reason"""
         from .minizephyr import MiniZephyr
         from .discretization import DiscretizationWrapper
         self._refuseMultiscale(what)
@@ -348,8 +365,25 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             raise NotImplementedError('%s does not serve the 2.5-D composite: the stored fields are the ky SUM, the exact derivative needs the fields per ky' % (what,))
         if sub is not None and not (isinstance(sub, MiniZephyr) and getattr(sub, 'ny', None) is None):
             raise NotImplementedError('%s serves the 2-D MiniZephyr operators: %s assembles its mass term differently' % (what, type(sub).__name__))
-        if 'rho' not in self.systemConfig or self.systemConfig['rho'] is None:
-            raise NotImplementedError('%s needs an explicit `rho` in the config: without one the Gardner density follows c, and its sensitivity is not built' % (what,))
+
+    def _resolveLinearisation(self, linearisation, parameter, what):
+        """the linearisation a route runs with, once what it does not serve is refused: 'full' with parameter='rho' is 'operator' -- the density derivative
+        leaves nothing out -- and needs the density to be a parameter of its own"""
+        what = '%s(linearisation=%r)' % (what, linearisation)
+        if linearisation == 'operator':
+            self._requireOperatorLinearisation(what)
+        elif linearisation == 'full':
+            self._requireFullLinearisation(what)
+            if parameter == 'rho':
+                if not self._hasDensity():
+                    raise NotImplementedError('%s with parameter=\'rho\' needs an explicit `rho` in the config: without one the density follows c and is '
+                                              'not a free parameter' % (what,))
+                return 'operator'
+        return linearisation
+
+    def _gardnerChain(self):
+        'd b / d c per cell of the default density at the current model, float64 (N,); None where the config gives the density'
+        return None if self._hasDensity() else gardnerChain(np.broadcast_to(np.asarray(self.systemConfig['c']).ravel(), (self.nrow,)))
 
     def _hermitianResidual(self, resid):
         """resid' with R_s^T resid'_s = R_s^H resid_s, for the device pipelines (which build R_s^T r): a receiver matrix is diag(srTerms) R0 with R0 the real
@@ -401,21 +435,36 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
     def _JtvecTranspose(self, resid, u, linearisation='scaler', parameter='c'):
         "Jtvec(adjoint='transpose') once the model is current and `resid` is (nrec, nsrc, nfreq)"
         self._refuseMultiscale("Jtvec(adjoint='transpose')")
+        linearisation = self._resolveLinearisation(linearisation, parameter, 'Jtvec')
         exact = linearisation == 'operator'
+        full = linearisation == 'full'
         density = parameter == 'rho'
-        if exact:
-            self._requireOperatorLinearisation("Jtvec(linearisation='operator')")
         adj = self.adjointSystem
         with self._forwardFields(u) as F:
             if isinstance(F, DeviceFields):
-                if exact:
+                if exact or full:
                     resid = self._hermitianResidual(resid)
                 if density:
                     return self._buoyancyChain() * device_survey.gradientFromFields(self, F, self._deviceBackSources(resid), resid, system=adj, linearisation=linearisation,
                                                                                     parameter='rho')
+                if full:
+                    return device_survey.gradientFromFields(self, F, self._deviceBackSources(resid), resid, system=adj, linearisation='full', chain=self._gardnerChain())
                 return device_survey.gradientFromFields(self, F, self._deviceBackSources(resid), resid, system=adj, linearisation=linearisation)
             g = np.zeros(self.nrow, dtype=np.complex128)
-            if density:
+            if full:
+                # the lag products of parameter='rho' against V^T, the transpose of frechet.velocityPlanes; where the density follows c the buoyancy
+                # gradient L^T P joins through the real chain d b / d c
+                st = complex(self.system.scaleTerm)
+                chain = self._gardnerChain()
+                qb = [q.conj() for q in self.survey.getResidualSources(np.conj(resid))]
+                for ifreq, uB in self._solveOwned(qb, adj):
+                    op = self.system.subProblems[ifreq]
+                    P = lagProducts(np.conj(np.asarray(uB) / st), np.conj(np.asarray(F[ifreq]) / st), op.nz, op.nx)
+                    gf = velocityAdjoint(op, P)
+                    if chain is not None:
+                        gf = gf + chain * buoyancyAdjoint(op, P)
+                    g += (-np.conj(st) / complex(op.premul)) * gf
+            elif density:
                 # z_s = A^-T premul R_s^H r_s and u^_s from the scaled, conjugated arrays the solves and the host fields are; g_b = Re -(conj(st) / premul) L^T P
                 st = complex(self.system.scaleTerm)
                 qb = [q.conj() for q in self.survey.getResidualSources(np.conj(resid))]
@@ -459,8 +508,18 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         u^_s = A_f^-1 premul qf_s (the conjugate of the unscaled forward solve), M0 the constant 9-point stencil of the mass weights (centre 0.6248, edges
         0.09381, corners 1.297e-6), mask_int zero on the four boundary lines (their rows are +-identity), omega_d = 2 pi f - i / tau.  v is real.  It is
         the exact adjoint of Jtvec(adjoint='transpose', linearisation='operator').  The dependence of the PML stretch on c is left out: the derivative is
-        exact for perturbations that vanish in the absorbing layers (inside them it is the mass-term part only).  `_requireOperatorLinearisation` lists
-        what it serves.
+        exact for perturbations that vanish in the absorbing layers (inside them it is the mass-term part only; linearisation='full' is exact there too).
+        `_requireOperatorLinearisation` lists what it serves.
+        linearisation='full': the TOTAL derivative of `dpred` with respect to the velocity, v non-zero anywhere.  The absorbing layers lie inside the grid and
+        their stretch factors X, Z, px, pz are functions of the velocity of the row's own cell; without `rho` in the config the density follows c as well
+        (Gardner, rho = 310 Re(c)^0.25).  A row is star(row_i, bn, Kn), linear in (row, Kn) and in (bn, Kn), so the nine planes of delta A are
+
+            star(v_i d row_i / dc, bn[b], Kn_k = (-2 omega_d^2 / c_j^3) b_j v_j)  +  star(row_i, bn[db], Kn_k = kappa_j db_j),   db = -0.25 b / Re(c) (.) v
+
+        (frechet.velocityPlanes; boundary rows zero; the second star only without `rho`; the Kn of the first one alone is 'operator').  Then
+        dd[:, s, f] = R_s . scaleTerm conj(-A_f^-1 (delta A) u^_s) as for parameter='rho' below.  The exact adjoint of
+        Jtvec(adjoint='transpose', linearisation='full'); the same routes as 'operator', and a config without `rho` is served
+        (`_requireFullLinearisation`).
 
         parameter='c' (default): all of the above.  parameter='rho' (needs linearisation='operator'): v is a density perturbation and the result is
         d/dh dpred(c, rho + h v) at h = 0, at the rho of the config with c held fixed (m stays the velocity).  Every interior row of the operator is linear
@@ -477,27 +536,34 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         self._checkParameter(parameter, linearisation)
         self.updateModel(m)
         self._refuseMultiscale('JvecBorn')
-        exact = linearisation == 'operator'
+        linearisation = self._resolveLinearisation(linearisation, parameter, 'JvecBorn')
+        exact = linearisation in ('operator', 'full')
+        full = linearisation == 'full'
         density = parameter == 'rho'
-        if exact:
-            self._requireOperatorLinearisation("JvecBorn(linearisation='operator')")
         sv = self.survey
         pert = np.asarray(v).reshape((self.nrow,))
         if density:
             pert = self._buoyancyChain() * np.asarray(pert, dtype=np.float64)          # (db: the operator is linear in the buoyancy)
+        elif full:
+            pert = np.asarray(pert, dtype=np.float64)
+            chain = self._gardnerChain()
+            db = None if chain is None else chain * pert                                # (the buoyancy perturbation that goes with v: the density follows c)
         with self._forwardFields(u) as F:
             if isinstance(F, DeviceFields):
                 if density:
                     data = device_survey.bornFromFields(self, F, pert, linearisation=linearisation, parameter='rho')
+                elif full:
+                    data = device_survey.bornFromFields(self, F, pert, linearisation='full', db=db)
                 else:
                     data = device_survey.bornFromFields(self, F, pert, linearisation=linearisation)
             else:
                 data = np.zeros((sv.nrec, sv.nsrc, sv.nfreq), dtype=np.complex128)
                 owned = self.ownedFreqs
-                if density:
+                if density or full:
                     st = complex(self.system.scaleTerm)
                     subs = self.system.subProblems
-                    qv = [applyPlanes(buoyancyPlanes(subs[i], pert), np.conj(np.asarray(F[i]) / st), subs[i].nz, subs[i].nx) / -complex(subs[i].premul)
+                    planes = (lambda op: buoyancyPlanes(op, pert)) if density else (lambda op: velocityPlanes(op, pert, db))
+                    qv = [applyPlanes(planes(subs[i]), np.conj(np.asarray(F[i]) / st), subs[i].nz, subs[i].nx) / -complex(subs[i].premul)
                           if i in owned else None for i in range(sv.nfreq)]
                 elif exact:
                     # F[i] = scaleTerm conj(u^): the scaleTerm is divided out of the virtual source and comes back with the solve (_solveOwned scales)
@@ -525,9 +591,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         operator on real vectors, because the two halves are exact adjoints.  weights: optional, real, non-negative, the shape (or ravel) of the data.
         Both halves read the same forward fields: two solves of nsrc columns per frequency, no forward re-solve; with u None the fields are solved once
         (into HBM where the device path serves) for both halves.  Needs the factors of A and of A^T side by side (see `adjointSystem`).
-        linearisation: handed to both halves; with 'operator' this is the Gauss-Newton Hessian of 1/2 ||dpred - dobs||^2 (with 'scaler' it is not).
+        linearisation: handed to both halves; with 'operator' this is the Gauss-Newton Hessian of 1/2 ||dpred - dobs||^2 for perturbations that vanish in the
+        absorbing layers, with 'full' for any perturbation (with 'scaler' it is not).
         parameter: 'c' (default), 'rho', or a pair (input, output) handed to JvecBorn and Jtvec respectively -- ('c', 'rho') takes a velocity perturbation
-        and returns the density block row of the Hessian, the transpose of ('rho', 'c').  Anything with 'rho' needs linearisation='operator'."""
+        and returns the density block row of the Hessian, the transpose of ('rho', 'c').  Anything with 'rho' needs linearisation='operator' or 'full'."""
         self._requirePaired()
         if v is None:
             raise Exception('Actually, Hvec requires a vector')
@@ -537,8 +604,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         self._checkParameter(pout, linearisation)
         self.updateModel(m)
         self._refuseMultiscale('Hvec')
-        if linearisation == 'operator':
-            self._requireOperatorLinearisation("Hvec(linearisation='operator')")       # (before the fields are solved for both halves)
+        for par in (pin, pout):
+            self._resolveLinearisation(linearisation, par, 'Hvec')                      # (refusals before the fields are solved for both halves)
         if weights is not None:
             weights = np.asarray(weights)
             if np.iscomplexobj(weights) or weights.size != self.survey.nD or not np.all(weights >= 0):
