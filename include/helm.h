@@ -338,6 +338,30 @@ int helm_buoyancy_adjoint_device(helm_op *op, const void *dP, double w_re, doubl
 int helm_velocity_planes_device(helm_op *op, const void *dDc, const void *dDb, void *dC);
 int helm_velocity_adjoint_device(helm_op *op, const void *dP, double w_re, double w_im, int conj, void *dG);
 
+/* --- the pseudo-Hessian diagonal of the exact derivatives (HelmBaseProblem.illumination with linearisation='full' / 'operator') ------------------
+ * H[i] += alpha (dW ? W[i] : 1) sum_{s<nsrc} || (d A / d p_i) u^_s ||_2^2 for i < N, with U[s] = conj(u^_s) the stored columns (nsrc columns of ld >= N complex128,
+ * or, _c64, complex64 values with the int32 column exponents dExp of helm_pack_c64_device) and d A / d p_i the derivative of the operator the handle holds:
+ *     mode 0   p = c: star(d row_i / dc, bn[b], (d kappa_i / dc) b_i) -- the planes of helm_velocity_planes_device along e_i with dDb NULL
+ *     mode 1   p = b: the planes of helm_buoyancy_planes_device along e_i (the caller's W carries 1 / rho^4 for the density)
+ *     mode 2   p = c with the buoyancy following it: mode 0 plus dChain[i] times mode 1 (dChain: N float64, d b / d c; NULL for the other modes)
+ * A unit perturbation of cell i touches the rows of the 3 x 3 block around it, and in those the lags that point back into the block: at most 33 complex
+ * coefficients per cell, built in the kernel and kept in registers (the _packed entry points with dE != NULL read them from the array that
+ * helm_pseudo_hessian_coefficients_device wrote for the same mode and chain: 10 N complex128 for mode 0, 33 N otherwise).  W, H: N float64; alpha >= 0.
+ *
+ * The fields are read once plus the rows above and below a tile; no scratch array.  Plain fp64 in a fixed order (columns in groups of four over the four waves of
+ * a workgroup, the waves' sums added in wave order, one writer per cell), no atomics: the same bits on every run.  HELM_ERR_STATE before the first helm_assemble;
+ * Eurus, 3-D and ny > 0 handles HELM_ERR_UNSUPPORTED; null (other than dChain, dW, dE), misaligned (U: 16, U32: 8, dExp: 4, dE: 16, the rest 8) or overlapping
+ * pointers, nsrc < 1, ld < N, a negative or NaN alpha, a mode outside 0..2, a chain without mode 2 (or the reverse) and grids below 3 x 3 HELM_ERR_ARG.
+ * All device pointers; each call returns when its result is complete. */
+int helm_pseudo_hessian_accumulate_device(helm_op *op, const void *dU, int nsrc, long long ld, int mode, const void *dChain, double alpha, const void *dW, void *dH);
+int helm_pseudo_hessian_accumulate_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, int mode, const void *dChain, double alpha,
+                                              const void *dW, void *dH);
+int helm_pseudo_hessian_coefficients_device(helm_op *op, int mode, const void *dChain, void *dE);
+int helm_pseudo_hessian_accumulate_packed_device(helm_op *op, const void *dU, int nsrc, long long ld, int mode, const void *dChain, const void *dE, double alpha,
+                                                 const void *dW, void *dH);
+int helm_pseudo_hessian_accumulate_packed_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, int mode, const void *dChain,
+                                                     const void *dE, double alpha, const void *dW, void *dH);
+
 /* --- device-resident callers: sparse sources in, receiver samples out ---------------------------------- */
 /* Dense right-hand sides from the COO triplets of the reference's sparse source matrix (survey.py:162-169,
  * source.py:213-317): R (nrhs x rows, zeroed by the call), R[col[k]][row[k]] = val[k]; no duplicate entries.

@@ -1,7 +1,8 @@
 // What a survey runs on the device besides the solves: right-hand sides from sparse sources and from residual samples, receiver sampling, the imaging
 // condition, illumination (energy), axpby, the optional complex64 store of forward wavefields, the mass stencil of the exact Frechet derivative fused into
 // the virtual sources and the imaging sum, the exact density derivative: the buoyancy map, its stencil on stored columns, the nine lag products and its
-// transpose, and (last section) the planes of the total velocity derivative and their transpose.  Each kernel stands beside the C entry point that launches it.
+// transpose, the planes of the total velocity derivative and their transpose, and (last section) the pseudo-Hessian diagonal of these derivatives.  Each kernel
+// stands beside the C entry point that launches it.
 //
 // The complex64 store (zephyr_amd/fieldstore.py, config key fieldsDtype='complex64'): a wavefield column s is kept as
 // complex64 values x * 2^-e_s with ONE power-of-two scale per column, e_s the binary exponent of the column's largest component
@@ -1203,5 +1204,294 @@ extern "C" int helm_velocity_adjoint_device(helm_op *op, const void *dP, double 
     const dim3 grid((unsigned)((op->N + 255) / 256));
     if (conj) HELM_LAUNCH(k_velocity_adjoint<true>, grid, dim3(256), 0, op->stream, P, (const cplx *)op->d_c, (const double *)op->d_rho, (const cplx *)dP, cmake(w_re, w_im), (cplx *)dG);
     else HELM_LAUNCH(k_velocity_adjoint<false>, grid, dim3(256), 0, op->stream, P, (const cplx *)op->d_c, (const double *)op->d_rho, (const cplx *)dP, cmake(w_re, w_im), (cplx *)dG);
+    return launched(op);
+}
+
+// ------------------------------------------------------------------------------------------
+// the pseudo-Hessian diagonal of the exact derivatives: H[i] += alpha W[i] sum_s || (d A / d p_i) u^_s ||^2
+// ------------------------------------------------------------------------------------------
+// A unit perturbation of cell i (of its velocity, or of its buoyancy) touches only the rows j of the 3 x 3 block around i, and in those only the lags that point
+// back into the block (frechet.pseudoHessianDiagonal states the same).  Per cell that is a small matrix E_i, independent of the source:
+//     row i             nine coefficients: mz_star on the differentiated row factors and d kappa_i / dc b_i (velocity), on the row itself with the averages
+//                       1 / 2 and kappa_i (buoyancy)
+//     row j = i - o     velocity: the one mass weight m_o d kappa_i / dc b_i at the lag o, which multiplies u[i] -- the eight rows together are
+//                       |d kappa_i / dc b_i|^2 sum_j m_o^2 |u[i]|^2, one real weight S_i.
+//                       buoyancy: m_o kappa_i + T_o(j) / 2 at the lag o and -T_o(j) / 2 at the centre, T the row's own stiffness factor (mz_stiffness); a corner
+//                       row has +-tzx(j) / 2 at the two lags beside o as well.  2 coefficients per edge row, 4 per corner row: 9 + 8 + 16 = 33.
+//     Gardner           velocity + chain_i x buoyancy, coefficient by coefficient (the mass weight of the velocity part joins the lag o of row j).
+// The stored fields are conj(u^): the coefficients are conjugated once instead (|conj(E) conj(u)| = |E u|).
+//
+// The walk: a workgroup of PH_WAVES waves owns OP_TILE_X cells of one grid row, one lane per cell plus a halo lane at either end.  The lane's E_i stays in
+// registers for the whole kernel; the columns go to the waves in groups of PH_UNROLL (group g to wave g mod PH_WAVES).  Per column a lane loads the three rows
+// z - 1, z, z + 1 of its own x (3 PH_UNROLL loads in flight), takes the left and right neighbours from the adjacent lanes, forms the up to nine row sums and adds
+// their squared moduli to one double.  The waves add their sums into one LDS row in wave order and wave 0 adds alpha W (.) sum to H: one writer per cell, a
+// fixed order, no atomics -- the same bits on every run.  Rows z - 1 and z + 1 are the halo: the workgroups of the neighbouring rows load them at the same time.
+// PACKED: E_i is read from an array [ph_ncoef(MODE)][N] that k_pseudo_hessian_coefficients wrote (the same function, one lane per cell) instead of being built
+// by every wave of the workgroup.
+enum { PH_VELOCITY = 0, PH_BUOYANCY = 1, PH_GARDNER = 2 };
+constexpr int PH_WAVES = 4;         // waves per workgroup
+constexpr int PH_UNROLL = 4;        // columns a wave loads together
+
+// e[a]: the edge rows j = i - o, o = (-1, 0), (1, 0), (0, -1), (0, 1): {lag o, centre}.  k[a]: the corner rows, a = 2 [sz > 0] + [sx > 0]: {lag o, lag (0, sx) -> cell
+// i - (sz, 0), lag (sz, 0) -> cell i - (0, sx), centre}.  S: the real weight of |u[i]|^2 (velocity alone).
+struct PhCoef { cplx c[9]; cplx e[4][2]; cplx k[4][4]; double S; };
+__host__ __device__ constexpr int ph_ncoef(int mode) { return mode == PH_VELOCITY ? 10 : 33; }
+
+template <int MODE>
+__device__ __forceinline__ void ph_coefficients(const MzParams &P, const cplx *__restrict__ c, const double *__restrict__ rho, const double *__restrict__ chain,
+                                                int iz, int ix, PhCoef &E) {
+    const cplx zero = cmake(0.0, 0.0);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) E.c[k] = zero;
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        E.e[a][0] = E.e[a][1] = zero;
+        E.k[a][0] = E.k[a][1] = E.k[a][2] = E.k[a][3] = zero;
+    }
+    E.S = 0.0;
+    const long long i = (long long)iz * P.nx + ix;
+    const cplx ci = c[i];
+    const cplx kap = mz_kappa(P, ci);
+    const double ch = MODE == PH_GARDNER ? chain[i] : 1.0;
+    const cplx w = MODE != PH_BUOYANCY ? cscale(mz_kappa_dc(P, ci), 1.0 / rho[i]) : zero;       // d K_i / d c_i at the density of the handle
+    if (iz >= 1 && iz <= P.nz - 2 && ix >= 1 && ix <= P.nx - 2) {           // row i: the assembly's star on the unit perturbation
+        double bn[9];
+        cplx Kn[9];
+        if (MODE != PH_BUOYANCY) {
+            const double b0 = 1.0 / rho[i];
+#pragma unroll
+            for (int sz = -1; sz <= 1; ++sz)
+#pragma unroll
+                for (int sx = -1; sx <= 1; ++sx) {
+                    bn[mz_slot(sz, sx)] = (b0 + 1.0 / rho[i + (long long)sz * P.nx + sx]) / 2.0;
+                    Kn[mz_slot(sz, sx)] = zero;
+                }
+            Kn[4] = w;
+            mz_star(P, mz_row_dc_at(P, c, iz, ix), bn, Kn, E.c);
+        }
+        if (MODE != PH_VELOCITY) {
+            cplx more[9];
+#pragma unroll
+            for (int k = 0; k < 9; ++k) { bn[k] = 0.5; Kn[k] = zero; }
+            bn[4] = 1.0;
+            Kn[4] = kap;
+            mz_star(P, mz_row_at(P, c, iz, ix), bn, Kn, more);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) E.c[k] = MODE == PH_GARDNER ? cadd(E.c[k], cscale(more[k], ch)) : more[k];
+        }
+    }
+    double m2 = 0.0;
+#pragma unroll
+    for (int sz = -1; sz <= 1; ++sz)
+#pragma unroll
+        for (int sx = -1; sx <= 1; ++sx) {
+            if (sz == 0 && sx == 0) continue;
+            const int jz = iz - sz, jx = ix - sx;                 // row j sees cell i at the lag (sz, sx)
+            if (jz < 1 || jz > P.nz - 2 || jx < 1 || jx > P.nx - 2) continue;
+            const double m = (sz == 0 || sx == 0) ? MZ_WD : MZ_WE;
+            if (MODE == PH_VELOCITY) { m2 += m * m; continue; }
+            const MzStiff T = mz_stiffness<false>(P, mz_row_at(P, c, jz, jx));
+            const cplx t = sx == 0 ? T.tv[(sz + 1) / 2] : (sz == 0 ? T.th[(sx + 1) / 2] : T.tc[(sz + 1) / 2][(sx + 1) / 2]);
+            cplx lag = cscale(cadd(cscale(kap, m), cscale(t, 0.5)), ch);
+            if (MODE == PH_GARDNER) lag = cadd(lag, cscale(w, m));
+            const cplx ctr = cscale(t, -0.5 * ch);
+            if (sz != 0 && sx != 0) {
+                const int a = 2 * ((sz + 1) / 2) + (sx + 1) / 2;
+                E.k[a][0] = lag;
+                E.k[a][1] = cscale(T.tzx, -0.5 * ch);            // row j's lag (0, sx): the horizontal neighbours take -tzx
+                E.k[a][2] = cscale(T.tzx, 0.5 * ch);             // row j's lag (sz, 0)
+                E.k[a][3] = ctr;
+            } else {
+                const int a = sx == 0 ? (sz + 1) / 2 : 2 + (sx + 1) / 2;
+                E.e[a][0] = lag;
+                E.e[a][1] = ctr;
+            }
+        }
+    if (MODE == PH_VELOCITY) E.S = m2 * (w.x * w.x + w.y * w.y);
+#pragma unroll
+    for (int k = 0; k < 9; ++k) E.c[k] = cconj(E.c[k]);
+#pragma unroll
+    for (int a = 0; a < 4; ++a) {
+        E.e[a][0] = cconj(E.e[a][0]); E.e[a][1] = cconj(E.e[a][1]);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) E.k[a][q] = cconj(E.k[a][q]);
+    }
+}
+
+// the packed order of a cell's coefficients: c[0..8], then (velocity) S, or e[0..3][0..1], k[0..3][0..3]
+template <int MODE, class FN>
+__device__ __forceinline__ void ph_each(PhCoef &E, FN &&fn) {
+#pragma unroll
+    for (int k = 0; k < 9; ++k) fn(k, E.c[k]);
+    if (MODE == PH_VELOCITY) {
+        cplx s = cmake(E.S, 0.0);
+        fn(9, s);
+        E.S = s.x;
+    } else {
+#pragma unroll
+        for (int a = 0; a < 4; ++a) { fn(9 + 2 * a, E.e[a][0]); fn(10 + 2 * a, E.e[a][1]); }
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) fn(17 + 4 * a + q, E.k[a][q]);
+    }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_pseudo_hessian_coefficients(MzParams P, const cplx *__restrict__ c, const double *__restrict__ rho,
+                                                                     const double *__restrict__ chain, cplx *__restrict__ Epk) {
+    const long long N = (long long)P.nz * P.nx;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    PhCoef E;
+    ph_coefficients<MODE>(P, c, rho, chain, (int)(i / P.nx), (int)(i % P.nx), E);
+    ph_each<MODE>(E, [&](int q, cplx &v) { Epk[(long long)q * N + i] = v; });
+}
+
+template <class F, int MODE, bool PACKED>
+__global__ __launch_bounds__(64 * PH_WAVES) void k_pseudo_hessian(F U, int nsrc, long long ld, MzParams P, const cplx *__restrict__ c, const double *__restrict__ rho,
+                                                                  const double *__restrict__ chain, const cplx *__restrict__ Epk, double alpha,
+                                                                  const double *__restrict__ W, double *__restrict__ H) {
+    __shared__ double part[64];
+    const int nz = P.nz, nx = P.nx;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ntx = (nx + OP_TILE_X - 1) / OP_TILE_X;
+    const int x = (int)(blockIdx.x % ntx) * OP_TILE_X + lane - 1, z = (int)(blockIdx.x / ntx);
+    const bool xin = x >= 0 && x < nx;
+    const bool store = lane >= 1 && lane <= OP_TILE_X && x < nx;
+    const long long N = (long long)nz * nx, i = (long long)z * nx + x;
+    PhCoef E;
+    if (store) {
+        if (PACKED) ph_each<MODE>(E, [&](int q, cplx &v) { v = Epk[(long long)q * N + i]; });
+        else ph_coefficients<MODE>(P, c, rho, chain, z, x, E);
+    } else {
+        ph_each<MODE>(E, [&](int, cplx &v) { v = cmake(0.0, 0.0); });       // (a halo lane adds nothing)
+    }
+    double acc = 0.0;
+    const int ngroups = (nsrc + PH_UNROLL - 1) / PH_UNROLL;
+    for (int g = wave; g < ngroups; g += PH_WAVES) {          // (wave-uniform: the lane exchanges stay complete)
+        const int s0 = g * PH_UNROLL, ncol = min(PH_UNROLL, nsrc - s0);
+        typename F::raw raw[PH_UNROLL][3];
+        double sc[PH_UNROLL];
+#pragma unroll
+        for (int j = 0; j < PH_UNROLL; ++j) {
+            sc[j] = U.scale(s0 + min(j, ncol - 1));
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const int zz = z - 1 + r;
+                raw[j][r] = (xin && j < ncol && zz >= 0 && zz < nz) ? U.load((long long)(s0 + j) * ld + (long long)zz * nx + x) : typename F::raw{};
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < PH_UNROLL; ++j) {
+            cplx v[9];                                          // the 3 x 3 block around the lane's cell in the slot order of the operator
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                v[3 * r + 1] = U.scaled(raw[j][r], sc[j]);
+                lane_left_right(v[3 * r + 1], v[3 * r], v[3 * r + 2]);
+            }
+            cplx r0 = cmake(0.0, 0.0);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) cfma(r0, E.c[k], v[k]);
+            double sum = cabs2(r0);
+            if (MODE == PH_VELOCITY) sum += E.S * cabs2(v[4]);
+            else {
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {                   // the edge row j = i - o sits at the slot of -o
+                    const int sz = a < 2 ? 2 * a - 1 : 0, sx = a < 2 ? 0 : 2 * (a - 2) - 1;
+                    cplx r1 = cmul(E.e[a][0], v[4]);
+                    cfma(r1, E.e[a][1], v[mz_slot(-sz, -sx)]);
+                    sum += cabs2(r1);
+                }
+#pragma unroll
+                for (int a = 0; a < 4; ++a) {
+                    const int sz = 2 * (a / 2) - 1, sx = 2 * (a % 2) - 1;
+                    cplx r2 = cmul(E.k[a][0], v[4]);
+                    cfma(r2, E.k[a][1], v[mz_slot(-sz, 0)]);     // j + (0, sx) = i - (sz, 0)
+                    cfma(r2, E.k[a][2], v[mz_slot(0, -sx)]);     // j + (sz, 0) = i - (0, sx)
+                    cfma(r2, E.k[a][3], v[mz_slot(-sz, -sx)]);
+                    sum += cabs2(r2);
+                }
+            }
+            if (j < ncol) acc += sum;
+        }
+    }
+    for (int w = 0; w < PH_WAVES; ++w) {
+        if (wave == w) part[lane] = w == 0 ? acc : part[lane] + acc;
+        __syncthreads();
+    }
+    if (wave == 0 && store) H[i] = H[i] + (W ? alpha * W[i] : alpha) * part[lane];
+}
+
+template <class F>
+static int pseudo_hessian_launch(helm_op *op, F U, size_t esize, const void *dU, int nsrc, long long ld, int mode, const void *dChain, const void *dE, double alpha,
+                                 const void *dW, void *dH, const char *what) {
+    if (!op || !dU || !dH || nsrc < 1 || ld < op->N || !(alpha >= 0.0) || mode < PH_VELOCITY || mode > PH_GARDNER) return HELM_ERR_ARG;
+    if ((mode == PH_GARDNER) != (dChain != nullptr) && !dE) return HELM_ERR_ARG;       // (the chain goes with the Gardner mode alone; packed coefficients carry it)
+    if (int rc = mz_handle_args(op, what)) return rc;
+    if (op->nz < 3 || op->nx < 3 || ((((uintptr_t)dChain) | ((uintptr_t)dW) | ((uintptr_t)dH)) & 7) || (((uintptr_t)dE) & 15)) return HELM_ERR_ARG;
+    const size_t hbytes = (size_t)op->N * 8;
+    if (ranges_overlap(dU, (size_t)nsrc * ld * esize, dH, hbytes) || (dW && ranges_overlap(dW, hbytes, dH, hbytes)) || (dChain && ranges_overlap(dChain, hbytes, dH, hbytes)) ||
+        (dE && ranges_overlap(dE, (size_t)op->N * ph_ncoef(mode) * sizeof(cplx), dH, hbytes)))
+        return HELM_ERR_ARG;
+    MzParams P;
+    if (helm_mz_params(op, &P)) HELM_FAIL(op, HELM_ERR_STATE, "%s: the handle holds no assembled operator", what);
+    HIP_TRY(op, hipSetDevice(op->device));
+    const dim3 grid((unsigned)(((op->nx + OP_TILE_X - 1) / OP_TILE_X) * op->nz)), block(64 * PH_WAVES);
+    const cplx *c = (const cplx *)op->d_c, *E = (const cplx *)dE;
+    const double *rho = (const double *)op->d_rho, *chain = (const double *)dChain, *W = (const double *)dW;
+    double *H = (double *)dH;
+#define PH_GO(MODE) do { \
+        if (E) HELM_LAUNCH((k_pseudo_hessian<F, MODE, true>), grid, block, 0, op->stream, U, nsrc, ld, P, c, rho, chain, E, alpha, W, H); \
+        else HELM_LAUNCH((k_pseudo_hessian<F, MODE, false>), grid, block, 0, op->stream, U, nsrc, ld, P, c, rho, chain, E, alpha, W, H); } while (0)
+    if (mode == PH_VELOCITY) PH_GO(PH_VELOCITY);
+    else if (mode == PH_BUOYANCY) PH_GO(PH_BUOYANCY);
+    else PH_GO(PH_GARDNER);
+#undef PH_GO
+    return launched(op);
+}
+
+// H[i] += alpha (W ? W[i] : 1) sum_{s<nsrc} sum_j |sum_n E_i[j][n] U[s ld + n]|^2 for i < N: U the stored (conjugated) fields, E_i the derivative of the operator the
+// handle holds with respect to the velocity of cell i (mode 0, at the handle's density), to its buoyancy (mode 1), or to its velocity with the buoyancy following
+// it by dChain (mode 2: dChain N float64, NULL otherwise).  dE NULL: the coefficients are built in the kernel; else the array of
+// helm_pseudo_hessian_coefficients_device for the same mode and chain.  Returns when H is complete.
+extern "C" int helm_pseudo_hessian_accumulate_packed_device(helm_op *op, const void *dU, int nsrc, long long ld, int mode, const void *dChain, const void *dE,
+                                                            double alpha, const void *dW, void *dH) {
+    helm_tuning_refresh();
+    if (((uintptr_t)dU) & 15) return HELM_ERR_ARG;
+    return pseudo_hessian_launch(op, FieldC128{(const cplx *)dU}, sizeof(cplx), dU, nsrc, ld, mode, dChain, dE, alpha, dW, dH, "helm_pseudo_hessian_accumulate_device");
+}
+extern "C" int helm_pseudo_hessian_accumulate_packed_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, int mode, const void *dChain,
+                                                                const void *dE, double alpha, const void *dW, void *dH) {
+    helm_tuning_refresh();
+    if (!dExp || (((uintptr_t)dU32) & 7) || (((uintptr_t)dExp) & 3)) return HELM_ERR_ARG;
+    return pseudo_hessian_launch(op, FieldC64{(const cplxf32 *)dU32, (const int *)dExp}, sizeof(cplxf32), dU32, nsrc, ld, mode, dChain, dE, alpha, dW, dH,
+                                 "helm_pseudo_hessian_accumulate_c64_device");
+}
+extern "C" int helm_pseudo_hessian_accumulate_device(helm_op *op, const void *dU, int nsrc, long long ld, int mode, const void *dChain, double alpha, const void *dW,
+                                                     void *dH) {
+    return helm_pseudo_hessian_accumulate_packed_device(op, dU, nsrc, ld, mode, dChain, nullptr, alpha, dW, dH);
+}
+extern "C" int helm_pseudo_hessian_accumulate_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, int mode, const void *dChain,
+                                                         double alpha, const void *dW, void *dH) {
+    return helm_pseudo_hessian_accumulate_packed_c64_device(op, dU32, dExp, nsrc, ld, mode, dChain, nullptr, alpha, dW, dH);
+}
+
+// dE[ph_ncoef(mode)][N] complex128: the coefficients E_i of every cell, what the _packed entry points read (10 planes for mode 0, 33 otherwise)
+extern "C" int helm_pseudo_hessian_coefficients_device(helm_op *op, int mode, const void *dChain, void *dE) {
+    helm_tuning_refresh();
+    if (!op || !dE || mode < PH_VELOCITY || mode > PH_GARDNER || (mode == PH_GARDNER) != (dChain != nullptr)) return HELM_ERR_ARG;
+    if (int rc = mz_handle_args(op, "helm_pseudo_hessian_coefficients_device")) return rc;
+    if (op->nz < 3 || op->nx < 3 || (((uintptr_t)dChain) & 7) || (((uintptr_t)dE) & 15)) return HELM_ERR_ARG;
+    if (dChain && ranges_overlap(dChain, (size_t)op->N * 8, dE, (size_t)op->N * ph_ncoef(mode) * sizeof(cplx))) return HELM_ERR_ARG;
+    MzParams P;
+    if (helm_mz_params(op, &P)) HELM_FAIL(op, HELM_ERR_STATE, "helm_pseudo_hessian_coefficients_device: the handle holds no assembled operator");
+    HIP_TRY(op, hipSetDevice(op->device));
+    const dim3 grid((unsigned)((op->N + 255) / 256));
+    const cplx *c = (const cplx *)op->d_c;
+    const double *rho = (const double *)op->d_rho, *chain = (const double *)dChain;
+    if (mode == PH_VELOCITY) HELM_LAUNCH(k_pseudo_hessian_coefficients<PH_VELOCITY>, grid, dim3(256), 0, op->stream, P, c, rho, chain, (cplx *)dE);
+    else if (mode == PH_BUOYANCY) HELM_LAUNCH(k_pseudo_hessian_coefficients<PH_BUOYANCY>, grid, dim3(256), 0, op->stream, P, c, rho, chain, (cplx *)dE);
+    else HELM_LAUNCH(k_pseudo_hessian_coefficients<PH_GARDNER>, grid, dim3(256), 0, op->stream, P, c, rho, chain, (cplx *)dE);
     return launched(op);
 }

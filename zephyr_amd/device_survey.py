@@ -45,6 +45,7 @@ import scipy.sparse as sp
 
 from . import _lib
 from . import dispatch
+from . import frechet
 from . import parallel
 
 
@@ -766,16 +767,49 @@ def _gradientPlanesFromFields(prob, F, qb, resid, system, velocity=False, chain=
 # H = sum_f w_f (.) sum_s |u_s|^2 of wavefields that are in HBM anyway: `illumination` solves them into the workspace and drops them,
 # `illuminationFromFields` reads a store.  One kernel per item (helm_energy_accumulate_device, or its complex64 form) adds alpha * W (.) sum_s |U_s|^2 to
 # the worker's float64 partial `ws.H`; the store and the workspace hold the unscaled solves, so |scaleTerm|^2 is part of alpha.
+# With linearisation='full' or parameter='rho' the kernel is helm_pseudo_hessian_accumulate_device instead (`_accumulate`): the same item bodies.
 
-def _energyWeight(prob, kind, scale, freqs):
-    """step(ws, op, ifreq) -> (alpha, d_w): what an item's energy kernel multiplies its sum by, alpha a float and d_w the device address of a float64
-    array the worker's cache keeps, or None.  'energy': |scale|^2 and no array.  'pseudoHessian': |gradientScaler|^2 |scale|^2 = omega^4 / |c|^6 |scale|^2
+def _energyWeight(prob, kind, scale, freqs, linearisation='scaler', parameter='c'):
+    """step(ws, op, ifreq) -> (mode, d_chain, alpha, d_w): the accumulate call of an item (`_accumulate`) and what it multiplies its sum by.  mode None: the
+    energy kernel, alpha (.) W (.) sum_s |U_s|^2; else the mode of BaseDiscretization.pseudoHessianAccumulateDevice with its chain.  alpha is a float, d_w and
+    d_chain device addresses of float64 arrays the worker's cache keeps, or None.
+    'energy': |scale|^2 and no array.  'pseudoHessian', linearisation 'scaler': |gradientScaler|^2 |scale|^2 = omega^4 / |c|^6 |scale|^2
     -- with the problem's own scaler W = |1 / c^3|^2 is made once per worker from the cached inv_c3 of _addOnNativeGrid and omega^4 |scale|^2 goes into
     alpha (no torch work per item); otherwise |prob.gradientScaler(ifreq)|^2 is made here, on the calling thread, and uploaded once per worker and
-    frequency.  A step may enqueue torch work; the item body issues the wait_torch_stream."""
+    frequency.  'operator' (the resolved one) with 'c': the closed form, the energy kernel with W = S / |c^3 rho|^2 (S the squared mass weights of the interior
+    rows around a cell) and 4 |omega_d|^4 |scale|^2 in alpha.  'full': the velocity star, with d b / d c of the Gardner density where the config gives none.
+    'rho': the buoyancy star and W = 1 / rho^4.  A step may enqueue torch work; the item body issues the wait_torch_stream."""
     a2 = scale.real * scale.real + scale.imag * scale.imag
     if kind == 'energy':
-        return lambda ws, op, ifreq: (a2, None)
+        return lambda ws, op, ifreq: (None, None, a2, None)
+    if parameter == 'rho':
+        def step(ws, op, ifreq):
+            rho = op.rho
+            W = ws.cached(('ph_inv_rho4', id(rho)), lambda: _lib.to_device(np.broadcast_to(np.asarray(rho, dtype=np.float64).ravel(), (int(op.nrow),)) ** -4.0, ws.device, np.float64),
+                          keep=rho)
+            return 'buoyancy', None, a2, W.data_ptr()
+        return step
+    if linearisation == 'full':
+        gardner = not prob._hasDensity()
+
+        def step(ws, op, ifreq):
+            if not gardner:
+                return 'velocity', None, a2, None
+            cm = op.c
+            ch = ws.cached(('ph_chain', id(cm)), lambda: _lib.to_device(frechet.gardnerChain(np.broadcast_to(np.asarray(cm).ravel(), (int(op.nrow),))), ws.device,
+                                                                        np.float64), keep=cm)
+            return 'gardner', ch.data_ptr(), a2, None
+        return step
+    if linearisation == 'operator':
+        def step(ws, op, ifreq):
+            cm, rho = op.c, op.rho
+            inv = _cachedInverseC3Rho(ws, op)
+            W = ws.cached(('ph_operator_weight', id(cm), id(rho)),
+                          lambda: (inv.real * inv.real + inv.imag * inv.imag) * _lib.to_device(frechet.massWeightSquares(op.nz, op.nx), ws.device, np.float64),
+                          keep=(cm, rho))
+            om = frechet.dampedOmega(op)
+            return None, None, 4.0 * abs(om * om) ** 2 * a2, W.data_ptr()
+        return step
     sv = prob.survey
     if prob._plainGradientScaler():
         def step(ws, op, ifreq):
@@ -783,7 +817,7 @@ def _energyWeight(prob, kind, scale, freqs):
             inv = _cachedInverseCube(ws, cm)
             W = ws.cached(('abs2_inv_c3', id(cm)), lambda: inv.real * inv.real + inv.imag * inv.imag, keep=cm)
             omega = 2 * np.pi * sv.freqs[ifreq]
-            return (omega ** 4) * a2, W.data_ptr()
+            return None, None, (omega ** 4) * a2, W.data_ptr()
         return step
     host = {}
     for ifreq in freqs:
@@ -791,8 +825,17 @@ def _energyWeight(prob, kind, scale, freqs):
         host[ifreq] = np.square(w.real) + np.square(w.imag)
 
     def step(ws, op, ifreq):
-        return a2, ws.cached(('abs2_scaler', ifreq), lambda: _lib.to_device(host[ifreq], ws.device, np.float64)).data_ptr()
+        return None, None, a2, ws.cached(('abs2_scaler', ifreq), lambda: _lib.to_device(host[ifreq], ws.device, np.float64)).data_ptr()
     return step
+
+
+def _accumulate(op, d_u, k, spec, row, d_exp, rows):
+    "the accumulate call a step of `_energyWeight` chose: the energy kernel, or the pseudo-Hessian kernel in its mode"
+    mode, d_chain, alpha, d_w = spec
+    if mode is None:
+        op.energyAccumulateDevice(d_u, k, alpha, d_w, row, d_exp=d_exp, rows=rows)
+    else:
+        op.pseudoHessianAccumulateDevice(d_u, k, mode, d_chain, alpha, d_w, row, d_exp=d_exp, rows=rows)
 
 
 def _energyRow(ws, shape, ifreq):
@@ -812,7 +855,7 @@ def _sumEnergyPartials(prob, parts, shape):
     return parallel.allreduce_sum(h) if prob._sharded else h
 
 
-def illumination(prob, owned, kind, side, perFreq):
+def illumination(prob, owned, kind, side, perFreq, linearisation='scaler', parameter='c'):
     """prob.illumination(u=None) with the wavefields kept in HBM (single-grid surveys): per work item (frequency, column batch) the sparse columns -- the
     sources, or the receiver array used as sources -- are expanded on the item's GPU, solved into the workspace's U and accumulated into the worker's
     partial.  Nothing is stored and only the result comes down."""
@@ -826,7 +869,7 @@ def illumination(prob, owned, kind, side, perFreq):
         q, ncols = sv.getSources(), sv.nsrc
     else:
         q, ncols = sp.csc_matrix(sv.rVec(0, owned[0]).T), sv.nrec            # (one grid: the one matrix of a fixed array; srTerms included, no tsTerms)
-    weight = _energyWeight(prob, kind, scale, owned)
+    weight = _energyWeight(prob, kind, scale, owned, linearisation, parameter)
     devs, items = deviceItems(prob.system, owned, ncols)
 
     def one(ws, op, ifreq, c0, c1):
@@ -834,14 +877,14 @@ def illumination(prob, owned, kind, side, perFreq):
         row = _energyRow(ws, shape, ifreq)
         U, R = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
         _expandColumns(op, q, ifreq, c0, c1, R)
-        alpha, d_w = weight(ws, op, ifreq)
+        spec = weight(ws, op, ifreq)
         _lib.wait_torch_stream(ws.device)                # (covers the zeroed partial and the weight: keep it between the torch work and the library calls)
         op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
-        op.energyAccumulateDevice(U.data_ptr(), k, alpha, d_w, row, rows=Ni)
+        _accumulate(op, U.data_ptr(), k, spec, row, None, Ni)
     return _sumEnergyPartials(prob, [ws.H for ws in runOnDevices(devs, items, one) if ws.H is not None], shape)
 
 
-def illuminationFromFields(prob, F, kind, perFreq):
+def illuminationFromFields(prob, F, kind, perFreq, linearisation='scaler', parameter='c'):
     """prob.illumination(u=F) from forward fields already in HBM: no solve, every item of the store reads its slice where it lies, in either store
     format, and adds it to its worker's partial."""
     F.checkCurrent(prob)
@@ -850,14 +893,14 @@ def illuminationFromFields(prob, F, kind, perFreq):
     shape = (sv.nfreq, N) if perFreq else (N,)
     if not F.items:
         return _sumEnergyPartials(prob, [], shape)
-    weight = _energyWeight(prob, kind, F.scale, F.ownedFreqs)
+    weight = _energyWeight(prob, kind, F.scale, F.ownedFreqs, linearisation, parameter)
     devs, items = _storedItems(prob.system, F)
 
     def one(ws, op, ifreq, c0, c1):
         k, Ni = c1 - c0, int(op.nrow)
         d_uF, d_exp = F.pointers(ifreq, c0)
         row = _energyRow(ws, shape, ifreq)
-        alpha, d_w = weight(ws, op, ifreq)
+        spec = weight(ws, op, ifreq)
         _lib.wait_torch_stream(ws.device)
-        op.energyAccumulateDevice(d_uF, k, alpha, d_w, row, d_exp=d_exp, rows=Ni)
+        _accumulate(op, d_uF, k, spec, row, d_exp, Ni)
     return _sumEnergyPartials(prob, [ws.H for ws in runOnDevices(devs, items, one, factor=False) if ws.H is not None], shape)

@@ -402,6 +402,25 @@ class BaseDiscretization(BaseModelDependent):
         w = complex(w)
         _lib.check(_lib.load().helm_velocity_adjoint_device(self.handle, ctypes.c_void_p(d_p), w.real, w.imag, 1 if conj else 0, ctypes.c_void_p(d_g)), self.handle)
 
+    PSEUDO_HESSIAN_MODES = {'velocity': 0, 'buoyancy': 1, 'gardner': 2}
+
+    def pseudoHessianAccumulateDevice(self, d_u, nsrc, mode, d_chain, alpha, d_w, d_h, d_exp=None, rows=None):
+        """H += alpha * W * sum_s ||(d A / d p_i) u^_s||^2 on the device, frechet.pseudoHessianDiagonal on the stored columns conj(u^): d_u [nsrc][rows]
+        complex128 (d_exp given: a complex64 store with those column exponents), mode 'velocity' (p = c at the density of the operator), 'buoyancy' (p = b)
+        or 'gardner' (p = c with d b / d c = d_chain, nrow float64; None otherwise), d_w (None: no weight) and d_h nrow float64, alpha >= 0.  All device
+        pointers; returns when H is complete.  2-D MiniZephyr operators."""
+        lib = _lib.load()
+        rows = int(self.nrow if rows is None else rows)
+        mode = self.PSEUDO_HESSIAN_MODES[mode]
+        w = None if d_w is None else ctypes.c_void_p(d_w)
+        ch = None if d_chain is None else ctypes.c_void_p(d_chain)
+        if d_exp is not None:
+            _lib.check(lib.helm_pseudo_hessian_accumulate_c64_device(self.handle, ctypes.c_void_p(d_u), ctypes.c_void_p(d_exp), int(nsrc), rows, mode, ch,
+                                                                     float(alpha), w, ctypes.c_void_p(d_h)), self.handle)
+            return
+        _lib.check(lib.helm_pseudo_hessian_accumulate_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), rows, mode, ch, float(alpha), w, ctypes.c_void_p(d_h)),
+                   self.handle)
+
     def packDevice(self, d_u, nsrc, d_out, d_exp, rows=None):
         """The complex64 store of the wavefields d_u ([nsrc][rows] complex128): d_out [nsrc][rows] complex64 values x * 2^-e_s, d_exp the nsrc int32 column
         exponents e_s (fieldstore.pack_reference states the format).  All device pointers; returns when both are complete."""

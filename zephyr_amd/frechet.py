@@ -340,3 +340,80 @@ def velocityAdjoint(op, P, dtype=np.complex128, magnitude=False, conj=False):
         stiff = stiff + (b + _at(b, sz, sx)) / 2 * q             # (zero on the boundary lines: the planes are zero there)
         mass = mass + (me if sz and sx else md) * _at(Pl[slot[o]], -sz, -sx)
     return (stiff + w * mass).ravel()
+
+
+# ---- the pseudo-Hessian diagonal of the exact derivatives ------------------------------------------------------------------------------------------
+# H_p[i] = sum_s || (d A / d p_i) u_s ||^2 (Shin, Jang & Min 2001, on the operator that is differentiated).  A unit perturbation of cell i touches only the
+# rows of the 3 x 3 block around i, and in those only the lags that point back into the block, so cells with equal (iz mod 3, ix mod 3) have disjoint
+# supports: the planes of the nine colour indicators, `applyPlanes`, |.|^2 and a 3 x 3 box sum give H exactly.  k_pseudo_hessian (csrc/survey.hip) is the
+# device kernel; it builds the per-cell coefficients instead.
+
+def _boxSum(e, nz, nx):
+    "sum of e (nz, nx) over the 3 x 3 block around every cell, cells outside the grid contributing nothing; the nine lags in the order of LAGS"
+    out = np.zeros_like(e)
+    for sz, sx in LAGS:
+        out = out + _at(e, sz, sx)
+    return out
+
+
+def colourSum(nz, nx, planes, u, magnitude=False, box=True):
+    """H[i] = sum_s sum_j |((d A)_i u_s)[j]|^2 over the rows j of the 3 x 3 block around i (box False: row i alone) from planes(v) -> (9, nz, nx), the planes of
+    d A along the field v, evaluated on the nine colour indicators.  u (N, nsrc) in the arithmetic the planes are in; magnitude: u >= 0 real and the planes
+    those of moduli, the squares plain."""
+    N = nz * nx
+    iz, ix = np.divmod(np.arange(N), nx)
+    H = None
+    for a in range(3):
+        for b in range(3):
+            mine = (iz % 3 == a) & (ix % 3 == b)
+            if not mine.any():
+                continue
+            r = applyPlanes(planes(mine.astype(np.float64)), u, nz, nx)
+            e = (np.square(r) if magnitude else np.square(r.real) + np.square(r.imag)).sum(axis=1).reshape((nz, nx))
+            if box:
+                e = _boxSum(e, nz, nx)
+            H = np.zeros(N, dtype=e.dtype) if H is None else H
+            H[mine] = e.ravel()[mine]
+    return H
+
+
+def pseudoHessianDiagonal(op, u, parameter='c', chain=None, dtype=np.complex128, magnitude=False):
+    """H (N,), real in the arithmetic of dtype: H[i] = sum_s || (d A / d p_i) u_s ||_2^2 for the 2-D MiniZephyr operator `op` and the columns u (N,) or
+    (N, nsrc) -- the unscaled solves u^, not the stored conjugates.  parameter 'c': the planes of `velocityPlanes` (mass term and PML stretch at the density of
+    the operator; chain (N,) = d b / d c where the density follows c, whose buoyancy planes are added).  parameter 'b': those of `buoyancyPlanes`; 'rho':
+    along -e_i / rho_i^2, i.e. H_b[i] / rho_i^4, in density units.  magnitude: sum_s sum_j (sum_n |E_i[j][n]| |u_s[n]|)^2, what bounds the rounding of the sum."""
+    if parameter not in ('c', 'rho', 'b'):
+        raise ValueError('parameter is %r: \'c\', \'rho\' or \'b\'' % (parameter,))
+    nz, nx = int(op.nz), int(op.nx)
+    R = _real(dtype)
+    ua = np.asarray(u).reshape((nz * nx, -1))
+    ua = np.abs(ua.astype(dtype)).astype(R) if magnitude else ua.astype(dtype)
+    if parameter == 'c':
+        ch = None if chain is None else np.asarray(chain, dtype=np.float64).ravel()
+        planes = lambda v: velocityPlanes(op, v, None if ch is None else ch * v, dtype, magnitude)
+    else:
+        planes = lambda v: buoyancyPlanes(op, v, dtype, magnitude)
+    H = colourSum(nz, nx, planes, ua, magnitude)
+    if parameter == 'rho':
+        rho = np.broadcast_to(np.asarray(op.rho, dtype=np.float64), (nz, nx)).astype(R).ravel()
+        H = H / (rho * rho * rho * rho)
+    return H
+
+
+def massWeightSquares(nz, nx):
+    "S (N,) float64: the sum of m_k^2 over the interior rows of the 3 x 3 block around every cell, m the mass weights (centre, edges, corners)"
+    nz, nx = int(nz), int(nx)
+    inside = _interiorMask(nz, nx).astype(np.float64)
+    mc, md, me = MZ_MASS
+    S = np.zeros((nz, nx))
+    for sz, sx in LAGS:
+        m = mc if (sz, sx) == (0, 0) else (md if sz == 0 or sx == 0 else me)
+        S = S + (m * m) * _at(inside, sz, sx)
+    return S.ravel()
+
+
+def operatorPseudoHessianWeight(op):
+    """|w_i|^2 S_i, float64 (N,): the pseudo-Hessian diagonal of the mass term alone (linearisation='operator', parameter='c') is this times sum_s |u_s[i]|^2.
+    (dA) u = mask_int M0(w e_i u) puts m_k w_i u[i] into the interior rows of the block around i: w = `operatorWeight`, S = `massWeightSquares`."""
+    w = operatorWeight(op)
+    return (np.square(w.real) + np.square(w.imag)) * massWeightSquares(op.nz, op.nx)

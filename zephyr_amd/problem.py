@@ -32,6 +32,7 @@ from .fieldstore import DeviceFields
 from .frechet import MZ_MASS, maskInterior, massStencil, operatorWeight      # noqa: F401 (what linearisation='operator' is made of)
 from .frechet import applyPlanes, buoyancyAdjoint, buoyancyPlanes, lagProducts      # (and what parameter='rho' is made of)
 from .frechet import gardnerChain, velocityAdjoint, velocityPlanes                  # (and linearisation='full')
+from .frechet import operatorPseudoHessianWeight, pseudoHessianDiagonal              # (and the pseudo-Hessian diagonal of either)
 
 EPS = 1e-15
 
@@ -618,7 +619,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             return self.Jtvec(None, d, u=F, adjoint='transpose', linearisation=linearisation, parameter=pout)
 
     # ---- illumination / diagonal pseudo-Hessian ------------------------------------------------------------
-    def illumination(self, m=None, u=None, kind='pseudoHessian', side='source', perFreq=False):
+    def illumination(self, m=None, u=None, kind='pseudoHessian', side='source', perFreq=False, linearisation='scaler', parameter='c'):
         """What an FWI gradient is divided by: float64 (N,), or (nfreq, N) with perFreq, every entry >= 0.  With uF[f] = fields()[f] and
         E_f[i] = sum_s |uF[f][i, s]|^2:
 
@@ -629,6 +630,16 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         side 'receiver': the same with the receiver array as sources, uR_f = scaleTerm * (sub_f * rVec(0, f).T) -- srTerms included, no tsTerms; fixed
         arrays only, and u must be None.  A preconditioned gradient is g / (H + lambda * H.max()).
 
+        linearisation / parameter (kind 'pseudoHessian' only; the defaults are the weight above, which belongs to the 'scaler' gradient): the pseudo-Hessian
+        diagonal of the derivative that Jtvec(adjoint='transpose', linearisation=, parameter=) is the gradient of,
+
+            H_p[i] = |scaleTerm|^2 sum_f sum_s || (d A_f / d p_i) u^_s ||_2^2,     u^_s = A_f^-1 premul q_s,
+
+        with d A_f / d p_i the planes of frechet.velocityPlanes along e_i ('full': mass term, PML stretch and the Gardner density where the config gives
+        none), its mass term alone ('operator': the closed form |d K_i / d c|^2 S_i sum_s |u^_s[i]|^2), or of frechet.buoyancyPlanes along -e_i / rho_i^2
+        (parameter='rho': density units).  For 'scaler' d A / d c_i is the diagonal weight and this is the formula above.  Served and refused as JvecBorn
+        (`_resolveLinearisation`); the same routes, sides and perFreq as the default.
+
         u a DeviceFields (fieldsDevice): no solve, the store is read where it lies.  u None with the device path on a single-grid survey: the fields are
         solved into HBM, accumulated there and dropped; only the result comes down.  Otherwise (u a list of host arrays, no GPU, hostGradient, a host ky
         reduction, a multiscale survey): numpy on the host."""
@@ -637,6 +648,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             raise ValueError('kind is %r: \'energy\' or \'pseudoHessian\'' % (kind,))
         if side not in ('source', 'receiver'):
             raise ValueError('side is %r: \'source\' or \'receiver\'' % (side,))
+        self._checkLinearisation(linearisation)
+        self._checkParameter(parameter, linearisation)
+        if kind == 'energy' and (linearisation != 'scaler' or parameter != 'c'):
+            raise ValueError('kind=\'energy\' has no linearisation: linearisation=%r, parameter=%r go with kind=\'pseudoHessian\'' % (linearisation, parameter))
         sv = self.survey
         if side == 'receiver':
             if u is not None:
@@ -644,12 +659,14 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             if sv.mode != 'fixed':
                 raise ValueError('the receiver-side illumination serves fixed receiver arrays (mode is %r)' % (sv.mode,))
         self.updateModel(m)
+        if linearisation != 'scaler':
+            linearisation = self._resolveLinearisation(linearisation, parameter, 'illumination')
         owned = self.ownedFreqs
         if isinstance(u, DeviceFields):
             u.checkCurrent(self)
-            return device_survey.illuminationFromFields(self, u, kind, bool(perFreq))
+            return device_survey.illuminationFromFields(self, u, kind, bool(perFreq), linearisation, parameter)
         if u is None and not isinstance(sv, HelmMultiGridSurvey) and self._deviceGradientAvailable():
-            return device_survey.illumination(self, owned, kind, side, bool(perFreq))
+            return device_survey.illumination(self, owned, kind, side, bool(perFreq), linearisation, parameter)
         nf = sv.nfreq
         H = np.zeros((nf, self.nrow) if perFreq else self.nrow, dtype=np.float64)
         if u is None:
@@ -662,8 +679,11 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         for ifreq, uf in fieldsOf:
             uf = np.asarray(uf)
             uf = uf.reshape((uf.shape[0], -1))
-            E = np.add.reduce(np.square(uf.real) + np.square(uf.imag), axis=1)          # (no BLAS: _norm2 says why)
-            if kind == 'pseudoHessian':
+            if linearisation != 'scaler':
+                E = self._pseudoHessianHost(ifreq, uf, linearisation, parameter)
+            else:
+                E = np.add.reduce(np.square(uf.real) + np.square(uf.imag), axis=1)      # (no BLAS: _norm2 says why)
+            if kind == 'pseudoHessian' and linearisation == 'scaler':
                 w = np.asarray(self.gradientScaler(ifreq)).ravel()
                 E = (np.square(w.real) + np.square(w.imag)) * E
             if perFreq:
@@ -673,6 +693,17 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if self._sharded:
             H = parallel.allreduce_sum(H)
         return H
+
+    def _pseudoHessianHost(self, ifreq, uf, linearisation, parameter):
+        "one frequency's term of illumination(linearisation='operator' | 'full') on the host: uf = scaleTerm conj(u^) (N, ncols), the resolved linearisation"
+        st = complex(self.system.scaleTerm)
+        sub = self.system.subProblems[ifreq]
+        uh = np.conj(uf / st)
+        if linearisation == 'operator' and parameter == 'c':
+            H = operatorPseudoHessianWeight(sub) * np.add.reduce(np.square(uh.real) + np.square(uh.imag), axis=1)
+        else:
+            H = pseudoHessianDiagonal(sub, uh, parameter, self._gardnerChain() if parameter == 'c' else None)
+        return (st.real * st.real + st.imag * st.imag) * H
 
     # ---- device-resident gradient (mux branch) -------------------------------------------------------------
     def _deviceGradientAvailable(self):
