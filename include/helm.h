@@ -362,6 +362,28 @@ int helm_pseudo_hessian_accumulate_packed_device(helm_op *op, const void *dU, in
 int helm_pseudo_hessian_accumulate_packed_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, int mode, const void *dChain,
                                                      const void *dE, double alpha, const void *dW, void *dH);
 
+/* --- the exact diagonal of the Gauss-Newton Hessian (HelmBaseProblem.illumination with kind='gaussNewton') --------------------------------------------
+ * H[i] = sum_s sum_r |g_r^T (d A / d p_i) u^_s|^2 factorises through the 3 x 3 block around i: with Gamma and Phi the Gram blocks of the receiver Green's
+ * functions g_r and of the forward solves u^_s over the cells of the block it is Re tr(E_i^H Gamma_i E_i Phi_i), and two cells of a block are at most two steps
+ * apart in either direction, so both are read off the autocorrelation planes at the lags of (-2..2)^2.
+ *
+ * helm_lag_gram_accumulate_device:  C[l][i] += sum_{s<nsrc} U[s ld + i] conj(U[s ld + i + off_l]) for the 13 lags of the half plane, l = 0..2: (0, 0..2),
+ *     l = 3..7: (1, -2..2), l = 8..12: (2, -2..2) as (dz, dx), and every cell i whose partner i + off_l is inside the grid; the other entries are not touched (the
+ *     other twelve lags are the conjugates, read at the shifted cell).  U: nsrc columns of ld >= N complex128 (or, _c64, complex64 values with the int32 column
+ *     exponents dExp of helm_pack_c64_device); C: 13 N complex128.
+ * helm_gauss_newton_diagonal_device:  H[i] += alpha (dW ? W[i] : 1) Re tr(E_i^H Gamma_i E_i Phi_i), Phi from the planes dCu and Gamma from the planes dCg (13 N
+ *     complex128 each, of the stored conjugates: the coefficients are conjugated instead).  E_i by mode: 0, 1, 2 as helm_pseudo_hessian_accumulate_device (the
+ *     velocity modes with the eight mass rows m_o (d kappa_i / dc) b_i in full); 3 the mass term alone; 4 the unit diagonal, H[i] += alpha W[i] Gamma[i, i] Phi[i, i].
+ *     dChain: N float64 with mode 2, NULL otherwise.  W, H: N float64; alpha >= 0.
+ *
+ * Plain fp64 in a fixed order, one writer per entry, no atomics: the same bits on every run.  HELM_ERR_STATE before the first helm_assemble (the diagonal); Eurus,
+ * 3-D and ny > 0 handles HELM_ERR_UNSUPPORTED; null (other than dChain, dW), misaligned (U, C: 16, U32: 8, dExp: 4, the rest 8) or overlapping pointers, nsrc < 1,
+ * ld < N, a negative or NaN alpha, a mode outside 0..4, a chain without mode 2 (or the reverse) and grids below 3 x 3 (the diagonal) HELM_ERR_ARG.  All device
+ * pointers; each call returns when its result is complete. */
+int helm_lag_gram_accumulate_device(helm_op *op, const void *dU, int nsrc, long long ld, void *dC);
+int helm_lag_gram_accumulate_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, void *dC);
+int helm_gauss_newton_diagonal_device(helm_op *op, int mode, const void *dChain, const void *dW, const void *dCu, const void *dCg, double alpha, void *dH);
+
 /* --- device-resident callers: sparse sources in, receiver samples out ---------------------------------- */
 /* Dense right-hand sides from the COO triplets of the reference's sparse source matrix (survey.py:162-169,
  * source.py:213-317): R (nrhs x rows, zeroed by the call), R[col[k]][row[k]] = val[k]; no duplicate entries.

@@ -27,6 +27,8 @@ The eight pipelines, one row each.  Every row is a body of its own made of the s
                                                                                                       (no `rho`: and L^T P into Gb)         (and one Gb)
     illumination            dealt                source or receiver columns          k                energy kernel                         one partial H per worker
     illuminationFromFields  stored               --                                  0                -- (energy kernel reads the slice)    one partial H per worker
+      kind='gaussNewton'                         receiver columns, once per worker   nrec, once per   lag Gram of the slice, then the       one partial H per worker
+                                                 and frequency                       worker and freq. combine kernel
 
 Three rules hold everywhere below.  The shared steps carry them, so that a new pipeline inherits them with the steps it calls, and
 tests/test_gpu_pipeline_order.py holds the order of library calls and waits of every item against a recorded one.
@@ -549,9 +551,10 @@ def _factorBytes(op):
     return one * (len(subs) if subs is not None and not getattr(op, 'kyRelease', False) else 1)
 
 
-def _checkSecondFactorsFit(items, planes=0):
+def _checkSecondFactorsFit(items, planes=0, cols=None):
     """MemoryError unless every GPU has room for what a pass through the TRANSPOSED operators adds to a resident forward pass: their factors -- the factors of
-    A and of A^T are held side by side -- and the item's U and R (planes: and that many model-sized complex128 planes, the lag products of parameter='rho')"""
+    A and of A^T are held side by side -- and the item's U and R (planes: and that many model-sized complex128 planes, the lag products of parameter='rho';
+    cols: the columns solved per item where they are not the item's own, the receiver columns of kind='gaussNewton')"""
     seen = set()
 
     def factors(op, c0, c1):
@@ -559,7 +562,7 @@ def _checkSecondFactorsFit(items, planes=0):
         first = id(op) not in seen
         seen.add(id(op))
         return _factorBytes(op) if first and not op.factors and str(getattr(op, 'method', 'auto')).lower() in ('auto', 'direct') else 0
-    _checkItemsFit(items, held=factors, work=lambda op, c0, c1: (2 * (c1 - c0) + planes) * int(op.nrow) * 16)
+    _checkItemsFit(items, held=factors, work=lambda op, c0, c1: (2 * (c1 - c0 if cols is None else cols) + planes) * int(op.nrow) * 16)
 
 
 def gradientFromFields(prob, F, qb, resid, system=None, linearisation='scaler', parameter='c', chain=None):
@@ -768,6 +771,9 @@ def _gradientPlanesFromFields(prob, F, qb, resid, system, velocity=False, chain=
 # `illuminationFromFields` reads a store.  One kernel per item (helm_energy_accumulate_device, or its complex64 form) adds alpha * W (.) sum_s |U_s|^2 to
 # the worker's float64 partial `ws.H`; the store and the workspace hold the unscaled solves, so |scaleTerm|^2 is part of alpha.
 # With linearisation='full' or parameter='rho' the kernel is helm_pseudo_hessian_accumulate_device instead (`_accumulate`): the same item bodies.
+# kind='gaussNewton' (the exact diagonal of J^T J) reads a store through the TRANSPOSED operators' items: per item k_lag_gram makes the 13 autocorrelation planes
+# of the slice and k_gauss_newton_diagonal combines them with the planes of the receiver Green's functions, which the worker makes once per frequency and call
+# (`_receiverGram`); `illumination` solves the store first and drops it.
 
 def _energyWeight(prob, kind, scale, freqs, linearisation='scaler', parameter='c'):
     """step(ws, op, ifreq) -> (mode, d_chain, alpha, d_w): the accumulate call of an item (`_accumulate`) and what it multiplies its sum by.  mode None: the
@@ -782,6 +788,19 @@ def _energyWeight(prob, kind, scale, freqs, linearisation='scaler', parameter='c
     a2 = scale.real * scale.real + scale.imag * scale.imag
     if kind == 'energy':
         return lambda ws, op, ifreq: (None, None, a2, None)
+    if kind == 'gaussNewton':
+        # (mode, d_chain, alpha, d_w) of BaseDiscretization.gaussNewtonDiagonalDevice from the pseudo-Hessian's: the same star, chain and density weight.  The
+        # planes of the receiver columns are those of conj(premul g_r), so the exact derivatives divide |premul|^2 out; the diagonal weight of 'scaler' keeps
+        # it (its data carry premul) and takes |scale|^2 once more, for the scaled virtual source; the mass term alone has a mode of its own and no weight
+        base = _energyWeight(prob, 'pseudoHessian', scale, freqs, linearisation, parameter)
+
+        def step(ws, op, ifreq):
+            mode, d_chain, alpha, d_w = base(ws, op, ifreq) if not (linearisation == 'operator' and parameter == 'c') else ('mass', None, a2, None)
+            if mode is None:
+                return 'diagonal', None, abs(alpha) * a2, d_w          # (|omega^2|^2: a damped frequency is complex)
+            pm = complex(op.premul)
+            return mode, d_chain, alpha / (pm.real * pm.real + pm.imag * pm.imag), d_w
+        return step
     if parameter == 'rho':
         def step(ws, op, ifreq):
             rho = op.rho
@@ -855,6 +874,33 @@ def _sumEnergyPartials(prob, parts, shape):
     return parallel.allreduce_sum(h) if prob._sharded else h
 
 
+def _receiverGram(prob, freqs):
+    """gram(ws, op, ifreq) -> the 13 planes Gamma_f (a complex128 tensor the worker's cache keeps for the call) of kind='gaussNewton': the nrec columns of the
+    fixed array's rVec(0, f).T expanded as back-sources are, solved with the TRANSPOSED operator `op` into the workspace, and one k_lag_gram into zeroed planes.
+    The matrices are made here, on the calling thread.  gram issues its own wait_torch_stream before its library calls and returns when the planes are complete."""
+    import torch
+    sv = prob.survey
+    nrec = sv.nrec
+    q = {}
+    for ifreq in freqs:
+        gk = sv._gridKey(ifreq)
+        if gk not in q:
+            q[gk] = sp.csc_matrix(sv.rVec(0, ifreq).T)
+
+    def gram(ws, op, ifreq):
+        def make():
+            Ni = int(op.nrow)
+            U, R = ws.buffer('U', nrec * Ni), ws.buffer('R', nrec * Ni)
+            Cg = torch.zeros(13 * Ni, dtype=torch.complex128, device=ws.device)
+            _expandColumns(op, q[sv._gridKey(ifreq)], ifreq, 0, nrec, R)
+            _lib.wait_torch_stream(ws.device)
+            op.solveDevice(R.data_ptr(), U.data_ptr(), nrec, Ni)
+            op.lagGramAccumulateDevice(U.data_ptr(), nrec, Cg.data_ptr(), rows=Ni)
+            return Cg
+        return ws.cached(('gn_gamma', ifreq), make)
+    return gram
+
+
 def illumination(prob, owned, kind, side, perFreq, linearisation='scaler', parameter='c'):
     """prob.illumination(u=None) with the wavefields kept in HBM (single-grid surveys): per work item (frequency, column batch) the sparse columns -- the
     sources, or the receiver array used as sources -- are expanded on the item's GPU, solved into the workspace's U and accumulated into the worker's
@@ -862,6 +908,13 @@ def illumination(prob, owned, kind, side, perFreq, linearisation='scaler', param
     sv = prob.survey
     N = prob.nrow
     shape = (sv.nfreq, N) if perFreq else (N,)
+    if kind == 'gaussNewton':
+        # two sets of columns per frequency through two sets of factors: the forward fields go into a store, which `illuminationFromFields` reads and this call drops
+        F = fields(prob, owned, prob.fieldsDtype)
+        try:
+            return illuminationFromFields(prob, F, kind, perFreq, linearisation, parameter)
+        finally:
+            F.release()
     if not owned:
         return _sumEnergyPartials(prob, [], shape)
     scale = complex(prob.system.scaleTerm)
@@ -894,6 +947,25 @@ def illuminationFromFields(prob, F, kind, perFreq, linearisation='scaler', param
     if not F.items:
         return _sumEnergyPartials(prob, [], shape)
     weight = _energyWeight(prob, kind, F.scale, F.ownedFreqs, linearisation, parameter)
+    if kind == 'gaussNewton':
+        # the items of the TRANSPOSED operators (the same devices and replicas: every item finds its slice on its own GPU), which solve the receiver columns;
+        # the two kernels need an assembled 2-D MiniZephyr handle of the frequency, which those are
+        gram = _receiverGram(prob, F.ownedFreqs)
+        devs, items = _storedItems(prob.adjointSystem, F)
+        _checkSecondFactorsFit(items, planes=26, cols=sv.nrec)
+
+        def one(ws, op, ifreq, c0, c1):
+            k, Ni = c1 - c0, int(op.nrow)
+            d_uF, d_exp = F.pointers(ifreq, c0)
+            row = _energyRow(ws, shape, ifreq)
+            mode, d_chain, alpha, d_w = weight(ws, op, ifreq)
+            Cu = ws.buffer('gram', 13 * Ni)
+            Cu.zero_()
+            Cg = gram(ws, op, ifreq)
+            _lib.wait_torch_stream(ws.device)
+            op.lagGramAccumulateDevice(d_uF, k, Cu.data_ptr(), d_exp=d_exp, rows=Ni)
+            op.gaussNewtonDiagonalDevice(mode, d_chain, d_w, Cu.data_ptr(), Cg.data_ptr(), alpha, row)
+        return _sumEnergyPartials(prob, [ws.H for ws in runOnDevices(devs, items, one) if ws.H is not None], shape)
     devs, items = _storedItems(prob.system, F)
 
     def one(ws, op, ifreq, c0, c1):

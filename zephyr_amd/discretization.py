@@ -421,6 +421,28 @@ class BaseDiscretization(BaseModelDependent):
         _lib.check(lib.helm_pseudo_hessian_accumulate_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), rows, mode, ch, float(alpha), w, ctypes.c_void_p(d_h)),
                    self.handle)
 
+    GAUSS_NEWTON_MODES = {'velocity': 0, 'buoyancy': 1, 'gardner': 2, 'mass': 3, 'diagonal': 4}
+
+    def lagGramAccumulateDevice(self, d_u, nsrc, d_c, d_exp=None, rows=None):
+        """C_l += sum_s U[s] (.) conj(shift_l(U[s])) on the device for the 13 lags of frechet.GRAM_LAGS, wherever the partner is inside the grid (frechet.lagGram):
+        d_u [nsrc][rows] complex128 (d_exp given: a complex64 store with those column exponents), d_c 13 nrow complex128.  All device pointers; returns when C
+        is complete.  2-D MiniZephyr operators."""
+        lib = _lib.load()
+        rows = int(self.nrow if rows is None else rows)
+        if d_exp is not None:
+            _lib.check(lib.helm_lag_gram_accumulate_c64_device(self.handle, ctypes.c_void_p(d_u), ctypes.c_void_p(d_exp), int(nsrc), rows, ctypes.c_void_p(d_c)), self.handle)
+            return
+        _lib.check(lib.helm_lag_gram_accumulate_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), rows, ctypes.c_void_p(d_c)), self.handle)
+
+    def gaussNewtonDiagonalDevice(self, mode, d_chain, d_w, d_cu, d_cg, alpha, d_h):
+        """H += alpha * W * Re tr(E^H Gamma E Phi) per cell on the device, frechet.gaussNewtonDiagonal: d_cu and d_cg the planes of lagGramAccumulateDevice of the
+        stored columns and of the transposed solves of the receiver rows (13 nrow complex128 each), mode 'velocity', 'buoyancy', 'gardner' (d_chain nrow float64;
+        None otherwise), 'mass' (the mass term alone) or 'diagonal' (W the squared weight), d_w (None: no weight) and d_h nrow float64, alpha >= 0."""
+        w = None if d_w is None else ctypes.c_void_p(d_w)
+        ch = None if d_chain is None else ctypes.c_void_p(d_chain)
+        _lib.check(_lib.load().helm_gauss_newton_diagonal_device(self.handle, self.GAUSS_NEWTON_MODES[mode], ch, w, ctypes.c_void_p(d_cu), ctypes.c_void_p(d_cg),
+                                                                 float(alpha), ctypes.c_void_p(d_h)), self.handle)
+
     def packDevice(self, d_u, nsrc, d_out, d_exp, rows=None):
         """The complex64 store of the wavefields d_u ([nsrc][rows] complex128): d_out [nsrc][rows] complex64 values x * 2^-e_s, d_exp the nsrc int32 column
         exponents e_s (fieldstore.pack_reference states the format).  All device pointers; returns when both are complete."""

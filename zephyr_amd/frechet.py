@@ -417,3 +417,123 @@ def operatorPseudoHessianWeight(op):
     (dA) u = mask_int M0(w e_i u) puts m_k w_i u[i] into the interior rows of the block around i: w = `operatorWeight`, S = `massWeightSquares`."""
     w = operatorWeight(op)
     return (np.square(w.real) + np.square(w.imag)) * massWeightSquares(op.nz, op.nx)
+
+
+# ---- the exact diagonal of the Gauss-Newton Hessian ------------------------------------------------------------------------------------------------
+# H[i] = sum_s sum_r |g_r^T E_i u_s|^2 with E_i = d A / d p_i, u_s = A^-1 premul q_s and g_r = A^-T R_r^H the receiver Green's functions.  E_i lives on the rows
+# and columns of the 3 x 3 block around i (the section above), so with Gamma_i[j, j'] = sum_r g_r[j] conj(g_r[j']) and Phi_i[n, n'] = sum_s u_s[n] conj(u_s[n'])
+# over the cells of that block
+#     H[i] = Re sum_(j, n, j', n') conj(E_i[j', n']) Gamma_i[j, j'] E_i[j, n] Phi_i[n, n'] = Re tr(E^H Gamma^T E Phi).
+# Two cells of a block are at most two steps apart in either direction: Gamma and Phi are read off the autocorrelation planes at the 25 lags of (-2..2)^2, 13 of
+# which are stored (`lagGram`; the others are conjugates read at the shifted cell).  k_lag_gram and k_gauss_newton_diagonal (csrc/survey.hip) are the device
+# kernels; conjugating both sets of planes and the coefficients together leaves H as it is, which is how they read the stored conjugates.
+GRAM_LAGS = [(0, 0), (0, 1), (0, 2)] + [(dz, dx) for dz in (1, 2) for dx in (-2, -1, 0, 1, 2)]      # the stored half plane: plane l pairs cell i with i + GRAM_LAGS[l]
+
+
+def lagGram(u, nz, nx, dtype=np.complex128, magnitude=False):
+    """C (13, N): C[l][i] = sum_s u[i, s] conj(u[i + off_l, s]) for the 13 lags of GRAM_LAGS, zero where i + off_l is outside the grid.  u (N,) or (N, ncols).
+    magnitude: sum_s |u[i, s]| |u[i + off_l, s]|, real."""
+    nz, nx = int(nz), int(nx)
+    ua = np.asarray(u).reshape((nz, nx, -1)).astype(dtype)
+    if magnitude:
+        ua = np.abs(ua)
+    C = np.zeros((len(GRAM_LAGS), nz, nx), dtype=ua.dtype)
+    for l, (dz, dx) in enumerate(GRAM_LAGS):
+        C[l] = (ua * np.conj(_at(ua, dz, dx))).sum(axis=2)
+    return C.reshape((len(GRAM_LAGS), nz * nx))
+
+
+def _gramBlocks(C, nz, nx):
+    "B (N, 9, 9): B[i, p, q] = sum_s u[i + o_p] conj(u[i + o_q]) over the slots of LAGS from the planes of `lagGram`; zero where either cell is outside the grid"
+    Cl = np.asarray(C).reshape((len(GRAM_LAGS), nz, nx))
+    where = {o: l for l, o in enumerate(GRAM_LAGS)}
+    B = np.zeros((nz, nx, 9, 9), dtype=Cl.dtype)
+    for p, (pz, px) in enumerate(LAGS):
+        for q, (qz, qx) in enumerate(LAGS):
+            lag = (qz - pz, qx - px)
+            if lag in where:
+                B[:, :, p, q] = _at(Cl[where[lag]], pz, px)
+            else:
+                B[:, :, p, q] = np.conj(_at(Cl[where[(-lag[0], -lag[1])]], qz, qx))
+    return B.reshape((nz * nx, 9, 9))
+
+
+def massPlanes(op, dc, dtype=np.complex128, magnitude=False):
+    "the nine planes of linearisation='operator': the mass terms m_k (d kappa / dc) b dc of the neighbouring cell alone (`velocityPlanes` without the stretch)"
+    nz, nx = int(op.nz), int(op.nx)
+    R = _real(dtype)
+    dkb = massWeightDc(op, dtype) * _buoyancy(op, R) * np.asarray(dc).astype(R).reshape((nz, nx))
+    if magnitude:
+        dkb = np.abs(dkb)
+    mc, md, me = [R(w) for w in MZ_MASS]
+    C = np.zeros((9, nz, nx), dtype=dkb.dtype)
+    for k, (sz, sx) in enumerate(LAGS):
+        C[k] = (mc if (sz, sx) == (0, 0) else (me if sz and sx else md)) * _at(dkb, sz, sx)
+    C[:, ~_interiorMask(nz, nx)] = 0
+    return C
+
+
+def blockCoefficients(nz, nx, planes):
+    """E (N, 9, 9): E[i, j, n] the coefficient of d A / d p_i in row i + o_j at column i + o_n (slots of LAGS), from planes(v) -> (9, nz, nx) evaluated on the
+    nine colour indicators (cells with equal (iz mod 3, ix mod 3) have disjoint 3 x 3 blocks)"""
+    N = nz * nx
+    iz, ix = np.divmod(np.arange(N), nx)
+    slot = {o: k for k, o in enumerate(LAGS)}
+    E = None
+    for a in range(3):
+        for b in range(3):
+            mine = (iz % 3 == a) & (ix % 3 == b)
+            if not mine.any():
+                continue
+            C = np.asarray(planes(mine.astype(np.float64))).reshape((9, nz, nx))
+            E = np.zeros((N, 9, 9), dtype=C.dtype) if E is None else E
+            for j, (jz, jx) in enumerate(LAGS):
+                for n, (mz, mx) in enumerate(LAGS):
+                    k = slot.get((mz - jz, mx - jx))
+                    if k is not None:
+                        E[mine, j, n] = _at(C[k], jz, jx).ravel()[mine]
+    return E
+
+
+def gaussNewtonTrace(E, Gamma, Phi, magnitude=False):
+    "Re sum conj(E[j', n']) Gamma[j, j'] E[j, n] Phi[n, n'] per cell from (N, 9, 9) blocks, as T = E Phi, S = Gamma^T T, sum conj(E) S; magnitude: every term by its modulus"
+    if magnitude:
+        E, Gamma, Phi = np.abs(E), np.abs(Gamma), np.abs(Phi)
+    T = np.einsum('ijn,inm->ijm', E, Phi)
+    S = np.einsum('ijk,ijm->ikm', Gamma, T)
+    return (np.conj(E) * S).sum(axis=(1, 2)).real
+
+
+def gaussNewtonDiagonal(op, uh, gh, parameter='c', chain=None, linearisation='full', dtype=np.complex128, magnitude=False, weight=None):
+    """H (N,), real in the arithmetic of dtype: H[i] = sum_s sum_r |g_r^T (d A / d p_i) u_s|^2 for the 2-D MiniZephyr operator `op` from the planes
+    uh = lagGram(u) of the forward solves and gh = lagGram(g) of the receiver Green's functions (13, N) each.  linearisation 'full': d A / d p_i from
+    `velocityPlanes` (chain (N,) = d b / d c where the density follows c) for parameter 'c', from `buoyancyPlanes` for 'b' and 'rho' ('rho': along
+    -e_i / rho_i^2, density units); 'operator' with 'c': the mass term alone (`massPlanes`); 'scaler': the diagonal weight `weight` (N,), default the
+    reference's -(2 pi f)^2 / c^3, so H = |w|^2 gh[0] uh[0].  magnitude: uh and gh those of moduli, every term of the trace by its modulus."""
+    if parameter not in ('c', 'rho', 'b'):
+        raise ValueError('parameter is %r: \'c\', \'rho\' or \'b\'' % (parameter,))
+    if linearisation not in ('scaler', 'operator', 'full'):
+        raise ValueError('linearisation is %r: \'scaler\', \'operator\' or \'full\'' % (linearisation,))
+    nz, nx = int(op.nz), int(op.nx)
+    R = _real(dtype)
+    Cu = (np.abs(np.asarray(uh)).astype(R) if magnitude else np.asarray(uh).astype(dtype)).reshape((len(GRAM_LAGS), nz * nx))
+    Cg = (np.abs(np.asarray(gh)).astype(R) if magnitude else np.asarray(gh).astype(dtype)).reshape((len(GRAM_LAGS), nz * nx))
+    if linearisation == 'scaler':
+        if weight is None:
+            om = 2 * R(np.pi) * dtype(complex(op.freq))
+            c = np.asarray(op.c).astype(dtype).ravel()
+            weight = -(om * om) / (c * c * c)
+        w = np.asarray(weight).astype(dtype).ravel()
+        return (np.square(w.real) + np.square(w.imag)) * (Cg[0].real * Cu[0].real)
+    if parameter != 'c':
+        planes = lambda v: buoyancyPlanes(op, v, dtype, magnitude)
+    elif linearisation == 'operator':
+        planes = lambda v: massPlanes(op, v, dtype, magnitude)
+    else:
+        ch = None if chain is None else np.asarray(chain, dtype=np.float64).ravel()
+        planes = lambda v: velocityPlanes(op, v, None if ch is None else ch * v, dtype, magnitude)
+    H = gaussNewtonTrace(blockCoefficients(nz, nx, planes), _gramBlocks(Cg, nz, nx), _gramBlocks(Cu, nz, nx), magnitude)
+    if parameter == 'rho':
+        rho = np.broadcast_to(np.asarray(op.rho, dtype=np.float64), (nz, nx)).astype(R).ravel()
+        H = H / (rho * rho * rho * rho)
+    return H

@@ -14,7 +14,8 @@ over ranks and the only collective is one all-reduce of the gradient (problem.py
 frequencies) or of the receiver data.  The device-resident loops of `dpred` and the mux `Jtvec` (item dealing,
 per-worker buffers, partial gradients) live in `zephyr_amd.device_survey`; `_dpredDevice` / `_JtvecDevice` delegate to it.  `fieldsDevice` leaves the
 forward wavefields in HBM (`zephyr_amd.fieldstore.DeviceFields`) for `survey.dpred(m, u=F)` and `Jtvec(m, v, u=F)`.  `illumination` (no counterpart in the
-reference) returns the source- or receiver-side illumination or the diagonal pseudo-Hessian from those fields, what a gradient is preconditioned with.
+reference) returns the source- or receiver-side illumination, the diagonal pseudo-Hessian or the exact diagonal of the Gauss-Newton Hessian from those fields,
+what a gradient is preconditioned with.
 """
 import contextlib
 
@@ -33,6 +34,7 @@ from .frechet import MZ_MASS, maskInterior, massStencil, operatorWeight      # n
 from .frechet import applyPlanes, buoyancyAdjoint, buoyancyPlanes, lagProducts      # (and what parameter='rho' is made of)
 from .frechet import gardnerChain, velocityAdjoint, velocityPlanes                  # (and linearisation='full')
 from .frechet import operatorPseudoHessianWeight, pseudoHessianDiagonal              # (and the pseudo-Hessian diagonal of either)
+from .frechet import gaussNewtonDiagonal, lagGram                                   # (and the exact diagonal of the Gauss-Newton Hessian)
 
 EPS = 1e-15
 
@@ -625,6 +627,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
 
         kind 'energy':        sum_f E_f                                 (source-side illumination)
         kind 'pseudoHessian': sum_f |gradientScaler(f)|^2 (.) E_f       (the diagonal pseudo-Hessian of Shin, Jang & Min 2001)
+        kind 'gaussNewton':   diag(J^T J), sources and receivers         (below)
         perFreq:              the terms of the sum over f, one row each (rows of frequencies other ranks own arrive through the all-reduce)
 
         side 'receiver': the same with the receiver array as sources, uR_f = scaleTerm * (sub_f * rVec(0, f).T) -- srTerms included, no tsTerms; fixed
@@ -640,12 +643,25 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         (parameter='rho': density units).  For 'scaler' d A / d c_i is the diagonal weight and this is the formula above.  Served and refused as JvecBorn
         (`_resolveLinearisation`); the same routes, sides and perFreq as the default.
 
-        u a DeviceFields (fieldsDevice): no solve, the store is read where it lies.  u None with the device path on a single-grid survey: the fields are
-        solved into HBM, accumulated there and dropped; only the result comes down.  Otherwise (u a list of host arrays, no GPU, hostGradient, a host ky
-        reduction, a multiscale survey): numpy on the host."""
+        kind 'gaussNewton': the exact diagonal of the Gauss-Newton Hessian that `Hvec` applies, D[i] = e_i . Hvec(m, e_i, linearisation=, parameter=) for every
+        cell i -- the receiver side included, which the pseudo-Hessian leaves out:
+
+            D[i] = sum_f sum_s sum_r |d dpred_(r,s,f) / d p_i|^2 = |scaleTerm|^2 sum_f sum_s sum_r |g_r^T (d A_f / d p_i) u^_s|^2,     g_r = A_f^-T R_r^H,
+
+        evaluated as Re tr(E_i^H Gamma_i E_i Phi_i) over the 3 x 3 block around i, Gamma and Phi the Gram blocks of the receiver Green's functions and of the
+        forward solves read off their autocorrelation planes at the lags of (-2..2)^2 (frechet.gaussNewtonDiagonal).  Every linearisation and parameter, served
+        and refused as JvecBorn; for 'scaler' d A / d c_i is the diagonal weight and D[i] = |w_i|^2 sum_r |g_r[i]|^2 sum_s |u_s[i]|^2.  The receiver columns
+        are solved through `adjointSystem`, so the factors of A and of A^T are resident side by side: Helm2DProblem with MiniZephyr / MiniZephyrHD on one
+        grid; the 2.5-D composite, visco problems, Eurus, 3-D and multiscale surveys raise NotImplementedError for every linearisation.  Fixed receiver arrays
+        only (with an array that moves with the source Gamma depends on the source and the sum does not factorise: ValueError), side must stay 'source', and
+        there are no data weights: a general `weights` array of `Hvec` does not factorise either.
+
+        u a DeviceFields (fieldsDevice): no solve, the store is read where it lies ('gaussNewton': nothing but the nrec receiver columns is solved).  u None with
+        the device path on a single-grid survey: the fields are solved into HBM, accumulated there and dropped; only the result comes down.  Otherwise (u a
+        list of host arrays, no GPU, hostGradient, a host ky reduction, a multiscale survey): numpy on the host."""
         self._requirePaired()
-        if kind not in ('energy', 'pseudoHessian'):
-            raise ValueError('kind is %r: \'energy\' or \'pseudoHessian\'' % (kind,))
+        if kind not in ('energy', 'pseudoHessian', 'gaussNewton'):
+            raise ValueError('kind is %r: \'energy\', \'pseudoHessian\' or \'gaussNewton\'' % (kind,))
         if side not in ('source', 'receiver'):
             raise ValueError('side is %r: \'source\' or \'receiver\'' % (side,))
         self._checkLinearisation(linearisation)
@@ -653,15 +669,25 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if kind == 'energy' and (linearisation != 'scaler' or parameter != 'c'):
             raise ValueError('kind=\'energy\' has no linearisation: linearisation=%r, parameter=%r go with kind=\'pseudoHessian\'' % (linearisation, parameter))
         sv = self.survey
+        if kind == 'gaussNewton':
+            if side != 'source':
+                raise ValueError('kind=\'gaussNewton\' is the diagonal of J^T J, sources and receivers together: side must be \'source\'')
         if side == 'receiver':
             if u is not None:
                 raise ValueError('the receiver-side illumination solves its own fields: u must be None')
             if sv.mode != 'fixed':
                 raise ValueError('the receiver-side illumination serves fixed receiver arrays (mode is %r)' % (sv.mode,))
         self.updateModel(m)
+        if kind == 'gaussNewton' and linearisation == 'scaler':
+            self._requireFullLinearisation('illumination(linearisation=\'scaler\')')      # (this kind needs the transposed 2-D operator whatever the linearisation)
         if linearisation != 'scaler':
             linearisation = self._resolveLinearisation(linearisation, parameter, 'illumination')
+        if kind == 'gaussNewton' and sv.mode != 'fixed':          # (after the refusals: what is not served at all says so first)
+            raise ValueError('kind=\'gaussNewton\' serves fixed receiver arrays (mode is %r): with an array that moves with the source the sum over '
+                             'receivers depends on the source and does not factorise' % (sv.mode,))
         owned = self.ownedFreqs
+        if kind == 'gaussNewton' and linearisation != 'scaler' and (isinstance(u, DeviceFields) or (u is None and self._deviceGradientAvailable())):
+            self._hermitianResidual(np.zeros((sv.nrec, 1, 1)))          # (the device route solves R^T for R^H: refused where the receiver columns are complex)
         if isinstance(u, DeviceFields):
             u.checkCurrent(self)
             return device_survey.illuminationFromFields(self, u, kind, bool(perFreq), linearisation, parameter)
@@ -669,6 +695,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             return device_survey.illumination(self, owned, kind, side, bool(perFreq), linearisation, parameter)
         nf = sv.nfreq
         H = np.zeros((nf, self.nrow) if perFreq else self.nrow, dtype=np.float64)
+        if kind == 'gaussNewton':
+            green = self._receiverGreens(linearisation)
         if u is None:
             q = sv.getSources() if side == 'source' else [sp.csc_matrix(sv.rVec(0, i).T) for i in range(nf)]
             pps = sv.postProcessors
@@ -679,7 +707,9 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         for ifreq, uf in fieldsOf:
             uf = np.asarray(uf)
             uf = uf.reshape((uf.shape[0], -1))
-            if linearisation != 'scaler':
+            if kind == 'gaussNewton':
+                E = self._gaussNewtonHost(ifreq, uf, green[ifreq], linearisation, parameter)
+            elif linearisation != 'scaler':
                 E = self._pseudoHessianHost(ifreq, uf, linearisation, parameter)
             else:
                 E = np.add.reduce(np.square(uf.real) + np.square(uf.imag), axis=1)      # (no BLAS: _norm2 says why)
@@ -703,6 +733,28 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             H = operatorPseudoHessianWeight(sub) * np.add.reduce(np.square(uh.real) + np.square(uh.imag), axis=1)
         else:
             H = pseudoHessianDiagonal(sub, uh, parameter, self._gardnerChain() if parameter == 'c' else None)
+        return (st.real * st.real + st.imag * st.imag) * H
+
+    def _receiverGreens(self, linearisation):
+        """{ifreq: (N, nrec)} over the owned frequencies: the fixed array's rows back-propagated through the transposed operators as `_solveOwned` returns
+        them, scaleTerm conj(A_f^-T premul q).  q = R^H for the exact derivatives, whose data are R . conj(...); R^T for 'scaler', whose data are conj(R) . (...)."""
+        sv = self.survey
+        q = [sp.csc_matrix(sv.rVec(0, i).T) for i in range(sv.nfreq)]
+        if linearisation != 'scaler':
+            q = [m.conj() for m in q]
+        return {ifreq: np.asarray(g) for ifreq, g in self._solveOwned(q, self.adjointSystem)}
+
+    def _gaussNewtonHost(self, ifreq, uf, gf, linearisation, parameter):
+        """one frequency's term of illumination(kind='gaussNewton') on the host: uf = scaleTerm conj(u^) (N, nsrc), gf = scaleTerm conj(premul g) (N, nrec) of
+        `_receiverGreens`, the resolved linearisation.  'scaler': |d_(r,s) / v_i| = |w_i| |uf_s[i]| |gf_r[i]|, the planes of the arrays as they are."""
+        sub = self.system.subProblems[ifreq]
+        nz, nx = int(sub.nz), int(sub.nx)
+        if linearisation == 'scaler':
+            return gaussNewtonDiagonal(sub, lagGram(uf, nz, nx), lagGram(gf, nz, nx), linearisation='scaler', weight=self.gradientScaler(ifreq))
+        st = complex(self.system.scaleTerm)
+        uh = np.conj(uf / st)
+        gh = np.conj(gf / (st * np.conj(complex(sub.premul))))
+        H = gaussNewtonDiagonal(sub, lagGram(uh, nz, nx), lagGram(gh, nz, nx), parameter, self._gardnerChain() if parameter == 'c' else None, linearisation)
         return (st.real * st.real + st.imag * st.imag) * H
 
     # ---- device-resident gradient (mux branch) -------------------------------------------------------------
