@@ -230,6 +230,10 @@ def test_virtual_sources_kernel_against_extended_precision(helm_lib, op4800, nsr
     assert helm_lib.helm_virtual_sources_device(op.handle, P(dU.data_ptr()), nsrc, N - 1, P(dW.data_ptr()), P(out.data_ptr()), ldr) == -1
     assert helm_lib.helm_virtual_sources_device(op.handle, P(dU.data_ptr()), 0, ldu, P(dW.data_ptr()), P(out.data_ptr()), ldr) == -1
     assert helm_lib.helm_virtual_sources_device(op.handle, P(dU.data_ptr()), nsrc, ldu, P(dW.data_ptr()), P(out.data_ptr() + 8), ldr) == -1
+    if fmt == 'complex64':          # no field, no exponents, values off 8 bytes, exponents off 4, ld < N, the output on the field
+        u, e, r = dU.data_ptr(), dE.data_ptr(), P(out.data_ptr())
+        for pu, pe, l, pr in ((None, P(e), ldu, r), (P(u), None, ldu, r), (P(u + 4), P(e), ldu, r), (P(u), P(e + 2), ldu, r), (P(u), P(e), N - 1, r), (P(u), P(e), ldu, P(u))):
+            assert helm_lib.helm_virtual_sources_c64_device(op.handle, pu, pe, nsrc, l, P(dW.data_ptr()), pr, ldr) == -1
 
 
 # ---- 5. end to end on the device -----------------------------------------------------------------------------------------------------------

@@ -113,6 +113,15 @@ def test_field_kernels_against_the_80_bit_evaluation(helm_lib, case, fmt):
         assert helm_lib.helm_stencil_sources_device(op.handle, P(dU.data_ptr()), nsrc, ldu, P(dC.data_ptr()), 1.0, 0.0, 0, P(dC.data_ptr() + 16), N) == -1
         assert helm_lib.helm_lag_imaging_accumulate_device(op.handle, P(dU.data_ptr()), ldu, P(dB.data_ptr()), N - 1, nsrc, d_p) == -1
         assert helm_lib.helm_lag_imaging_accumulate_device(op.handle, P(dU.data_ptr()), ldu, P(dB.data_ptr()), ldb, nsrc, P(dB.data_ptr())) == -1
+    else:          # the complex64 halves: no field, no exponents, values off 8 bytes, exponents off 4, ld < N, the output inside the field
+        u, e, c, b = dU.data_ptr(), dE.data_ptr(), P(dC.data_ptr()), P(dB.data_ptr())
+        st, lg = helm_lib.helm_stencil_sources_c64_device, helm_lib.helm_lag_imaging_accumulate_c64_device
+        for pu, pe, l, r in ((None, P(e), ldu, d_r), (P(u), None, ldu, d_r), (P(u + 4), P(e), ldu, d_r), (P(u), P(e + 2), ldu, d_r), (P(u), P(e), N - 1, d_r),
+                             (P(u), P(e), ldu, P(u + 16))):
+            assert st(op.handle, pu, pe, nsrc, l, c, 1.0, 0.0, 0, r, ldr) == -1
+        for pu, pe, l, p in ((None, P(e), ldu, d_p), (P(u), None, ldu, d_p), (P(u + 4), P(e), ldu, d_p), (P(u), P(e + 2), ldu, d_p), (P(u), P(e), N - 1, d_p),
+                             (P(u), P(e), ldu, P(u + 16))):
+            assert lg(op.handle, pu, pe, l, b, ldb, nsrc, p) == -1
     op.close()
 
 

@@ -102,6 +102,14 @@ def test_imaging_c64_kernel_against_extended_precision(helm_lib, op, nsrc):
     torch.cuda.synchronize(dev)
     op.imagingAccumulateDevice(dF.data_ptr(), dB.data_ptr(), nsrc, dS.data_ptr(), dG.data_ptr())
     assert np.array_equal(dG.cpu().numpy().view(np.float64), outs[0].view(np.float64))
+    # a missing array or no column is refused before anything is launched (the pair takes no leading dimension and checks no alignment)
+    i128, i64 = helm_lib.helm_imaging_accumulate_device, helm_lib.helm_imaging_accumulate_c64_device
+    f, x, b, s, g = P(dF.data_ptr()), P(dE.data_ptr()), P(dB.data_ptr()), P(dS.data_ptr()), P(dG.data_ptr())
+    assert i128(op.handle, None, b, nsrc, s, g) == -1 and i128(op.handle, f, None, nsrc, s, g) == -1 and i128(op.handle, f, b, 0, s, g) == -1
+    assert i128(op.handle, f, b, nsrc, None, g) == -1 and i128(op.handle, f, b, nsrc, s, None) == -1 and i128(None, f, b, nsrc, s, g) == -1
+    p = P(dP.data_ptr())
+    assert i64(op.handle, None, x, b, nsrc, s, g) == -1 and i64(op.handle, p, None, b, nsrc, s, g) == -1 and i64(op.handle, p, x, None, nsrc, s, g) == -1
+    assert i64(op.handle, p, x, b, 0, s, g) == -1 and i64(op.handle, p, x, b, nsrc, None, g) == -1 and i64(op.handle, p, x, b, nsrc, s, None) == -1
 
 
 @pytest.mark.parametrize('nsrc', [1, 5, 13])

@@ -127,6 +127,15 @@ def test_both_kernels_against_the_80_bit_evaluation(helm_lib, handles, shape, ns
         assert helm_lib.helm_virtual_sources_op_device(op.handle, P(dU.data_ptr()), nsrc, ldu, P(dW.data_ptr()), 1.0, 0.0, 0, P(d_r.value + 8), ldr) == -1
         assert helm_lib.helm_imaging_op_accumulate_device(op.handle, P(dU.data_ptr()), ldu, P(dB.data_ptr()), N - 1, nsrc, P(dW.data_ptr()), d_g) == -1
         assert helm_lib.helm_imaging_op_accumulate_device(op.handle, P(dU.data_ptr()), ldu, P(dB.data_ptr()), ldb, nsrc, P(dW.data_ptr()), P(dW.data_ptr())) == -1
+    else:          # the complex64 halves: no field, no exponents, values off 8 bytes, exponents off 4, ld < N, the output on the field
+        u, e, w, b = dU.data_ptr(), dE.data_ptr(), P(dW.data_ptr()), P(dB.data_ptr())
+        vs, im = helm_lib.helm_virtual_sources_op_c64_device, helm_lib.helm_imaging_op_accumulate_c64_device
+        for pu, pe, l, r in ((None, P(e), ldu, d_r), (P(u), None, ldu, d_r), (P(u + 4), P(e), ldu, d_r), (P(u), P(e + 2), ldu, d_r), (P(u), P(e), N - 1, d_r),
+                             (P(u), P(e), ldu, P(u))):
+            assert vs(op.handle, pu, pe, nsrc, l, w, 1.0, 0.0, 0, r, ldr) == -1
+        for pu, pe, l, g in ((None, P(e), ldu, d_g), (P(u), None, ldu, d_g), (P(u + 4), P(e), ldu, d_g), (P(u), P(e + 2), ldu, d_g), (P(u), P(e), N - 1, d_g),
+                             (P(u), P(e), ldu, P(u))):
+            assert im(op.handle, pu, pe, l, b, ldb, nsrc, w, g) == -1
 
 
 def test_eurus_and_3d_handles_are_unsupported(helm_lib):

@@ -94,6 +94,11 @@ def test_lag_gram_against_the_80_bit_evaluation(helm_lib, case, fmt):
         assert f(op.handle, None, nsrc, ld, d_c) == -1 and f(op.handle, P(dU.data_ptr()), nsrc, ld, None) == -1
         assert f(op.handle, P(dU.data_ptr() + 8), nsrc, ld, d_c) == -1 and f(op.handle, P(dU.data_ptr()), nsrc, ld, P(d_c.value + 8)) == -1
         assert f(op.handle, P(dU.data_ptr()), nsrc, ld, P(dU.data_ptr() + 16)) == -1
+    else:          # no field, no exponents, values off 8 bytes, exponents off 4, ld < N, the output inside the field
+        f, u, e = helm_lib.helm_lag_gram_accumulate_c64_device, dU.data_ptr(), dE.data_ptr()
+        assert f(op.handle, None, P(e), nsrc, ld, d_c) == -1 and f(op.handle, P(u), None, nsrc, ld, d_c) == -1
+        assert f(op.handle, P(u + 4), P(e), nsrc, ld, d_c) == -1 and f(op.handle, P(u), P(e + 2), nsrc, ld, d_c) == -1
+        assert f(op.handle, P(u), P(e), nsrc, N - 1, d_c) == -1 and f(op.handle, P(u), P(e), nsrc, ld, P(u + 16)) == -1
     op.close()
 
 

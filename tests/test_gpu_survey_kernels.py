@@ -1,4 +1,5 @@
-"""GPU: what csrc/survey.hip makes structural.  The energy and sampling loops exist once, as templates over the reader of the forward field, so the
+"""GPU: what csrc/survey.hip makes structural.  The energy and sampling loops exist once, as templates over the reader of the forward field
+(csrc/survey_internal.hpp; each pair of entry points is one launcher), so the
 complex64 entry point on a packed field and the complex128 entry point on the unpacked field run the same arithmetic on the same numbers: the same bits
 (imaging: test_imaging_c64_kernel_against_extended_precision of tests/test_gpu_fieldstore.py).  And the plain sampling entry point, which multiplies by
 nothing, gives the values of the accumulating ones at alpha = 1, beta = 0."""

@@ -182,6 +182,15 @@ def test_entry_points_refuse_bad_arguments_without_a_gpu(helm_lib):
         assert sample(**{key: None}) == -1, key
     assert sample(nsrc=0) == -1 and sample(nrec=0) == -1 and sample(ld=0) == -1
     assert sample(stride=2) == -1 and sample(stride=1) == -1 and sample(stride=-3) == -1          # 0 or at least nrec
+    sr64 = helm_lib.helm_sample_rows_c64_device                  # the same refusals with a complex64 store, and one more for its exponents
+
+    def sample64(**kw):
+        v = dict(dict(good, dExp=a), **kw)
+        return sr64(v['op'], v['dU'], v['dExp'], v['nsrc'], v['ld'], v['rowptr'], v['col'], v['val'], v['nrec'], v['stride'], 1., 0., 0., 0., v['out'])
+    for key in ('op', 'dU', 'dExp', 'rowptr', 'col', 'val', 'out'):
+        assert sample64(**{key: None}) == -1, key
+    assert sample64(nsrc=0) == -1 and sample64(nrec=0) == -1 and sample64(ld=0) == -1
+    assert sample64(stride=2) == -1 and sample64(stride=1) == -1 and sample64(stride=-3) == -1
     rs = helm_lib.helm_rhs_from_samples_device
     good2 = dict(op=fake_op, resid=a, ld=4, nrec=3, nsrc=4, src0=0, tptr=a, tsrc=a, tcell=a, trec=a, tval=a, ntouch=7, R=b, rows=100)
 

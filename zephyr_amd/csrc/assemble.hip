@@ -29,7 +29,7 @@ __global__ __launch_bounds__(256) void k_assemble_mz(MzParams P, const cplx *__r
     if (i >= N) return;
     const int iz = (int)(i / P.nx), ix = (int)(i % P.nx);
 
-    // PML stretch factors from the local (unpadded) velocity (mz_row.hpp: the buoyancy derivative of survey.hip takes the same)
+    // PML stretch factors from the local (unpadded) velocity (mz_row.hpp: the buoyancy derivative of survey_frechet.hip takes the same)
     const MzRow row = mz_row_factors(P, c[i], distx[ix], sgnx[ix], distz[iz], sgnz[iz]);
 
     // neighbour properties with edge padding

@@ -388,7 +388,7 @@ int helm_launch_abs(helm_op *op, const cplx *in, cplx *out, long long n, double 
 int helm_ensure_host_model(helm_op *op);      // h_c, h_rho, ... (downloaded from the device on first use)
 int helm_adopt_model_device(helm_op *dst, const cplx *d_c, const double *d_rho);     // model of a multigrid level from device arrays (capi.hip)
 
-// ---- survey.hip --------------------------------------------------------------------------------
+// ---- survey.hip (what its three units share among themselves: survey_internal.hpp) --------------
 // the illumination kernel (k_energy<F>): columns loaded per lane before the first use, and the grid cap of its grid-stride loop (8 workgroups of 256
 // lanes per CU on 256 CUs)
 #define HELM_ENERGY_UNROLL 8

@@ -1,6 +1,6 @@
-// The row factors of the 2-D MiniZephyr operator, shared by its assembly (assemble.hip k_assemble_mz) and by the buoyancy derivative (survey.hip
+// The row factors of the 2-D MiniZephyr operator, shared by its assembly (assemble.hip k_assemble_mz) and by the buoyancy derivative (survey_frechet.hip
 // k_buoyancy_planes / k_buoyancy_adjoint): what a row takes from the velocity of its own cell and from the PML alone.  Their derivatives with respect to that
-// velocity (mz_row_factors_dc, mz_kappa_dc) serve the total velocity derivative (survey.hip k_velocity_planes / k_velocity_adjoint).
+// velocity (mz_row_factors_dc, mz_kappa_dc) serve the total velocity derivative (survey_frechet.hip k_velocity_planes / k_velocity_adjoint).
 #pragma once
 #include "helm_internal.hpp"
 

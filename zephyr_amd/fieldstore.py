@@ -7,7 +7,7 @@ the system's scaleTerm (the store holds the unscaled solves, as the mux pipeline
 `device_survey.fields`, `dpredFromFields` and `gradientFromFields`.
 
 The store is complex128, or complex64 with one power-of-two scale per column (`fieldsDtype='complex64'`, half the memory): `pack_reference` /
-`unpack_reference` state that format in numpy, csrc/survey.hip implements it.
+`unpack_reference` state that format in numpy, csrc/survey.hip (the pack) and csrc/survey_internal.hpp (the readers) implement it.
 """
 import numpy as np
 

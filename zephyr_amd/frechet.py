@@ -5,7 +5,7 @@ row by the mass weights, and overwrites its boundary rows by +-identity, so
     (dA) u = mask_int (.) M0(dK (.) u),      dK = -2 omega_d^2 v / (c^3 rho)
 
 The host routes of problem.py evaluate this here; the device routes (device_survey.py) take the scalars from here and run the stencil in
-k_virtual_sources_op / k_imaging_op (csrc/survey.hip).  The second part of the module is the derivative with respect to the density (parameter='rho'), the
+k_virtual_sources_op / k_imaging_op (csrc/survey_frechet.hip).  The second part of the module is the derivative with respect to the density (parameter='rho'), the
 third the total derivative with respect to the velocity (linearisation='full'): the mass term above, the PML stretch and the density that follows c."""
 import numpy as np
 
@@ -55,7 +55,7 @@ def operatorWeight(op):
 #     horizontal:  d kappa b (i+o) + th_o a_o - tzx (a_(1,sx) + a_(-1,sx))   th_o = A (X / dx + sx px / 2) / dx
 #     centre:      c kappa b (i)   - sum_o t_o a_o                           (the stiffness rows sum to zero)
 # and the four boundary lines are +-identity whatever b is.  L : db -> the nine planes of d A / d b along db (`buoyancyPlanes`), L^T its plain transpose
-# (`buoyancyAdjoint`).  The device kernels k_buoyancy_planes / k_buoyancy_adjoint (csrc/survey.hip) are these two; an interior row reads only cells inside
+# (`buoyancyAdjoint`).  The device kernels k_buoyancy_planes / k_buoyancy_adjoint (csrc/survey_frechet.hip) are these two; an interior row reads only cells inside
 # the grid, so the edge padding of the assembly never enters.
 MZ_STIFF = (0.5461, 0.4539)                   # the stiffness weights A, B of the rotated and the plain star (minizephyr.py:205-206)
 LAGS = [(sz, sx) for sz in (-1, 0, 1) for sx in (-1, 0, 1)]      # slot k = 3 (sz + 1) + (sx + 1): plane k multiplies u(iz + sz, ix + sx)
@@ -282,7 +282,7 @@ def lagProducts(z, u, nz, nx):
 #     dC_i = star(dc_i d row_i / dc, bn[b], Kn_k = (-2 omega_d^2 / c_j^3) b_j dc_j)           the mass term ('operator') and the stretch
 #          + star(row_i, bn[db], Kn_k = kappa_j db_j)                                        only where the density follows c: `buoyancyPlanes` of db
 # with db = gardnerChain(c) dc for the default density rho = 310 Re(c)^0.25.  Boundary rows zero.  `velocityPlanes` is the map, `velocityAdjoint` the plain
-# transpose of its first star (the second one's is `buoyancyAdjoint`); k_velocity_planes / k_velocity_adjoint (csrc/survey.hip) are the device kernels.
+# transpose of its first star (the second one's is `buoyancyAdjoint`); k_velocity_planes / k_velocity_adjoint (csrc/survey_frechet.hip) are the device kernels.
 
 def gardnerChain(c):
     "d b / d c per cell, float64 (N,), of the default density: b = 1 / (310 Re(c)^0.25), so -0.25 b / Re(c)"
@@ -345,7 +345,7 @@ def velocityAdjoint(op, P, dtype=np.complex128, magnitude=False, conj=False):
 # ---- the pseudo-Hessian diagonal of the exact derivatives ------------------------------------------------------------------------------------------
 # H_p[i] = sum_s || (d A / d p_i) u_s ||^2 (Shin, Jang & Min 2001, on the operator that is differentiated).  A unit perturbation of cell i touches only the
 # rows of the 3 x 3 block around i, and in those only the lags that point back into the block, so cells with equal (iz mod 3, ix mod 3) have disjoint
-# supports: the planes of the nine colour indicators, `applyPlanes`, |.|^2 and a 3 x 3 box sum give H exactly.  k_pseudo_hessian (csrc/survey.hip) is the
+# supports: the planes of the nine colour indicators, `applyPlanes`, |.|^2 and a 3 x 3 box sum give H exactly.  k_pseudo_hessian (csrc/survey_hessian.hip) is the
 # device kernel; it builds the per-cell coefficients instead.
 
 def _boxSum(e, nz, nx):
@@ -425,7 +425,7 @@ def operatorPseudoHessianWeight(op):
 # over the cells of that block
 #     H[i] = Re sum_(j, n, j', n') conj(E_i[j', n']) Gamma_i[j, j'] E_i[j, n] Phi_i[n, n'] = Re tr(E^H Gamma^T E Phi).
 # Two cells of a block are at most two steps apart in either direction: Gamma and Phi are read off the autocorrelation planes at the 25 lags of (-2..2)^2, 13 of
-# which are stored (`lagGram`; the others are conjugates read at the shifted cell).  k_lag_gram and k_gauss_newton_diagonal (csrc/survey.hip) are the device
+# which are stored (`lagGram`; the others are conjugates read at the shifted cell).  k_lag_gram and k_gauss_newton_diagonal (csrc/survey_hessian.hip) are the device
 # kernels; conjugating both sets of planes and the coefficients together leaves H as it is, which is how they read the stored conjugates.
 GRAM_LAGS = [(0, 0), (0, 1), (0, 2)] + [(dz, dx) for dz in (1, 2) for dx in (-2, -1, 0, 1, 2)]      # the stored half plane: plane l pairs cell i with i + GRAM_LAGS[l]
 
