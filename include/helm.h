@@ -338,6 +338,30 @@ int helm_buoyancy_adjoint_device(helm_op *op, const void *dP, double w_re, doubl
 int helm_velocity_planes_device(helm_op *op, const void *dDc, const void *dDb, void *dC);
 int helm_velocity_adjoint_device(helm_op *op, const void *dP, double w_re, double w_im, int conj, void *dG);
 
+/* --- the residual part of the Newton Hessian of the exact derivatives (HelmBaseProblem.Hvec with resid=) ------------------------------------------
+ * helm_velocity_curvature_device:  G[j] += w p[j] sum_{k, i} (d^2 A / dc_j^2)_{(k, i)} P[k][i] (conj != 0: the conjugated coefficients; stretch == 0: the mass term
+ *     alone).  At the density the handle assembled with a row is star(row_i(c_i), bn, Kn_k = kappa(c_j) b_j) and the second derivative of the operator is zero between
+ *     different cells: the sum is the transpose of helm_velocity_planes_device with d^2 row / dc^2 and d^2 kappa / dc^2 = 6 omega_d^2 / c^4 in the place of the first
+ *     derivatives, times p.  P: 9 N complex128, its boundary rows not read; p: N float64; G: N complex128.
+ * helm_stencil_sources_t_device:  R[s ldr + j] = coef sum_k C[8 - k][j + off_k] U[s][j + off_k] (conj != 0: conj(C)), cells outside the grid contributing nothing:
+ *     (dC)^T U, or (dC)^H U, the transposed application of the nine planes of helm_velocity_planes_device / helm_buoyancy_planes_device.  The transposed plane set is
+ *     not formed.  U, C, R as for helm_stencil_sources_device (note that conj conjugates the PLANES here, the columns there).  accumulate != 0: the CONJUGATE of
+ *     that value is added to R instead (the columns a survey pipeline holds are the conjugates of the fields: the result joins a right-hand side where it lies).
+ * helm_mass_planes_device:  dC[k][i] = m_k (d kappa_j / dc) b_j dc[j], j = i + off_k, on the interior rows, zero on the boundary rows: the mass term of
+ *     helm_velocity_planes_device alone (linearisation='operator'), m the mass weights (centre, edges, corners).  dc: N float64; dC: 9 N complex128.
+ * helm_mass_adjoint_device:  helm_velocity_adjoint_device for those planes, the transpose of the mass term alone.
+ *
+ * The same rules as above: plain fp64 in a fixed order, one writer per entry, no atomics; HELM_ERR_STATE before the first helm_assemble (the curvature); Eurus, 3-D
+ * and ny > 0 handles HELM_ERR_UNSUPPORTED; null, misaligned (16 bytes; U32: 8, dExp: 4, p: 8) or overlapping pointers, nsrc < 1, a leading dimension < N and grids
+ * below 3 x 3 HELM_ERR_ARG.  All device pointers; each call returns when its result is complete. */
+int helm_velocity_curvature_device(helm_op *op, const void *dP, const void *dp, double w_re, double w_im, int conj, int stretch, void *dG);
+int helm_stencil_sources_t_device(helm_op *op, const void *dU, int nsrc, long long ldu, const void *dC, double coef_re, double coef_im, int conj, int accumulate,
+                                  void *dR, long long ldr);
+int helm_stencil_sources_t_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ldu, const void *dC, double coef_re, double coef_im,
+                                      int conj, int accumulate, void *dR, long long ldr);
+int helm_mass_planes_device(helm_op *op, const void *dDc, void *dC);
+int helm_mass_adjoint_device(helm_op *op, const void *dP, double w_re, double w_im, int conj, void *dG);
+
 /* --- the pseudo-Hessian diagonal of the exact derivatives (HelmBaseProblem.illumination with linearisation='full' / 'operator') ------------------
  * H[i] += alpha (dW ? W[i] : 1) sum_{s<nsrc} || (d A / d p_i) u^_s ||_2^2 for i < N, with U[s] = conj(u^_s) the stored columns (nsrc columns of ld >= N complex128,
  * or, _c64, complex64 values with the int32 column exponents dExp of helm_pack_c64_device) and d A / d p_i the derivative of the operator the handle holds:

@@ -1,6 +1,7 @@
 // The row factors of the 2-D MiniZephyr operator, shared by its assembly (assemble.hip k_assemble_mz) and by the buoyancy derivative (survey_frechet.hip
 // k_buoyancy_planes / k_buoyancy_adjoint): what a row takes from the velocity of its own cell and from the PML alone.  Their derivatives with respect to that
-// velocity (mz_row_factors_dc, mz_kappa_dc) serve the total velocity derivative (survey_frechet.hip k_velocity_planes / k_velocity_adjoint).
+// velocity (mz_row_factors_dc, mz_kappa_dc) serve the total velocity derivative (survey_frechet.hip k_velocity_planes / k_velocity_adjoint), the second
+// derivatives (mz_row_factors_d2c, mz_kappa_d2c) the residual part of the Newton Hessian (survey_newton.hip k_velocity_curvature).
 #pragma once
 #include "helm_internal.hpp"
 
@@ -53,6 +54,27 @@ __device__ __forceinline__ MzRow mz_row_factors_dc(const MzParams &P, cplx c0, d
     return r;
 }
 
+// d^2 (X, px) / dc^2 along one axis, from the same inputs: with a = f d^2, X = (i om)^2 / den^2 and p = s 2 f d (i om)^2 c / den^3,
+//   d2X/dc2 = 6 X a^2 / den^2,   d2p/dc2 = s 2 f d (2 d2X/dc2 c - 6 X a / den) / den.  Outside the layers d = 0 and both are zero.
+__device__ __forceinline__ void mz_axis_factors_d2c(cplx iom, double f, cplx c0, double d, double s, cplx &d2S, cplx &d2p) {
+    const double fdd = f * d * d;
+    const cplx den = cadd(cscale(c0, fdd), iom);
+    const cplx r1 = cdiv(iom, den);
+    const cplx S = cmul(r1, r1);
+    const cplx Sa = cdiv(cscale(S, fdd), den);
+    d2S = cdiv(cscale(Sa, 6.0 * fdd), den);
+    const cplx inner = csub(cscale(cmul(d2S, c0), 2.0), cscale(Sa, 6.0));
+    d2p = cdiv(cscale(inner, s * 2.0 * f * d), den);
+}
+// d^2 (X, Z, px, pz) / dc^2 of mz_row_factors: what the second derivative of a row with respect to the velocity of its own cell is made of
+__device__ __forceinline__ MzRow mz_row_factors_d2c(const MzParams &P, cplx c0, double dX, double sX, double dZ, double sZ) {
+    const cplx iom = cmake(-P.om.y, P.om.x);          // 1j * om
+    MzRow r;
+    mz_axis_factors_d2c(iom, P.fx, c0, dX, sX, r.X, r.px);
+    mz_axis_factors_d2c(iom, P.fz, c0, dZ, sZ, r.Z, r.pz);
+    return r;
+}
+
 // kappa = omega_d^2 / c^2 - ky^2 of a cell: K = kappa / rho
 __device__ __forceinline__ cplx mz_kappa(const MzParams &P, cplx cj) {
     cplx k = cdiv(cmul(P.om, P.om), cmul(cj, cj));
@@ -62,6 +84,12 @@ __device__ __forceinline__ cplx mz_kappa(const MzParams &P, cplx cj) {
 // d kappa / dc = -2 omega_d^2 / c^3 of a cell
 __device__ __forceinline__ cplx mz_kappa_dc(const MzParams &P, cplx cj) {
     return cdiv(cscale(cmul(P.om, P.om), -2.0), cmul(cmul(cj, cj), cj));
+}
+
+// d^2 kappa / dc^2 = 6 omega_d^2 / c^4 of a cell
+__device__ __forceinline__ cplx mz_kappa_d2c(const MzParams &P, cplx cj) {
+    const cplx c2 = cmul(cj, cj);
+    return cdiv(cscale(cmul(P.om, P.om), 6.0), cmul(c2, c2));
 }
 
 __host__ __device__ inline int mz_slot(int dz, int dx) { return 3 * (dz + 1) + (dx + 1); }

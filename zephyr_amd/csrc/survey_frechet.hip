@@ -581,62 +581,45 @@ extern "C" int helm_velocity_planes_device(helm_op *op, const void *dDc, const v
     return launched(op);
 }
 
-// G[j] += w sum_(k, i) V_((k, i), j) P_k[i] (CONJ: conj(V)): the transpose of the first star of k_velocity_planes, one lane per cell j.  The mass part is the
-// gather of k_buoyancy_adjoint over the interior rows i = j - o, times (d kappa_j / dc) b_j.  The stretch part is local to row j: its differentiated stiffness
-// factors dT (mz_stiffness is linear in the row) times the averaged buoyancies a_o = (b_j + b_(j+o)) / 2 and the Q-differences of P at j (lag_coefficient); a
-// boundary row has none.  One writer per cell, a fixed order; the boundary rows of P are not read.
-template <bool CONJ>
+// G[j] += w sum_(k, i) V_((k, i), j) P_k[i] (CONJ: conj(V)): the transpose of the first star of k_velocity_planes, one lane per cell j -- mz_transpose_at
+// (survey_internal.hpp) with the first derivatives.  STRETCH false: the transpose of the mass term alone, the planes of k_mass_planes (survey_newton.hip).  One writer
+// per cell, a fixed order; the boundary rows of P are not read.
+template <bool CONJ, bool STRETCH>
 __global__ __launch_bounds__(256) void k_velocity_adjoint(MzParams P, const cplx *__restrict__ c, const double *__restrict__ rho, const cplx *__restrict__ Pl, cplx w,
                                                           cplx *__restrict__ G) {
     const long long N = (long long)P.nz * P.nx;
     const long long j = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (j >= N) return;
-    const int jz = (int)(j / P.nx), jx = (int)(j % P.nx);
-    const double bj = 1.0 / rho[j];
-    cplx mass = cmake(0.0, 0.0), stretch = cmake(0.0, 0.0);
-#pragma unroll
-    for (int sz = -1; sz <= 1; ++sz)
-#pragma unroll
-        for (int sx = -1; sx <= 1; ++sx) {
-            const int iz = jz - sz, ix = jx - sx;                 // row i sees cell j at the lag (sz, sx)
-            if (iz < 1 || iz > P.nz - 2 || ix < 1 || ix > P.nx - 2) continue;
-            const double m = (sz == 0 && sx == 0) ? MZ_WC : ((sz == 0 || sx == 0) ? MZ_WD : MZ_WE);
-            const cplx p = Pl[(long long)mz_slot(sz, sx) * N + (long long)iz * P.nx + ix];
-            mass.x += m * p.x; mass.y += m * p.y;
-        }
-    if (jz >= 1 && jz <= P.nz - 2 && jx >= 1 && jx <= P.nx - 2) {
-        const MzStiff dt = mz_stiffness<CONJ>(P, mz_row_dc_at(P, c, jz, jx));
-#pragma unroll
-        for (int oz = -1; oz <= 1; ++oz)
-#pragma unroll
-            for (int ox = -1; ox <= 1; ++ox)
-                if (oz != 0 || ox != 0) {
-                    const double a = (bj + 1.0 / rho[j + (long long)oz * P.nx + ox]) / 2.0;
-                    stretch = cadd(stretch, cscale(lag_coefficient(dt, Pl, N, j, oz, ox), a));
-                }
-    }
-    cplx dk = cscale(mz_kappa_dc(P, c[j]), bj);
-    if (CONJ) dk = cconj(dk);
-    cplx sum = stretch;
-    cfma(sum, dk, mass);
+    const cplx sum = mz_transpose_at<1, CONJ, STRETCH>(P, c, rho, Pl, j);
     cplx g = G[j];
     cfma(g, w, sum);
     G[j] = g;
 }
 
 // G[j] += w sum_(k, i) V_((k, i), j) P_k[i] for j < N (conj != 0: the conjugated coefficients), V the map of helm_velocity_planes_device with dDb NULL for the
-// operator the handle holds: P [9][N] complex128 (its boundary rows are not read), G N complex128.  G must not overlap P.  Returns when G is complete.
-extern "C" int helm_velocity_adjoint_device(helm_op *op, const void *dP, double w_re, double w_im, int conj, void *dG) {
+// operator the handle holds (helm_mass_adjoint_device: of helm_mass_planes_device, the mass term alone): P [9][N] complex128 (its boundary rows are not read), G N
+// complex128.  G must not overlap P.  Returns when G is complete.
+static int velocity_adjoint_launch(helm_op *op, const char *what, const void *dP, cplx w, int conj, bool stretch, void *dG) {
     helm_tuning_refresh();
     if (!op || !dP || !dG) return HELM_ERR_ARG;
-    if (int rc = mz_handle_args(op, "helm_velocity_adjoint_device")) return rc;
+    if (int rc = mz_handle_args(op, what)) return rc;
     if (op->nz < 3 || op->nx < 3 || ((((uintptr_t)dP) | ((uintptr_t)dG)) & 15)) return HELM_ERR_ARG;
     if (ranges_overlap(dP, (size_t)op->N * 9 * sizeof(cplx), dG, (size_t)op->N * sizeof(cplx))) return HELM_ERR_ARG;
     MzParams P;
-    if (helm_mz_params(op, &P)) HELM_FAIL(op, HELM_ERR_STATE, "helm_velocity_adjoint_device: the handle holds no assembled operator");
+    if (helm_mz_params(op, &P)) HELM_FAIL(op, HELM_ERR_STATE, "%s: the handle holds no assembled operator", what);
     HIP_TRY(op, hipSetDevice(op->device));
     const dim3 grid((unsigned)((op->N + 255) / 256));
-    if (conj) HELM_LAUNCH(k_velocity_adjoint<true>, grid, dim3(256), 0, op->stream, P, (const cplx *)op->d_c, (const double *)op->d_rho, (const cplx *)dP, cmake(w_re, w_im), (cplx *)dG);
-    else HELM_LAUNCH(k_velocity_adjoint<false>, grid, dim3(256), 0, op->stream, P, (const cplx *)op->d_c, (const double *)op->d_rho, (const cplx *)dP, cmake(w_re, w_im), (cplx *)dG);
+#define VADJOINT(CJ, ST) HELM_LAUNCH((k_velocity_adjoint<CJ, ST>), grid, dim3(256), 0, op->stream, P, (const cplx *)op->d_c, (const double *)op->d_rho, (const cplx *)dP, w, (cplx *)dG)
+    if (conj && stretch) VADJOINT(true, true);
+    else if (conj) VADJOINT(true, false);
+    else if (stretch) VADJOINT(false, true);
+    else VADJOINT(false, false);
+#undef VADJOINT
     return launched(op);
+}
+extern "C" int helm_velocity_adjoint_device(helm_op *op, const void *dP, double w_re, double w_im, int conj, void *dG) {
+    return velocity_adjoint_launch(op, "helm_velocity_adjoint_device", dP, cmake(w_re, w_im), conj, true, dG);
+}
+extern "C" int helm_mass_adjoint_device(helm_op *op, const void *dP, double w_re, double w_im, int conj, void *dG) {
+    return velocity_adjoint_launch(op, "helm_mass_adjoint_device", dP, cmake(w_re, w_im), conj, false, dG);
 }

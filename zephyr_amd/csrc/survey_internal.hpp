@@ -1,5 +1,6 @@
 // What the translation units of a survey share: survey.hip (the plumbing: right-hand sides, axpby, the complex64 pack, imaging, energy, sampling),
-// survey_frechet.hip (the derivative kernels of the 2-D MiniZephyr operator) and survey_hessian.hip (the two Hessian diagonals built on them).  The readers
+// survey_frechet.hip (the derivative kernels of the 2-D MiniZephyr operator), survey_hessian.hip (the two Hessian diagonals built on them) and survey_newton.hip
+// (the second derivative and the transposed planes of the Newton Hessian-vector product).  The readers
 // of a stored field on the device (FieldC128 / FieldC64) and its description on the host (HostField), how an entry point ends and refuses, the walk of the
 // stencil kernels over the grid, and the row factors of MiniZephyr at a cell.
 //
@@ -134,6 +135,16 @@ __device__ __forceinline__ MzRow mz_row_dc_at(const MzParams &P, const cplx *__r
     return mz_row_factors_dc(P, c[(long long)iz * P.nx + ix], dX, sX, dZ, sZ);
 }
 
+// the same for the derivative of order ORDER (1 or 2) of the factors along c
+template <int ORDER>
+__device__ __forceinline__ MzRow mz_row_dnc_at(const MzParams &P, const cplx *__restrict__ c, int iz, int ix) {
+    double dX, sX, dZ, sZ;
+    mz_profile_at(P.nx, P.npml, P.dx, P.fs3, P.fs1, ix, dX, sX);
+    mz_profile_at(P.nz, P.npml, P.dz, P.fs0, P.fs2, iz, dZ, sZ);
+    const cplx c0 = c[(long long)iz * P.nx + ix];
+    return ORDER == 1 ? mz_row_factors_dc(P, c0, dX, sX, dZ, sZ) : mz_row_factors_d2c(P, c0, dX, sX, dZ, sZ);
+}
+
 // T of a row (mz_star: corners tc, verticals tv, horizontals th, the cross term tzx): what multiplies the averaged buoyancies.  survey_frechet.hip
 // (k_buoyancy_adjoint) says how the transposes use it.
 struct MzStiff { cplx tv[2], th[2], tc[2][2], tzx; };
@@ -165,4 +176,43 @@ __device__ __forceinline__ cplx lag_coefficient(const MzStiff &t, const cplx *__
     cplx q = cmul(t.tc[(sz + 1) / 2][(sx + 1) / 2], d);
     cfma(q, t.tzx, csub(Pl[(long long)mz_slot(sz, 0) * N + i], Pl[(long long)mz_slot(0, sx) * N + i]));
     return q;
+}
+
+// sum_(k, i) (d^ORDER A / dc_j^ORDER)_((k, i)) P_k[i] at cell j (CONJ: the conjugated coefficients; STRETCH false: the mass term alone): the body that the
+// transposes of the first and of the second derivative share (survey_frechet.hip k_velocity_adjoint; survey_newton.hip k_velocity_curvature).  The mass part is the
+// gather of k_buoyancy_adjoint over the interior rows i = j - o, times (d^ORDER kappa_j / dc^ORDER) b_j.  The stretch part is local to row j: its differentiated
+// stiffness factors (mz_stiffness is linear in the row) times the averaged buoyancies a_o = (b_j + b_(j+o)) / 2 and the Q-differences of P at j (lag_coefficient); a
+// boundary row has none.  A fixed order; the boundary rows of P are not read.
+template <int ORDER, bool CONJ, bool STRETCH>
+__device__ __forceinline__ cplx mz_transpose_at(const MzParams &P, const cplx *__restrict__ c, const double *__restrict__ rho, const cplx *__restrict__ Pl, long long j) {
+    const long long N = (long long)P.nz * P.nx;
+    const int jz = (int)(j / P.nx), jx = (int)(j % P.nx);
+    const double bj = 1.0 / rho[j];
+    cplx mass = cmake(0.0, 0.0), stretch = cmake(0.0, 0.0);
+#pragma unroll
+    for (int sz = -1; sz <= 1; ++sz)
+#pragma unroll
+        for (int sx = -1; sx <= 1; ++sx) {
+            const int iz = jz - sz, ix = jx - sx;                 // row i sees cell j at the lag (sz, sx)
+            if (iz < 1 || iz > P.nz - 2 || ix < 1 || ix > P.nx - 2) continue;
+            const double m = (sz == 0 && sx == 0) ? MZ_WC : ((sz == 0 || sx == 0) ? MZ_WD : MZ_WE);
+            const cplx p = Pl[(long long)mz_slot(sz, sx) * N + (long long)iz * P.nx + ix];
+            mass.x += m * p.x; mass.y += m * p.y;
+        }
+    if (STRETCH && jz >= 1 && jz <= P.nz - 2 && jx >= 1 && jx <= P.nx - 2) {
+        const MzStiff dt = mz_stiffness<CONJ>(P, mz_row_dnc_at<ORDER>(P, c, jz, jx));
+#pragma unroll
+        for (int oz = -1; oz <= 1; ++oz)
+#pragma unroll
+            for (int ox = -1; ox <= 1; ++ox)
+                if (oz != 0 || ox != 0) {
+                    const double a = (bj + 1.0 / rho[j + (long long)oz * P.nx + ox]) / 2.0;
+                    stretch = cadd(stretch, cscale(lag_coefficient(dt, Pl, N, j, oz, ox), a));
+                }
+    }
+    cplx dk = cscale(ORDER == 1 ? mz_kappa_dc(P, c[j]) : mz_kappa_d2c(P, c[j]), bj);
+    if (CONJ) dk = cconj(dk);
+    cplx sum = stretch;
+    cfma(sum, dk, mass);
+    return sum;
 }

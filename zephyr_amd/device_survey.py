@@ -9,7 +9,7 @@ The same loop serves forward fields that outlive a call (`fieldstore.DeviceField
 `dpredFromFields` samples the store and `gradientFromFields` images against it, both over the items the store recorded.  `illumination` and
 `illuminationFromFields` (last section) are the same two loops again with the energy kernel in the place of the imaging kernel and a float64 partial.
 
-The eight pipelines, one row each.  Every row is a body of its own made of the shared item steps of the next section.
+The nine pipelines, one row each.  Every row is a body of its own made of the shared item steps of the next section.
 
     pipeline                items                what fills R                        columns solved   what consumes U                       what comes down
     dpred                   dealt                source columns                      k                sampleDevice (2.5-D: sampleSumDevice) nrec x k samples per item
@@ -25,6 +25,9 @@ The eight pipelines, one row each.  Every row is a body of its own made of the s
       parameter='rho'                            qb of R^H r                         k                lag imaging into P, then L^T P        one partial G per worker
       linearisation='full'                       qb of R^H r                         k                lag imaging into P, then V^T P        one partial G per worker
                                                                                                       (no `rho`: and L^T P into Gb)         (and one Gb)
+    newtonFromFields        stored               qb of R^H r; the planes of p on     3k               lag imaging into P0 and P1, then      one partial G per worker
+                                                 the slice; the gathered samples of                   V^T P1 and the curvature kernel on P0 (parameter='rho': and one Gb)
+                                                 du plus the transposed planes on lambda
     illumination            dealt                source or receiver columns          k                energy kernel                         one partial H per worker
     illuminationFromFields  stored               --                                  0                -- (energy kernel reads the slice)    one partial H per worker
       kind='gaussNewton'                         receiver columns, once per worker   nrec, once per   lag Gram of the slice, then the       one partial H per worker
@@ -551,10 +554,11 @@ def _factorBytes(op):
     return one * (len(subs) if subs is not None and not getattr(op, 'kyRelease', False) else 1)
 
 
-def _checkSecondFactorsFit(items, planes=0, cols=None):
+def _checkSecondFactorsFit(items, planes=0, cols=None, blocks=2):
     """MemoryError unless every GPU has room for what a pass through the TRANSPOSED operators adds to a resident forward pass: their factors -- the factors of
     A and of A^T are held side by side -- and the item's U and R (planes: and that many model-sized complex128 planes, the lag products of parameter='rho';
-    cols: the columns solved per item where they are not the item's own, the receiver columns of kind='gaussNewton')"""
+    cols: the columns solved per item where they are not the item's own, the receiver columns of kind='gaussNewton'; blocks: the column blocks of an item where
+    they are more than U and R, the four of `newtonFromFields`)"""
     seen = set()
 
     def factors(op, c0, c1):
@@ -562,7 +566,7 @@ def _checkSecondFactorsFit(items, planes=0, cols=None):
         first = id(op) not in seen
         seen.add(id(op))
         return _factorBytes(op) if first and not op.factors and str(getattr(op, 'method', 'auto')).lower() in ('auto', 'direct') else 0
-    _checkItemsFit(items, held=factors, work=lambda op, c0, c1: (2 * (c1 - c0 if cols is None else cols) + planes) * int(op.nrow) * 16)
+    _checkItemsFit(items, held=factors, work=lambda op, c0, c1: (blocks * (c1 - c0 if cols is None else cols) + planes) * int(op.nrow) * 16)
 
 
 def gradientFromFields(prob, F, qb, resid, system=None, linearisation='scaler', parameter='c', chain=None):
@@ -764,6 +768,103 @@ def _gradientPlanesFromFields(prob, F, qb, resid, system, velocity=False, chain=
     wss = runOnDevices(devs, items, one)
     g = _sumPartials(prob, [ws.G for ws in wss if ws.G is not None]).real
     return g + chain * _sumPartials(prob, [ws.Gb for ws in wss if ws.Gb is not None]).real if gardner else g
+
+
+def newtonFromFields(prob, F, p, qb, resid, system, linearisation, parameter):
+    """prob.Hvec(u=F, resid=): the full Newton Hessian of 1/2 ||dpred - dobs||^2 times p (N,) float64, float64 (N,), from forward fields already in HBM.  Three
+    solves of the item's k columns per stored item, made of the steps of `_gradientPlanesFromFields` and `_bornPlanesFromFields`; `system` the transposed
+    operators, whose items the loop runs over (the forward operator of an item is that of the same frequency and batch: the same GPU), qb / resid those of
+    R_s^H r.  The store and every solve hold the conjugates of u^, lambda, du and dlambda, so the coefficients are conjugated, not the fields:
+
+      1. lambda~ = the transposed solve of the back-sources of resid                                  (what the gradient solves)
+      2. the planes C of p, once per item (k_velocity_planes, k_mass_planes for 'operator', or k_buoyancy_planes of -p / rho^2); R = -(1 / premul) C shift(conj(slice)) (k_stencil_sources),
+         du~ = the forward solve
+      3. the samples of du~ times scaleTerm (and the phase of `_hermitianResidual`) gathered into back-sources through the survey's adjoint plan
+         (helm_rhs_from_samples_device, fixed and moving arrays alike), plus the conjugate of -(1 / conj(premul)) C^H lambda~, which k_stencil_sources_t adds
+         to R where it lies; dlambda~ = the transposed solve
+      4. P1 += lag(dlambda~, slice) + lag(lambda~, du~), P0 += lag(lambda~, slice) (k_lag_imaging), then G += w conj(V)^T P1 (k_velocity_adjoint) + w p (.) the
+         conjugated second derivative contracted with P0 (k_velocity_curvature), w = -scaleTerm / conj(premul).
+
+    parameter='rho': the buoyancy transpose of P1 into G and of P0 into Gb; the worker's partial is then (d b / d rho) G + p (d^2 b / d rho^2) Gb, so that the ranks
+    still end in one all-reduce.  linearisation is the resolved one; 'operator' with parameter='c' runs k_mass_planes, the mass-only k_velocity_adjoint and the
+    curvature kernel without its stretch part.  Four column blocks (R, lambda~, du~, dlambda~) and 27 planes per worker."""
+    import torch
+    F.checkCurrent(prob)
+    sv = prob.survey
+    N, nrec = prob.nrow, sv.nrec
+    scale = F.scale
+    density = parameter == 'rho'
+    stretch = linearisation == 'full'                  # ('operator' with parameter='c': the mass term alone in planes, transpose and curvature)
+    if not F.items:
+        return _sumPartials(prob, []).real
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    pert = np.ascontiguousarray(prob._buoyancyChain() * p) if density else p
+    owned = F.ownedFreqs
+    _prepareBackSources(sv, None, owned)                 # (the adjoint plans: step 3 gathers the samples of du through them for a fixed array too, whose qb serves step 1 only)
+    Rms = _receiverMatrices(sv, owned)
+    stride = nrec if sv.mode != 'fixed' else 0
+    phase = scale * np.asarray(prob._hermitianResidual(np.ones((nrec, 1, 1), dtype=np.complex128)), dtype=np.complex128).reshape((nrec, 1))
+    devs, items = _storedItems(system, F)
+    forward = {(ifreq, c0): op for _, op, ifreq, c0, _ in _storedItems(prob.system, F)[1]}
+    _checkSecondFactorsFit(items, planes=27, blocks=4)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        dev = ws.device
+        fop = forward[(ifreq, c0)]
+        pm = complex(op.premul)
+        d_uF, d_exp = F.pointers(ifreq, c0)
+        G = _partial(ws, 'G', N, torch.complex128)
+        Gb = _partial(ws, 'Gb', N, torch.complex128) if density else None
+        vd = ws.cached(('newton_v', id(pert)), lambda: _lib.to_device(pert, dev, np.float64), keep=pert)          # (p, or the buoyancy perturbation that goes with it)
+        ph = ws.cached(('newton_phase',), lambda: _lib.to_device(phase, dev, np.complex128))
+        gk = sv._gridKey(ifreq)
+        csr, out = _csrOnDevice(ws, Rms[gk], gk, nrec, stride, c0), ws.buffer('out', (nrec, k))
+        plan = _planOnDevice(ws, sv, ifreq)
+        R, L, D, Z = ws.buffer('R', k * Ni), ws.buffer('U', k * Ni), ws.buffer('dU', k * Ni), ws.buffer('dL', k * Ni)
+        C, P0, P1 = ws.buffer('planes', 9 * Ni), ws.buffer('lags', 9 * Ni), ws.buffer('lags1', 9 * Ni)
+        # 1. lambda~
+        _backSources(ws, sv, op, qb, resid, ifreq, c0, c1, R.data_ptr(), Ni)
+        P0.zero_()
+        P1.zero_()
+        _lib.wait_torch_stream(dev)
+        op.solveDevice(R.data_ptr(), L.data_ptr(), k, Ni)
+        # 2. du~
+        if density:
+            fop.buoyancyPlanesDevice(vd.data_ptr(), C.data_ptr())
+        elif stretch:
+            fop.velocityPlanesDevice(vd.data_ptr(), None, C.data_ptr())
+        else:
+            fop.massPlanesDevice(vd.data_ptr(), C.data_ptr())
+        fop.stencilSourcesDevice(d_uF, k, C.data_ptr(), -1.0 / pm, R.data_ptr(), conj=True, d_exp=d_exp, rows=Ni)
+        fop.solveDevice(R.data_ptr(), D.data_ptr(), k, Ni)
+        # 3. dlambda~
+        fop.sampleDevice(D.data_ptr(), k, csr, out.data_ptr())
+        out.mul_(ph)                                     # (in place: nrec x k)
+        _lib.wait_torch_stream(dev)
+        op.rhsFromSamplesDevice(out.data_ptr(), k, plan, c0, c1, R.data_ptr(), rows=Ni)
+        op.stencilSourcesTransposedDevice(L.data_ptr(), k, C.data_ptr(), np.conj(-1.0 / pm), R.data_ptr(), conj=True, rows=Ni, accumulate=True)      # (R += its conjugate: no block of its own)
+        op.solveDevice(R.data_ptr(), Z.data_ptr(), k, Ni)
+        # 4. the lag products and their transposes
+        op.lagImagingAccumulateDevice(d_uF, L.data_ptr(), k, P0.data_ptr(), d_exp=d_exp, rows=Ni)
+        op.lagImagingAccumulateDevice(d_uF, Z.data_ptr(), k, P1.data_ptr(), d_exp=d_exp, rows=Ni)
+        op.lagImagingAccumulateDevice(D.data_ptr(), L.data_ptr(), k, P1.data_ptr(), rows=Ni)
+        w = -scale / np.conj(pm)
+        if density:
+            op.buoyancyAdjointDevice(P1.data_ptr(), w, G.data_ptr(), conj=True)
+            op.buoyancyAdjointDevice(P0.data_ptr(), w, Gb.data_ptr(), conj=True)
+        else:
+            if stretch:
+                op.velocityAdjointDevice(P1.data_ptr(), w, G.data_ptr(), conj=True)
+            else:
+                op.massAdjointDevice(P1.data_ptr(), w, G.data_ptr(), conj=True)
+            op.velocityCurvatureDevice(P0.data_ptr(), vd.data_ptr(), w, G.data_ptr(), conj=True, stretch=stretch)
+    wss = [ws for ws in runOnDevices(devs, items, one) if ws.G is not None]
+    if density:
+        chain, curve = prob._buoyancyChain(), p * prob._buoyancyCurvature()
+        for ws in wss:
+            ws.G.mul_(_lib.to_device(chain, ws.device, np.float64)).add_(ws.Gb * _lib.to_device(curve, ws.device, np.float64))
+    return _sumPartials(prob, [ws.G for ws in wss]).real
 
 
 # ---- illumination / diagonal pseudo-Hessian ---------------------------------------------------------------------------------------------------

@@ -402,6 +402,36 @@ class BaseDiscretization(BaseModelDependent):
         w = complex(w)
         _lib.check(_lib.load().helm_velocity_adjoint_device(self.handle, ctypes.c_void_p(d_p), w.real, w.imag, 1 if conj else 0, ctypes.c_void_p(d_g)), self.handle)
 
+    def velocityCurvatureDevice(self, d_p, d_v, w, d_g, conj=False, stretch=True):
+        """G += w v (.) (the second derivative of the operator along e_j contracted with P) on the device, frechet.velocityCurvature: d_p 9 nrow complex128, d_v nrow
+        float64 (the perturbation), d_g nrow complex128, w a complex number; conj: the conjugated coefficients; stretch False: the mass term alone"""
+        w = complex(w)
+        _lib.check(_lib.load().helm_velocity_curvature_device(self.handle, ctypes.c_void_p(d_p), ctypes.c_void_p(d_v), w.real, w.imag, 1 if conj else 0,
+                                                              1 if stretch else 0, ctypes.c_void_p(d_g)), self.handle)
+
+    def massPlanesDevice(self, d_dc, d_c):
+        "dC = the mass term of velocityPlanesDevice alone on the device, frechet.massPlanes (linearisation='operator'): d_dc nrow float64, d_c 9 nrow complex128"
+        _lib.check(_lib.load().helm_mass_planes_device(self.handle, ctypes.c_void_p(d_dc), ctypes.c_void_p(d_c)), self.handle)
+
+    def massAdjointDevice(self, d_p, w, d_g, conj=False):
+        "G += w M^T P (conj: conj(M)^T P) on the device, M the map of massPlanesDevice: frechet.velocityAdjoint(stretch=False); arguments as velocityAdjointDevice"
+        w = complex(w)
+        _lib.check(_lib.load().helm_mass_adjoint_device(self.handle, ctypes.c_void_p(d_p), w.real, w.imag, 1 if conj else 0, ctypes.c_void_p(d_g)), self.handle)
+
+    def stencilSourcesTransposedDevice(self, d_u, nsrc, d_c, coef, d_r, conj=False, d_exp=None, rows=None, accumulate=False):
+        """R[s] = coef (dC)^T U[s] (conj: (dC)^H U[s]) on the device, frechet.applyPlanesTransposed: d_c the nine planes of velocityPlanesDevice or
+        buoyancyPlanesDevice, read at the neighbouring cell -- the transposed set is never formed; the other arguments as for stencilSourcesDevice, but conj
+        conjugates the planes, not the columns.  accumulate: R[s] += the CONJUGATE of that value instead."""
+        lib = _lib.load()
+        rows = int(self.nrow if rows is None else rows)
+        coef = complex(coef)
+        if d_exp is not None:
+            _lib.check(lib.helm_stencil_sources_t_c64_device(self.handle, ctypes.c_void_p(d_u), ctypes.c_void_p(d_exp), int(nsrc), rows, ctypes.c_void_p(d_c),
+                                                             coef.real, coef.imag, 1 if conj else 0, 1 if accumulate else 0, ctypes.c_void_p(d_r), rows), self.handle)
+            return
+        _lib.check(lib.helm_stencil_sources_t_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), rows, ctypes.c_void_p(d_c), coef.real, coef.imag,
+                                                     1 if conj else 0, 1 if accumulate else 0, ctypes.c_void_p(d_r), rows), self.handle)
+
     PSEUDO_HESSIAN_MODES = {'velocity': 0, 'buoyancy': 1, 'gardner': 2}
 
     def pseudoHessianAccumulateDevice(self, d_u, nsrc, mode, d_chain, alpha, d_w, d_h, d_exp=None, rows=None):

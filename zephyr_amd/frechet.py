@@ -6,7 +6,9 @@ row by the mass weights, and overwrites its boundary rows by +-identity, so
 
 The host routes of problem.py evaluate this here; the device routes (device_survey.py) take the scalars from here and run the stencil in
 k_virtual_sources_op / k_imaging_op (csrc/survey_frechet.hip).  The second part of the module is the derivative with respect to the density (parameter='rho'), the
-third the total derivative with respect to the velocity (linearisation='full'): the mass term above, the PML stretch and the density that follows c."""
+third the total derivative with respect to the velocity (linearisation='full'): the mass term above, the PML stretch and the density that follows c; then
+the second derivative of the operator and the transposed planes, what Hvec(resid=) adds to the Gauss-Newton product (k_velocity_curvature / k_stencil_sources_t,
+csrc/survey_newton.hip)."""
 import numpy as np
 
 
@@ -140,6 +142,36 @@ def massWeightDc(op, dtype=np.complex128):
     "d kappa / d c = -2 omega_d^2 / c^3 per cell (nz, nx), kappa = omega_d^2 / c^2 - (2 pi ky)^2, in the arithmetic of dtype"
     c, om = _pmlAxes(op, dtype)[:2]
     return -2 * om * om / (c * c * c)
+
+
+def rowFactorsD2c(op, dtype=np.complex128, magnitude=False):
+    """d^2 (X, Z, px, pz) / d c^2 of `rowFactors`, each (nz, nx).  Per axis, in the notation of `rowFactorsDc` and with a = f d^2, X = (i omega_d)^2 / den^2 and
+    p = s 2 f d (i omega_d)^2 c / den^3, so
+
+        d^2 X / dc^2 = 6 X a^2 / den^2,      d^2 p / dc^2 = s 2 f d (2 (d^2 X / dc^2) c / den - 6 X a / den^2)
+
+    Outside the layers d = 0 and all four vanish.  magnitude: the moduli, d^2 p / dc^2 as the sum of the moduli of its two terms (they cancel in part)."""
+    c, _, iom, ax, az = _pmlAxes(op, dtype)
+    out = []
+    for f, d, s in (ax, az):
+        a = f * d ** 2
+        den = a * c + iom
+        S = (iom / den) ** 2
+        Sa = S * a / den
+        d2S = 6 * Sa * a / den
+        terms = (2 * d2S * c / den, -6 * Sa / den)
+        if magnitude:
+            d2S, d2p = np.abs(d2S), np.abs(s) * (2 * f * d) * (np.abs(terms[0]) + np.abs(terms[1]))
+        else:
+            d2p = s * (2 * f * d) * (terms[0] + terms[1])
+        out.append((d2S + 0 * c.real, d2p + 0 * c.real) if magnitude else (d2S + 0 * c, d2p + 0 * c))
+    return out[0][0], out[1][0], out[0][1], out[1][1]
+
+
+def massWeightD2c(op, dtype=np.complex128):
+    "d^2 kappa / d c^2 = 6 omega_d^2 / c^4 per cell (nz, nx), in the arithmetic of dtype"
+    c, om = _pmlAxes(op, dtype)[:2]
+    return 6 * om * om / ((c * c) * (c * c))
 
 
 def _stiffness(op, rf, magnitude=False):
@@ -310,14 +342,21 @@ def velocityPlanes(op, dc, db=None, dtype=np.complex128, magnitude=False):
     return C if db is None else C + buoyancyPlanes(op, db, dtype, magnitude)
 
 
-def velocityAdjoint(op, P, dtype=np.complex128, magnitude=False, conj=False):
+def velocityAdjoint(op, P, dtype=np.complex128, magnitude=False, conj=False, stretch=True):
     """V^T P: (N,) with <velocityPlanes(op, dc), P> = <dc, V^T P> under the bilinear pairing sum_k sum_i (no conjugate), P (9, N) or (9, nz, nx) complex; its
     boundary rows are not read.  Cell j takes (d kappa_j / dc) b_j times the mass weights from the planes of the rows around it, and from its own row the
-    differentiated stiffness factors times the averaged buoyancies.  conj: conj(V)^T P.  magnitude: the sum of the moduli of the terms."""
+    differentiated stiffness factors times the averaged buoyancies.  conj: conj(V)^T P.  magnitude: the sum of the moduli of the terms.  stretch False: the
+    transpose of `massPlanes`, the mass term alone."""
+    return _rowAdjoint(op, P, rowFactorsDc(op, dtype, magnitude), massWeightDc(op, dtype), dtype, magnitude, conj, stretch)
+
+
+def _rowAdjoint(op, P, drow, dkappa, dtype, magnitude, conj, stretch):
+    """the transpose of dc -> star(dc_i drow_i, bn[b], Kn_k = dkappa_j b_j dc_j) applied to the planes P, (N,): `velocityAdjoint` with the first derivatives of the row
+    factors and of kappa, the per-cell factor of `velocityCurvature` with the second ones"""
     nz, nx = int(op.nz), int(op.nx)
     R = _real(dtype)
     b = _buoyancy(op, R)
-    drow, w = rowFactorsDc(op, dtype, magnitude), massWeightDc(op, dtype) * b
+    w = dkappa * b
     if conj:
         drow, w = tuple(np.conj(x) for x in drow), np.conj(w)
     t, tzx = _stiffness(op, drow, magnitude)
@@ -339,7 +378,53 @@ def velocityAdjoint(op, P, dtype=np.complex128, magnitude=False, conj=False):
             q = q + tzx * (Pl[slot[(sz, 0)]] + sgn * Pl[slot[(0, sx)]])
         stiff = stiff + (b + _at(b, sz, sx)) / 2 * q             # (zero on the boundary lines: the planes are zero there)
         mass = mass + (me if sz and sx else md) * _at(Pl[slot[o]], -sz, -sx)
-    return (stiff + w * mass).ravel()
+    return (stiff + w * mass).ravel() if stretch else (w * mass).ravel()
+
+
+# ---- the second derivative of the operator: what the full Newton Hessian adds to J^T J ---------------------------------------------------------------------
+# With an explicit density a row is star(row_i(c_i), bn, Kn_k = kappa(c_j) b_j) and the star has no product of a row factor with a mass term, so
+# d^2 A / dc_i dc_j = 0 for i != j: the second derivative along (p, q) is star(p_i q_i d^2 row_i / dc^2, bn[b], Kn_k = (d^2 kappa_j / dc^2) b_j p_j q_j)
+# (`velocityPlanes2`), and its contraction with nine lag products is local to a cell (`velocityCurvature`; k_velocity_curvature, csrc/survey_newton.hip).  Where the
+# density follows c (Gardner) b_j(c_j) multiplies row_i(c_i) in the averages and the mixed derivative is not zero: not built.
+
+def velocityPlanes2(op, dc, dc2=None, dtype=np.complex128, magnitude=False, stretch=True):
+    """The nine planes (9, nz, nx) of the second derivative of A along the real velocity perturbations dc and dc2 (default dc again) at the density of the operator,
+    boundary rows zero: d/dh of velocityPlanes(op at c + h dc2, dc) at h = 0.  stretch False: the mass term alone, the derivative of `massPlanes`."""
+    nz, nx = int(op.nz), int(op.nx)
+    R = _real(dtype)
+    v = np.asarray(dc).astype(R).reshape((nz, nx)) * np.asarray(dc if dc2 is None else dc2).astype(R).reshape((nz, nx))
+    if magnitude:
+        v = np.abs(v)
+    b = _buoyancy(op, R)
+    d2row = [x * (v if stretch else 0 * v) for x in rowFactorsD2c(op, dtype, magnitude)]
+    d2kb = massWeightD2c(op, dtype) * b * v
+    t, tzx = _stiffness(op, d2row, magnitude)
+    return _starPlanes(t, tzx, b, np.abs(d2kb) if magnitude else d2kb, R, dtype, magnitude)
+
+
+def velocityCurvature(op, P, p, conj=False, stretch=True, dtype=np.complex128, magnitude=False):
+    """(N,): w with <dc2, w> = <velocityPlanes2(op, p, dc2), P> under the bilinear pairing for every dc2 -- the third term of the Newton Hessian-vector product,
+    p_j [(d^2 kappa_j / dc^2) b_j (the mass gather of P at j) + (the stretch part of `velocityAdjoint` with d^2 row_j / dc^2)].  P (9, N) or (9, nz, nx) complex, its
+    boundary rows not read; p (N,) real.  conj: the conjugated coefficients.  stretch False: the mass term alone.  magnitude: the sum of the moduli of the terms."""
+    R = _real(dtype)
+    v = np.asarray(p).astype(R).ravel()
+    return (np.abs(v) if magnitude else v) * _rowAdjoint(op, P, rowFactorsD2c(op, dtype, magnitude), massWeightD2c(op, dtype), dtype, magnitude, conj, stretch)
+
+
+def applyPlanesTransposed(C, U, nz=None, nx=None, magnitude=False):
+    """(dA)^T U column by column of U ((N,) or (N, k)) from the planes C (9, nz, nx) (or (9, N) with nz, nx given) of dA, cells outside the grid contributing
+    nothing: sum_k CT_k (.) U(i + off_k) with CT_k[i] = C_(8-k)[i + off_k], the transposed plane set, which is never formed.  magnitude: every term by its modulus."""
+    if nz is None:
+        nz, nx = np.shape(C)[1:3]
+    nz, nx = int(nz), int(nx)
+    a = np.asarray(U).reshape((nz, nx) + np.shape(U)[1:])
+    Cb = np.asarray(C).reshape((9, nz, nx) + (1,) * (a.ndim - 2))
+    if magnitude:
+        a, Cb = np.abs(a), np.abs(Cb)
+    out = np.zeros(a.shape, dtype=np.result_type(a.dtype, Cb.dtype))
+    for k, (sz, sx) in enumerate(LAGS):
+        out = out + _at(Cb[8 - k] * a, sz, sx)
+    return out.reshape(np.shape(U))
 
 
 # ---- the pseudo-Hessian diagonal of the exact derivatives ------------------------------------------------------------------------------------------

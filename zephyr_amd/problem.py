@@ -35,6 +35,7 @@ from .frechet import applyPlanes, buoyancyAdjoint, buoyancyPlanes, lagProducts  
 from .frechet import gardnerChain, velocityAdjoint, velocityPlanes                  # (and linearisation='full')
 from .frechet import operatorPseudoHessianWeight, pseudoHessianDiagonal              # (and the pseudo-Hessian diagonal of either)
 from .frechet import gaussNewtonDiagonal, lagGram                                   # (and the exact diagonal of the Gauss-Newton Hessian)
+from .frechet import applyPlanesTransposed, massPlanes, velocityCurvature           # (and the residual part of the Newton Hessian)
 
 EPS = 1e-15
 
@@ -589,7 +590,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             data = parallel.allreduce_sum(data)
         return data.ravel()
 
-    def Hvec(self, m=None, v=None, u=None, weights=None, linearisation='scaler', parameter='c'):
+    def Hvec(self, m=None, v=None, u=None, weights=None, linearisation='scaler', parameter='c', resid=None):
         """Gauss-Newton Hessian times v: Jtvec(JvecBorn(v) (.) weights, adjoint='transpose'), float64 (N,).  Symmetric and positive semi-definite as an
         operator on real vectors, because the two halves are exact adjoints.  weights: optional, real, non-negative, the shape (or ravel) of the data.
         Both halves read the same forward fields: two solves of nsrc columns per frequency, no forward re-solve; with u None the fields are solved once
@@ -597,7 +598,25 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         linearisation: handed to both halves; with 'operator' this is the Gauss-Newton Hessian of 1/2 ||dpred - dobs||^2 for perturbations that vanish in the
         absorbing layers, with 'full' for any perturbation (with 'scaler' it is not).
         parameter: 'c' (default), 'rho', or a pair (input, output) handed to JvecBorn and Jtvec respectively -- ('c', 'rho') takes a velocity perturbation
-        and returns the density block row of the Hessian, the transpose of ('rho', 'c').  Anything with 'rho' needs linearisation='operator' or 'full'."""
+        and returns the density block row of the Hessian, the transpose of ('rho', 'c').  Anything with 'rho' needs linearisation='operator' or 'full'.
+
+        resid (default None: all of the above, unchanged): the data residual dpred(m) - dobs, the size of the data.  The result is then the FULL Newton Hessian
+        of phi(m) = 1/2 ||dpred(m) - dobs||^2 times v: with g(m) = Jtvec(m, dpred(m) - dobs, adjoint='transpose', linearisation=, parameter=) at fixed dobs,
+        d/dh g(m + h v) at h = 0.  Per frequency and source, with u the stored forward solve, lambda = A^-T (the back-source of resid) what the gradient solves,
+        dA[v] the planes of the perturbation and du = -A^-1 dA[v] u the Born field, ONE more solve through A^T gives
+        dlambda = A^-T (R^H R du - dA[v]^T lambda), and
+
+            (H v)_i = -Re[ <dlambda, d_i A u> + <lambda, d_i A du> + <lambda, (d_i dA[v]) u> ]
+
+        up to the scaleTerm and premul factors of Jtvec: the adjoint of the derivative applied to the lag products of (dlambda, u) and (lambda, du), plus the
+        second derivative of the planes contracted with the lag products of (lambda, u) -- the gradient's own.  With an explicit density d^2 A / dc_i dc_j = 0 for
+        i != j and that term is local to a cell (frechet.velocityCurvature); for parameter='rho' it is v (.) 2 / rho^3 (.) the buoyancy gradient.  The R^H R du part
+        alone is the Gauss-Newton product: with resid = 0 the two agree.  Symmetric; NOT positive semi-definite in general -- the residual part has either
+        sign, which is what a truncated-Newton iteration has to cope with.  Three solves of nsrc columns per frequency instead of two.
+        Served: Helm2DProblem with MiniZephyr / MiniZephyrHD on one grid and an explicit `rho`; linearisation='full', and 'operator' (the stretch parts of both
+        derivatives left out: exact for v that vanishes in the absorbing layers); parameter 'c' or 'rho'; fixed and moving receiver arrays; u a DeviceFields or
+        None with the device path (both store formats), host lists or no GPU: numpy.  linearisation='scaler' is no derivative and has no Hessian (ValueError); a parameter pair and a
+        config without `rho` raise NotImplementedError (the mixed second derivatives are not local to a cell); `weights` together with `resid`: ValueError."""
         self._requirePaired()
         if v is None:
             raise Exception('Actually, Hvec requires a vector')
@@ -605,6 +624,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         pin, pout = parameter if isinstance(parameter, (tuple, list)) and len(parameter) == 2 else (parameter, parameter)
         self._checkParameter(pin, linearisation)
         self._checkParameter(pout, linearisation)
+        if resid is not None and linearisation == 'scaler':
+            raise ValueError('linearisation=\'scaler\' is not the derivative of dpred and has no Hessian: Hvec(resid=) needs \'operator\' or \'full\'')
+        if resid is not None and weights is not None:
+            raise ValueError('Hvec(resid=) takes no data weights: the residual of a weighted misfit is the caller\'s to weigh')
         self.updateModel(m)
         self._refuseMultiscale('Hvec')
         for par in (pin, pout):
@@ -614,11 +637,89 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             if np.iscomplexobj(weights) or weights.size != self.survey.nD or not np.all(weights >= 0):
                 raise ValueError('weights are real, non-negative and of the size of the data (%d)' % (self.survey.nD,))
             weights = weights.astype(np.float64).ravel()
+        if resid is not None:
+            if pin != pout:
+                raise NotImplementedError('Hvec(resid=) serves one parameter: the mixed second derivative of the operator with respect to c and b is not local to a cell')
+            if not self._hasDensity():
+                raise NotImplementedError('Hvec(resid=) needs an explicit `rho` in the config: where the density follows c the buoyancy of a cell multiplies the '
+                                          'stretch factors of its neighbours\' rows, and the second derivative of the operator is not local to a cell')
+            resid = np.asarray(resid)
+            if resid.size != self.survey.nD:
+                raise ValueError('resid is of the size of the data (%d), not %d' % (self.survey.nD, resid.size))
+            resid = resid.astype(np.complex128).reshape((self.survey.nrec, self.survey.nsrc, self.survey.nfreq))
+            return self._HvecNewton(np.asarray(v, dtype=np.float64).reshape((self.nrow,)), u, resid, self._resolveLinearisation(linearisation, pin, 'Hvec'), pin)
         with self._forwardFields(u) as F:
             d = self.JvecBorn(None, v, u=F, linearisation=linearisation, parameter=pin)
             if weights is not None:
                 d = d * weights
             return self.Jtvec(None, d, u=F, adjoint='transpose', linearisation=linearisation, parameter=pout)
+
+    def _HvecNewton(self, p, u, resid, linearisation, parameter):
+        """Hvec(resid=) once the model is current and the refusals are past: p float64 (N,), resid (nrec, nsrc, nfreq), the resolved linearisation.  The numpy
+        route below follows `_JtvecTranspose` and the host branch of `JvecBorn` for scaleTerm, premul and conjugations: the host fields are scaleTerm conj(u^),
+        a solve returns scaleTerm conj(A^-1 premul q) (A^-T through `adjointSystem`), and the weight of a frequency is -conj(scaleTerm) / premul."""
+        sv = self.survey
+        density = parameter == 'rho'
+        stretch = linearisation == 'full'
+        adj = self.adjointSystem
+        with self._forwardFields(u) as F:
+            if isinstance(F, DeviceFields):
+                rd = self._hermitianResidual(resid)
+                return device_survey.newtonFromFields(self, F, p, self._deviceBackSources(rd), rd, adj, linearisation, parameter)
+            st = complex(self.system.scaleTerm)
+            subs = self.system.subProblems
+            owned = self.ownedFreqs
+            nf = sv.nfreq
+            hermitian = lambda r: [q.conj() for q in sv.getResidualSources(np.conj(r))]          # (R_s^H r_s = conj(R_s^T conj(r_s)))
+            unscaled = lambda a: np.conj(np.asarray(a) / st)
+            if density:
+                pert = self._buoyancyChain() * p
+                planes = lambda op: buoyancyPlanes(op, pert)
+            else:
+                planes = (lambda op: velocityPlanes(op, p)) if stretch else (lambda op: massPlanes(op, p))
+            # 1. lambda = A^-T premul R^H r, what the gradient solves
+            lam = {i: unscaled(uB) for i, uB in self._solveOwned(hermitian(resid), adj)}
+            # 2. the Born field du = -A^-1 dA[p] u^ and its samples
+            C = {i: planes(subs[i]) for i in owned}
+            uh = {i: unscaled(F[i]) for i in owned}
+            qv = [applyPlanes(C[i], uh[i], subs[i].nz, subs[i].nx) / -complex(subs[i].premul) if i in owned else None for i in range(nf)]
+            du, dd = {}, np.zeros((sv.nrec, sv.nsrc, nf), dtype=np.complex128)
+            for i, uB in self._solveOwned(qv):
+                uB = np.asarray(uB)
+                du[i] = unscaled(uB)
+                if sv.mode == 'fixed':
+                    dd[:, :, i] = sv.rVec(0, i) * uB
+                else:
+                    for isrc in range(sv.nsrc):
+                        dd[:, isrc, i] = sv.rVec(isrc, i) * uB[:, isrc]
+            # 3. dlambda = A^-T (premul R^H R du - dA[p]^T lambda): the first part alone is the Gauss-Newton product
+            qr = hermitian(dd)
+            q3 = [np.asarray(qr[i].toarray()) - applyPlanesTransposed(C[i], lam[i], subs[i].nz, subs[i].nx) / complex(subs[i].premul) if i in owned else None
+                  for i in range(nf)]
+            g = np.zeros(self.nrow, dtype=np.complex128)
+            g0 = np.zeros(self.nrow, dtype=np.complex128)
+            for i, uB in self._solveOwned(q3, adj):
+                op = subs[i]
+                dlam = unscaled(uB)
+                P1 = lagProducts(dlam, uh[i], op.nz, op.nx) + lagProducts(lam[i], du[i], op.nz, op.nx)
+                P0 = lagProducts(lam[i], uh[i], op.nz, op.nx)          # (the gradient's own lag products)
+                w = -np.conj(st) / complex(op.premul)
+                if density:
+                    g += w * buoyancyAdjoint(op, P1)
+                    g0 += w * buoyancyAdjoint(op, P0)
+                else:
+                    g += w * (velocityAdjoint(op, P1, stretch=stretch) + velocityCurvature(op, P0, p, stretch=stretch))
+        if density:
+            # b = 1 / rho: d b / d rho = -1 / rho^2 on the first two terms, d^2 b / d rho^2 = 2 / rho^3 times the buoyancy gradient for the third
+            g = self._buoyancyChain() * g.real + p * self._buoyancyCurvature() * g0.real
+        else:
+            g = g.real
+        return parallel.allreduce_sum(g) if self._sharded else g
+
+    def _buoyancyCurvature(self):
+        "d^2 b / d rho^2 = 2 / rho^3 per cell, float64 (N,), at the density of the config"
+        rho = np.broadcast_to(np.asarray(self.systemConfig['rho'], dtype=np.float64).ravel(), (self.nrow,))
+        return 2.0 / (rho * rho * rho)
 
     # ---- illumination / diagonal pseudo-Hessian ------------------------------------------------------------
     def illumination(self, m=None, u=None, kind='pseudoHessian', side='source', perFreq=False, linearisation='scaler', parameter='c'):
