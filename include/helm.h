@@ -362,6 +362,23 @@ int helm_stencil_sources_t_c64_device(helm_op *op, const void *dU32, const void 
 int helm_mass_planes_device(helm_op *op, const void *dDc, void *dC);
 int helm_mass_adjoint_device(helm_op *op, const void *dP, double w_re, double w_im, int conj, void *dG);
 
+/* --- the mixed (c, b) second derivative of MiniZephyr (HelmBaseProblem.Hvec with parameter='joint' and resid=) --------------------------------------
+ * A row is star(row_i(c_i), bn[b], Kn_k = kappa(c_j) b_j), bilinear in (row, bn) and linear in Kn: d^2 A / db^2 = 0 and along a velocity perturbation p and a buoyancy
+ * perturbation beta the mixed derivative is star(p_i d row_i / dc, bn[beta], Kn_k = (d kappa_j / dc) beta_j p_j) -- the planes of helm_velocity_planes_device with
+ * beta in the place of 1 / rho.
+ *
+ * helm_velocity_adjoint_b_device:  G[j] += w sum_{k, i} (those planes along p = e_j)_{(k, i)} P[k][i], the transpose in the velocity: helm_velocity_adjoint_device
+ *     (stretch == 0: helm_mass_adjoint_device) with dB[j] read where it has 1 / rho[j].  dB: N float64 of any sign, zeros included; it is never inverted.
+ * helm_mixed_adjoint_device:  G[j] += w sum_{k, i} (those planes along beta = e_j)_{(k, i)} P[k][i], the transpose in the buoyancy: the gather of
+ *     helm_buoyancy_adjoint_device with the stiffness factors of row i replaced by p_i d row_i / dc and kappa_j by (d kappa_j / dc) p_j; cell j reads p at the rows
+ *     around it.  dp: N float64 of any sign.  stretch == 0: the mass term alone, (d kappa_j / dc) p_j times the mass gather of P.
+ *
+ * conj != 0: the conjugated coefficients.  P: 9 N complex128, its boundary rows not read; G: N complex128.  The same rules as above: plain fp64 in a fixed order, one
+ * writer per entry, no atomics; HELM_ERR_STATE before the first helm_assemble; Eurus, 3-D and ny > 0 handles HELM_ERR_UNSUPPORTED; null, misaligned (16 bytes; dB,
+ * dp: 8) or overlapping pointers and grids below 3 x 3 HELM_ERR_ARG.  All device pointers; each call returns when its result is complete. */
+int helm_velocity_adjoint_b_device(helm_op *op, const void *dP, const void *dB, double w_re, double w_im, int conj, int stretch, void *dG);
+int helm_mixed_adjoint_device(helm_op *op, const void *dP, const void *dp, double w_re, double w_im, int conj, int stretch, void *dG);
+
 /* --- the pseudo-Hessian diagonal of the exact derivatives (HelmBaseProblem.illumination with linearisation='full' / 'operator') ------------------
  * H[i] += alpha (dW ? W[i] : 1) sum_{s<nsrc} || (d A / d p_i) u^_s ||_2^2 for i < N, with U[s] = conj(u^_s) the stored columns (nsrc columns of ld >= N complex128,
  * or, _c64, complex64 values with the int32 column exponents dExp of helm_pack_c64_device) and d A / d p_i the derivative of the operator the handle holds:

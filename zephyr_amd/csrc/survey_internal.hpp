@@ -1,6 +1,6 @@
 // What the translation units of a survey share: survey.hip (the plumbing: right-hand sides, axpby, the complex64 pack, imaging, energy, sampling),
 // survey_frechet.hip (the derivative kernels of the 2-D MiniZephyr operator), survey_hessian.hip (the two Hessian diagonals built on them) and survey_newton.hip
-// (the second derivative and the transposed planes of the Newton Hessian-vector product).  The readers
+// (the second derivative and the transposed planes of the Newton Hessian-vector product) and survey_joint.hip (the transposes of the mixed (c, b) derivative).  The readers
 // of a stored field on the device (FieldC128 / FieldC64) and its description on the host (HostField), how an entry point ends and refuses, the walk of the
 // stencil kernels over the grid, and the row factors of MiniZephyr at a cell.
 //
@@ -182,12 +182,13 @@ __device__ __forceinline__ cplx lag_coefficient(const MzStiff &t, const cplx *__
 // transposes of the first and of the second derivative share (survey_frechet.hip k_velocity_adjoint; survey_newton.hip k_velocity_curvature).  The mass part is the
 // gather of k_buoyancy_adjoint over the interior rows i = j - o, times (d^ORDER kappa_j / dc^ORDER) b_j.  The stretch part is local to row j: its differentiated
 // stiffness factors (mz_stiffness is linear in the row) times the averaged buoyancies a_o = (b_j + b_(j+o)) / 2 and the Q-differences of P at j (lag_coefficient); a
-// boundary row has none.  A fixed order; the boundary rows of P are not read.
-template <int ORDER, bool CONJ, bool STRETCH>
+// boundary row has none.  A fixed order; the boundary rows of P are not read.  BARRAY: `rho` is not a density but the field that stands in the place of the
+// buoyancy, read as it is -- any sign, zeros included (survey_joint.hip k_velocity_adjoint_b, the transpose of the mixed derivative d^2 A / dc db in c).
+template <int ORDER, bool CONJ, bool STRETCH, bool BARRAY = false>
 __device__ __forceinline__ cplx mz_transpose_at(const MzParams &P, const cplx *__restrict__ c, const double *__restrict__ rho, const cplx *__restrict__ Pl, long long j) {
     const long long N = (long long)P.nz * P.nx;
     const int jz = (int)(j / P.nx), jx = (int)(j % P.nx);
-    const double bj = 1.0 / rho[j];
+    const double bj = BARRAY ? rho[j] : 1.0 / rho[j];
     cplx mass = cmake(0.0, 0.0), stretch = cmake(0.0, 0.0);
 #pragma unroll
     for (int sz = -1; sz <= 1; ++sz)
@@ -206,7 +207,8 @@ __device__ __forceinline__ cplx mz_transpose_at(const MzParams &P, const cplx *_
 #pragma unroll
             for (int ox = -1; ox <= 1; ++ox)
                 if (oz != 0 || ox != 0) {
-                    const double a = (bj + 1.0 / rho[j + (long long)oz * P.nx + ox]) / 2.0;
+                    const double bo = rho[j + (long long)oz * P.nx + ox];
+                    const double a = (bj + (BARRAY ? bo : 1.0 / bo)) / 2.0;
                     stretch = cadd(stretch, cscale(lag_coefficient(dt, Pl, N, j, oz, ox), a));
                 }
     }

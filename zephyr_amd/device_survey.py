@@ -9,7 +9,7 @@ The same loop serves forward fields that outlive a call (`fieldstore.DeviceField
 `dpredFromFields` samples the store and `gradientFromFields` images against it, both over the items the store recorded.  `illumination` and
 `illuminationFromFields` (last section) are the same two loops again with the energy kernel in the place of the imaging kernel and a float64 partial.
 
-The nine pipelines, one row each.  Every row is a body of its own made of the shared item steps of the next section.
+The ten pipelines, one row each.  Every row is a body of its own made of the shared item steps of the next section.
 
     pipeline                items                what fills R                        columns solved   what consumes U                       what comes down
     dpred                   dealt                source columns                      k                sampleDevice (2.5-D: sampleSumDevice) nrec x k samples per item
@@ -28,7 +28,11 @@ The nine pipelines, one row each.  Every row is a body of its own made of the sh
     newtonFromFields        stored               qb of R^H r; the planes of p on     3k               lag imaging into P0 and P1, then      one partial G per worker
                                                  the slice; the gathered samples of                   V^T P1 and the curvature kernel on P0 (parameter='rho': and one Gb)
                                                  du plus the transposed planes on lambda
-    illumination            dealt                source or receiver columns          k                energy kernel                         one partial H per worker
+      parameter='joint'                          the same with the planes of [c; rho]  3k               the same, and the two mixed transposes one stacked partial G (2N), and Gb
+                                                                                                      on P0 (k_velocity_adjoint_b, k_mixed_adjoint)
+    jointGradientFromFields stored               qb of R^H r                         k                lag imaging into P, then V^T P and    one stacked partial G (2N) per worker
+                                                                                                      L^T P into the halves of G
+    illumination           dealt                source or receiver columns          k                energy kernel                         one partial H per worker
     illuminationFromFields  stored               --                                  0                -- (energy kernel reads the slice)    one partial H per worker
       kind='gaussNewton'                         receiver columns, once per worker   nrec, once per   lag Gram of the slice, then the       one partial H per worker
                                                  and frequency                       worker and freq. combine kernel
@@ -239,7 +243,7 @@ def _cachedInverseC3Rho(ws, op):
 
 
 def _partial(ws, name, shape, dtype):
-    "the worker's partial result ws.<name> ('G': gradient, 'Gb': its buoyancy part, 'H': illumination), zeroed on first use"
+    "the worker's partial result ws.<name> ('G': gradient -- 2 N entries, [c; b], for parameter='joint' --, 'Gb': its buoyancy part, 'H': illumination), zeroed on first use"
     import torch
     if getattr(ws, name) is None:
         setattr(ws, name, torch.zeros(shape, dtype=dtype, device=ws.device))
@@ -353,11 +357,12 @@ def gradient(prob, qb, owned, resid):
     return _sumPartials(prob, [ws.G for ws in runOnDevices(devs, items, one) if ws.G is not None])
 
 
-def _sumPartials(prob, parts):
+def _sumPartials(prob, parts, n=None):
     """the gradient from the workers' partial gradients: summed on the host, then ONE all-reduce over ranks when the frequencies are sharded (no partial:
-    a rank that owns no frequency brings zeros to that all-reduce)"""
+    a rank that owns no frequency brings zeros to that all-reduce).  n: the length of a partial where it is not the grid's (2 N: the stacked [c; b] of
+    parameter='joint')"""
     import torch
-    N = prob.nrow
+    N = prob.nrow if n is None else int(n)
     if len(parts) == 1:
         G = parts[0]
         if prob._sharded:
@@ -621,7 +626,10 @@ def bornFromFields(prob, F, v, linearisation='scaler', parameter='c', db=None):
     through the CONJUGATED receiver CSR (row stride 0 for a fixed array, nrec for one that moves with the source) come down: nrec x k values per item.
     linearisation='operator': `_bornOperatorFromFields`; with parameter='rho' (v the BUOYANCY perturbation -v_rho / rho^2): `_bornPlanesFromFields`.
     linearisation='full': the same pipeline with the velocity planes of v; db (N,) float64 the buoyancy perturbation that goes with v where the density follows
-    c, or None."""
+    c, or None.  parameter='joint': v the velocity half and db = -v_rho / rho^2 the buoyancy half of a stacked [c; rho] perturbation -- one set of planes
+    V[v] + L[db] and one solve ('operator': the mass term of V alone)."""
+    if parameter == 'joint':
+        return _bornPlanesFromFields(prob, F, db, dc=v, stretch=linearisation == 'full')
     if parameter == 'rho':
         return _bornPlanesFromFields(prob, F, v)
     if linearisation == 'full':
@@ -690,13 +698,27 @@ def _bornOperatorFromFields(prob, F, v):
     return data
 
 
-def _bornPlanesFromFields(prob, F, db, dc=None):
+def _jointPlanes(ws, fop, dcd, dbd, C, stretch, spare):
+    """C = V[dc] + L[db] of the forward operator `fop`, the planes of a stacked [c; rho] perturbation: one call of k_velocity_planes; stretch False
+    ('operator'): k_mass_planes into C, k_buoyancy_planes into `spare` (nine planes the caller has no other use for yet) and their sum by torch, followed by the
+    hand-over to the library's stream"""
+    if stretch:
+        fop.velocityPlanesDevice(dcd.data_ptr(), dbd.data_ptr(), C.data_ptr())
+        return
+    fop.massPlanesDevice(dcd.data_ptr(), C.data_ptr())
+    fop.buoyancyPlanesDevice(dbd.data_ptr(), spare.data_ptr())
+    C.add_(spare)
+    _lib.wait_torch_stream(ws.device)
+
+
+def _bornPlanesFromFields(prob, F, db, dc=None, stretch=True):
     """prob.JvecBorn(u=F, linearisation='operator', parameter='rho'): the derivative of dpred along the buoyancy perturbation db (N,) float64.  The items,
     calls and waits of `_bornOperatorFromFields` with the virtual-source step in two calls: k_buoyancy_planes makes the nine planes L_f[db] of the item's
     frequency in the workspace (db goes up once per worker), k_stencil_sources writes R = -(1 / premul) sum_k L_f[db]_k (.) shift_k(conj(slice)).
     dc given (N,) float64: prob.JvecBorn(u=F, linearisation='full'), the total derivative along the velocity perturbation dc -- the same body with
     k_velocity_planes in the place of k_buoyancy_planes: the planes V_f[dc] of the mass term and the PML stretch, plus L_f[db] where the density follows c
-    (db = (d b / d c) dc then; None with an explicit density)."""
+    (db = (d b / d c) dc then; None with an explicit density).  stretch False (parameter='joint' with linearisation='operator', dc and db both given): the
+    mass term of V[dc] alone plus L[db], `_jointPlanes`."""
     F.checkCurrent(prob)
     data, stage, sample = _sampling(prob, F.ownedFreqs, F.scale)
     if not F.items:
@@ -713,8 +735,11 @@ def _bornPlanesFromFields(prob, F, db, dc=None):
         dbd = None if db is None else ws.cached(('born_db', id(db)), lambda: _lib.to_device(db, dev, np.float64), keep=db)
         dcd = None if dc is None else ws.cached(('born_dc', id(dc)), lambda: _lib.to_device(dc, dev, np.float64), keep=dc)
         U, R, C = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni), ws.buffer('planes', 9 * Ni)
+        spare = None if stretch else ws.buffer('lags', 9 * Ni)
         _lib.wait_torch_stream(dev)
-        if dcd is None:
+        if not stretch:
+            _jointPlanes(ws, op, dcd, dbd, C, False, spare)
+        elif dcd is None:
             op.buoyancyPlanesDevice(dbd.data_ptr(), C.data_ptr())
         else:
             op.velocityPlanesDevice(dcd.data_ptr(), None if dbd is None else dbd.data_ptr(), C.data_ptr())
@@ -770,6 +795,43 @@ def _gradientPlanesFromFields(prob, F, qb, resid, system, velocity=False, chain=
     return g + chain * _sumPartials(prob, [ws.Gb for ws in wss if ws.Gb is not None]).real if gardner else g
 
 
+def jointGradientFromFields(prob, F, qb, resid, system, linearisation):
+    """prob.Jtvec(u=F, adjoint='transpose', parameter='joint') up to d b / d rho on the second half: [g_c; g_b], float64 (2 N,), from ONE back-propagation per
+    stored item.  The item body of `_gradientPlanesFromFields` with both transposes applied to the same lag products P0: k_velocity_adjoint (the mass-only one
+    for linearisation='operator') into the first half of the worker's partial G (2 N complex128), k_buoyancy_adjoint into the second.  One all-reduce of the
+    stacked vector where the frequencies are sharded."""
+    import torch
+    F.checkCurrent(prob)
+    sv = prob.survey
+    N = prob.nrow
+    scale = F.scale
+    stretch = linearisation == 'full'
+    if not F.items:
+        return _sumPartials(prob, [], n=2 * N).real
+    _prepareBackSources(sv, qb, F.ownedFreqs)
+    devs, items = _storedItems(system, F)
+    _checkSecondFactorsFit(items, planes=9)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        d_uF, d_exp = F.pointers(ifreq, c0)
+        G = _partial(ws, 'G', 2 * N, torch.complex128)
+        U, R, P = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni), ws.buffer('lags', 9 * Ni)
+        _backSources(ws, sv, op, qb, resid, ifreq, c0, c1, R.data_ptr(), Ni)
+        P.zero_()
+        _lib.wait_torch_stream(ws.device)
+        op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+        op.lagImagingAccumulateDevice(d_uF, U.data_ptr(), k, P.data_ptr(), d_exp=d_exp, rows=Ni)
+        w = -scale / np.conj(complex(op.premul))
+        if stretch:
+            op.velocityAdjointDevice(P.data_ptr(), w, G.data_ptr(), conj=True)
+        else:
+            op.massAdjointDevice(P.data_ptr(), w, G.data_ptr(), conj=True)
+        op.buoyancyAdjointDevice(P.data_ptr(), w, G.data_ptr() + 16 * N, conj=True)
+    wss = runOnDevices(devs, items, one)
+    return _sumPartials(prob, [ws.G for ws in wss if ws.G is not None], n=2 * N).real
+
+
 def newtonFromFields(prob, F, p, qb, resid, system, linearisation, parameter):
     """prob.Hvec(u=F, resid=): the full Newton Hessian of 1/2 ||dpred - dobs||^2 times p (N,) float64, float64 (N,), from forward fields already in HBM.  Three
     solves of the item's k columns per stored item, made of the steps of `_gradientPlanesFromFields` and `_bornPlanesFromFields`; `system` the transposed
@@ -787,18 +849,29 @@ def newtonFromFields(prob, F, p, qb, resid, system, linearisation, parameter):
 
     parameter='rho': the buoyancy transpose of P1 into G and of P0 into Gb; the worker's partial is then (d b / d rho) G + p (d^2 b / d rho^2) Gb, so that the ranks
     still end in one all-reduce.  linearisation is the resolved one; 'operator' with parameter='c' runs k_mass_planes, the mass-only k_velocity_adjoint and the
-    curvature kernel without its stretch part.  Four column blocks (R, lambda~, du~, dlambda~) and 27 planes per worker."""
+    curvature kernel without its stretch part.  Four column blocks (R, lambda~, du~, dlambda~) and 27 planes per worker.
+
+    parameter='joint': p = [p_c; p_rho] (2 N,), the result (2 N,).  The same item body with the planes of the stacked perturbation, V[p_c] + L[db],
+    db = -p_rho / rho^2 (`_jointPlanes`), and three partials: the c half of G takes V^T P1, the curvature along p_c and M_c^T[db] P0 (k_velocity_adjoint_b: the
+    velocity transpose at the buoyancy db); the b half of G takes L^T P1 and M_b^T[p_c] P0 (k_mixed_adjoint); Gb takes L^T P0.  The worker's partial is then
+    [G_c; (d b / d rho) G_b + p_rho (d^2 b / d rho^2) Gb]: one stacked vector, one all-reduce.  The workspace stays at four column blocks and 27 planes ('operator'
+    borrows P1, before it is needed, for the second set of planes)."""
     import torch
     F.checkCurrent(prob)
     sv = prob.survey
     N, nrec = prob.nrow, sv.nrec
     scale = F.scale
     density = parameter == 'rho'
+    joint = parameter == 'joint'
     stretch = linearisation == 'full'                  # ('operator' with parameter='c': the mass term alone in planes, transpose and curvature)
     if not F.items:
-        return _sumPartials(prob, []).real
+        return _sumPartials(prob, [], n=2 * N if joint else None).real
     p = np.ascontiguousarray(p, dtype=np.float64)
-    pert = np.ascontiguousarray(prob._buoyancyChain() * p) if density else p
+    if joint:
+        pert, prho = np.ascontiguousarray(p[:N]), np.ascontiguousarray(p[N:])          # (the velocity half; the density half and its buoyancy perturbation)
+        pertb = np.ascontiguousarray(prob._buoyancyChain() * prho)
+    else:
+        pert = np.ascontiguousarray(prob._buoyancyChain() * p) if density else p
     owned = F.ownedFreqs
     _prepareBackSources(sv, None, owned)                 # (the adjoint plans: step 3 gathers the samples of du through them for a fixed array too, whose qb serves step 1 only)
     Rms = _receiverMatrices(sv, owned)
@@ -814,9 +887,10 @@ def newtonFromFields(prob, F, p, qb, resid, system, linearisation, parameter):
         fop = forward[(ifreq, c0)]
         pm = complex(op.premul)
         d_uF, d_exp = F.pointers(ifreq, c0)
-        G = _partial(ws, 'G', N, torch.complex128)
-        Gb = _partial(ws, 'Gb', N, torch.complex128) if density else None
+        G = _partial(ws, 'G', 2 * N if joint else N, torch.complex128)
+        Gb = _partial(ws, 'Gb', N, torch.complex128) if density or joint else None
         vd = ws.cached(('newton_v', id(pert)), lambda: _lib.to_device(pert, dev, np.float64), keep=pert)          # (p, or the buoyancy perturbation that goes with it)
+        bd = ws.cached(('newton_b', id(pertb)), lambda: _lib.to_device(pertb, dev, np.float64), keep=pertb) if joint else None
         ph = ws.cached(('newton_phase',), lambda: _lib.to_device(phase, dev, np.complex128))
         gk = sv._gridKey(ifreq)
         csr, out = _csrOnDevice(ws, Rms[gk], gk, nrec, stride, c0), ws.buffer('out', (nrec, k))
@@ -830,7 +904,12 @@ def newtonFromFields(prob, F, p, qb, resid, system, linearisation, parameter):
         _lib.wait_torch_stream(dev)
         op.solveDevice(R.data_ptr(), L.data_ptr(), k, Ni)
         # 2. du~
-        if density:
+        if joint:
+            _jointPlanes(ws, fop, vd, bd, C, stretch, P1)          # (P1 is not in use yet: zeroed again below where it served as the spare planes)
+            if not stretch:
+                P1.zero_()
+                _lib.wait_torch_stream(dev)
+        elif density:
             fop.buoyancyPlanesDevice(vd.data_ptr(), C.data_ptr())
         elif stretch:
             fop.velocityPlanesDevice(vd.data_ptr(), None, C.data_ptr())
@@ -850,7 +929,19 @@ def newtonFromFields(prob, F, p, qb, resid, system, linearisation, parameter):
         op.lagImagingAccumulateDevice(d_uF, Z.data_ptr(), k, P1.data_ptr(), d_exp=d_exp, rows=Ni)
         op.lagImagingAccumulateDevice(D.data_ptr(), L.data_ptr(), k, P1.data_ptr(), rows=Ni)
         w = -scale / np.conj(pm)
-        if density:
+        if joint:
+            # G = [G_c; G_b]: the c half takes V^T P1, the curvature and M_c^T[db] P0; the b half L^T P1 and M_b^T[p_c] P0; Gb = L^T P0, which d^2 b / d rho^2 multiplies
+            d_gb = G.data_ptr() + 16 * N
+            if stretch:
+                op.velocityAdjointDevice(P1.data_ptr(), w, G.data_ptr(), conj=True)
+            else:
+                op.massAdjointDevice(P1.data_ptr(), w, G.data_ptr(), conj=True)
+            op.velocityCurvatureDevice(P0.data_ptr(), vd.data_ptr(), w, G.data_ptr(), conj=True, stretch=stretch)
+            op.velocityAdjointBuoyancyDevice(P0.data_ptr(), bd.data_ptr(), w, G.data_ptr(), conj=True, stretch=stretch)
+            op.buoyancyAdjointDevice(P1.data_ptr(), w, d_gb, conj=True)
+            op.mixedAdjointDevice(P0.data_ptr(), vd.data_ptr(), w, d_gb, conj=True, stretch=stretch)
+            op.buoyancyAdjointDevice(P0.data_ptr(), w, Gb.data_ptr(), conj=True)
+        elif density:
             op.buoyancyAdjointDevice(P1.data_ptr(), w, G.data_ptr(), conj=True)
             op.buoyancyAdjointDevice(P0.data_ptr(), w, Gb.data_ptr(), conj=True)
         else:
@@ -864,7 +955,11 @@ def newtonFromFields(prob, F, p, qb, resid, system, linearisation, parameter):
         chain, curve = prob._buoyancyChain(), p * prob._buoyancyCurvature()
         for ws in wss:
             ws.G.mul_(_lib.to_device(chain, ws.device, np.float64)).add_(ws.Gb * _lib.to_device(curve, ws.device, np.float64))
-    return _sumPartials(prob, [ws.G for ws in wss]).real
+    elif joint:
+        chain, curve = prob._buoyancyChain(), prho * prob._buoyancyCurvature()
+        for ws in wss:          # (the buoyancy half alone: the three partials become one stacked vector per worker, and the ranks still end in one all-reduce)
+            ws.G[N:].mul_(_lib.to_device(chain, ws.device, np.float64)).add_(ws.Gb * _lib.to_device(curve, ws.device, np.float64))
+    return _sumPartials(prob, [ws.G for ws in wss], n=2 * N if joint else None).real
 
 
 # ---- illumination / diagonal pseudo-Hessian ---------------------------------------------------------------------------------------------------

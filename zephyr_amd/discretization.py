@@ -418,6 +418,20 @@ class BaseDiscretization(BaseModelDependent):
         w = complex(w)
         _lib.check(_lib.load().helm_mass_adjoint_device(self.handle, ctypes.c_void_p(d_p), w.real, w.imag, 1 if conj else 0, ctypes.c_void_p(d_g)), self.handle)
 
+    def velocityAdjointBuoyancyDevice(self, d_p, d_b, w, d_g, conj=False, stretch=True):
+        """G += w (V at the buoyancy B)^T P on the device, frechet.mixedAdjointC: velocityAdjointDevice (stretch False: massAdjointDevice) with the field d_b (nrow
+        float64, any sign) in the place of 1 / rho -- the transpose in the velocity of the mixed (c, b) second derivative"""
+        w = complex(w)
+        _lib.check(_lib.load().helm_velocity_adjoint_b_device(self.handle, ctypes.c_void_p(d_p), ctypes.c_void_p(d_b), w.real, w.imag, 1 if conj else 0,
+                                                              1 if stretch else 0, ctypes.c_void_p(d_g)), self.handle)
+
+    def mixedAdjointDevice(self, d_p, d_v, w, d_g, conj=False, stretch=True):
+        """G += w M_b^T[v] P on the device, frechet.mixedAdjointB: the transpose in the buoyancy of the mixed (c, b) second derivative along the velocity
+        perturbation d_v (nrow float64); d_p 9 nrow complex128, d_g nrow complex128, w a complex number; stretch False: the mass term alone"""
+        w = complex(w)
+        _lib.check(_lib.load().helm_mixed_adjoint_device(self.handle, ctypes.c_void_p(d_p), ctypes.c_void_p(d_v), w.real, w.imag, 1 if conj else 0,
+                                                         1 if stretch else 0, ctypes.c_void_p(d_g)), self.handle)
+
     def stencilSourcesTransposedDevice(self, d_u, nsrc, d_c, coef, d_r, conj=False, d_exp=None, rows=None, accumulate=False):
         """R[s] = coef (dC)^T U[s] (conj: (dC)^H U[s]) on the device, frechet.applyPlanesTransposed: d_c the nine planes of velocityPlanesDevice or
         buoyancyPlanesDevice, read at the neighbouring cell -- the transposed set is never formed; the other arguments as for stencilSourcesDevice, but conj

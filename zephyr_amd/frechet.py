@@ -8,7 +8,8 @@ The host routes of problem.py evaluate this here; the device routes (device_surv
 k_virtual_sources_op / k_imaging_op (csrc/survey_frechet.hip).  The second part of the module is the derivative with respect to the density (parameter='rho'), the
 third the total derivative with respect to the velocity (linearisation='full'): the mass term above, the PML stretch and the density that follows c; then
 the second derivative of the operator and the transposed planes, what Hvec(resid=) adds to the Gauss-Newton product (k_velocity_curvature / k_stencil_sources_t,
-csrc/survey_newton.hip)."""
+csrc/survey_newton.hip); and the mixed second derivative with respect to velocity and buoyancy, what parameter='joint' adds to that (k_velocity_adjoint_b /
+k_mixed_adjoint, csrc/survey_joint.hip)."""
 import numpy as np
 
 
@@ -254,12 +255,18 @@ def buoyancyPlanes(op, db, dtype=np.complex128, magnitude=False):
 def buoyancyAdjoint(op, P, dtype=np.complex128, magnitude=False, conj=False):
     """L^T P: (N,) with <L[db], P> = <db, L^T P> under the bilinear pairing sum_k sum_i (no conjugate), P (9, N) or (9, nz, nx) complex; its boundary rows
     are not read.  conj: conj(L)^T P.  magnitude: the sum of the moduli of the terms."""
+    rf = rowFactors(op, dtype)
+    return _buoyancyGather(op, P, rf[:4], rf[4], dtype, magnitude, conj)
+
+
+def _buoyancyGather(op, P, rf, kappa, dtype, magnitude, conj):
+    """the transpose of b -> star(rf_i, bn[b], Kn_k = kappa_j b_j) applied to the planes P, (N,): `buoyancyAdjoint` with the row factors and kappa of the operator,
+    `mixedAdjointB` with their derivatives along a velocity perturbation.  rf: (X, Z, px, pz) of the rows (moduli with magnitude), kappa per cell."""
     nz, nx = int(op.nz), int(op.nx)
     R = _real(dtype)
-    rf = rowFactors(op, dtype)
     if conj:
-        rf = tuple(np.conj(x) for x in rf)
-    kappa = np.abs(rf[4]) if magnitude else rf[4]
+        rf, kappa = tuple(np.conj(x) for x in rf), np.conj(kappa)
+    kappa = np.abs(kappa) if magnitude else kappa
     t, tzx = _stiffness(op, rf, magnitude)
     Pl = np.asarray(P).astype(dtype).reshape((9, nz, nx)).copy()
     Pl[:, ~_interiorMask(nz, nx)] = 0
@@ -350,12 +357,13 @@ def velocityAdjoint(op, P, dtype=np.complex128, magnitude=False, conj=False, str
     return _rowAdjoint(op, P, rowFactorsDc(op, dtype, magnitude), massWeightDc(op, dtype), dtype, magnitude, conj, stretch)
 
 
-def _rowAdjoint(op, P, drow, dkappa, dtype, magnitude, conj, stretch):
+def _rowAdjoint(op, P, drow, dkappa, dtype, magnitude, conj, stretch, b=None):
     """the transpose of dc -> star(dc_i drow_i, bn[b], Kn_k = dkappa_j b_j dc_j) applied to the planes P, (N,): `velocityAdjoint` with the first derivatives of the row
-    factors and of kappa, the per-cell factor of `velocityCurvature` with the second ones"""
+    factors and of kappa, the per-cell factor of `velocityCurvature` with the second ones.  b (nz, nx): the field in the place of the buoyancy of the operator
+    (`mixedAdjointC`; its moduli with magnitude)."""
     nz, nx = int(op.nz), int(op.nx)
     R = _real(dtype)
-    b = _buoyancy(op, R)
+    b = _buoyancy(op, R) if b is None else b
     w = dkappa * b
     if conj:
         drow, w = tuple(np.conj(x) for x in drow), np.conj(w)
@@ -409,6 +417,50 @@ def velocityCurvature(op, P, p, conj=False, stretch=True, dtype=np.complex128, m
     R = _real(dtype)
     v = np.asarray(p).astype(R).ravel()
     return (np.abs(v) if magnitude else v) * _rowAdjoint(op, P, rowFactorsD2c(op, dtype, magnitude), massWeightD2c(op, dtype), dtype, magnitude, conj, stretch)
+
+
+# ---- the mixed second derivative with respect to velocity and buoyancy: what couples the two halves of a joint (c, rho) Newton product ------------------------
+# A row star(row_i(c_i), bn[b], Kn_k = kappa(c_j) b_j) is bilinear in (row, bn) and linear in Kn, so d^2 A / db^2 = 0 and along a velocity perturbation p and a
+# buoyancy perturbation beta
+#     d^2 A / dc db [p, beta] = star(p_i d row_i / dc, bn[beta], Kn_k = (d kappa_j / dc) beta_j p_j)
+# -- `velocityPlanes` with beta in the place of the buoyancy (`mixedPlanes`).  Its transpose in p is `velocityAdjoint` with beta for b (`mixedAdjointC`, local to
+# a cell but for the mass gather); its transpose in beta is `buoyancyAdjoint` with the stiffness factors of ROW i replaced by p_i d row_i / dc and kappa_j by
+# (d kappa_j / dc) p_j (`mixedAdjointB`: cell j sees p at the eight rows around it).  k_velocity_adjoint_b / k_mixed_adjoint (csrc/survey_joint.hip).
+
+def mixedPlanes(op, dc, db, stretch=True, dtype=np.complex128, magnitude=False):
+    """The nine planes (9, nz, nx) of d^2 A / dc db along the real velocity perturbation dc and the real buoyancy perturbation db (N,) each, any sign, boundary rows
+    zero: d/dh of buoyancyPlanes(op at c + h dc, db) at h = 0.  stretch False: the mass term alone.  magnitude: every term by its modulus."""
+    nz, nx = int(op.nz), int(op.nx)
+    R = _real(dtype)
+    v = np.asarray(dc).astype(R).reshape((nz, nx))
+    beta = np.asarray(db).astype(R).reshape((nz, nx))
+    if magnitude:
+        v, beta = np.abs(v), np.abs(beta)
+    drow = [x * (v if stretch else 0 * v) for x in rowFactorsDc(op, dtype, magnitude)]
+    dkb = massWeightDc(op, dtype) * beta * v
+    t, tzx = _stiffness(op, drow, magnitude)
+    return _starPlanes(t, tzx, beta, np.abs(dkb) if magnitude else dkb, R, dtype, magnitude)
+
+
+def mixedAdjointC(op, P, db, conj=False, stretch=True, dtype=np.complex128, magnitude=False):
+    """M_c^T[db] P: (N,) with <mixedPlanes(op, dc, db), P> = <dc, M_c^T[db] P> under the bilinear pairing for every dc -- `velocityAdjoint` with db (N,) real, any
+    sign, in the place of the buoyancy.  P (9, N) or (9, nz, nx) complex, its boundary rows not read.  conj: the conjugated coefficients.  stretch False: the mass
+    term alone.  magnitude: the sum of the moduli of the terms."""
+    R = _real(dtype)
+    beta = np.asarray(db).astype(R).reshape((int(op.nz), int(op.nx)))
+    return _rowAdjoint(op, P, rowFactorsDc(op, dtype, magnitude), massWeightDc(op, dtype), dtype, magnitude, conj, stretch, b=np.abs(beta) if magnitude else beta)
+
+
+def mixedAdjointB(op, P, dc, conj=False, stretch=True, dtype=np.complex128, magnitude=False):
+    """M_b^T[dc] P: (N,) with <mixedPlanes(op, dc, db), P> = <db, M_b^T[dc] P> under the bilinear pairing for every db -- `buoyancyAdjoint` with the stiffness factors
+    of row i replaced by dc_i d row_i / dc and kappa_j by (d kappa_j / dc) dc_j; not local: cell j sees dc at the eight rows around it.  Arguments as
+    `mixedAdjointC`, dc (N,) real."""
+    R = _real(dtype)
+    v = np.asarray(dc).astype(R).reshape((int(op.nz), int(op.nx)))
+    if magnitude:
+        v = np.abs(v)
+    drow = [x * (v if stretch else 0 * v) for x in rowFactorsDc(op, dtype, magnitude)]
+    return _buoyancyGather(op, P, drow, massWeightDc(op, dtype) * v, dtype, magnitude, conj)
 
 
 def applyPlanesTransposed(C, U, nz=None, nx=None, magnitude=False):

@@ -36,6 +36,7 @@ from .frechet import gardnerChain, velocityAdjoint, velocityPlanes              
 from .frechet import operatorPseudoHessianWeight, pseudoHessianDiagonal              # (and the pseudo-Hessian diagonal of either)
 from .frechet import gaussNewtonDiagonal, lagGram                                   # (and the exact diagonal of the Gauss-Newton Hessian)
 from .frechet import applyPlanesTransposed, massPlanes, velocityCurvature           # (and the residual part of the Newton Hessian)
+from .frechet import mixedAdjointB, mixedAdjointC                                   # (and the mixed second derivative of parameter='joint')
 
 EPS = 1e-15
 
@@ -281,6 +282,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             g_b = Re sum_f -(conj(scaleTerm) / premul) L_f^T P_f,      g_rho = -g_b / rho^2.
         m stays the velocity.  The same routes as 'c'.  With linearisation='full' and an explicit `rho` this is 'operator' under another name; without one
         the density is not a free parameter and the call raises NotImplementedError.
+        parameter='joint' ('operator' or 'full', an explicit `rho`): [g_c; g_rho], float64 (2 N,), from ONE back-propagation per source and frequency -- both are
+        transposes applied to the same lag products, g_c = Re w V_f^T P_f (its mass term alone for 'operator'), g_rho = -(Re w L_f^T P_f) / rho^2.
         """
         self._requirePaired()
         if v is None:
@@ -288,7 +291,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if adjoint not in ('reciprocity', 'transpose'):
             raise ValueError('adjoint is %r: \'reciprocity\' or \'transpose\'' % (adjoint,))
         self._checkLinearisation(linearisation)
-        self._checkParameter(parameter, linearisation)
+        self._checkParameter(parameter, linearisation, joint=True)
         if linearisation in ('operator', 'full') and adjoint != 'transpose':
             raise ValueError('linearisation=%r needs adjoint=\'transpose\': the exact derivative back-propagates through A^-T' % (linearisation,))
         self.updateModel(m)
@@ -332,8 +335,13 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             raise ValueError('linearisation is %r: \'scaler\', \'operator\' or \'full\'' % (linearisation,))
 
     @staticmethod
-    def _checkParameter(parameter, linearisation):
-        "parameter is 'c' or 'rho'; the density has no scaler in the reference, so 'rho' needs linearisation='operator' (or 'full', which is the same there)"
+    def _checkParameter(parameter, linearisation, joint=False):
+        """parameter is 'c' or 'rho'; the density has no scaler in the reference, so 'rho' needs linearisation='operator' (or 'full', which is the same there).
+        joint: 'joint' is served too -- the stacked pair [c; rho], which has no scaler either"""
+        if joint and isinstance(parameter, str) and parameter == 'joint':
+            if linearisation not in ('operator', 'full'):
+                raise ValueError('parameter=\'joint\' needs linearisation=\'operator\' or \'full\': the reference has no gradient scaler for the density')
+            return
         if parameter not in ('c', 'rho'):
             raise ValueError('parameter is %r: \'c\' or \'rho\'' % (parameter,))
         if parameter == 'rho' and linearisation not in ('operator', 'full'):
@@ -343,6 +351,14 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         "d b / d rho = -1 / rho^2 per cell, float64 (N,), at the density of the config: b = 1 / rho is what the operator is linear in"
         rho = np.broadcast_to(np.asarray(self.systemConfig['rho'], dtype=np.float64).ravel(), (self.nrow,))       # (a scalar rho is one value for every cell)
         return -1.0 / (rho * rho)
+
+    def _splitJoint(self, v, what):
+        "(v_c, v_rho), float64 (N,) each, of a stacked vector [v_c; v_rho] of parameter='joint'; ValueError unless it has 2 N entries"
+        v = np.asarray(v)
+        if v.size != 2 * self.nrow:
+            raise ValueError('%s(parameter=\'joint\') takes the stacked vector [c; rho] of %d entries, not %d' % (what, 2 * self.nrow, v.size))
+        v = np.asarray(v, dtype=np.float64).reshape((2 * self.nrow,))
+        return np.ascontiguousarray(v[:self.nrow]), np.ascontiguousarray(v[self.nrow:])
 
     def _hasDensity(self):
         'the config gives the density: it is a parameter of its own.  Otherwise it follows the velocity, rho = 310 Re(c)^0.25 (Gardner)'
@@ -374,6 +390,13 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         """the linearisation a route runs with, once what it does not serve is refused: 'full' with parameter='rho' is 'operator' -- the density derivative
         leaves nothing out -- and needs the density to be a parameter of its own"""
         what = '%s(linearisation=%r)' % (what, linearisation)
+        if parameter == 'joint':
+            # [c; rho] stacked: what 'full' serves, and the density a parameter of its own; 'operator' stays 'operator' (the stretch parts left out of the c half)
+            self._requireFullLinearisation(what)
+            if not self._hasDensity():
+                raise NotImplementedError('%s with parameter=\'joint\' needs an explicit `rho` in the config: without one the density follows c and is '
+                                          'not a free parameter' % (what,))
+            return linearisation
         if linearisation == 'operator':
             self._requireOperatorLinearisation(what)
         elif linearisation == 'full':
@@ -440,6 +463,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         "Jtvec(adjoint='transpose') once the model is current and `resid` is (nrec, nsrc, nfreq)"
         self._refuseMultiscale("Jtvec(adjoint='transpose')")
         linearisation = self._resolveLinearisation(linearisation, parameter, 'Jtvec')
+        if parameter == 'joint':
+            return self._JtvecJoint(resid, u, linearisation)
         exact = linearisation == 'operator'
         full = linearisation == 'full'
         density = parameter == 'rho'
@@ -492,6 +517,34 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             g = parallel.allreduce_sum(g)
         return self._buoyancyChain() * g.real if density else g.real
 
+    def _JtvecJoint(self, resid, u, linearisation):
+        """Jtvec(adjoint='transpose', parameter='joint') once the refusals are past: [g_c; g_rho], float64 (2N,), from ONE back-propagation per source and
+        frequency.  Both gradients are transposes applied to the same nine lag products P0 = lag(z, u^): g_c = Re w V^T P0 (the mass term alone for
+        'operator'), g_rho = (-1 / rho^2) Re w L^T P0, w = -conj(scaleTerm) / premul."""
+        stretch = linearisation == 'full'
+        adj = self.adjointSystem
+        N = self.nrow
+        with self._forwardFields(u) as F:
+            if isinstance(F, DeviceFields):
+                rd = self._hermitianResidual(resid)
+                g = device_survey.jointGradientFromFields(self, F, self._deviceBackSources(rd), rd, adj, linearisation)
+                g[N:] *= self._buoyancyChain()
+                return g
+            g = np.zeros(2 * N, dtype=np.complex128)
+            st = complex(self.system.scaleTerm)
+            qb = [q.conj() for q in self.survey.getResidualSources(np.conj(resid))]
+            for ifreq, uB in self._solveOwned(qb, adj):
+                op = self.system.subProblems[ifreq]
+                P = lagProducts(np.conj(np.asarray(uB) / st), np.conj(np.asarray(F[ifreq]) / st), op.nz, op.nx)
+                w = -np.conj(st) / complex(op.premul)
+                g[:N] += w * velocityAdjoint(op, P, stretch=stretch)
+                g[N:] += w * buoyancyAdjoint(op, P)
+        if self._sharded:
+            g = parallel.allreduce_sum(g)
+        g = g.real.copy()
+        g[N:] *= self._buoyancyChain()
+        return g
+
     def JvecBorn(self, m=None, v=None, u=None, linearisation='scaler', parameter='c'):
         """Born data of the model perturbation v from the forward fields, the ravel of (nrec, nsrc, nfreq) complex128:
 
@@ -532,12 +585,16 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
 
             dd[:, s, f] = R_s . scaleTerm conj(-A_f^-1 (delta A) u^_s),   (delta A) u^ = sum_k L_f[db]_k (.) shift_k(u^)
 
-        exact everywhere, the absorbing layers and the boundary lines included.  The exact adjoint of Jtvec(..., parameter='rho'); the same routes."""
+        exact everywhere, the absorbing layers and the boundary lines included.  The exact adjoint of Jtvec(..., parameter='rho'); the same routes.
+
+        parameter='joint' ('operator' or 'full', an explicit `rho`): v = [v_c; v_rho] of 2 N entries, the derivative of dpred along both at once from one Born
+        solve: delta A = V_f[v_c] + L_f[-v_rho / rho^2] is one set of planes (for 'operator' the mass term of V_f alone).  The exact adjoint of
+        Jtvec(..., parameter='joint')."""
         self._requirePaired()
         if v is None:
             raise Exception('Actually, JvecBorn requires a perturbation vector')
         self._checkLinearisation(linearisation)
-        self._checkParameter(parameter, linearisation)
+        self._checkParameter(parameter, linearisation, joint=True)
         self.updateModel(m)
         self._refuseMultiscale('JvecBorn')
         linearisation = self._resolveLinearisation(linearisation, parameter, 'JvecBorn')
@@ -545,16 +602,24 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         full = linearisation == 'full'
         density = parameter == 'rho'
         sv = self.survey
-        pert = np.asarray(v).reshape((self.nrow,))
+        joint = parameter == 'joint'
+        if joint:
+            # [v_c; v_rho]: dA = V[v_c] + L[db], db = -v_rho / rho^2 -- one set of planes, one Born solve ('operator': the mass term of V alone)
+            pert, db = self._splitJoint(v, 'JvecBorn')
+            db = self._buoyancyChain() * db
+        else:
+            pert = np.asarray(v).reshape((self.nrow,))
         if density:
             pert = self._buoyancyChain() * np.asarray(pert, dtype=np.float64)          # (db: the operator is linear in the buoyancy)
-        elif full:
+        elif full and not joint:
             pert = np.asarray(pert, dtype=np.float64)
             chain = self._gardnerChain()
             db = None if chain is None else chain * pert                                # (the buoyancy perturbation that goes with v: the density follows c)
         with self._forwardFields(u) as F:
             if isinstance(F, DeviceFields):
-                if density:
+                if joint:
+                    data = device_survey.bornFromFields(self, F, pert, linearisation=linearisation, parameter='joint', db=db)
+                elif density:
                     data = device_survey.bornFromFields(self, F, pert, linearisation=linearisation, parameter='rho')
                 elif full:
                     data = device_survey.bornFromFields(self, F, pert, linearisation='full', db=db)
@@ -563,10 +628,13 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             else:
                 data = np.zeros((sv.nrec, sv.nsrc, sv.nfreq), dtype=np.complex128)
                 owned = self.ownedFreqs
-                if density or full:
+                if density or full or joint:
                     st = complex(self.system.scaleTerm)
                     subs = self.system.subProblems
-                    planes = (lambda op: buoyancyPlanes(op, pert)) if density else (lambda op: velocityPlanes(op, pert, db))
+                    if joint and not full:
+                        planes = lambda op: massPlanes(op, pert) + buoyancyPlanes(op, db)
+                    else:
+                        planes = (lambda op: buoyancyPlanes(op, pert)) if density else (lambda op: velocityPlanes(op, pert, db))
                     qv = [applyPlanes(planes(subs[i]), np.conj(np.asarray(F[i]) / st), subs[i].nz, subs[i].nx) / -complex(subs[i].premul)
                           if i in owned else None for i in range(sv.nfreq)]
                 elif exact:
@@ -614,16 +682,30 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         alone is the Gauss-Newton product: with resid = 0 the two agree.  Symmetric; NOT positive semi-definite in general -- the residual part has either
         sign, which is what a truncated-Newton iteration has to cope with.  Three solves of nsrc columns per frequency instead of two.
         Served: Helm2DProblem with MiniZephyr / MiniZephyrHD on one grid and an explicit `rho`; linearisation='full', and 'operator' (the stretch parts of both
-        derivatives left out: exact for v that vanishes in the absorbing layers); parameter 'c' or 'rho'; fixed and moving receiver arrays; u a DeviceFields or
+        derivatives left out: exact for v that vanishes in the absorbing layers); parameter 'c', 'rho' or 'joint'; fixed and moving receiver arrays; u a DeviceFields or
         None with the device path (both store formats), host lists or no GPU: numpy.  linearisation='scaler' is no derivative and has no Hessian (ValueError); a parameter pair and a
-        config without `rho` raise NotImplementedError (the mixed second derivatives are not local to a cell); `weights` together with `resid`: ValueError."""
+        config without `rho` raise NotImplementedError (the mixed second derivatives are not local to a cell); `weights` together with `resid`: ValueError.
+
+        parameter='joint' (not inside a pair; 'operator' or 'full'; an explicit `rho`): v = [v_c; v_rho] of 2 N entries, the result [H_c; H_rho] of 2 N entries in
+        the units of 'c' and 'rho'.  resid None: the sum of the four blocks above from ONE Born solve and ONE back-solve per source and frequency -- the planes
+        of the stacked perturbation are one set, V[v_c] + L[db] with db = -v_rho / rho^2.  With resid: d/dh of the joint gradient at (c + h v_c, rho + h v_rho),
+        three solves -- the off-diagonal blocks of the Newton Hessian included, which no pair reaches.  A row is bilinear in its stretch factors (of c_i) and the
+        averaged buoyancies and linear in the mass terms, so d^2 A / db^2 = 0 and d^2 A / dc db [p, beta] is `velocityPlanes` with beta in the place of the
+        buoyancy (frechet.mixedPlanes); with P1 and P0 the lag products above,
+
+            H_c   = Re w [ V^T P1 + velocityCurvature(P0, v_c) + M_c^T[db] P0 ]
+            H_rho = (-1 / rho^2) (.) Re w [ L^T P1 + M_b^T[v_c] P0 ]  +  v_rho (.) 2 / rho^3 (.) Re w L^T P0
+
+        M_c^T and M_b^T the transposes of the mixed derivative in its velocity and in its buoyancy argument (frechet.mixedAdjointC / mixedAdjointB; the second
+        gathers v_c from the eight rows around a cell).  Hvec([p; 0], resid=r) is [H_cc p; H_rho,c p]."""
         self._requirePaired()
         if v is None:
             raise Exception('Actually, Hvec requires a vector')
         self._checkLinearisation(linearisation)
         pin, pout = parameter if isinstance(parameter, (tuple, list)) and len(parameter) == 2 else (parameter, parameter)
-        self._checkParameter(pin, linearisation)
-        self._checkParameter(pout, linearisation)
+        joint = isinstance(parameter, str) and parameter == 'joint'           # ('joint' inside a pair is no parameter: ValueError below)
+        self._checkParameter(pin, linearisation, joint=joint)
+        self._checkParameter(pout, linearisation, joint=joint)
         if resid is not None and linearisation == 'scaler':
             raise ValueError('linearisation=\'scaler\' is not the derivative of dpred and has no Hessian: Hvec(resid=) needs \'operator\' or \'full\'')
         if resid is not None and weights is not None:
@@ -637,6 +719,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             if np.iscomplexobj(weights) or weights.size != self.survey.nD or not np.all(weights >= 0):
                 raise ValueError('weights are real, non-negative and of the size of the data (%d)' % (self.survey.nD,))
             weights = weights.astype(np.float64).ravel()
+        if joint:
+            self._splitJoint(v, 'Hvec')                                                 # (ValueError unless v is the stacked vector of 2 N entries)
         if resid is not None:
             if pin != pout:
                 raise NotImplementedError('Hvec(resid=) serves one parameter: the mixed second derivative of the operator with respect to c and b is not local to a cell')
@@ -647,7 +731,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             if resid.size != self.survey.nD:
                 raise ValueError('resid is of the size of the data (%d), not %d' % (self.survey.nD, resid.size))
             resid = resid.astype(np.complex128).reshape((self.survey.nrec, self.survey.nsrc, self.survey.nfreq))
-            return self._HvecNewton(np.asarray(v, dtype=np.float64).reshape((self.nrow,)), u, resid, self._resolveLinearisation(linearisation, pin, 'Hvec'), pin)
+            return self._HvecNewton(np.asarray(v, dtype=np.float64).reshape((2 * self.nrow if joint else self.nrow,)), u, resid,
+                                    self._resolveLinearisation(linearisation, pin, 'Hvec'), pin)
         with self._forwardFields(u) as F:
             d = self.JvecBorn(None, v, u=F, linearisation=linearisation, parameter=pin)
             if weights is not None:
@@ -659,7 +744,9 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         route below follows `_JtvecTranspose` and the host branch of `JvecBorn` for scaleTerm, premul and conjugations: the host fields are scaleTerm conj(u^),
         a solve returns scaleTerm conj(A^-1 premul q) (A^-T through `adjointSystem`), and the weight of a frequency is -conj(scaleTerm) / premul."""
         sv = self.survey
+        N = self.nrow
         density = parameter == 'rho'
+        joint = parameter == 'joint'
         stretch = linearisation == 'full'
         adj = self.adjointSystem
         with self._forwardFields(u) as F:
@@ -672,7 +759,11 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             nf = sv.nfreq
             hermitian = lambda r: [q.conj() for q in sv.getResidualSources(np.conj(r))]          # (R_s^H r_s = conj(R_s^T conj(r_s)))
             unscaled = lambda a: np.conj(np.asarray(a) / st)
-            if density:
+            if joint:
+                pc, prho = p[:N], p[N:]
+                db = self._buoyancyChain() * prho
+                planes = (lambda op: velocityPlanes(op, pc, db)) if stretch else (lambda op: massPlanes(op, pc) + buoyancyPlanes(op, db))
+            elif density:
                 pert = self._buoyancyChain() * p
                 planes = lambda op: buoyancyPlanes(op, pert)
             else:
@@ -696,20 +787,27 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             qr = hermitian(dd)
             q3 = [np.asarray(qr[i].toarray()) - applyPlanesTransposed(C[i], lam[i], subs[i].nz, subs[i].nx) / complex(subs[i].premul) if i in owned else None
                   for i in range(nf)]
-            g = np.zeros(self.nrow, dtype=np.complex128)
-            g0 = np.zeros(self.nrow, dtype=np.complex128)
+            g = np.zeros(2 * N if joint else N, dtype=np.complex128)
+            g0 = np.zeros(N, dtype=np.complex128)
             for i, uB in self._solveOwned(q3, adj):
                 op = subs[i]
                 dlam = unscaled(uB)
                 P1 = lagProducts(dlam, uh[i], op.nz, op.nx) + lagProducts(lam[i], du[i], op.nz, op.nx)
                 P0 = lagProducts(lam[i], uh[i], op.nz, op.nx)          # (the gradient's own lag products)
                 w = -np.conj(st) / complex(op.premul)
-                if density:
+                if joint:
+                    # the two mixed terms on the gradient's own lag products: M_c^T[db] P0 joins the c half, M_b^T[p_c] P0 the buoyancy half
+                    g[:N] += w * (velocityAdjoint(op, P1, stretch=stretch) + velocityCurvature(op, P0, pc, stretch=stretch) + mixedAdjointC(op, P0, db, stretch=stretch))
+                    g[N:] += w * (buoyancyAdjoint(op, P1) + mixedAdjointB(op, P0, pc, stretch=stretch))
+                    g0 += w * buoyancyAdjoint(op, P0)
+                elif density:
                     g += w * buoyancyAdjoint(op, P1)
                     g0 += w * buoyancyAdjoint(op, P0)
                 else:
                     g += w * (velocityAdjoint(op, P1, stretch=stretch) + velocityCurvature(op, P0, p, stretch=stretch))
-        if density:
+        if joint:
+            g = np.concatenate((g[:N].real, self._buoyancyChain() * g[N:].real + prho * self._buoyancyCurvature() * g0.real))
+        elif density:
             # b = 1 / rho: d b / d rho = -1 / rho^2 on the first two terms, d^2 b / d rho^2 = 2 / rho^3 times the buoyancy gradient for the third
             g = self._buoyancyChain() * g.real + p * self._buoyancyCurvature() * g0.real
         else:
