@@ -425,6 +425,25 @@ int helm_lag_gram_accumulate_device(helm_op *op, const void *dU, int nsrc, long 
 int helm_lag_gram_accumulate_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, void *dC);
 int helm_gauss_newton_diagonal_device(helm_op *op, int mode, const void *dChain, const void *dW, const void *dCu, const void *dCg, double alpha, void *dH);
 
+/* --- the per-cell 2 x 2 blocks of the joint (c, rho) Hessian (HelmBaseProblem.hessianBlocks) -----------------------------------------------------------
+ * With E^c_i the derivative of the operator the handle holds with respect to the velocity of cell i at the handle's density (stretch != 0: mode 0 above; stretch 0:
+ * the mass term alone, mode 3 of the diagonal) and E^b_i that with respect to its buoyancy (mode 1), the pair has a 2 x 2 Gram matrix (cc, cb, bb) under either
+ * inner product of the two sections above.  Three rows of N float64, ldH >= N apart, in density units (d b / d rho = -1 / rho^2):
+ *     H[0][i] += alpha cc_i,     H[ldH + i] += -alpha cb_i / rho_i^2,     H[2 ldH + i] += alpha bb_i / rho_i^4
+ *
+ * helm_gauss_newton_blocks_device:    xy_i = Re tr(E^x_i^H Gamma_i E^y_i Phi_i), Phi from dCu and Gamma from dCg as helm_gauss_newton_diagonal_device takes them.
+ * helm_pseudo_hessian_blocks_device:  xy_i = sum_{s<nsrc} Re <E^x_i u^_s, E^y_i u^_s> over the rows of the 3 x 3 block, U as helm_pseudo_hessian_accumulate_device
+ *     takes it (_c64: the complex64 store with its column exponents).
+ * Rows 0 and 2 are what the diagonal entry points give for modes 0 / 3 and 1 (with W = 1 / rho^4); the middle row has either sign and xy^2 <= xx yy.
+ *
+ * Plain fp64 in a fixed order, one writer per entry, no atomics, no scratch: the same bits on every run.  HELM_ERR_STATE before the first helm_assemble; Eurus, 3-D
+ * and ny > 0 handles HELM_ERR_UNSUPPORTED; null, misaligned (U, C: 16, U32: 8, dExp: 4, H: 8) or overlapping pointers (H counts 2 ldH + N entries), nsrc < 1,
+ * ld < N, ldH < N, a negative or NaN alpha, a stretch outside 0..1 and grids below 3 x 3 HELM_ERR_ARG.  All device pointers; each call returns when its result
+ * is complete. */
+int helm_gauss_newton_blocks_device(helm_op *op, int stretch, const void *dCu, const void *dCg, double alpha, void *dH, long long ldH);
+int helm_pseudo_hessian_blocks_device(helm_op *op, const void *dU, int nsrc, long long ld, int stretch, double alpha, void *dH, long long ldH);
+int helm_pseudo_hessian_blocks_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, int stretch, double alpha, void *dH, long long ldH);
+
 /* --- device-resident callers: sparse sources in, receiver samples out ---------------------------------- */
 /* Dense right-hand sides from the COO triplets of the reference's sparse source matrix (survey.py:162-169,
  * source.py:213-317): R (nrhs x rows, zeroed by the call), R[col[k]][row[k]] = val[k]; no duplicate entries.

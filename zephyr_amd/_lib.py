@@ -155,6 +155,12 @@ _SIGNATURES = {
     'helm_lag_gram_accumulate_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p]),
     'helm_gauss_newton_diagonal_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                          ctypes.c_double, ctypes.c_void_p]),
+    'helm_gauss_newton_blocks_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+                                                       ctypes.c_longlong]),
+    'helm_pseudo_hessian_blocks_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_double,
+                                                         ctypes.c_void_p, ctypes.c_longlong]),
+    'helm_pseudo_hessian_blocks_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int,
+                                                             ctypes.c_double, ctypes.c_void_p, ctypes.c_longlong]),
     'helm_num_blocks': (ctypes.c_int, [ctypes.c_void_p]),
     'helm_num_points': (ctypes.c_longlong, [ctypes.c_void_p]),
     'helm_get_diagonals': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p]),

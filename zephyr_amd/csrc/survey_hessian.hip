@@ -1,6 +1,7 @@
 // The two Hessian diagonals of the exact MiniZephyr derivatives (survey_frechet.hip) from stored columns, each kernel beside the C entry point that launches it:
 // the pseudo-Hessian diagonal, and the exact diagonal of the Gauss-Newton Hessian (the autocorrelation planes of a set of columns and the per-cell trace), which
-// is built from the coefficients of the first.  survey_internal.hpp holds what they share with the derivative kernels.
+// is built from the coefficients of the first.  survey_internal.hpp holds what they share with the derivative kernels.  The last section holds the per-cell 2 x 2
+// blocks of the joint (c, rho) Hessian under either of the two: the same walks and coefficient sets with three sums per cell, so they live beside what they extend.
 #include "survey_internal.hpp"
 
 // ------------------------------------------------------------------------------------------
@@ -561,4 +562,231 @@ extern "C" int helm_gauss_newton_diagonal_device(helm_op *op, int mode, const vo
     else GN_GO(GN_DIAGONAL);
 #undef GN_GO
     return launched(op);
+}
+
+// ------------------------------------------------------------------------------------------
+// the per-cell 2 x 2 blocks of the joint (c, rho) Hessian: rows H_cc, H_crho, H_rhorho of H, ldH apart
+// ------------------------------------------------------------------------------------------
+// The pair (E^c_i, E^b_i) of a cell -- the velocity star at the density of the handle (STRETCH) or its mass term alone, and the buoyancy star -- has a 2 x 2 Gram
+// matrix under either inner product of the sections above: (cc, cb, bb).  In density units, d b / d rho = -1 / rho^2:
+//     H[0][i] += alpha cc,     H[1][i] += -alpha cb / rho_i^2,     H[2][i] += alpha bb / rho_i^4.
+// Rows 0 and 2 are what the diagonal kernels give for the two parameters; the cross term is what is new, and it has either sign.
+
+// what the three sums of a cell end in: one writer per cell
+__device__ __forceinline__ void blocks_store(double *__restrict__ H, long long ldH, long long i, double alpha, double rho, double cc, double cb, double bb) {
+    const double r2 = rho * rho;
+    H[i] = H[i] + alpha * cc;
+    H[ldH + i] = H[ldH + i] + (-alpha / r2) * cb;
+    H[2 * ldH + i] = H[2 * ldH + i] + (alpha / (r2 * r2)) * bb;
+}
+
+// k_gauss_newton_blocks: the walk of k_gauss_newton_diagonal with both coefficient sets of the lane in registers -- 17 (STRETCH: the nine of its own row and the
+// eight mass rows) or 9 (the mass term alone) live velocity coefficients beside the 33 of the buoyancy.  Per column n' of Phi the nine entries are loaded once and
+// both t^c = E^c Phi[:, n'] and t^b = E^b Phi[:, n'] formed; per row j' the nine entries of Gamma are loaded once for s^c = Gamma^T t^c and s^b = Gamma^T t^b, and
+// Re conj(e^c) s^c, Re conj(e^c) s^b, Re conj(e^b) s^b go to the three sums.  Both loops stay real loops, as there.  One writer per cell, every sum in the order of
+// the code, no atomics, no LDS, no scratch.
+template <bool STRETCH>
+__global__ __launch_bounds__(64) void k_gauss_newton_blocks(MzParams P, const cplx *__restrict__ c, const double *__restrict__ rho, const cplx *__restrict__ Cu,
+                                                            const cplx *__restrict__ Cg, double alpha, double *__restrict__ H, long long ldH) {
+    constexpr int CM = STRETCH ? GN_VELOCITY : GN_MASS;
+    const int nz = P.nz, nx = P.nx;
+    const long long N = (long long)nz * nx, i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const int iz = (int)(i / nx), ix = (int)(i % nx);
+    cplx ec[GN_NCOEF], eb[GN_NCOEF];
+    gn_coefficients<CM>(P, c, rho, nullptr, iz, ix, ec);
+    gn_coefficients<GN_BUOYANCY>(P, c, rho, nullptr, iz, ix, eb);
+    double cc = 0.0, cb = 0.0, bb = 0.0;
+#pragma unroll 1
+    for (int n2 = 0; n2 < 9; ++n2) {
+        cplx phi[9], tc[9], tb[9];
+#pragma unroll
+        for (int n = 0; n < 9; ++n) {
+            phi[n] = gn_gram(Cu, N, nz, nx, iz, ix, n, n2);
+            tc[n] = tb[n] = cmake(0.0, 0.0);
+        }
+        gn_for<GN_NCOEF>([&](auto qc) {
+            constexpr int q = decltype(qc)::value;
+            if constexpr (gn_live(CM, q)) cfma(tc[gn_row(q)], ec[q], phi[gn_col(q)]);
+            cfma(tb[gn_row(q)], eb[q], phi[gn_col(q)]);
+        });
+#pragma unroll 1
+        for (int j2 = 0; j2 < 9; ++j2) {
+            cplx xc = cmake(0.0, 0.0), xb = cmake(0.0, 0.0);
+            bool anyc = false, anyb = false;
+            gn_for<GN_NCOEF>([&](auto qc) {
+                constexpr int q = decltype(qc)::value;
+                if (gn_row(q) == j2 && gn_col(q) == n2) {           // (uniform over the wave; at most one q)
+                    xb = eb[q]; anyb = true;
+                    if (gn_live(CM, q)) { xc = ec[q]; anyc = true; }
+                }
+            });
+            if (!anyb) continue;                                    // (every live velocity entry is a buoyancy entry too)
+            cplx sc = cmake(0.0, 0.0), sb = cmake(0.0, 0.0);
+#pragma unroll
+            for (int j = 0; j < 9; ++j) {
+                const cplx g = gn_gram(Cg, N, nz, nx, iz, ix, j, j2);
+                cfma(sc, g, tc[j]);
+                cfma(sb, g, tb[j]);
+            }
+            if (anyc) {
+                cc = fma(xc.x, sc.x, cc); cc = fma(xc.y, sc.y, cc);      // Re conj(e^c) s^c
+                cb = fma(xc.x, sb.x, cb); cb = fma(xc.y, sb.y, cb);      // Re conj(e^c) s^b
+            }
+            bb = fma(xb.x, sb.x, bb); bb = fma(xb.y, sb.y, bb);          // Re conj(e^b) s^b
+        }
+    }
+    blocks_store(H, ldH, i, alpha, rho[i], cc, cb, bb);
+}
+
+// H[a][i] += alpha d_a(i) Re tr(E^a_i^H Gamma_i E^b_i Phi_i) for the three entries (c, c), (c, rho), (rho, rho) of the block of cell i < N, row a at dH + a ldH: Phi from
+// dCu and Gamma from dCg as helm_gauss_newton_diagonal_device takes them; E^c the velocity star at the handle's density (stretch != 0) or its mass term alone,
+// E^rho = -E^b / rho_i^2.  dH: float64, ldH >= N; alpha >= 0.  Returns when H is complete.
+extern "C" int helm_gauss_newton_blocks_device(helm_op *op, int stretch, const void *dCu, const void *dCg, double alpha, void *dH, long long ldH) {
+    helm_tuning_refresh();
+    if (!op || !dCu || !dCg || !dH || !(alpha >= 0.0) || stretch < 0 || stretch > 1 || ldH < op->N) return HELM_ERR_ARG;
+    if (int rc = mz_handle_args(op, "helm_gauss_newton_blocks_device")) return rc;
+    if (op->nz < 3 || op->nx < 3 || (((uintptr_t)dH) & 7) || ((((uintptr_t)dCu) | ((uintptr_t)dCg)) & 15)) return HELM_ERR_ARG;
+    const size_t hbytes = ((size_t)2 * ldH + op->N) * 8, cbytes = (size_t)op->N * LG_NLAG * sizeof(cplx);
+    if (ranges_overlap(dCu, cbytes, dH, hbytes) || ranges_overlap(dCg, cbytes, dH, hbytes)) return HELM_ERR_ARG;
+    MzParams P;
+    if (helm_mz_params(op, &P)) HELM_FAIL(op, HELM_ERR_STATE, "helm_gauss_newton_blocks_device: the handle holds no assembled operator");
+    HIP_TRY(op, hipSetDevice(op->device));
+    const dim3 grid((unsigned)((op->N + 63) / 64)), block(64);
+    const cplx *c = (const cplx *)op->d_c, *Cu = (const cplx *)dCu, *Cg = (const cplx *)dCg;
+    const double *rho = (const double *)op->d_rho;
+    if (stretch) HELM_LAUNCH(k_gauss_newton_blocks<true>, grid, block, 0, op->stream, P, c, rho, Cu, Cg, alpha, (double *)dH, ldH);
+    else HELM_LAUNCH(k_gauss_newton_blocks<false>, grid, block, 0, op->stream, P, c, rho, Cu, Cg, alpha, (double *)dH, ldH);
+    return launched(op);
+}
+
+// k_pseudo_hessian_blocks: the walk of k_pseudo_hessian with three sums per lane.  Per column the lane forms the velocity row sum r^c_0 of its own row and the
+// buoyancy row sums r^b_0 and r^b_j of the buoyancy mode.  The eight neighbouring velocity rows are conj(m_o w) v[4] (w = d kappa_i / dc b_i): their part of cc is
+// the real weight S |v[4]|^2 of the velocity mode, their part of the cross term one weighted sum, Re[conj(conj(w) v[4]) sum_j m_o r^b_j] -- a row j outside the
+// interior has no buoyancy coefficient, so r^b_j = 0 there and the weights are those of the lag alone.  !STRETCH: row i holds the centre mass weight alone.
+template <class F, bool STRETCH>
+__global__ __launch_bounds__(64 * PH_WAVES) void k_pseudo_hessian_blocks(F U, int nsrc, long long ld, MzParams P, const cplx *__restrict__ c,
+                                                                         const double *__restrict__ rho, double alpha, double *__restrict__ H, long long ldH) {
+    __shared__ double part[3][64];
+    const int nz = P.nz, nx = P.nx;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ntx = (nx + OP_TILE_X - 1) / OP_TILE_X;
+    const int x = (int)(blockIdx.x % ntx) * OP_TILE_X + lane - 1, z = (int)(blockIdx.x / ntx);
+    const bool xin = x >= 0 && x < nx;
+    const bool store = lane >= 1 && lane <= OP_TILE_X && x < nx;
+    const long long i = (long long)z * nx + x;
+    PhCoef Eb, Ec;
+    cplx wc = cmake(0.0, 0.0);                                  // conj(w): the velocity coefficient of a neighbouring row without its mass weight
+    if (store) {
+        ph_coefficients<PH_BUOYANCY>(P, c, rho, nullptr, z, x, Eb);
+        ph_coefficients<PH_VELOCITY>(P, c, rho, nullptr, z, x, Ec);
+        wc = cconj(cscale(mz_kappa_dc(P, c[i]), 1.0 / rho[i]));
+        if (!STRETCH) {
+#pragma unroll
+            for (int k = 0; k < 9; ++k) Ec.c[k] = cmake(0.0, 0.0);
+            if (z >= 1 && z <= nz - 2 && x >= 1 && x <= nx - 2) Ec.c[4] = cscale(wc, MZ_WC);
+        }
+    } else {
+        ph_each<PH_BUOYANCY>(Eb, [&](int, cplx &v) { v = cmake(0.0, 0.0); });       // (a halo lane adds nothing)
+        ph_each<PH_VELOCITY>(Ec, [&](int, cplx &v) { v = cmake(0.0, 0.0); });
+    }
+    double acc_cc = 0.0, acc_cb = 0.0, acc_bb = 0.0;
+    const int ngroups = (nsrc + PH_UNROLL - 1) / PH_UNROLL;
+    for (int g = wave; g < ngroups; g += PH_WAVES) {          // (wave-uniform: the lane exchanges stay complete)
+        const int s0 = g * PH_UNROLL, ncol = min(PH_UNROLL, nsrc - s0);
+        typename F::raw raw[PH_UNROLL][3];
+        double sc[PH_UNROLL];
+#pragma unroll
+        for (int j = 0; j < PH_UNROLL; ++j) {
+            sc[j] = U.scale(s0 + min(j, ncol - 1));
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                const int zz = z - 1 + r;
+                raw[j][r] = (xin && j < ncol && zz >= 0 && zz < nz) ? U.load((long long)(s0 + j) * ld + (long long)zz * nx + x) : typename F::raw{};
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < PH_UNROLL; ++j) {
+            cplx v[9];
+#pragma unroll
+            for (int r = 0; r < 3; ++r) {
+                v[3 * r + 1] = U.scaled(raw[j][r], sc[j]);
+                lane_left_right(v[3 * r + 1], v[3 * r], v[3 * r + 2]);
+            }
+            cplx rc = cmake(0.0, 0.0), rb = cmake(0.0, 0.0);
+            if (STRETCH) {
+#pragma unroll
+                for (int k = 0; k < 9; ++k) cfma(rc, Ec.c[k], v[k]);
+            } else {
+                rc = cmul(Ec.c[4], v[4]);
+            }
+#pragma unroll
+            for (int k = 0; k < 9; ++k) cfma(rb, Eb.c[k], v[k]);
+            double scc = cabs2(rc) + Ec.S * cabs2(v[4]);
+            double sbb = cabs2(rb);
+            double scb = rc.x * rb.x + rc.y * rb.y;
+            cplx medge = cmake(0.0, 0.0), mcorner = cmake(0.0, 0.0);
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const int sz = a < 2 ? 2 * a - 1 : 0, sx = a < 2 ? 0 : 2 * (a - 2) - 1;
+                cplx r1 = cmul(Eb.e[a][0], v[4]);
+                cfma(r1, Eb.e[a][1], v[mz_slot(-sz, -sx)]);
+                sbb += cabs2(r1);
+                medge = cadd(medge, r1);
+            }
+#pragma unroll
+            for (int a = 0; a < 4; ++a) {
+                const int sz = 2 * (a / 2) - 1, sx = 2 * (a % 2) - 1;
+                cplx r2 = cmul(Eb.k[a][0], v[4]);
+                cfma(r2, Eb.k[a][1], v[mz_slot(-sz, 0)]);
+                cfma(r2, Eb.k[a][2], v[mz_slot(0, -sx)]);
+                cfma(r2, Eb.k[a][3], v[mz_slot(-sz, -sx)]);
+                sbb += cabs2(r2);
+                mcorner = cadd(mcorner, r2);
+            }
+            const cplx msum = cadd(cscale(medge, MZ_WD), cscale(mcorner, MZ_WE));
+            const cplx rn = cmul(wc, v[4]);
+            scb += rn.x * msum.x + rn.y * msum.y;
+            if (j < ncol) { acc_cc += scc; acc_cb += scb; acc_bb += sbb; }
+        }
+    }
+    for (int w = 0; w < PH_WAVES; ++w) {
+        if (wave == w) {
+            part[0][lane] = w == 0 ? acc_cc : part[0][lane] + acc_cc;
+            part[1][lane] = w == 0 ? acc_cb : part[1][lane] + acc_cb;
+            part[2][lane] = w == 0 ? acc_bb : part[2][lane] + acc_bb;
+        }
+        __syncthreads();
+    }
+    if (wave == 0 && store) blocks_store(H, ldH, i, alpha, rho[i], part[0][lane], part[1][lane], part[2][lane]);
+}
+
+static int pseudo_hessian_blocks_launch(helm_op *op, HostField U, int nsrc, long long ld, int stretch, double alpha, void *dH, long long ldH) {
+    helm_tuning_refresh();
+    const char *what = U.c64 ? "helm_pseudo_hessian_blocks_c64_device" : "helm_pseudo_hessian_blocks_device";
+    if (!op || !U.ok() || !dH || nsrc < 1 || ld < op->N || ldH < op->N || !(alpha >= 0.0) || stretch < 0 || stretch > 1) return HELM_ERR_ARG;
+    if (int rc = mz_handle_args(op, what)) return rc;
+    if (op->nz < 3 || op->nx < 3 || (((uintptr_t)dH) & 7)) return HELM_ERR_ARG;
+    if (ranges_overlap(U.u, U.bytes(nsrc, ld), dH, ((size_t)2 * ldH + op->N) * 8)) return HELM_ERR_ARG;
+    MzParams P;
+    if (helm_mz_params(op, &P)) HELM_FAIL(op, HELM_ERR_STATE, "%s: the handle holds no assembled operator", what);
+    HIP_TRY(op, hipSetDevice(op->device));
+    const dim3 grid((unsigned)(((op->nx + OP_TILE_X - 1) / OP_TILE_X) * op->nz)), block(64 * PH_WAVES);
+    const cplx *c = (const cplx *)op->d_c;
+    const double *rho = (const double *)op->d_rho;
+    return U.with([&](auto F) {
+        if (stretch) HELM_LAUNCH((k_pseudo_hessian_blocks<decltype(F), true>), grid, block, 0, op->stream, F, nsrc, ld, P, c, rho, alpha, (double *)dH, ldH);
+        else HELM_LAUNCH((k_pseudo_hessian_blocks<decltype(F), false>), grid, block, 0, op->stream, F, nsrc, ld, P, c, rho, alpha, (double *)dH, ldH);
+        return launched(op);
+    });
+}
+
+// H[a][i] += alpha d_a(i) sum_{s<nsrc} Re <E^a_i u^_s, E^b_i u^_s> for the three entries (c, c), (c, rho), (rho, rho) of the block of cell i < N, row a at dH + a ldH:
+// U the stored (conjugated) fields as helm_pseudo_hessian_accumulate_device takes them, E^c and E^rho as helm_gauss_newton_blocks_device.  Returns when H is complete.
+extern "C" int helm_pseudo_hessian_blocks_device(helm_op *op, const void *dU, int nsrc, long long ld, int stretch, double alpha, void *dH, long long ldH) {
+    return pseudo_hessian_blocks_launch(op, HostField::c128(dU), nsrc, ld, stretch, alpha, dH, ldH);
+}
+extern "C" int helm_pseudo_hessian_blocks_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, int stretch, double alpha, void *dH,
+                                                     long long ldH) {
+    return pseudo_hessian_blocks_launch(op, HostField::packed(dU32, dExp), nsrc, ld, stretch, alpha, dH, ldH);
 }

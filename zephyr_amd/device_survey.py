@@ -1172,3 +1172,90 @@ def illuminationFromFields(prob, F, kind, perFreq, linearisation='scaler', param
         _lib.wait_torch_stream(ws.device)
         _accumulate(op, d_uF, k, spec, row, d_exp, Ni)
     return _sumEnergyPartials(prob, [ws.H for ws in runOnDevices(devs, items, one, factor=False) if ws.H is not None], shape)
+
+
+# ---- per-cell 2 x 2 blocks of the joint (c, rho) Hessian -----------------------------------------------------------------------------------------
+# The item steps of `illumination` / `illuminationFromFields` with a partial of three rows per frequency (H_cc, H_crho, H_rhorho) and the accumulate calls of
+# the block kernels: k_pseudo_hessian_blocks where the pseudo-Hessian kernel stood, k_gauss_newton_blocks on the same 26 planes where the diagonal's trace stood.
+# The density weights are the kernels' own (the handle's rho), so there is no weight array: alpha is |scaleTerm|^2 (over |premul|^2 for 'gaussNewton', whose
+# receiver planes carry premul).
+
+def _blocksRow(ws, shape, ifreq):
+    "device pointer of the three rows of the worker's partial blocks that frequency ifreq adds to (the partial zeroed on first use)"
+    import torch
+    H = _partial(ws, 'H', shape, torch.float64)
+    return H.data_ptr() + (ifreq * 3 * shape[-1] * 8 if len(shape) == 3 else 0)
+
+
+def hessianBlocks(prob, owned, kind, side, perFreq, linearisation='full'):
+    """prob.hessianBlocks(u=None) with the wavefields kept in HBM (single-grid surveys): `illumination` with the block kernels.  'gaussNewton' solves the forward
+    fields into a store, which `hessianBlocksFromFields` reads and this call drops."""
+    sv = prob.survey
+    N = prob.nrow
+    shape = (sv.nfreq, 3, N) if perFreq else (3, N)
+    if kind == 'gaussNewton':
+        F = fields(prob, owned, prob.fieldsDtype)
+        try:
+            return hessianBlocksFromFields(prob, F, kind, perFreq, linearisation)
+        finally:
+            F.release()
+    if not owned:
+        return _sumEnergyPartials(prob, [], shape)
+    scale = complex(prob.system.scaleTerm)
+    a2 = scale.real * scale.real + scale.imag * scale.imag
+    if side == 'source':
+        q, ncols = sv.getSources(), sv.nsrc
+    else:
+        q, ncols = sp.csc_matrix(sv.rVec(0, owned[0]).T), sv.nrec            # (one grid: the one matrix of a fixed array; srTerms included, no tsTerms)
+    stretch = linearisation == 'full'
+    devs, items = deviceItems(prob.system, owned, ncols)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        row = _blocksRow(ws, shape, ifreq)
+        U, R = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
+        _expandColumns(op, q, ifreq, c0, c1, R)
+        _lib.wait_torch_stream(ws.device)                # (covers the zeroed partial: keep it between the torch work and the library calls)
+        op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+        op.pseudoHessianBlocksDevice(U.data_ptr(), k, stretch, a2, row, ldh=Ni, rows=Ni)
+    return _sumEnergyPartials(prob, [ws.H for ws in runOnDevices(devs, items, one) if ws.H is not None], shape)
+
+
+def hessianBlocksFromFields(prob, F, kind, perFreq, linearisation='full'):
+    """prob.hessianBlocks(u=F) from forward fields already in HBM: no forward solve, every item of the store reads its slice where it lies, in either store
+    format, and adds its three rows to its worker's partial."""
+    F.checkCurrent(prob)
+    sv = prob.survey
+    N = prob.nrow
+    shape = (sv.nfreq, 3, N) if perFreq else (3, N)
+    if not F.items:
+        return _sumEnergyPartials(prob, [], shape)
+    scale = F.scale
+    a2 = scale.real * scale.real + scale.imag * scale.imag
+    stretch = linearisation == 'full'
+    if kind == 'gaussNewton':
+        gram = _receiverGram(prob, F.ownedFreqs)
+        devs, items = _storedItems(prob.adjointSystem, F)
+        _checkSecondFactorsFit(items, planes=26, cols=sv.nrec)
+
+        def one(ws, op, ifreq, c0, c1):
+            k, Ni = c1 - c0, int(op.nrow)
+            d_uF, d_exp = F.pointers(ifreq, c0)
+            row = _blocksRow(ws, shape, ifreq)
+            pm = complex(op.premul)
+            Cu = ws.buffer('gram', 13 * Ni)
+            Cu.zero_()
+            Cg = gram(ws, op, ifreq)
+            _lib.wait_torch_stream(ws.device)
+            op.lagGramAccumulateDevice(d_uF, k, Cu.data_ptr(), d_exp=d_exp, rows=Ni)
+            op.gaussNewtonBlocksDevice(stretch, Cu.data_ptr(), Cg.data_ptr(), a2 / (pm.real * pm.real + pm.imag * pm.imag), row, ldh=Ni)
+        return _sumEnergyPartials(prob, [ws.H for ws in runOnDevices(devs, items, one) if ws.H is not None], shape)
+    devs, items = _storedItems(prob.system, F)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        d_uF, d_exp = F.pointers(ifreq, c0)
+        row = _blocksRow(ws, shape, ifreq)
+        _lib.wait_torch_stream(ws.device)
+        op.pseudoHessianBlocksDevice(d_uF, k, stretch, a2, row, ldh=Ni, d_exp=d_exp, rows=Ni)
+    return _sumEnergyPartials(prob, [ws.H for ws in runOnDevices(devs, items, one, factor=False) if ws.H is not None], shape)

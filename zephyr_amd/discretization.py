@@ -487,6 +487,27 @@ class BaseDiscretization(BaseModelDependent):
         _lib.check(_lib.load().helm_gauss_newton_diagonal_device(self.handle, self.GAUSS_NEWTON_MODES[mode], ch, w, ctypes.c_void_p(d_cu), ctypes.c_void_p(d_cg),
                                                                  float(alpha), ctypes.c_void_p(d_h)), self.handle)
 
+    def gaussNewtonBlocksDevice(self, stretch, d_cu, d_cg, alpha, d_h, ldh=None):
+        """The three rows H_cc, H_crho, H_rhorho of the per-cell (c, rho) blocks, H[a] += alpha d_a Re tr(E^a^H Gamma E^b Phi), on the device
+        (frechet.gaussNewtonBlocks): d_cu, d_cg as for gaussNewtonDiagonalDevice, stretch False: the mass term alone for E^c; d_h three rows of nrow float64, ldh
+        (default nrow) apart; alpha >= 0."""
+        ldh = int(self.nrow if ldh is None else ldh)
+        _lib.check(_lib.load().helm_gauss_newton_blocks_device(self.handle, 1 if stretch else 0, ctypes.c_void_p(d_cu), ctypes.c_void_p(d_cg), float(alpha),
+                                                               ctypes.c_void_p(d_h), ldh), self.handle)
+
+    def pseudoHessianBlocksDevice(self, d_u, nsrc, stretch, alpha, d_h, ldh=None, d_exp=None, rows=None):
+        """The same three rows for the pseudo-Hessian, H[a] += alpha d_a sum_s Re <E^a u^_s, E^b u^_s> (frechet.pseudoHessianBlocks), from the stored columns d_u as
+        pseudoHessianAccumulateDevice takes them (d_exp given: the complex64 store)."""
+        lib = _lib.load()
+        rows = int(self.nrow if rows is None else rows)
+        ldh = int(self.nrow if ldh is None else ldh)
+        if d_exp is not None:
+            _lib.check(lib.helm_pseudo_hessian_blocks_c64_device(self.handle, ctypes.c_void_p(d_u), ctypes.c_void_p(d_exp), int(nsrc), rows, 1 if stretch else 0,
+                                                                 float(alpha), ctypes.c_void_p(d_h), ldh), self.handle)
+            return
+        _lib.check(lib.helm_pseudo_hessian_blocks_device(self.handle, ctypes.c_void_p(d_u), int(nsrc), rows, 1 if stretch else 0, float(alpha), ctypes.c_void_p(d_h),
+                                                         ldh), self.handle)
+
     def packDevice(self, d_u, nsrc, d_out, d_exp, rows=None):
         """The complex64 store of the wavefields d_u ([nsrc][rows] complex128): d_out [nsrc][rows] complex64 values x * 2^-e_s, d_exp the nsrc int32 column
         exponents e_s (fieldstore.pack_reference states the format).  All device pointers; returns when both are complete."""

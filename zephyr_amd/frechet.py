@@ -674,3 +674,113 @@ def gaussNewtonDiagonal(op, uh, gh, parameter='c', chain=None, linearisation='fu
         rho = np.broadcast_to(np.asarray(op.rho, dtype=np.float64), (nz, nx)).astype(R).ravel()
         H = H / (rho * rho * rho * rho)
     return H
+
+
+# ---- the per-cell 2 x 2 blocks of the joint (c, rho) Hessian ------------------------------------------------------------------------------------------
+# With E^c_i = d A / d c_i (velocityPlanes at the operator's density for 'full', massPlanes for 'operator') and E^b_i = d A / d b_i (buoyancyPlanes), the block of
+# cell i is the 2 x 2 Gram matrix of the pair: rows cc, cb, bb, in density units cc, -cb / rho_i^2, bb / rho_i^4 (d b / d rho = -1 / rho^2).  Both kinds use
+# what the diagonals above use; only the cross term is new.  k_gauss_newton_blocks and k_pseudo_hessian_blocks (csrc/survey_hessian.hip) are the device kernels.
+
+def gaussNewtonCrossTrace(Ea, Gamma, Eb, Phi, magnitude=False):
+    """Re sum conj(Ea[j', n']) Gamma[j, j'] Eb[j, n] Phi[n, n'] per cell from (N, 9, 9) blocks, as T = Eb Phi, S = Gamma^T T, sum conj(Ea) S: the two-sided form
+    of `gaussNewtonTrace`, symmetric in (Ea, Eb) for Hermitian Gamma and Phi; magnitude: every term by its modulus"""
+    if magnitude:
+        Ea, Eb, Gamma, Phi = np.abs(Ea), np.abs(Eb), np.abs(Gamma), np.abs(Phi)
+    T = np.einsum('ijn,inm->ijm', Eb, Phi)
+    S = np.einsum('ijk,ijm->ikm', Gamma, T)
+    return (np.conj(Ea) * S).sum(axis=(1, 2)).real
+
+
+def _checkBlocksLinearisation(linearisation):
+    if linearisation not in ('operator', 'full'):
+        raise ValueError('linearisation is %r: the (c, rho) blocks serve \'operator\' or \'full\' (the reference has no scaler for the density)' % (linearisation,))
+
+
+def _densityRows(op, cc, cb, bb, R, magnitude):
+    "(3, N): the (c, b) entries of a block in density units, rows cc, -cb / rho^2, bb / rho^4 (magnitude: +cb / rho^2)"
+    rho = np.broadcast_to(np.asarray(op.rho, dtype=np.float64), (int(op.nz), int(op.nx))).astype(R).ravel()
+    r2 = rho * rho
+    return np.stack([cc, (cb if magnitude else -cb) / r2, bb / (r2 * r2)])
+
+
+def gaussNewtonBlocks(op, uh, gh, linearisation='full', dtype=np.complex128, magnitude=False):
+    """B (3, N), real in the arithmetic of dtype: the 2 x 2 block of the Gauss-Newton Hessian of the pair (c_i, rho_i) per cell, rows H_cc, H_crho, H_rhorho,
+        B[a, b][i] = sum_s sum_r Re conj(g_r^T E^a_i u_s) (g_r^T E^b_i u_s) = Re tr(E^a_i^H Gamma_i E^b_i Phi_i)
+    from the planes uh = lagGram(u), gh = lagGram(g) of `gaussNewtonDiagonal`.  E^c_i from `velocityPlanes` at the density of the operator ('full') or
+    `massPlanes` ('operator'); E^rho_i = -E^b_i / rho_i^2 with E^b_i from `buoyancyPlanes`.  Rows 0 and 2 are gaussNewtonDiagonal(parameter='c' / 'rho').
+    magnitude: uh and gh those of moduli, every term by its modulus (the cross term too: +1 / rho^2)."""
+    _checkBlocksLinearisation(linearisation)
+    nz, nx = int(op.nz), int(op.nx)
+    R = _real(dtype)
+    Cu = (np.abs(np.asarray(uh)).astype(R) if magnitude else np.asarray(uh).astype(dtype)).reshape((len(GRAM_LAGS), nz * nx))
+    Cg = (np.abs(np.asarray(gh)).astype(R) if magnitude else np.asarray(gh).astype(dtype)).reshape((len(GRAM_LAGS), nz * nx))
+    if linearisation == 'operator':
+        Ec = blockCoefficients(nz, nx, lambda v: massPlanes(op, v, dtype, magnitude))
+    else:
+        Ec = blockCoefficients(nz, nx, lambda v: velocityPlanes(op, v, None, dtype, magnitude))
+    Eb = blockCoefficients(nz, nx, lambda v: buoyancyPlanes(op, v, dtype, magnitude))
+    Gamma, Phi = _gramBlocks(Cg, nz, nx), _gramBlocks(Cu, nz, nx)
+    cc = gaussNewtonCrossTrace(Ec, Gamma, Ec, Phi, magnitude)
+    cb = gaussNewtonCrossTrace(Ec, Gamma, Eb, Phi, magnitude)
+    bb = gaussNewtonCrossTrace(Eb, Gamma, Eb, Phi, magnitude)
+    return _densityRows(op, cc, cb, bb, R, magnitude)
+
+
+def pseudoHessianBlocks(op, u, linearisation='full', dtype=np.complex128, magnitude=False):
+    """B (3, N), real in the arithmetic of dtype: the 2 x 2 block of the pseudo-Hessian of the pair (c_i, rho_i) per cell, rows H_cc, H_crho, H_rhorho,
+        B[a, b][i] = sum_s Re <E^a_i u_s, E^b_i u_s>,
+    the inner product over the rows of the 3 x 3 block around i; u (N,) or (N, nsrc) the unscaled solves.  E^c, E^rho as for `gaussNewtonBlocks`: it is that
+    block with Gamma the identity.  Rows 0 and 2 are pseudoHessianDiagonal(parameter='c' / 'rho') ('operator': the closed form of
+    `operatorPseudoHessianWeight`).  Evaluated on the nine colour indicators.  magnitude: every term by its modulus (the cross term too: +1 / rho^2)."""
+    _checkBlocksLinearisation(linearisation)
+    nz, nx = int(op.nz), int(op.nx)
+    N = nz * nx
+    R = _real(dtype)
+    ua = np.asarray(u).reshape((N, -1))
+    ua = np.abs(ua.astype(dtype)).astype(R) if magnitude else ua.astype(dtype)
+    if linearisation == 'operator':
+        planesC = lambda v: massPlanes(op, v, dtype, magnitude)
+    else:
+        planesC = lambda v: velocityPlanes(op, v, None, dtype, magnitude)
+    iz, ix = np.divmod(np.arange(N), nx)
+    out = np.zeros((3, N), dtype=R)
+    for a in range(3):
+        for b in range(3):
+            mine = (iz % 3 == a) & (ix % 3 == b)
+            if not mine.any():
+                continue
+            ind = mine.astype(np.float64)
+            rc = applyPlanes(planesC(ind), ua, nz, nx)
+            rb = applyPlanes(buoyancyPlanes(op, ind, dtype, magnitude), ua, nz, nx)
+            if magnitude:
+                terms = (rc * rc, rc * rb, rb * rb)
+            else:
+                terms = (np.square(rc.real) + np.square(rc.imag), rc.real * rb.real + rc.imag * rb.imag, np.square(rb.real) + np.square(rb.imag))
+            for k, e in enumerate(terms):
+                out[k, mine] = _boxSum(e.sum(axis=1).reshape((nz, nx)), nz, nx).ravel()[mine]
+    return _densityRows(op, out[0], out[1], out[2], R, magnitude)
+
+
+def blockSolve(B, g, damping):
+    """z (2N,) float64: the stacked gradient g = [g_c; g_rho] (2N,) divided by the per-cell 2 x 2 blocks B (3, N) of `hessianBlocks`, cell by cell
+        [[B0 + l_c, B1], [B1, B2 + l_rho]] z_i = [g_c[i]; g_rho[i]],     l_c = damping max(B0), l_rho = damping max(B2).
+    damping must be > 0: blocks that are exactly zero exist (boundary cells), and with it every block is positive definite (a Gram matrix plus a positive
+    diagonal).  With B1 = 0 this is g / (H + damping H.max()) one parameter at a time."""
+    B = np.asarray(B, dtype=np.float64)
+    g = np.asarray(g, dtype=np.float64)
+    if B.ndim != 2 or B.shape[0] != 3:
+        raise ValueError('B has shape %r: (3, N), the rows H_cc, H_crho, H_rhorho of hessianBlocks' % (B.shape,))
+    N = B.shape[1]
+    if g.ndim != 1 or g.size != 2 * N:
+        raise ValueError('g has shape %r: the stacked vector [g_c; g_rho] of %d entries' % (g.shape, 2 * N))
+    if not (np.ndim(damping) == 0 and float(damping) > 0.0 and np.isfinite(float(damping))):
+        raise ValueError('damping is %r: a positive number (exactly zero blocks exist, so the undamped blocks are singular)' % (damping,))
+    if not (np.all(np.isfinite(B)) and np.all(np.isfinite(g))):
+        raise ValueError('B and g must be finite')
+    lc, lr = float(damping) * (B[0].max() if N else 0.0), float(damping) * (B[2].max() if N else 0.0)
+    if N and not (lc > 0.0 and lr > 0.0):
+        raise ValueError('max(B[0]) = %g, max(B[2]) = %g: both diagonals need a positive entry for the damping to act' % (B[0].max(), B[2].max()))
+    a, b, d = B[0] + lc, B[1], B[2] + lr
+    det = a * d - b * b
+    gc, gr = g[:N], g[N:]
+    return np.concatenate([(d * gc - b * gr) / det, (a * gr - b * gc) / det])

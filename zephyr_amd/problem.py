@@ -15,7 +15,8 @@ frequencies) or of the receiver data.  The device-resident loops of `dpred` and 
 per-worker buffers, partial gradients) live in `zephyr_amd.device_survey`; `_dpredDevice` / `_JtvecDevice` delegate to it.  `fieldsDevice` leaves the
 forward wavefields in HBM (`zephyr_amd.fieldstore.DeviceFields`) for `survey.dpred(m, u=F)` and `Jtvec(m, v, u=F)`.  `illumination` (no counterpart in the
 reference) returns the source- or receiver-side illumination, the diagonal pseudo-Hessian or the exact diagonal of the Gauss-Newton Hessian from those fields,
-what a gradient is preconditioned with.
+what a gradient is preconditioned with; `hessianBlocks` returns the per-cell 2 x 2 blocks of the joint (c, rho) Hessian for a two-parameter gradient
+(`frechet.blockSolve` divides by them).
 """
 import contextlib
 
@@ -37,6 +38,7 @@ from .frechet import operatorPseudoHessianWeight, pseudoHessianDiagonal         
 from .frechet import gaussNewtonDiagonal, lagGram                                   # (and the exact diagonal of the Gauss-Newton Hessian)
 from .frechet import applyPlanesTransposed, massPlanes, velocityCurvature           # (and the residual part of the Newton Hessian)
 from .frechet import mixedAdjointB, mixedAdjointC                                   # (and the mixed second derivative of parameter='joint')
+from .frechet import gaussNewtonBlocks, pseudoHessianBlocks                         # (and the per-cell 2 x 2 blocks of the joint Hessian)
 
 EPS = 1e-15
 
@@ -955,6 +957,87 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         gh = np.conj(gf / (st * np.conj(complex(sub.premul))))
         H = gaussNewtonDiagonal(sub, lagGram(uh, nz, nx), lagGram(gh, nz, nx), parameter, self._gardnerChain() if parameter == 'c' else None, linearisation)
         return (st.real * st.real + st.imag * st.imag) * H
+
+    # ---- per-cell 2 x 2 blocks of the joint (c, rho) Hessian -----------------------------------------------
+    def hessianBlocks(self, m=None, u=None, kind='gaussNewton', side='source', perFreq=False, linearisation='full'):
+        """What a two-parameter gradient [g_c; g_rho] is divided by: float64 (3, N), or (nfreq, 3, N) with perFreq -- the rows H_cc, H_crho, H_rhorho of the
+        2 x 2 diagonal block of the joint Hessian per cell, for frechet.blockSolve.  With E^c_i = d A_f / d c_i (frechet.velocityPlanes along e_i at the config's
+        density for 'full', frechet.massPlanes for 'operator'), E^rho_i = -E^b_i / rho_i^2 (E^b_i of frechet.buoyancyPlanes), u^_s = A_f^-1 premul q_s and
+        g_r = A_f^-T R_r^H:
+
+        kind 'gaussNewton':   B[a, b][i] = |scaleTerm|^2 sum_f sum_s sum_r Re conj(g_r^T E^a_i u^_s) (g_r^T E^b_i u^_s) = |scaleTerm|^2 sum_f Re tr(E^a_i^H Gamma_i E^b_i Phi_i),
+                              the block of the operator Hvec(parameter='joint') applies: B[1][i] = Hvec(m, [0; e_i], parameter='joint')[i], rows 0 and 2 are
+                              illumination(kind='gaussNewton', parameter='c' / 'rho').  Fixed receiver arrays, side 'source', as that diagonal.
+        kind 'pseudoHessian': B[a, b][i] = |scaleTerm|^2 sum_f sum_s Re <E^a_i u^_s, E^b_i u^_s> over the rows of the 3 x 3 block: the same with Gamma the identity;
+                              rows 0 and 2 are illumination(linearisation=, parameter='c' / 'rho').  side 'receiver' and moving arrays as `illumination`.
+
+        Every block is a Gram matrix: B[0], B[2] >= 0, B[1]^2 <= B[0] B[2]; B[1] has either sign.  Served and refused as Hvec(parameter='joint'): an explicit
+        `rho`, 'operator' or 'full' (`_resolveLinearisation`).  The routes of `illumination`: u a DeviceFields, u None (solved into HBM and dropped), or numpy on
+        the host; sharded ranks end in one all-reduce."""
+        self._requirePaired()
+        if kind not in ('pseudoHessian', 'gaussNewton'):
+            raise ValueError('kind is %r: \'pseudoHessian\' or \'gaussNewton\' (the energy has no density entry)' % (kind,))
+        if side not in ('source', 'receiver'):
+            raise ValueError('side is %r: \'source\' or \'receiver\'' % (side,))
+        self._checkLinearisation(linearisation)
+        self._checkParameter('joint', linearisation, joint=True)
+        sv = self.survey
+        if kind == 'gaussNewton' and side != 'source':
+            raise ValueError('kind=\'gaussNewton\' is the block of J^T J, sources and receivers together: side must be \'source\'')
+        if side == 'receiver':
+            if u is not None:
+                raise ValueError('the receiver-side blocks solve their own fields: u must be None')
+            if sv.mode != 'fixed':
+                raise ValueError('the receiver-side blocks serve fixed receiver arrays (mode is %r)' % (sv.mode,))
+        self.updateModel(m)
+        linearisation = self._resolveLinearisation(linearisation, 'joint', 'hessianBlocks')
+        if kind == 'gaussNewton' and sv.mode != 'fixed':
+            raise ValueError('kind=\'gaussNewton\' serves fixed receiver arrays (mode is %r): with an array that moves with the source the sum over '
+                             'receivers depends on the source and does not factorise' % (sv.mode,))
+        owned = self.ownedFreqs
+        if kind == 'gaussNewton' and (isinstance(u, DeviceFields) or (u is None and self._deviceGradientAvailable())):
+            self._hermitianResidual(np.zeros((sv.nrec, 1, 1)))          # (the device route solves R^T for R^H: refused where the receiver columns are complex)
+        if isinstance(u, DeviceFields):
+            u.checkCurrent(self)
+            return device_survey.hessianBlocksFromFields(self, u, kind, bool(perFreq), linearisation)
+        if u is None and self._deviceGradientAvailable():
+            return device_survey.hessianBlocks(self, owned, kind, side, bool(perFreq), linearisation)
+        nf = sv.nfreq
+        B = np.zeros((nf, 3, self.nrow) if perFreq else (3, self.nrow), dtype=np.float64)
+        if kind == 'gaussNewton':
+            green = self._receiverGreens(linearisation)
+        if u is None:
+            q = sv.getSources() if side == 'source' else [sp.csc_matrix(sv.rVec(0, i).T) for i in range(nf)]
+            pps = sv.postProcessors
+            fieldsOf = ((ifreq, pps[ifreq](uf)) for ifreq, uf in self._solveOwned(q))
+        else:
+            uF = list(u)
+            fieldsOf = ((ifreq, uF[ifreq]) for ifreq in owned)
+        for ifreq, uf in fieldsOf:
+            uf = np.asarray(uf)
+            uf = uf.reshape((uf.shape[0], -1))
+            E = self._gaussNewtonBlocksHost(ifreq, uf, green[ifreq], linearisation) if kind == 'gaussNewton' else self._pseudoHessianBlocksHost(ifreq, uf, linearisation)
+            if perFreq:
+                B[ifreq] = E
+            else:
+                B += E
+        if self._sharded:
+            B = parallel.allreduce_sum(B)
+        return B
+
+    def _pseudoHessianBlocksHost(self, ifreq, uf, linearisation):
+        "one frequency's term of hessianBlocks(kind='pseudoHessian') on the host: uf = scaleTerm conj(u^) (N, ncols)"
+        st = complex(self.system.scaleTerm)
+        return (st.real * st.real + st.imag * st.imag) * pseudoHessianBlocks(self.system.subProblems[ifreq], np.conj(uf / st), linearisation)
+
+    def _gaussNewtonBlocksHost(self, ifreq, uf, gf, linearisation):
+        "one frequency's term of hessianBlocks(kind='gaussNewton') on the host: uf and gf as `_gaussNewtonHost` takes them"
+        sub = self.system.subProblems[ifreq]
+        nz, nx = int(sub.nz), int(sub.nx)
+        st = complex(self.system.scaleTerm)
+        uh = np.conj(uf / st)
+        gh = np.conj(gf / (st * np.conj(complex(sub.premul))))
+        return (st.real * st.real + st.imag * st.imag) * gaussNewtonBlocks(sub, lagGram(uh, nz, nx), lagGram(gh, nz, nx), linearisation)
 
     # ---- device-resident gradient (mux branch) -------------------------------------------------------------
     def _deviceGradientAvailable(self):
