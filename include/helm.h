@@ -379,6 +379,25 @@ int helm_mass_adjoint_device(helm_op *op, const void *dP, double w_re, double w_
 int helm_velocity_adjoint_b_device(helm_op *op, const void *dP, const void *dB, double w_re, double w_im, int conj, int stretch, void *dG);
 int helm_mixed_adjoint_device(helm_op *op, const void *dP, const void *dp, double w_re, double w_im, int conj, int stretch, void *dG);
 
+/* --- the chain from (c, Q) to the complex velocity of a visco problem (HelmBaseProblem.JvecBorn / Jtvec / Hvec with parameter 'c', 'Q', 'cQ') -------------
+ * A visco wrapper gives the handle of frequency f the complex velocity c~ = c (1 + lam q) (1 + i q / 2), q = 1 / Q, lam = ln(f / freqBase) / pi (0 without
+ * dispersion).  With an explicit density every coefficient of MiniZephyr is holomorphic in c~, so the derivative along real (dc, dQ) is the derivative along the
+ * complex perturbation dc~ = gamma dc + chi dQ, gamma = (1 + lam q)(1 + i q / 2), chi = -c~ q^2 [lam / (1 + lam q) + (i / 2) / (1 + i q / 2)].  The chain is computed
+ * in the kernels from the handle's c~, the array dQ (N float64; inf allowed: gamma = 1, chi = 0) and the scalar lam.
+ *
+ * helm_visco_perturbation_device:   dDcz[i] = gamma_i vc[i] + chi_i vQ[i].  dVc, dVq: N float64, either may be NULL (not both); dDcz: N complex128.
+ * helm_velocity_planes_z_device:    dC = V[dc~], helm_velocity_planes_device (dDb NULL) with the complex perturbation dDcz (N complex128); dC: 9 N complex128.
+ *     (The mass term alone, linearisation='operator', is helm_virtual_sources_op_device with the complex weight W = -2 omega_d^2 dc~ / (c~^3 rho).)
+ * helm_visco_chain_adjoint_device:  dGc[j] += gamma_j T[j], dGq[j] += chi_j T[j] (conj != 0: the conjugated chain), T the complex cell gradient of one item (what
+ *     helm_velocity_adjoint_device / helm_mass_adjoint_device / helm_imaging_op_accumulate_device add into a zeroed buffer).  dGc or dGq may be NULL (not both).
+ *
+ * The same rules as above: plain fp64 in a fixed order, one lane and one writer per cell, no atomics; HELM_ERR_STATE before the first helm_assemble; Eurus, 3-D
+ * and ny > 0 handles HELM_ERR_UNSUPPORTED; null (other than named), misaligned (16 bytes; dQ, dVc, dVq: 8) or overlapping pointers, a NaN lam and (planes) grids
+ * below 3 x 3 HELM_ERR_ARG.  All device pointers; each call returns when its result is complete. */
+int helm_visco_perturbation_device(helm_op *op, const void *dQ, double lam, const void *dVc, const void *dVq, void *dDcz);
+int helm_velocity_planes_z_device(helm_op *op, const void *dDcz, void *dC);
+int helm_visco_chain_adjoint_device(helm_op *op, const void *dQ, double lam, const void *dT, int conj, void *dGc, void *dGq);
+
 /* --- the pseudo-Hessian diagonal of the exact derivatives (HelmBaseProblem.illumination with linearisation='full' / 'operator') ------------------
  * H[i] += alpha (dW ? W[i] : 1) sum_{s<nsrc} || (d A / d p_i) u^_s ||_2^2 for i < N, with U[s] = conj(u^_s) the stored columns (nsrc columns of ld >= N complex128,
  * or, _c64, complex64 values with the int32 column exponents dExp of helm_pack_c64_device) and d A / d p_i the derivative of the operator the handle holds:

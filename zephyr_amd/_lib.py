@@ -141,6 +141,10 @@ _SIGNATURES = {
                                                       ctypes.c_void_p]),
     'helm_mixed_adjoint_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_void_p]),
+    'helm_visco_perturbation_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'helm_velocity_planes_z_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'helm_visco_chain_adjoint_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p,
+                                                       ctypes.c_void_p]),
     'helm_pseudo_hessian_accumulate_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p,
                                                              ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
     'helm_pseudo_hessian_accumulate_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int,

@@ -1,6 +1,7 @@
 // What the translation units of a survey share: survey.hip (the plumbing: right-hand sides, axpby, the complex64 pack, imaging, energy, sampling),
 // survey_frechet.hip (the derivative kernels of the 2-D MiniZephyr operator), survey_hessian.hip (the two Hessian diagonals built on them) and survey_newton.hip
-// (the second derivative and the transposed planes of the Newton Hessian-vector product) and survey_joint.hip (the transposes of the mixed (c, b) derivative).  The readers
+// (the second derivative and the transposed planes of the Newton Hessian-vector product), survey_joint.hip (the transposes of the mixed (c, b) derivative) and
+// survey_visco.hip (the chain from (c, Q) to the complex velocity of a visco problem).  The readers
 // of a stored field on the device (FieldC128 / FieldC64) and its description on the host (HostField), how an entry point ends and refuses, the walk of the
 // stencil kernels over the grid, and the row factors of MiniZephyr at a cell.
 //

@@ -832,6 +832,104 @@ def jointGradientFromFields(prob, F, qb, resid, system, linearisation):
     return _sumPartials(prob, [ws.G for ws in wss if ws.G is not None], n=2 * N).real
 
 
+# ---- visco problems: the chain from (c, Q) to the complex velocity --------------------------------------------------------------------------------
+# The operators of a visco wrapper hold the complex velocity c~_f of their frequency; the derivative along real (dc, dQ) is the derivative along the complex
+# perturbation gamma_f dc + chi_f dQ (frechet.viscoChain).  The two pipelines below are the item bodies of `_bornPlanesFromFields` / `_bornOperatorFromFields` and of
+# `_gradientPlanesFromFields` / `gradientFromFields` with the chain kernels of csrc/survey_visco.hip inserted.  Q goes up once per worker and call; the chain itself
+# is made in the kernels from the handle's c~, Q and the scalar lam_f.  What a worker caches per frequency (1 / (c~^3 rho), keyed by the operator's own model array)
+# lives in its Workspace, which goes with the call.
+
+def _viscoQOnDevice(ws, Q):
+    return ws.cached(('visco_Q', id(Q)), lambda: _lib.to_device(Q, ws.device, np.float64), keep=Q)
+
+
+def viscoBornFromFields(prob, F, vc, vQ, linearisation, Q, lams):
+    """prob.JvecBorn(u=F, parameter='c' | 'Q' | 'cQ') of a visco problem: the derivative of dpred along the real perturbations vc and vQ (N,) float64, either may be
+    None.  Per stored item k_visco_perturbation makes dc~ = gamma_f vc + chi_f vQ; then 'full': k_velocity_planes_z and k_stencil_sources, the body of
+    `_bornPlanesFromFields`; 'operator': k_virtual_sources_op with the complex weight W = -2 omega_d^2 dc~ / (c~^3 rho), the body of `_bornOperatorFromFields`.
+    One Born solve per item.  Q (N,) float64, lams the dispersion scalar per frequency."""
+    from .frechet import dampedOmega
+    F.checkCurrent(prob)
+    data, stage, sample = _sampling(prob, F.ownedFreqs, F.scale)
+    if not F.items:
+        return data
+    stretch = linearisation == 'full'
+    devs, items = _storedItems(prob.system, F)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        dev = ws.device
+        d_uF, d_exp = F.pointers(ifreq, c0)
+        staged = stage(ws, ifreq, c0, c1)
+        Qd = _viscoQOnDevice(ws, Q)
+        vcd = None if vc is None else ws.cached(('born_dc', id(vc)), lambda: _lib.to_device(vc, dev, np.float64), keep=vc)
+        vQd = None if vQ is None else ws.cached(('born_dq', id(vQ)), lambda: _lib.to_device(vQ, dev, np.float64), keep=vQ)
+        U, R, dcz = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni), ws.buffer('dcz', Ni)
+        C = ws.buffer('planes', 9 * Ni) if stretch else None
+        inv = None if stretch else _cachedInverseC3Rho(ws, op)
+        _lib.wait_torch_stream(dev)
+        op.viscoPerturbationDevice(Qd.data_ptr(), lams[ifreq], None if vcd is None else vcd.data_ptr(), None if vQd is None else vQd.data_ptr(), dcz.data_ptr())
+        if stretch:
+            op.velocityPlanesComplexDevice(dcz.data_ptr(), C.data_ptr())
+            op.stencilSourcesDevice(d_uF, k, C.data_ptr(), -1.0 / complex(op.premul), R.data_ptr(), conj=True, d_exp=d_exp, rows=Ni)
+        else:
+            om = dampedOmega(op)
+            W = inv * dcz * complex(-2.0 * om * om)          # (dcz is complete: the library call has returned)
+            _lib.wait_torch_stream(dev)
+            op.virtualSourcesOpDevice(d_uF, k, W.data_ptr(), -1.0 / complex(op.premul), R.data_ptr(), conj=True, d_exp=d_exp, rows=Ni)
+        op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+        sample(op, ifreq, c0, c1, staged, U.data_ptr())
+    runOnDevices(devs, items, one)
+    return data
+
+
+def viscoGradientFromFields(prob, F, qb, resid, system, linearisation, parameter, Q, lams):
+    """prob.Jtvec(u=F, adjoint='transpose', parameter='c' | 'Q' | 'cQ') of a visco problem: float64 (N,), or [g_c; g_Q] (2 N,), from ONE back-propagation and one
+    imaging pass per stored item, whatever the parameter.  The item's complex cell gradient T -- conj(V_f)^T P of `_gradientPlanesFromFields` for 'full', the imaging
+    sum of k_imaging_op for 'operator' -- goes into a buffer zeroed per item (a worker's items belong to different frequencies), and k_visco_chain_adjoint adds
+    conj(gamma_f) T and conj(chi_f) T into the worker's partial: the pipeline holds the conjugates of the fields, so T is the conjugate of the host route's t_f.
+    One all-reduce of the (N,) or (2 N,) vector where the frequencies are sharded."""
+    import torch
+    F.checkCurrent(prob)
+    sv = prob.survey
+    N = prob.nrow
+    scale = F.scale
+    stretch = linearisation == 'full'
+    wantC, wantQ = parameter in ('c', 'cQ'), parameter in ('Q', 'cQ')
+    n = 2 * N if parameter == 'cQ' else N
+    if not F.items:
+        return _sumPartials(prob, [], n=n).real
+    _prepareBackSources(sv, qb, F.ownedFreqs)
+    devs, items = _storedItems(system, F)
+    _checkSecondFactorsFit(items, planes=10 if stretch else 1)
+    add = None if stretch else _addOperator(prob, scale)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        d_uF, d_exp = F.pointers(ifreq, c0)
+        G = _partial(ws, 'G', n, torch.complex128)
+        Qd = _viscoQOnDevice(ws, Q)
+        U, R, T = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni), ws.buffer('T', Ni)
+        _backSources(ws, sv, op, qb, resid, ifreq, c0, c1, R.data_ptr(), Ni)
+        T.zero_()
+        if stretch:
+            P = ws.buffer('lags', 9 * Ni)
+            P.zero_()
+        else:
+            W = add(ws, op, ifreq, Ni)[0]
+        _lib.wait_torch_stream(ws.device)
+        op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+        if stretch:
+            op.lagImagingAccumulateDevice(d_uF, U.data_ptr(), k, P.data_ptr(), d_exp=d_exp, rows=Ni)
+            op.velocityAdjointDevice(P.data_ptr(), -scale / np.conj(complex(op.premul)), T.data_ptr(), conj=True)
+        else:
+            op.imagingOpAccumulateDevice(d_uF, U.data_ptr(), k, W.data_ptr(), T.data_ptr(), d_exp=d_exp, rows=Ni)
+        op.viscoChainAdjointDevice(Qd.data_ptr(), lams[ifreq], T.data_ptr(), G.data_ptr() if wantC else None,
+                                   (G.data_ptr() + (16 * N if wantC else 0)) if wantQ else None, conj=True)
+    wss = runOnDevices(devs, items, one)
+    return _sumPartials(prob, [ws.G for ws in wss if ws.G is not None], n=n).real
+
+
 def newtonFromFields(prob, F, p, qb, resid, system, linearisation, parameter):
     """prob.Hvec(u=F, resid=): the full Newton Hessian of 1/2 ||dpred - dobs||^2 times p (N,) float64, float64 (N,), from forward fields already in HBM.  Three
     solves of the item's k columns per stored item, made of the steps of `_gradientPlanesFromFields` and `_bornPlanesFromFields`; `system` the transposed

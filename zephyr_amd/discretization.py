@@ -432,6 +432,22 @@ class BaseDiscretization(BaseModelDependent):
         _lib.check(_lib.load().helm_mixed_adjoint_device(self.handle, ctypes.c_void_p(d_p), ctypes.c_void_p(d_v), w.real, w.imag, 1 if conj else 0,
                                                          1 if stretch else 0, ctypes.c_void_p(d_g)), self.handle)
 
+    def viscoPerturbationDevice(self, d_q, lam, d_vc, d_vq, d_dcz):
+        """dc~ = gamma vc + chi vQ on the device, frechet.viscoChain at the complex velocity this operator holds: d_q nrow float64 (Q, inf allowed), lam the
+        dispersion scalar of its frequency, d_vc / d_vq nrow float64 (either may be None), d_dcz nrow complex128"""
+        vc, vq = (None if p is None else ctypes.c_void_p(p) for p in (d_vc, d_vq))
+        _lib.check(_lib.load().helm_visco_perturbation_device(self.handle, ctypes.c_void_p(d_q), float(lam), vc, vq, ctypes.c_void_p(d_dcz)), self.handle)
+
+    def velocityPlanesComplexDevice(self, d_dcz, d_c):
+        "dC = V[dc~] on the device, frechet.velocityPlanes with a complex perturbation: d_dcz nrow complex128 (viscoPerturbationDevice), d_c 9 nrow complex128"
+        _lib.check(_lib.load().helm_velocity_planes_z_device(self.handle, ctypes.c_void_p(d_dcz), ctypes.c_void_p(d_c)), self.handle)
+
+    def viscoChainAdjointDevice(self, d_q, lam, d_t, d_gc, d_gq, conj=False):
+        """Gc += gamma (.) T, GQ += chi (.) T (conj: the conjugated chain) on the device, the transpose of viscoPerturbationDevice: d_t nrow complex128, the complex
+        cell gradient of one item; d_gc / d_gq nrow complex128 (either may be None)"""
+        gc, gq = (None if p is None else ctypes.c_void_p(p) for p in (d_gc, d_gq))
+        _lib.check(_lib.load().helm_visco_chain_adjoint_device(self.handle, ctypes.c_void_p(d_q), float(lam), ctypes.c_void_p(d_t), 1 if conj else 0, gc, gq), self.handle)
+
     def stencilSourcesTransposedDevice(self, d_u, nsrc, d_c, coef, d_r, conj=False, d_exp=None, rows=None, accumulate=False):
         """R[s] = coef (dC)^T U[s] (conj: (dC)^H U[s]) on the device, frechet.applyPlanesTransposed: d_c the nine planes of velocityPlanesDevice or
         buoyancyPlanesDevice, read at the neighbouring cell -- the transposed set is never formed; the other arguments as for stencilSourcesDevice, but conj

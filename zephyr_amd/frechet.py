@@ -9,7 +9,8 @@ k_virtual_sources_op / k_imaging_op (csrc/survey_frechet.hip).  The second part 
 third the total derivative with respect to the velocity (linearisation='full'): the mass term above, the PML stretch and the density that follows c; then
 the second derivative of the operator and the transposed planes, what Hvec(resid=) adds to the Gauss-Newton product (k_velocity_curvature / k_stencil_sources_t,
 csrc/survey_newton.hip); and the mixed second derivative with respect to velocity and buoyancy, what parameter='joint' adds to that (k_velocity_adjoint_b /
-k_mixed_adjoint, csrc/survey_joint.hip)."""
+k_mixed_adjoint, csrc/survey_joint.hip); and the chain from the real velocity and the quality factor of a visco problem to the complex velocity its operators are
+assembled at (`viscoChain`; k_visco_perturbation / k_velocity_planes_z / k_visco_chain_adjoint, csrc/survey_visco.hip)."""
 import numpy as np
 
 
@@ -329,18 +330,51 @@ def gardnerChain(c):
     return -0.25 / (310. * cr ** 0.25) / cr
 
 
+def viscoChain(c, Q, lam=0.0, dtype=np.complex128, magnitude=False):
+    """(gamma, chi), each (N,): the derivatives of the complex velocity of a visco problem (distributors.ViscoMultiFreq.spUpdates),
+
+        c~ = c (1 + lam q) (1 + i q / 2),     q = 1 / Q,     lam = ln(f / freqBase) / pi  (0 without dispersion),
+
+    with respect to the real velocity c and to the quality factor Q per cell:
+
+        gamma = d c~ / d c = (1 + lam q) (1 + i q / 2),      chi = d c~ / d Q = -c~ q^2 [ lam / (1 + lam q) + (i / 2) / (1 + i q / 2) ]
+
+    Every coefficient of MiniZephyr with an explicit density is holomorphic in c~, so the derivative of A along real (dc, dQ) is the derivative along the
+    complex perturbation gamma dc + chi dQ.  Evaluated through q: Q = inf gives gamma = 1, chi = 0 with no infinity in any product.  dtype np.clongdouble: in
+    80-bit arithmetic.  magnitude: moduli, every sum a sum of moduli -- what bounds the rounding of the evaluation per component."""
+    R = _real(dtype)
+    cr = np.asarray(c).real.astype(R).ravel()
+    q = 1 / np.broadcast_to(np.asarray(Q, dtype=np.float64).ravel(), cr.shape).astype(R)
+    lam = R(lam)
+    half = dtype(0.5j)
+    if magnitude:
+        gamma = (1 + abs(lam) * q) * (1 + q / 2)
+        return gamma, (np.abs(cr) * gamma) * (q * q) * (abs(lam) / np.abs(1 + lam * q) + R(0.5) / np.abs(1 + half * q))
+    disp, att = 1 + lam * q, 1 + half * q
+    gamma = disp * att
+    return gamma, -(cr * gamma) * (q * q) * (lam / disp + half / att)
+
+
 def _buoyancy(op, R):
     "b = 1 / rho (nz, nx) at the density the operator is assembled with (its config's, or the Gardner default)"
     return 1 / np.broadcast_to(np.asarray(op.rho, dtype=np.float64), (int(op.nz), int(op.nx))).astype(R)
 
 
+def _perturbation(dc, R, dtype, shape):
+    """a velocity perturbation in the arithmetic of dtype: a real one is cast to the real type R as it always was; a complex one (the perturbation of the
+    complex velocity of a visco problem, `viscoChain`) keeps both parts -- the row factors and kappa are holomorphic in c, so the same formulas hold"""
+    dc = np.asarray(dc)
+    return dc.astype(dtype if np.iscomplexobj(dc) else R).reshape(shape)
+
+
 def velocityPlanes(op, dc, db=None, dtype=np.complex128, magnitude=False):
     """The nine planes (9, nz, nx) of d A / d c along the real velocity perturbation dc (N,), boundary rows zero, for the 2-D MiniZephyr operator `op`:
     mass term and PML stretch at the density of the operator.  db (N,): the buoyancy perturbation that goes with dc (gardnerChain(c) dc where the density
-    follows c), whose planes `buoyancyPlanes(op, db)` are added.  magnitude: the same sum with every term replaced by its modulus."""
+    follows c), whose planes `buoyancyPlanes(op, db)` are added.  magnitude: the same sum with every term replaced by its modulus.
+    dc complex (explicit density only, db None): the derivative along that perturbation of a complex velocity, what a visco problem applies."""
     nz, nx = int(op.nz), int(op.nx)
     R = _real(dtype)
-    v = np.asarray(dc).astype(R).reshape((nz, nx))
+    v = _perturbation(dc, R, dtype, (nz, nx))
     b = _buoyancy(op, R)
     drow = [x * v for x in rowFactorsDc(op, dtype, magnitude)]
     dkb = massWeightDc(op, dtype) * b * v
@@ -599,7 +633,7 @@ def massPlanes(op, dc, dtype=np.complex128, magnitude=False):
     "the nine planes of linearisation='operator': the mass terms m_k (d kappa / dc) b dc of the neighbouring cell alone (`velocityPlanes` without the stretch)"
     nz, nx = int(op.nz), int(op.nx)
     R = _real(dtype)
-    dkb = massWeightDc(op, dtype) * _buoyancy(op, R) * np.asarray(dc).astype(R).reshape((nz, nx))
+    dkb = massWeightDc(op, dtype) * _buoyancy(op, R) * _perturbation(dc, R, dtype, (nz, nx))          # (dc complex: as `velocityPlanes`)
     if magnitude:
         dkb = np.abs(dkb)
     mc, md, me = [R(w) for w in MZ_MASS]

@@ -39,6 +39,7 @@ from .frechet import gaussNewtonDiagonal, lagGram                               
 from .frechet import applyPlanesTransposed, massPlanes, velocityCurvature           # (and the residual part of the Newton Hessian)
 from .frechet import mixedAdjointB, mixedAdjointC                                   # (and the mixed second derivative of parameter='joint')
 from .frechet import gaussNewtonBlocks, pseudoHessianBlocks                         # (and the per-cell 2 x 2 blocks of the joint Hessian)
+from .frechet import viscoChain                                                     # (and the chain from (c, Q) to the complex velocity of a visco problem)
 
 EPS = 1e-15
 
@@ -60,6 +61,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         'shardFreqs':       (False,    '_shard',    bool),
         'hostGradient':     (False,    '_hostGradient', bool),    # force the numpy imaging condition
         'fieldsDtype':      (False,    '_fieldsDtype', str),      # what fieldsDevice() keeps: 'complex128' (default) or 'complex64' (half the memory)
+        'viscoDerivatives': (False,    '_viscoDerivatives', bool),    # a visco problem serves the exact derivatives ('operator' / 'full') through the chain from (c, Q)
     }
 
     surveyPair = HelmBaseSurvey
@@ -286,6 +288,15 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         the density is not a free parameter and the call raises NotImplementedError.
         parameter='joint' ('operator' or 'full', an explicit `rho`): [g_c; g_rho], float64 (2 N,), from ONE back-propagation per source and frequency -- both are
         transposes applied to the same lag products, g_c = Re w V_f^T P_f (its mass term alone for 'operator'), g_rho = -(Re w L_f^T P_f) / rho^2.
+
+        A visco problem (Helm2DViscoProblem: `system` a ViscoMultiFreq; MiniZephyr / MiniZephyrHD on one grid, an explicit `rho`) with 'operator' or 'full' is
+        served when the config sets viscoDerivatives=True (opt-in; without the key it is refused with NotImplementedError, as it always was): the
+        operator of frequency f is assembled at the complex velocity c~_f = c (1 + lam_f / Q)(1 + i / (2 Q)) and is holomorphic in it, so with
+        t_f = w V_f^T P_f the complex cell gradient with respect to c~_f and (gamma_f, chi_f) = d c~_f / d (c, Q) (frechet.viscoChain)
+            parameter='c': g_c = Re sum_f gamma_f t_f (at fixed Q),   parameter='Q': g_Q = Re sum_f chi_f t_f,   parameter='cQ': [g_c; g_Q], float64 (2 N,),
+        all from ONE back-propagation per source and frequency.  The derivative is with respect to Q itself (for 1 / Q multiply by -Q^2).  parameter='rho' is what
+        it is above, at the complex velocity.  'Q' / 'cQ' with 'scaler' or on a problem without Q: ValueError; parameter='joint' and a config without `rho`
+        (Gardner's density is not holomorphic in c~): NotImplementedError.  'scaler' on a visco problem stays the reference's weight.
         """
         self._requirePaired()
         if v is None:
@@ -293,7 +304,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if adjoint not in ('reciprocity', 'transpose'):
             raise ValueError('adjoint is %r: \'reciprocity\' or \'transpose\'' % (adjoint,))
         self._checkLinearisation(linearisation)
-        self._checkParameter(parameter, linearisation, joint=True)
+        if not self._checkViscoParameter(parameter, linearisation):
+            self._checkParameter(parameter, linearisation, joint=True)
         if linearisation in ('operator', 'full') and adjoint != 'transpose':
             raise ValueError('linearisation=%r needs adjoint=\'transpose\': the exact derivative back-propagates through A^-T' % (linearisation,))
         self.updateModel(m)
@@ -366,6 +378,126 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         'the config gives the density: it is a parameter of its own.  Otherwise it follows the velocity, rho = 310 Re(c)^0.25 (Gardner)'
         return self.systemConfig.get('rho', None) is not None
 
+    # ---- visco problems: the chain from (c, Q) to the complex velocity ----------------------------------------
+    def _isVisco(self):
+        'the system wrapper makes a complex velocity from c and Q per frequency (ViscoMultiFreq): the exact derivatives then run through `viscoChain`'
+        return isinstance(self.system, ViscoMultiFreq)
+
+    def _checkViscoParameter(self, parameter, linearisation, stacked=True):
+        """True when parameter is 'Q' or the stacked 'cQ' and the call may go on (nothing else is left to check of it); False for every other parameter, which
+        `_checkParameter` then checks as before.  ValueError: on a problem that has no Q, with the scaler (the reference has none for Q), 'cQ' inside a pair"""
+        if not (isinstance(parameter, str) and parameter in ('Q', 'cQ')):
+            return False
+        if parameter == 'cQ' and not stacked:
+            raise ValueError('parameter=\'cQ\' is the stacked vector [c; Q] and cannot be half of a pair: pairs are made of \'c\', \'Q\' and \'rho\'')
+        if not self._isVisco():
+            raise ValueError('parameter=%r is the quality factor of a visco problem (Helm2DViscoProblem): %s has no Q' % (parameter, type(self.system).__name__))
+        if linearisation not in ('operator', 'full'):
+            raise ValueError('parameter=%r needs linearisation=\'operator\' or \'full\': the reference has no gradient scaler for Q' % (parameter,))
+        return True
+
+    def _refuseViscoDiagonal(self, what):
+        if self._isVisco():
+            raise NotImplementedError('%s does not serve visco problems: the Hessian diagonals and blocks are not built with the chain from (c, Q) to the complex '
+                                      'velocity' % (what,))
+
+    def _viscoLambda(self, ifreq):
+        "lam_f = ln(f / freqBase) / pi of `viscoChain` for a frequency of the wrapper, 0 where it does not disperse (no freqBase, or Q infinite everywhere)"
+        sysw = self.system
+        if not sysw.disperseFreqs:
+            return 0.0
+        f = complex(sysw.freqs[ifreq])
+        if f.imag != 0.0:
+            raise ValueError('a visco problem with dispersion (freqBase > 0) needs real frequencies: ln(f / freqBase) of the complex frequency %r is not what '
+                             'the Kolsky-Futterman law is defined with' % (sysw.freqs[ifreq],))
+        return float(np.log(f.real / float(sysw.freqBase)) / np.pi)
+
+    def _viscoQ(self):
+        'Q per cell, float64 (N,), as the wrapper has it: inf where the config gives none'
+        return np.ascontiguousarray(np.broadcast_to(np.asarray(self.system.Q, dtype=np.float64).ravel(), (self.nrow,)))
+
+    def _viscoChainOf(self, ifreq):
+        '(gamma_f, chi_f) of `viscoChain` per cell at the current model'
+        c = np.broadcast_to(np.asarray(self.systemConfig['c']).real.ravel(), (self.nrow,))
+        return viscoChain(c, self._viscoQ(), self._viscoLambda(ifreq))
+
+    def _splitStacked(self, v, what):
+        "(v_c, v_Q), float64 (N,) each, of a stacked vector [v_c; v_Q] of parameter='cQ'; ValueError unless it has 2 N entries"
+        v = np.asarray(v)
+        if v.size != 2 * self.nrow:
+            raise ValueError('%s(parameter=\'cQ\') takes the stacked vector [c; Q] of %d entries, not %d' % (what, 2 * self.nrow, v.size))
+        v = np.asarray(v, dtype=np.float64).reshape((2 * self.nrow,))
+        return np.ascontiguousarray(v[:self.nrow]), np.ascontiguousarray(v[self.nrow:])
+
+    def _viscoHalves(self, v, parameter, what):
+        "(v_c, v_Q) of a perturbation of 'c', 'Q' or 'cQ': float64 (N,) each, None for the half that is not perturbed"
+        if parameter == 'cQ':
+            return self._splitStacked(v, what)
+        v = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape((self.nrow,)))
+        return (v, None) if parameter == 'c' else (None, v)
+
+    def _JtvecVisco(self, resid, u, linearisation, parameter):
+        """Jtvec(adjoint='transpose') of a visco problem for parameter 'c', 'Q' or 'cQ' once the refusals are past: float64 (N,), or [g_c; g_Q] (2N,), from ONE
+        back-propagation per source and frequency.  t_f = w V_f^T P0 is the complex cell gradient with respect to the complex velocity (the mass term alone for
+        'operator'), w = -conj(scaleTerm) / premul; the chain is applied per frequency, before the sum: g_c = Re sum_f gamma_f t_f, g_Q = Re sum_f chi_f t_f."""
+        stretch = linearisation == 'full'
+        adj = self.adjointSystem
+        N = self.nrow
+        wantC, wantQ = parameter in ('c', 'cQ'), parameter in ('Q', 'cQ')
+        lams = [self._viscoLambda(i) for i in range(self.survey.nfreq)]
+        with self._forwardFields(u) as F:
+            if isinstance(F, DeviceFields):
+                rd = self._hermitianResidual(resid)
+                return device_survey.viscoGradientFromFields(self, F, self._deviceBackSources(rd), rd, adj, linearisation, parameter, self._viscoQ(), lams)
+            g = np.zeros(2 * N if parameter == 'cQ' else N, dtype=np.complex128)
+            st = complex(self.system.scaleTerm)
+            qb = [q.conj() for q in self.survey.getResidualSources(np.conj(resid))]
+            for ifreq, uB in self._solveOwned(qb, adj):
+                op = self.system.subProblems[ifreq]
+                P = lagProducts(np.conj(np.asarray(uB) / st), np.conj(np.asarray(F[ifreq]) / st), op.nz, op.nx)
+                t = (-np.conj(st) / complex(op.premul)) * velocityAdjoint(op, P, stretch=stretch)
+                gamma, chi = self._viscoChainOf(ifreq)
+                if wantC:
+                    g[:N] += gamma * t
+                if wantQ:
+                    g[-N:] += chi * t
+        if self._sharded:
+            g = parallel.allreduce_sum(g)
+        return g.real.copy()
+
+    def _JvecBornVisco(self, v, u, linearisation, parameter):
+        """JvecBorn of a visco problem for parameter 'c', 'Q' or 'cQ' once the refusals are past: the derivative of dpred along real (v_c, v_Q) is the
+        derivative along the complex perturbation gamma_f v_c + chi_f v_Q of the complex velocity of frequency f -- one set of planes and one Born solve."""
+        sv = self.survey
+        vc, vQ = self._viscoHalves(v, parameter, 'JvecBorn')
+        lams = [self._viscoLambda(i) for i in range(sv.nfreq)]
+        stretch = linearisation == 'full'
+        with self._forwardFields(u) as F:
+            if isinstance(F, DeviceFields):
+                data = device_survey.viscoBornFromFields(self, F, vc, vQ, linearisation, self._viscoQ(), lams)
+            else:
+                data = np.zeros((sv.nrec, sv.nsrc, sv.nfreq), dtype=np.complex128)
+                owned = self.ownedFreqs
+                st = complex(self.system.scaleTerm)
+                subs = self.system.subProblems
+
+                def source(i):
+                    gamma, chi = self._viscoChainOf(i)
+                    dcz = (0 if vc is None else gamma * vc) + (0 if vQ is None else chi * vQ)
+                    C = velocityPlanes(subs[i], dcz) if stretch else massPlanes(subs[i], dcz)
+                    return applyPlanes(C, np.conj(np.asarray(F[i]) / st), subs[i].nz, subs[i].nx) / -complex(subs[i].premul)
+                qv = [source(i) if i in owned else None for i in range(sv.nfreq)]
+                for ifreq, uB in self._solveOwned(qv):
+                    uB = np.asarray(uB)
+                    if sv.mode == 'fixed':
+                        data[:, :, ifreq] = sv.rVec(0, ifreq) * uB
+                    else:
+                        for isrc in range(sv.nsrc):
+                            data[:, isrc, ifreq] = sv.rVec(isrc, ifreq) * uB[:, isrc]
+        if self._sharded:
+            data = parallel.allreduce_sum(data)
+        return data.ravel()
+
     def _requireOperatorLinearisation(self, what):
         """linearisation='operator' serves Helm2DProblem with MiniZephyr / MiniZephyrHD on a single grid and an explicit density: everything else is refused
         here with the reason"""
@@ -380,8 +512,13 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         from .minizephyr import MiniZephyr
         from .discretization import DiscretizationWrapper
         self._refuseMultiscale(what)
-        if isinstance(self.system, ViscoMultiFreq):
-            raise NotImplementedError('%s does not serve visco problems: the chain factor of the complex velocity with respect to c and Q is not built' % (what,))
+        if self._isVisco() and not getattr(self, '_viscoDerivatives', False):
+            # opt-in: with the key parameter='c' means d/dc at fixed Q through the chain; without it a visco problem is refused as it always was
+            raise NotImplementedError('%s does not serve visco problems unless the config sets viscoDerivatives=True: the exact derivatives then run through the chain '
+                                      'factor of the complex velocity with respect to c and Q (frechet.viscoChain)' % (what,))
+        if self._isVisco() and not self._hasDensity():
+            raise NotImplementedError('%s on a visco problem needs an explicit `rho` in the config: the default density rho = 310 Re(c~)^0.25 (Gardner) is not '
+                                      'holomorphic in the complex velocity c~, and the chain from (c, Q) runs through the holomorphic derivative' % (what,))
         sub = self.system.subProblems[0] if self.system.subProblems else None
         if sub is not None and isinstance(sub, DiscretizationWrapper):
             raise NotImplementedError('%s does not serve the 2.5-D composite: the stored fields are the ky SUM, the exact derivative needs the fields per ky' % (what,))
@@ -392,6 +529,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         """the linearisation a route runs with, once what it does not serve is refused: 'full' with parameter='rho' is 'operator' -- the density derivative
         leaves nothing out -- and needs the density to be a parameter of its own"""
         what = '%s(linearisation=%r)' % (what, linearisation)
+        if parameter == 'joint' and self._isVisco():
+            self._requireFullLinearisation(what)              # (what refuses the operator itself says so first)
+            raise NotImplementedError('%s with parameter=\'joint\' does not serve visco problems: the stacked (c, rho) routes are not built with the chain through '
+                                      'the complex velocity (parameter \'cQ\' and \'rho\' are served, one call each)' % (what,))
         if parameter == 'joint':
             # [c; rho] stacked: what 'full' serves, and the density a parameter of its own; 'operator' stays 'operator' (the stretch parts left out of the c half)
             self._requireFullLinearisation(what)
@@ -467,6 +608,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         linearisation = self._resolveLinearisation(linearisation, parameter, 'Jtvec')
         if parameter == 'joint':
             return self._JtvecJoint(resid, u, linearisation)
+        if linearisation != 'scaler' and parameter in ('c', 'Q', 'cQ') and self._isVisco():
+            return self._JtvecVisco(resid, u, linearisation, parameter)
         exact = linearisation == 'operator'
         full = linearisation == 'full'
         density = parameter == 'rho'
@@ -591,15 +734,22 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
 
         parameter='joint' ('operator' or 'full', an explicit `rho`): v = [v_c; v_rho] of 2 N entries, the derivative of dpred along both at once from one Born
         solve: delta A = V_f[v_c] + L_f[-v_rho / rho^2] is one set of planes (for 'operator' the mass term of V_f alone).  The exact adjoint of
-        Jtvec(..., parameter='joint')."""
+        Jtvec(..., parameter='joint').
+
+        A visco problem with 'operator' or 'full' (served and refused as in `Jtvec`): parameter 'c', 'Q' or the stacked 'cQ' (v = [v_c; v_Q] of 2 N entries) is
+        the derivative of dpred along real perturbations of c and of Q, one Born solve: delta A = V_f[gamma_f v_c + chi_f v_Q], the planes of a COMPLEX
+        perturbation of the complex velocity of frequency f (frechet.viscoChain; `_JvecBornVisco`)."""
         self._requirePaired()
         if v is None:
             raise Exception('Actually, JvecBorn requires a perturbation vector')
         self._checkLinearisation(linearisation)
-        self._checkParameter(parameter, linearisation, joint=True)
+        if not self._checkViscoParameter(parameter, linearisation):
+            self._checkParameter(parameter, linearisation, joint=True)
         self.updateModel(m)
         self._refuseMultiscale('JvecBorn')
         linearisation = self._resolveLinearisation(linearisation, parameter, 'JvecBorn')
+        if linearisation != 'scaler' and parameter in ('c', 'Q', 'cQ') and self._isVisco():
+            return self._JvecBornVisco(v, u, linearisation, parameter)
         exact = linearisation in ('operator', 'full')
         full = linearisation == 'full'
         density = parameter == 'rho'
@@ -699,15 +849,21 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             H_rho = (-1 / rho^2) (.) Re w [ L^T P1 + M_b^T[v_c] P0 ]  +  v_rho (.) 2 / rho^3 (.) Re w L^T P0
 
         M_c^T and M_b^T the transposes of the mixed derivative in its velocity and in its buoyancy argument (frechet.mixedAdjointC / mixedAdjointB; the second
-        gathers v_c from the eight rows around a cell).  Hvec([p; 0], resid=r) is [H_cc p; H_rho,c p]."""
+        gathers v_c from the eight rows around a cell).  Hvec([p; 0], resid=r) is [H_cc p; H_rho,c p].
+
+        A visco problem with resid None: parameter 'c', 'Q', 'rho', a pair of them, or the stacked 'cQ' (not inside a pair; v and the result of 2 N entries) --
+        the composition of the two halves as above, two solves per source and frequency.  Hvec(resid=) raises NotImplementedError there: the second derivative
+        of the chain from (c, Q) to the complex velocity is not built."""
         self._requirePaired()
         if v is None:
             raise Exception('Actually, Hvec requires a vector')
         self._checkLinearisation(linearisation)
         pin, pout = parameter if isinstance(parameter, (tuple, list)) and len(parameter) == 2 else (parameter, parameter)
         joint = isinstance(parameter, str) and parameter == 'joint'           # ('joint' inside a pair is no parameter: ValueError below)
-        self._checkParameter(pin, linearisation, joint=joint)
-        self._checkParameter(pout, linearisation, joint=joint)
+        stacked = isinstance(parameter, str) and parameter == 'cQ'            # (and neither is 'cQ')
+        for par in (pin, pout):
+            if not self._checkViscoParameter(par, linearisation, stacked=stacked):
+                self._checkParameter(par, linearisation, joint=joint)
         if resid is not None and linearisation == 'scaler':
             raise ValueError('linearisation=\'scaler\' is not the derivative of dpred and has no Hessian: Hvec(resid=) needs \'operator\' or \'full\'')
         if resid is not None and weights is not None:
@@ -723,6 +879,11 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             weights = weights.astype(np.float64).ravel()
         if joint:
             self._splitJoint(v, 'Hvec')                                                 # (ValueError unless v is the stacked vector of 2 N entries)
+        if stacked:
+            self._splitStacked(v, 'Hvec')
+        if resid is not None and self._isVisco():
+            raise NotImplementedError('Hvec(resid=) does not serve visco problems: the second derivative of the chain from (c, Q) to the complex velocity, '
+                                      'd^2 c~ / dQ^2 and d^2 c~ / dc dQ, is not built (resid=None, the Gauss-Newton product, is served)')
         if resid is not None:
             if pin != pout:
                 raise NotImplementedError('Hvec(resid=) serves one parameter: the mixed second derivative of the operator with respect to c and b is not local to a cell')
@@ -881,8 +1042,11 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         self.updateModel(m)
         if kind == 'gaussNewton' and linearisation == 'scaler':
             self._requireFullLinearisation('illumination(linearisation=\'scaler\')')      # (this kind needs the transposed 2-D operator whatever the linearisation)
+            self._refuseViscoDiagonal('illumination(linearisation=\'scaler\')')
         if linearisation != 'scaler':
-            linearisation = self._resolveLinearisation(linearisation, parameter, 'illumination')
+            resolved = self._resolveLinearisation(linearisation, parameter, 'illumination')
+            self._refuseViscoDiagonal('illumination(linearisation=%r)' % (linearisation,))
+            linearisation = resolved
         if kind == 'gaussNewton' and sv.mode != 'fixed':          # (after the refusals: what is not served at all says so first)
             raise ValueError('kind=\'gaussNewton\' serves fixed receiver arrays (mode is %r): with an array that moves with the source the sum over '
                              'receivers depends on the source and does not factorise' % (sv.mode,))
