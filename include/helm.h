@@ -163,11 +163,26 @@ int helm_assemble(helm_op *op, double freq_re, double freq_im, double tau, doubl
 int helm_set_transposed(helm_op *op, int on);
 int helm_get_transposed(const helm_op *op);    /* 1: the planes in the handle (helm_get_diagonals) are those of A^T, 0: of A */
 
+/* The transposed first block of an Eurus handle.  With eps == delta everywhere the Eurus system is block-triangular and an N-row right-hand side is solved
+ * through M1 alone, u = M1^-1 q; on != 0 makes the NEXT helm_assemble leave the planes of M1^T in block 0 (on == 0: of M1 again), by the plane formula above, and
+ * helm_get_transposed then returns 1.  helm_solve* with an N-row right-hand side returns conj(M1^-T (premul rhs)) through the direct path.  A handle that holds M1^T
+ * serves nothing else: a stacked 2N right-hand side, blocks 1 .. 3 (helm_get_block_diagonals, helm_get_diagonals, helm_apply), the scaled planes, a Krylov `method`
+ * and the Krylov fallback after a failed factorisation return HELM_ERR_UNSUPPORTED -- the untransposed blocks are never served in its place.  A model with
+ * eps != delta anywhere (the coupled 2N x 2N system has no transposed solve), a MiniZephyr or a 3-D handle: HELM_ERR_UNSUPPORTED; before helm_set_model:
+ * HELM_ERR_STATE.  helm_set_transposed keeps refusing Eurus handles. */
+int helm_set_transposed_m1(helm_op *op, int on);
+/* on != 0: helm_stencil_sources[_c64]_device and helm_lag_imaging_accumulate[_c64]_device serve this 2-D Eurus handle (they read nothing but nine planes and the
+ * grid; the derivative routes of an Eurus problem run them on the planes of helm_eurus_planes_device).  0, the default: they return HELM_ERR_UNSUPPORTED for it as
+ * they always did.  Any other handle: HELM_ERR_UNSUPPORTED. */
+int helm_set_eurus_derivatives(helm_op *op, int on);
+
 int helm_num_blocks(const helm_op *op);        /* 1 (MiniZephyr) or 4 (Eurus) */
 long long helm_num_points(const helm_op *op);  /* N = nz*nx */
 
 /* out: num_blocks * 9 * N complex, layout C[block][k][i] */
 int helm_get_diagonals(helm_op *op, double *out);
+/* out: 9 * N complex, the planes C[block][k][i] of one block.  Block 0 of an Eurus handle needs no other block to exist. */
+int helm_get_block_diagonals(helm_op *op, int block, double *out);
 
 /* --- operator application (parity / microbenchmark) ----------------------------------- */
 /* Y[r] = M_block X[r], r < nrhs; adjoint != 0 applies the conjugate transpose. */
@@ -296,6 +311,25 @@ int helm_virtual_sources_op_c64_device(helm_op *op, const void *dU32, const void
 int helm_imaging_op_accumulate_device(helm_op *op, const void *dUF, long long ldf, const void *dUB, long long ldb, int nsrc, const void *dW, void *dG);
 int helm_imaging_op_accumulate_c64_device(helm_op *op, const void *dUF32, const void *dExp, long long ldf, const void *dUB, long long ldb, int nsrc, const void *dW,
                                           void *dG);
+
+/* --- the derivative maps of the Eurus block M1 (eps == delta) ---------------------------------------------------------------------------------
+ * A row of M1 is linear and homogeneous in the buoyancies b = 1 / rho and the mass terms K = omega_d^2 b / c^2 of the 3 x 3 (edge-clamped) cells around it; its PML
+ * averages do not depend on the model.  The entry built from the neighbour (sz, sx) lies in the matrix slot (-sz, sx).  An edge row keeps its centre entry alone,
+ * and that entry depends on the model.
+ *
+ * helm_eurus_planes_device:  dC = V[dc] + L[db], the nine planes of d M1 along real (dc, db); either may be NULL.  L[db] is the row at b -> db,
+ *     K -> omega_d^2 db / c^2; V[dc] the mass entries at K -> -2 omega_d^2 b dc / c^3.  dc, db: N float64; dC: 9 N complex128.
+ * helm_eurus_adjoint_device:  Gc[j] += w (V^T P)[j], Gb[j] += w (L^T P)[j] (conj != 0: the conjugated coefficients) from one pass over P; either output may
+ *     be NULL, not both.  P: 9 N complex128 (on edge rows the centre plane alone is read); Gc, Gb: N complex128.
+ * helm_lag_centre_edges_accumulate[_c64]_device:  P[4][i] += sum_{s<nsrc} UB[s ldb + i] UF[s ldf + i] on the 2 (nz + nx) - 4 boundary cells i, which
+ *     helm_lag_imaging_accumulate_device leaves alone.  Arguments as there.
+ *
+ * Plain fp64 in a fixed order, no atomics: the same bits on every run.  2-D Eurus handles whose model has eps == delta; anything else: HELM_ERR_UNSUPPORTED.
+ * The maps are those of M1 whether or not the handle holds M1^T.  Argument checks as for the MiniZephyr derivatives below. */
+int helm_eurus_planes_device(helm_op *op, const void *dDc, const void *dDb, void *dC);
+int helm_eurus_adjoint_device(helm_op *op, const void *dP, double w_re, double w_im, int conj, void *dGc, void *dGb);
+int helm_lag_centre_edges_accumulate_device(helm_op *op, const void *dUF, long long ldf, const void *dUB, long long ldb, int nsrc, void *dP);
+int helm_lag_centre_edges_accumulate_c64_device(helm_op *op, const void *dUF32, const void *dExp, long long ldf, const void *dUB, long long ldb, int nsrc, void *dP);
 
 /* --- the exact density derivative of MiniZephyr (HelmBaseProblem.JvecBorn / Jtvec with linearisation='operator', parameter='rho') ---------------
  * Every interior row of MiniZephyr is linear and homogeneous in the buoyancy field b = 1 / rho; its boundary rows are +-identity.  L maps a real field db (N) to

@@ -105,6 +105,15 @@ _SIGNATURES = {
                                      ctypes.c_double, ctypes.c_double]),
     'helm_set_transposed': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'helm_get_transposed': (ctypes.c_int, [ctypes.c_void_p]),
+    'helm_set_transposed_m1': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'helm_set_eurus_derivatives': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
+    'helm_get_block_diagonals': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
+    'helm_eurus_planes_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'helm_eurus_adjoint_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'helm_lag_centre_edges_accumulate_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                                               ctypes.c_void_p]),
+    'helm_lag_centre_edges_accumulate_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
+                                                                   ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p]),
     'helm_virtual_sources_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
                                                    ctypes.c_longlong]),
     'helm_virtual_sources_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p,

@@ -12,6 +12,7 @@
 // row-equilibrated coupled Eurus system (k_rowscale_system) and Gardner's density (k_gardner_rho).
 #include "helm_internal.hpp"
 #include "mz_row.hpp"
+#include "eu_row.hpp"
 
 namespace {
 
@@ -68,16 +69,8 @@ __global__ __launch_bounds__(256) void k_assemble_mz(MzParams P, const cplx *__r
     for (int k = 0; k < 9; ++k) C[(long long)k * N + i] = out[k];
 }
 
-struct EuParams {
-    int nz, nx;
-    double dx, dz;
-    cplx om;
-    int aniso;
-    int nblk_out;     // 4, or 1 to build only M1
-};
-
 // Eurus: eurus.py:140-168 (PML averages), :170-226 (buoyancy squares/lines), :229-269 (mass),
-// :279-295 (TTI fields), :300-427 (the nine entries), :479-485 (edges), :117-127 (z-flipped slots)
+// :279-295 (TTI fields), :300-427 (the nine entries), :479-485 (edges), :117-127 (z-flipped slots); the formulas themselves are eu_row.hpp's
 __global__ __launch_bounds__(256) void k_assemble_eurus(EuParams P, const cplx *__restrict__ c,
                                                         const double *__restrict__ rho,
                                                         const double *__restrict__ theta, const double *__restrict__ eps,
@@ -88,15 +81,11 @@ __global__ __launch_bounds__(256) void k_assemble_eurus(EuParams P, const cplx *
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= N) return;
     const int iz = (int)(i / P.nx), ix = (int)(i % P.nx);
-    const double dxx = P.dx * P.dx, dzz = P.dz * P.dz;
 
     // padded 1-D PML profiles: index p = i+1
     const cplx xl = xix[ix], xc = xix[ix + 1], xr = xix[ix + 2];
     const cplx zl = xiz[iz], zc = xiz[iz + 1], zr = xiz[iz + 2];
-    const cplx xM = cscale(cadd(xl, xc), 0.5), xP = cscale(cadd(xc, xr), 0.5);
-    const cplx zM = cscale(cadd(zl, zc), 0.5), zP = cscale(cadd(zc, zr), 0.5);
-    const cplx Lx4 = crecip(cscale(xc, 4 * dxx)), Lx = crecip(cscale(xc, dxx));
-    const cplx Lz4 = crecip(cscale(zc, 4 * dzz)), Lz = crecip(cscale(zc, dzz));
+    const EuPml pml = eu_pml_of(P.dx, P.dz, xl, xc, xr, zl, zc, zr);
 
     double b[9];
     cplx K[9];
@@ -112,89 +101,25 @@ __global__ __launch_bounds__(256) void k_assemble_eurus(EuParams P, const cplx *
             b[slot(sz, sx)] = 1.0 / r;
             K[slot(sz, sx)] = cdiv(om2, cscale(cmul(cj, cj), r));
         }
-    // property-space names: m = index-1, p = index+1; first letter z, second x
-    const double bmm = b[0], bm0 = b[1], bmp = b[2], b0m = b[3], b00 = b[4], b0p = b[5], bpm = b[6], bp0 = b[7], bpp = b[8];
-    const double sq1 = (bpm + bp0 + b0m + b00) / 4, sq2 = (bp0 + bpp + b00 + b0p) / 4;
-    const double sq3 = (b0m + b00 + bmm + bm0) / 4, sq4 = (b00 + b0p + bm0 + bmp) / 4;
-    const cplx rxM = crecip(xM), rxP = crecip(xP), rzM = crecip(zM), rzP = crecip(zP), rxC = crecip(xc), rzC = crecip(zc);
-    // NB: the reference divides (b / xi); multiply by the reciprocal differs by <= 1 ulp-level rounding
-    const cplx s1x = cdiv(cmake(sq1, 0), xM), s2x = cdiv(cmake(sq2, 0), xP), s3x = cdiv(cmake(sq3, 0), xM), s4x = cdiv(cmake(sq4, 0), xP);
-    const cplx s1z = cdiv(cmake(sq1, 0), zM), s2z = cdiv(cmake(sq2, 0), zM), s3z = cdiv(cmake(sq3, 0), zP), s4z = cdiv(cmake(sq4, 0), zP);
-    (void)rxM; (void)rxP; (void)rzM; (void)rzP; (void)rxC; (void)rzC;
-    const cplx ln1 = cdiv(cmake((bp0 + b00) / 2, 0), zM), ln2 = cdiv(cmake((b0m + b00) / 2, 0), xM);
-    const cplx ln3 = cdiv(cmake((b00 + b0p) / 2, 0), xP), ln4 = cdiv(cmake((b00 + bm0) / 2, 0), zP);
-    const cplx ln1c = cdiv(cmake((bp0 + b00) / 2, 0), xc), ln2c = cdiv(cmake((b0m + b00) / 2, 0), zc);
-    const cplx ln3c = cdiv(cmake((b00 + b0p) / 2, 0), zc), ln4c = cdiv(cmake((b00 + bm0) / 2, 0), xc);
-
-    const double wm1 = 0.6287326, wm2r = 0.3712667;
-    const double wm2 = 0.25 * wm2r, wm3 = 0.25 * (1.0 - wm1 - wm2r), w1 = 0.4382634, w1c = 1.0 - 0.4382634;
-    const cplx Kmm = cscale(K[0], wm3), Km0 = cscale(K[1], wm2), Kmp = cscale(K[2], wm3);
-    const cplx K0m = cscale(K[3], wm2), K00 = cscale(K[4], wm1), K0p = cscale(K[5], wm2);
-    const cplx Kpm = cscale(K[6], wm3), Kp0 = cscale(K[7], wm2), Kpp = cscale(K[8], wm3);
+    const EuStiff stiff = eu_stiffness(pml, b);
+    cplx Kw[9];
+    eu_mass_weighted(K, Kw);
 
     double th = 0, ep = 0, de = 0;
     if (P.aniso) { th = theta ? theta[i] : 0.0; ep = eps ? eps[i] : 0.0; de = delta ? delta[i] : 0.0; }
-    const double ct = cos(th), st = sin(th), s2t = sin(2.0 * th);
-    const double ct2 = ct * ct, st2 = st * st;
-    const double Ax = 1.0 + (2.0 * de) * ct2, Bx = (-1.0 * de) * s2t, Cx = (1.0 + (2.0 * de)) * ct2;
-    const double Dx = (-0.5 * (1.0 + (2.0 * de))) * s2t, Ex = (2.0 * (ep - de)) * ct2, Fx = (-1.0 * (ep - de)) * s2t;
-    const double Bz = 1.0 + (2.0 * de) * st2, Dz = (1.0 + (2.0 * de)) * st2, Fz = (2.0 * (ep - de)) * st2;
+    const EuTti t = eu_tti(th, ep, de);
     const double massv[4] = {1.0, 0.0, 0.0, 1.0};
-    const double c1xv[4] = {Ax, Cx, Ex, Ex}, c1zv[4] = {Bx, Dx, Fx, Fx};
-    const double c2xv[4] = {Bx, Dx, Fx, Fx}, c2zv[4] = {Bz, Dz, Fz, Fz};
+    const double c1xv[4] = {t.Ax, t.Cx, t.Ex, t.Ex}, c1zv[4] = {t.Bx, t.Dx, t.Fx, t.Fx};
+    const double c2xv[4] = {t.Bx, t.Dx, t.Fx, t.Fx}, c2zv[4] = {t.Bz, t.Dz, t.Fz, t.Fz};
 
     const bool edge = (ix == 0) || (ix == P.nx - 1) || (iz == 0) || (iz == P.nz - 1);
 
 #pragma unroll
     for (int m = 0; m < 4; ++m) {
         if (m >= P.nblk_out) break;
-        const double mass = massv[m], c1x = c1xv[m], c1z = c1zv[m], c2x = c2xv[m], c2z = c2zv[m];
-        const cplx ax = cscale(Lx4, c1x), bx = cscale(Lx4, c2x), az = cscale(Lz4, c1z), bz = cscale(Lz4, c2z);
-        const cplx axf = cscale(Lx, c1x), bzf = cscale(Lz, c2z);
-        cplx GG, HH, II, DD, EE, FF, AA, BB, CC, t, u;
-        // GG
-        t = csub(csub(cmul(ax, s3x), cmul(bx, s3z)), cmul(az, s3x)); t = cadd(t, cmul(bz, s3z));
-        u = cneg(cadd(cmul(bx, ln2c), cmul(az, ln4c)));
-        GG = cadd(cscale(Kmm, mass), cadd(cscale(t, w1), cscale(u, w1c)));
-        // HH
-        t = cadd(cadd(cmul(ax, cneg(cadd(s3x, s4x))), cmul(bx, csub(s4z, s3z))),
-                 cadd(cmul(az, csub(s3x, s4x)), cmul(bz, cadd(s3z, s4z))));
-        u = cadd(cmul(bx, csub(ln3c, ln2c)), cmul(bzf, ln4));
-        HH = cadd(cscale(Km0, mass), cadd(cscale(t, w1), cscale(u, w1c)));
-        // II
-        t = cadd(cadd(cmul(ax, s4x), cmul(bx, s4z)), cadd(cmul(az, s4x), cmul(bz, s4z)));
-        u = cadd(cmul(bx, ln3c), cmul(az, ln4c));
-        II = cadd(cscale(Kmp, mass), cadd(cscale(t, w1), cscale(u, w1c)));
-        // DD
-        t = cadd(cadd(cmul(ax, cadd(s3x, s1x)), cmul(bx, csub(s3z, s1z))),
-                 cadd(cmul(az, csub(s1x, s3x)), cmul(bz, cneg(cadd(s3z, s1z)))));
-        u = cadd(cmul(axf, ln2), cmul(az, csub(ln1c, ln4c)));
-        DD = cadd(cscale(K0m, mass), cadd(cscale(t, w1), cscale(u, w1c)));
-        // EE
-        t = cadd(cadd(cmul(cneg(ax), cadd(cadd(s1x, s2x), cadd(s3x, s4x))),
-                      cmul(bx, csub(cadd(s2z, s3z), cadd(s1z, s4z)))),
-                 cadd(cmul(az, csub(cadd(s2x, s3x), cadd(s1x, s4x))),
-                      cmul(cneg(bz), cadd(cadd(s1z, s2z), cadd(s3z, s4z)))));
-        u = cadd(cmul(axf, cneg(cadd(ln2, ln3))), cmul(bzf, cneg(cadd(ln1, ln4))));
-        EE = cadd(cscale(K00, mass), cadd(cscale(t, w1), cscale(u, w1c)));
-        // FF
-        t = cadd(cadd(cmul(ax, cadd(s2x, s4x)), cmul(bx, csub(s2z, s4z))),
-                 cadd(cmul(az, csub(s4x, s2x)), cmul(bz, cneg(cadd(s2z, s4z)))));
-        u = cadd(cmul(axf, ln3), cmul(az, csub(ln4c, ln1c)));
-        FF = cadd(cscale(K0p, mass), cadd(cscale(t, w1), cscale(u, w1c)));
-        // AA
-        t = cadd(cadd(cmul(ax, s1x), cmul(bx, s1z)), cadd(cmul(az, s1x), cmul(bz, s1z)));
-        u = cadd(cmul(bx, ln2c), cmul(az, ln1c));
-        AA = cadd(cscale(Kpm, mass), cadd(cscale(t, w1), cscale(u, w1c)));
-        // BB
-        t = cadd(cadd(cmul(ax, cneg(cadd(s2x, s1x))), cmul(bx, csub(s1z, s2z))),
-                 cadd(cmul(az, csub(s2x, s1x)), cmul(bz, cadd(s2z, s1z))));
-        u = cadd(cmul(bx, csub(ln2c, ln3c)), cmul(bzf, ln1));
-        BB = cadd(cscale(Kp0, mass), cadd(cscale(t, w1), cscale(u, w1c)));
-        // CC
-        t = csub(csub(cmul(ax, s2x), cmul(bx, s2z)), cmul(az, s2x)); t = cadd(t, cmul(bz, s2z));
-        u = cneg(cadd(cmul(bx, ln3c), cmul(az, ln1c)));
-        CC = cadd(cscale(Kpp, mass), cadd(cscale(t, w1), cscale(u, w1c)));
+        const EuEntries e = eu_row_entries(pml, stiff, Kw, massv[m], c1xv[m], c1zv[m], c2xv[m], c2zv[m]);
+        // nine locals, not e.GG .. e.CC in the stores: `edge ? zero : X` selects between addresses, and against the struct the kernel takes 16 bytes more stack
+        const cplx GG = e.GG, HH = e.HH, II = e.II, DD = e.DD, EE = e.EE, FF = e.FF, AA = e.AA, BB = e.BB, CC = e.CC;
 
         const cplx zero = cmake(0.0, 0.0);
         cplx *Cm = C + (long long)m * 9 * N;
@@ -305,6 +230,28 @@ __global__ __launch_bounds__(256) void k_gardner_rho(const cplx *__restrict__ c,
 
 }  // namespace
 
+// The padded C-PML profiles xi = 1 - i gamma / omega of an Eurus handle along x (nx + 2) and z (nz + 2), eurus.py:77-97.  np.arange(0, L+h, h) has
+// ceil((L+h)/h) entries; the reference breaks (broadcast ValueError) when float rounding makes that != nPML: non-zero then.
+static int eu_profiles(const helm_op *op, cplx om, double cPML, std::vector<cplx> &xix, std::vector<cplx> &xiz) {
+    auto build = [&](int n, double h, std::vector<cplx> &xi) -> int {
+        const double L = h * (op->nPML - 1);
+        const int len = (int)ceil((L + h) / h);
+        if (len != op->nPML && !op->block0_only) return HELM_ERR_PML;   // preconditioner levels are free of the hazard
+        std::vector<double> g(n, 0.0);
+        for (int k = 0; k < op->nPML; ++k) g[k] = cPML * cos((M_PI / 2) * ((0.0 + k * h) / L));
+        for (int k = 0; k < op->nPML; ++k) g[n - op->nPML + k] = cPML * cos((M_PI / 2) * ((0.0 + (op->nPML - 1 - k) * h) / L));
+        xi.resize(n + 2);
+        for (int p = 0; p < n + 2; ++p) {
+            const int k = p == 0 ? 0 : (p == n + 1 ? n - 1 : p - 1);
+            // xi = 1 - (1j*gamma)/om
+            cplx q = cdiv(cmake(0.0, g[k]), om);
+            xi[p] = cmake(1.0 - q.x, -q.y);
+        }
+        return 0;
+    };
+    return (build(op->nx, op->dx, xix) || build(op->nz, op->dz, xiz)) ? HELM_ERR_PML : 0;
+}
+
 // MzParams of a handle's grid and PML at a frequency: what k_assemble_mz is launched with
 static MzParams mz_params_at(const helm_op *op, cplx om, double ky) {
     MzParams P;
@@ -328,6 +275,29 @@ int helm_mz_params(const helm_op *op, MzParams *P) {
     if (!op || !P || op->variant != HELM_MINIZEPHYR || op->ny > 0 || !op->assembled || op->nPML < 2) return HELM_ERR_ARG;
     *P = mz_params_at(op, mz_damped_omega(op->a_freq_re, op->a_freq_im, op->a_tau), op->a_ky);
     return HELM_OK;
+}
+
+// EuParams and the device PML profiles of the Eurus operator the handle holds, from the arguments its last assembly recorded: what the derivative kernels of
+// survey_eurus.hip are launched with.  The profiles (nx + nz + 4 values) are uploaded at the first call after an assembly and kept until the next one.
+int helm_eu_params(helm_op *op, EuParams *P, const cplx **xix, const cplx **xiz) {
+    if (!op || !P || op->variant != HELM_EURUS || op->ny > 0 || !op->assembled || op->nPML < 2) return HELM_ERR_ARG;
+    const cplx om = mz_damped_omega(op->a_freq_re, op->a_freq_im, op->a_tau);
+    P->nz = op->nz; P->nx = op->nx; P->dx = op->dx; P->dz = op->dz; P->om = om; P->aniso = op->aniso ? 1 : 0; P->nblk_out = 1;
+    if (!op->d_eu_xi) {
+        std::vector<cplx> hx, hz;
+        if (eu_profiles(op, om, op->a_cpml, hx, hz)) return HELM_ERR_PML;
+        hx.insert(hx.end(), hz.begin(), hz.end());
+        const size_t bytes = sizeof(cplx) * ((size_t)op->nx + op->nz + 4);
+        cplx *d = (cplx *)helm_pool_alloc(op->device, bytes);
+        if (!d) return HELM_ERR_DEVICE;
+        if (helm_upload_staged(op, d, hx.data(), bytes)) { helm_pool_free(op->device, d, bytes); return HELM_ERR_DEVICE; }
+        op->d_eu_xi = d;
+    }
+    *xix = op->d_eu_xi; *xiz = op->d_eu_xi + op->nx + 2;
+    return HELM_OK;
+}
+void helm_eu_params_drop(helm_op *op) {
+    if (op->d_eu_xi) { helm_pool_free(op->device, op->d_eu_xi, sizeof(cplx) * ((size_t)op->nx + op->nz + 4)); op->d_eu_xi = nullptr; }
 }
 
 int helm_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau, double ky, double cPML) {
@@ -364,26 +334,8 @@ int helm_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau
     } else {
         if (op->nPML < 2) HELM_FAIL(op, HELM_ERR_ARG, "nPML must be >= 2");
         if (op->nPML > nx || op->nPML > nz) HELM_FAIL(op, HELM_ERR_ARG, "nPML larger than the grid");
-        // gamma profiles, eurus.py:77-97.  np.arange(0, L+h, h) has ceil((L+h)/h) entries; the
-        // reference breaks (broadcast ValueError) when float rounding makes that != nPML.
-        auto build = [&](int n, double h, std::vector<cplx> &xi) -> int {
-            const double L = h * (op->nPML - 1);
-            const int len = (int)ceil((L + h) / h);
-            if (len != op->nPML && !op->block0_only) return HELM_ERR_PML;   // preconditioner levels are free of the hazard
-            std::vector<double> g(n, 0.0);
-            for (int k = 0; k < op->nPML; ++k) g[k] = cPML * cos((M_PI / 2) * ((0.0 + k * h) / L));
-            for (int k = 0; k < op->nPML; ++k) g[n - op->nPML + k] = cPML * cos((M_PI / 2) * ((0.0 + (op->nPML - 1 - k) * h) / L));
-            xi.resize(n + 2);
-            for (int p = 0; p < n + 2; ++p) {
-                const int k = p == 0 ? 0 : (p == n + 1 ? n - 1 : p - 1);
-                // xi = 1 - (1j*gamma)/om
-                cplx q = cdiv(cmake(0.0, g[k]), om);
-                xi[p] = cmake(1.0 - q.x, -q.y);
-            }
-            return 0;
-        };
         std::vector<cplx> xix, xiz;
-        if (build(nx, op->dx, xix) || build(nz, op->dz, xiz))
+        if (eu_profiles(op, om, cPML, xix, xiz))
             HELM_FAIL(op, HELM_ERR_PML, "np.arange(0, L+h, h) length != nPML for this dx/dz/nPML (reference raises ValueError, eurus.py:84-91)");
         cplx *d_xi = nullptr;
         const size_t bytes = sizeof(cplx) * ((size_t)nx + nz + 4);
@@ -401,6 +353,7 @@ int helm_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau
         HIP_TRY(op, hipStreamSynchronize(op->stream));
         helm_pool_free(op->device, d_xi, bytes);
         op->blocks_ready = P.nblk_out;
+        if (op->transposed) { const int rct = helm_launch_transpose_block0(op); if (rct) return rct; }
     }
     return HELM_OK;
 }
@@ -417,6 +370,22 @@ int helm_launch_transpose_planes(helm_op *op) {
     if (e1 != hipSuccess || e2 != hipSuccess) { helm_pool_free(op->device, d_T, bytes); HIP_TRY(op, e1); HIP_TRY(op, e2); }
     helm_pool_free(op->device, op->d_C, bytes);       // (nothing reads the old planes any more: the stream is drained)
     op->d_C = d_T;
+    return HELM_OK;
+}
+
+// Block 0 of an Eurus handle's d_C <- the planes of M1^T (helm_set_transposed_m1): the buffer of the four blocks keeps its size, so the transpose goes to a
+// pool buffer of one block and is copied back.  On op->stream, behind the assembly it follows; returns when the planes are complete.
+int helm_launch_transpose_block0(helm_op *op) {
+    if (op->ny > 0 || op->variant != HELM_EURUS || op->nplanes != 9) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "the transposed M1 exists for 2-D Eurus handles only");
+    const size_t bytes = (size_t)9 * (size_t)op->N * sizeof(cplx);
+    cplx *d_T = (cplx *)helm_pool_alloc(op->device, bytes);
+    if (!d_T) HELM_FAIL(op, HELM_ERR_DEVICE, "hipMalloc of the transposed coefficient planes failed");
+    HELM_LAUNCH(k_transpose_planes, dim3((unsigned)((op->N + 255) / 256)), dim3(256), 0, op->stream, (const cplx *)op->d_C, d_T, op->nz, op->nx);
+    const hipError_t e1 = hipGetLastError();
+    const hipError_t e2 = hipMemcpyAsync(op->d_C, d_T, bytes, hipMemcpyDeviceToDevice, op->stream);
+    const hipError_t e3 = hipStreamSynchronize(op->stream);
+    helm_pool_free(op->device, d_T, bytes);
+    HIP_TRY(op, e1); HIP_TRY(op, e2); HIP_TRY(op, e3);
     return HELM_OK;
 }
 

@@ -87,6 +87,7 @@ extern "C" void helm_destroy(helm_op *op) {
     if (op->stream) hipStreamSynchronize(op->stream);
     helm_pool_free(op->device, op->d_c, (size_t)op->N * sizeof(cplx)); helm_pool_free(op->device, op->d_rho, (size_t)op->N * sizeof(double));
     helm_pool_free(op->device, op->d_theta, (size_t)op->N * sizeof(double)); helm_pool_free(op->device, op->d_eps, (size_t)op->N * sizeof(double)); helm_pool_free(op->device, op->d_delta, (size_t)op->N * sizeof(double));
+    helm_eu_params_drop(op);
     helm_pool_free(op->device, op->d_K3, (size_t)op->N * sizeof(cplx)); helm_pool_free(op->device, op->d_b3, (size_t)op->N * sizeof(double));
     helm_pool_free(op->device, op->d_L3, op->l3_elems * sizeof(cplx));
     {
@@ -254,7 +255,13 @@ extern "C" int helm_assemble(helm_op *op, double freq_re, double freq_im, double
     // quarters of the 604 MB the assembly writes at 1024^2 -- are built when something asks for them (helm_need_all_blocks: a stacked 2N right-hand side,
     // helm_get_diagonals, an apply of another block, the scaled planes of the Krylov paths)
     op->asm_nblk = (op->variant == HELM_EURUS && op->block_zero[2] && !op->block0_only && helm_tuning_now().auto_direct != 0) ? 1 : 4;
+    if (op->variant == HELM_EURUS && op->transposed_next && !op->block_zero[2])
+        HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "helm_assemble: the handle was asked for M1^T (helm_set_transposed_m1) but its model now has eps != delta: the coupled 2N system has no transposed solve");
     op->transposed = op->transposed_next;        // (helm_set_transposed: in force from here; assemble.hip leaves the planes of A^T in d_C)
+    if (op->variant == HELM_EURUS) {
+        if (op->transposed) op->asm_nblk = 1;    // (M1^T alone: a transposed Eurus handle serves the direct path and N-row right-hand sides only)
+        helm_eu_params_drop(op);                 // (the PML profiles belong to the frequency that is being replaced)
+    }
     SetupStream setup_stream(op);
     int rc = op->ny > 0 ? helm3d_launch_assemble(op, freq_re, freq_im, tau, cPML) : helm_launch_assemble(op, freq_re, freq_im, tau, ky, cPML);
     if (rc) return rc;
@@ -289,9 +296,39 @@ extern "C" int helm_set_transposed(helm_op *op, int on) {
     op->direct_failed = false;
     return HELM_OK;
 }
+// The next helm_assemble leaves M1^T in block 0 of a 2-D Eurus handle (on != 0) or M1 again (0), as helm_set_transposed does for MiniZephyr.  Only where the model
+// has eps == delta everywhere: then an N-row right-hand side is solved through M1 alone, and M1^T serves the exact adjoint.  The coupled system has no transposed solve.
+extern "C" int helm_set_transposed_m1(helm_op *op, int on) {
+    helm_tuning_refresh();
+    if (!op) return HELM_ERR_ARG;
+    if (op->variant != HELM_EURUS || op->ny > 0) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "helm_set_transposed_m1: M1^T exists for 2-D Eurus handles (MiniZephyr handles take helm_set_transposed)");
+    if (!op->has_model) HELM_FAIL(op, HELM_ERR_STATE, "helm_set_transposed_m1: helm_set_model must be called first (whether eps == delta decides)");
+    if (on && !op->block_zero[2]) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "helm_set_transposed_m1: the model has eps != delta, so the two fields are coupled: the coupled 2N x 2N system [[M1, M2], [M3, M4]] has no transposed solve");
+    const bool want = on != 0;
+    if (want == op->transposed_next) return HELM_OK;
+    HIP_TRY(op, hipSetDevice(op->device));
+    helm_pf_retire(op);
+    op->transposed_next = want;
+    op->scaled_ok = false;
+    if (op->mg || op->mg3) mg_destroy(op);
+    op->mg3_no_keep = false;
+    for (int b = 0; b < 4; ++b) { nd_free(op->direct[b]); op->direct[b] = nullptr; }
+    op->direct_failed = false;
+    return HELM_OK;
+}
+// on != 0: helm_stencil_sources[_c64]_device and helm_lag_imaging_accumulate[_c64]_device, which read nothing but nine planes and the grid, serve this 2-D Eurus
+// handle (the derivative routes of an Eurus problem run them on the planes of helm_eurus_planes_device); 0, the default: they refuse it as they always did.
+extern "C" int helm_set_eurus_derivatives(helm_op *op, int on) {
+    if (!op) return HELM_ERR_ARG;
+    if (op->variant != HELM_EURUS || op->ny > 0) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "helm_set_eurus_derivatives: a 2-D Eurus handle is what opts in");
+    op->eu_derivatives = on != 0;
+    return HELM_OK;
+}
 extern "C" int helm_get_transposed(const helm_op *op) { return op ? (op->transposed ? 1 : 0) : HELM_ERR_ARG; }
 
 int helm_need_all_blocks(helm_op *op) {
+    if (op->variant == HELM_EURUS && op->transposed && op->ny == 0)
+        HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "the handle holds M1^T (helm_set_transposed_m1): it serves the direct path and N-row right-hand sides only -- M2 .. M4, a stacked 2N right-hand side and the scaled planes of the Krylov paths belong to the untransposed coupled system");
     if (op->variant != HELM_EURUS || op->block0_only || op->ny > 0 || !op->assembled || op->blocks_ready >= op->nblocks) return HELM_OK;
     op->asm_nblk = 4;                            // (M1 is written again with the same values: a factorisation reading it meanwhile sees no change)
     return helm_launch_assemble(op, op->a_freq_re, op->a_freq_im, op->a_tau, op->a_ky, op->a_cpml);
@@ -317,6 +354,18 @@ extern "C" int helm_get_diagonals(helm_op *op, double *out) {
     HIP_TRY(op, hipSetDevice(op->device));
     { const int rcb = helm_need_all_blocks(op); if (rcb) return rcb; }
     if (helm_download_staged(op, out, op->d_C, (size_t)op->nblocks * op->nplanes * op->N * sizeof(cplx))) return HELM_ERR_DEVICE;
+    return HELM_OK;
+}
+
+// One block of the planes: what helm_get_diagonals returns for that block alone.  Block 0 of a lazily assembled or transposed Eurus handle needs nothing else.
+extern "C" int helm_get_block_diagonals(helm_op *op, int block, double *out) {
+    helm_tuning_refresh();
+    if (!op || !out || block < 0 || block >= op->nblocks) return HELM_ERR_ARG;
+    if (!op->assembled) HELM_FAIL(op, HELM_ERR_STATE, "operator not assembled");
+    HIP_TRY(op, hipSetDevice(op->device));
+    if (block > 0) { const int rcb = helm_need_all_blocks(op); if (rcb) return rcb; }
+    const size_t bb = (size_t)op->nplanes * op->N * sizeof(cplx);
+    if (helm_download_staged(op, out, op->d_C + (size_t)block * op->nplanes * op->N, bb)) return HELM_ERR_DEVICE;
     return HELM_OK;
 }
 
@@ -465,6 +514,8 @@ int solve_block(helm_op *op, int block, const cplx *dRHS, long long rhs_ld, long
             if (info) std::copy(saved.begin(), saved.end(), info);
         }
     }
+    if (op->variant == HELM_EURUS && op->transposed)
+        HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "the handle holds M1^T (helm_set_transposed_m1): it is solved by the direct path only -- the Krylov path (method, or the fallback after a failed factorisation) is not served for it");
     return solve_block_krylov(op, block, dRHS, rhs_ld, row_off, premul, sub, dXout, nrhs, o, info, sys2, rows_in);
 }
 }  // namespace

@@ -160,6 +160,8 @@ struct helm_op {
     bool otf3 = false; double otf_idx2 = 0, otf_idy2 = 0, otf_idz2 = 0, otf_blend = 0.5;
     int fstream_prio = 0;                                  // priority class fstream was acquired with (it goes back to that class's free list)
     double *d_rho = nullptr, *d_theta = nullptr, *d_eps = nullptr, *d_delta = nullptr;
+    bool eu_derivatives = false;           // Eurus: the handle has opted in to the loops over stored columns of the derivative routes (helm_set_eurus_derivatives)
+    cplx *d_eu_xi = nullptr;               // Eurus: the padded PML profiles xi_x (nx + 2) | xi_z (nz + 2) of the last assembly, made when a derivative kernel first asks (helm_eu_params)
     bool has_model = false, aniso = false;
 
     // host copies of the model (coarse levels of the multigrid preconditioner are built from them; filled on demand by
@@ -326,6 +328,8 @@ int mg3_retreat(helm_op *op, int batch);                   // rebuild as the sta
 // ---- launchers implemented in assemble.hip ----------------------------------------------------
 int helm_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau, double ky, double cPML);
 int helm_launch_transpose_planes(helm_op *op);   // d_C (one 2-D block) <- the planes of its transpose, out of place through a pool buffer, on op->stream
+int helm_launch_transpose_block0(helm_op *op);   // block 0 of an Eurus handle's d_C <- the planes of M1^T, through a pool buffer of one block, on op->stream
+void helm_eu_params_drop(helm_op *op);           // the cached PML profiles of an Eurus handle go back to the pool (a re-assembly, helm_destroy)
 int helm_launch_scale_planes(helm_op *op);       // d_Cs, d_dinv from d_C
 int helm_launch_rowscaled_system(helm_op *op);   // d_S, d_rs: the coupled Eurus system, every row divided by its 2-norm
 int helm_launch_gardner_rho(helm_op *op);        // d_rho = 310 Re(d_c)^0.25

@@ -321,7 +321,7 @@ __global__ __launch_bounds__(256) void k_stencil_sources(F U, int nsrc, long lon
 static int stencil_sources_launch(helm_op *op, HostField U, int nsrc, long long ldu, const void *dC, cplx coef, int conj, void *dR, long long ldr) {
     helm_tuning_refresh();
     if (!op || !U.u || !dC || !dR || nsrc < 1 || nsrc > 65535 * OP_UNROLL || ldu < op->N || ldr < op->N) return HELM_ERR_ARG;
-    if (int rc = mz_handle_args(op, "helm_stencil_sources_device")) return rc;       // (both entry points refuse under this name)
+    if (int rc = planes_handle_args(op, "helm_stencil_sources_device")) return rc;       // (both entry points refuse under this name)
     const size_t rbytes = (size_t)nsrc * ldr * sizeof(cplx);
     if (ranges_overlap(U.u, U.bytes(nsrc, ldu), dR, rbytes) || ranges_overlap(dC, (size_t)op->N * 9 * sizeof(cplx), dR, rbytes)) return HELM_ERR_ARG;
     if (!U.ok() || ((((uintptr_t)dC) | ((uintptr_t)dR)) & 15)) return HELM_ERR_ARG;       // (the exponents and every alignment come after the handle; 16-byte loads and stores)
@@ -429,7 +429,7 @@ static dim3 lag_grid(const helm_op *op) {
 static int lag_imaging_launch(helm_op *op, HostField UF, long long ldf, const void *dUB, long long ldb, int nsrc, void *dP) {
     helm_tuning_refresh();
     if (!op || !UF.u || !dUB || !dP || nsrc < 1 || ldf < op->N || ldb < op->N) return HELM_ERR_ARG;
-    if (int rc = mz_handle_args(op, "helm_lag_imaging_accumulate_device")) return rc;       // (both entry points refuse under this name)
+    if (int rc = planes_handle_args(op, "helm_lag_imaging_accumulate_device")) return rc;       // (both entry points refuse under this name)
     const size_t pbytes = (size_t)op->N * 9 * sizeof(cplx);
     if (ranges_overlap(UF.u, UF.bytes(nsrc, ldf), dP, pbytes) || ranges_overlap(dUB, (size_t)nsrc * ldb * sizeof(cplx), dP, pbytes)) return HELM_ERR_ARG;
     if (!UF.ok() || ((((uintptr_t)dUB) | ((uintptr_t)dP)) & 15)) return HELM_ERR_ARG;       // (the exponents and every alignment come after the handle)

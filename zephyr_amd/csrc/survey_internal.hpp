@@ -32,6 +32,12 @@ static inline int mz_handle_args(helm_op *op, const char *what) {
     if (op->variant != HELM_MINIZEPHYR || op->ny > 0) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "%s: the density and velocity derivatives are those of the 2-D MiniZephyr operator", what);
     return HELM_OK;
 }
+// the two loops over stored columns that read nothing but nine planes and the grid (k_stencil_sources, k_lag_imaging) serve a 2-D Eurus handle too once it has
+// opted in (helm_set_eurus_derivatives); without that every handle is refused as it always was
+static inline int planes_handle_args(helm_op *op, const char *what) {
+    if (op->variant == HELM_EURUS && op->ny == 0 && op->eu_derivatives) return HELM_OK;
+    return mz_handle_args(op, what);
+}
 
 // ------------------------------------------------------------------------------------------
 // the loops over a forward field, one body for both formats of the store

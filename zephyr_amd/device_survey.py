@@ -823,6 +823,9 @@ def jointGradientFromFields(prob, F, qb, resid, system, linearisation):
         op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
         op.lagImagingAccumulateDevice(d_uF, U.data_ptr(), k, P.data_ptr(), d_exp=d_exp, rows=Ni)
         w = -scale / np.conj(complex(op.premul))
+        if getattr(op, 'eurusDerivatives', False):
+            op.jointAdjointDevice(P.data_ptr(), w, G.data_ptr(), G.data_ptr() + 16 * N, conj=True)          # (Eurus: both transposes from one read of P)
+            return
         if stretch:
             op.velocityAdjointDevice(P.data_ptr(), w, G.data_ptr(), conj=True)
         else:

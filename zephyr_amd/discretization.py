@@ -51,6 +51,7 @@ class BaseDiscretization(BaseModelDependent):
     }
 
     TRANSPOSABLE = False       # classes whose device operator has a transposed assembly (the 2-D MiniZephyr family)
+    _SET_TRANSPOSED = 'helm_set_transposed'      # the entry point that asks the handle for the transposed planes (Eurus: helm_set_transposed_m1)
 
     # ---- model properties -----------------------------------------------------------------
     @property
@@ -141,7 +142,8 @@ class BaseDiscretization(BaseModelDependent):
                 c, rho, theta, eps, delta = self._model_arrays()
                 _lib.check(lib.helm_set_model(h, _lib.ptr(c), _lib.ptr(rho), _lib.ptr(theta), _lib.ptr(eps), _lib.ptr(delta)), h)
                 if self.transposed:
-                    _lib.check(lib.helm_set_transposed(h, 1), h)
+                    _lib.check(getattr(lib, self._SET_TRANSPOSED)(h, 1), h)
+                self._configureHandle(lib, h)
                 f = complex(self.freq)
                 _lib.check(lib.helm_assemble(h, f.real, f.imag, float(self.tau), float(ky), float(cpml)), h)
             except Exception:
@@ -149,6 +151,9 @@ class BaseDiscretization(BaseModelDependent):
                 raise
             self._handle = h
         return self._handle
+
+    def _configureHandle(self, lib, h):
+        'what a class sets on a fresh handle before its first assembly (Eurus: the opt-in of its derivative routes)'
 
     @property
     def Ainv(self):

@@ -303,9 +303,10 @@ def applyPlanes(C, u, nz, nx):
     return out.reshape(np.shape(u))
 
 
-def lagProducts(z, u, nz, nx):
+def lagProducts(z, u, nz, nx, edges=False):
     """P (9, N): P_k[i] = sum_s z[i, s] u[i + off_k, s] for the nine lags, zero where i is on a boundary line (an interior i has every i + off_k inside the
-    grid).  z, u: (N, nsrc).  sum_s z_s^T (dA) u_s = sum_k sum_i C_k[i] P_k[i] for planes C with zero boundary rows."""
+    grid).  z, u: (N, nsrc).  sum_s z_s^T (dA) u_s = sum_k sum_i C_k[i] P_k[i] for planes C with zero boundary rows.  edges: the centre plane P_4 on the
+    boundary lines too -- what planes with a centre entry there (Eurus: `eurusPlanes`) need."""
     nz, nx = int(nz), int(nx)
     za = np.asarray(z).reshape((nz, nx, -1))
     ua = np.asarray(u).reshape((nz, nx, -1))
@@ -313,6 +314,8 @@ def lagProducts(z, u, nz, nx):
     P = np.zeros((9, nz, nx), dtype=np.result_type(za.dtype, ua.dtype))
     for k, (sz, sx) in enumerate(LAGS):
         P[k] = np.where(inside, (za * _at(ua, sz, sx)).sum(axis=2), 0)
+    if edges:
+        P[4] = (za * ua).sum(axis=2)
     return P.reshape((9, nz * nx))
 
 
@@ -818,3 +821,178 @@ def blockSolve(B, g, damping):
     det = a * d - b * b
     gc, gr = g[:N], g[N:]
     return np.concatenate([(d * gc - b * gr) / det, (a * gr - b * gc) / det])
+
+
+# ---- the derivative maps of the Eurus block M1 (eps == delta) ---------------------------------------------------------------------------------------------
+# Written out from the assembly (eurus.py:28-485; csrc/eu_row.hpp eu_m1_row).  A row of M1 is linear and homogeneous in the buoyancies b = 1 / rho and the mass
+# terms K = omega_d^2 b / c^2 of the 3 x 3 cells around it (edge-clamped: a neighbour outside the grid is the nearest cell inside); its C-PML averages are 1-D
+# functions of cPML and omega_d and do not depend on the model, theta and delta of the row's own cell are coefficients.  The entry built from the property
+# neighbour (sz, sx) lies in the matrix slot (-sz, sx), the reference's z-flipped ordering.  The four boundary lines keep their centre entry EE alone -- which
+# depends on the model, unlike MiniZephyr's +-identity.  Along real (dc, db):
+#     dC = V[dc] + L[db],    L[db] = row(b -> db, K -> omega_d^2 db / c^2),    V[dc] = the mass entries at K -> -2 omega_d^2 b dc / c^3
+# `eurusPlanes` is the map, `eurusAdjoint` the plain transposes of both halves; k_eurus_planes / k_eurus_adjoint (csrc/survey_eurus.hip) are the device kernels.
+EU_MASS = (0.6287326, 0.25 * 0.3712667, 0.25 * (1.0 - 0.6287326 - 0.3712667))      # centre, edge, corner (eurus.py:229-269)
+EU_W1 = 0.4382634                                                                 # the blend of the rotated and the plain stiffness star
+
+
+def _euGamma(n, npml, h, cpml):
+    'the C-PML damping profile along an axis in float64, as the library makes it (eurus.py:77-91)'
+    L = h * (npml - 1)
+    vals = np.arange(npml) * h
+    g = np.zeros(n)
+    g[:npml] = cpml * np.cos((np.pi / 2) * (vals / L))
+    g[n - npml:] = cpml * np.cos((np.pi / 2) * (vals[::-1] / L))
+    return g
+
+
+def _euSetup(op, dtype):
+    """what a row of M1 takes from the operator alone, in the arithmetic of dtype: (c, b, om2, pml, tti) with c (nz, nx) complex, b = 1 / rho, om2 = omega_d^2, pml
+    the dict of the averages xM, xP, zM, zP, xC, zC and the factors Lx4, Lx, Lz4, Lz broadcast over the grid, tti = (Ax, Bx, Bz) of the row's own theta, delta"""
+    R = _real(dtype)
+    nz, nx, npml = int(op.nz), int(op.nx), int(op.nPML)
+    c = np.asarray(op.c).astype(dtype).reshape((nz, nx))
+    b = 1 / np.asarray(op.rho).astype(R).reshape((nz, nx))
+    f = complex(op.freq)
+    om = 2 * R(np.pi) * (R(f.real) + dtype(1j) * R(f.imag))
+    tau = float(op.tau)
+    if np.isfinite(tau) and tau != 0.0:
+        om = om - dtype(1j) / R(tau)
+    dx, dz = R(float(op.dx)), R(float(op.dz))
+    pad = lambda g: np.concatenate((g[:1], g, g[-1:])).astype(R)
+    xi_x = 1 - (dtype(1j) * pad(_euGamma(nx, npml, float(op.dx), float(op.cPML)))) / om
+    xi_z = 1 - (dtype(1j) * pad(_euGamma(nz, npml, float(op.dz), float(op.cPML)))) / om
+    xC, zC = xi_x[1:-1][None, :], xi_z[1:-1][:, None]
+    pml = dict(xM=((xi_x[:-2] + xi_x[1:-1]) / 2)[None, :], xP=((xi_x[1:-1] + xi_x[2:]) / 2)[None, :], xC=xC,
+               zM=((xi_z[:-2] + xi_z[1:-1]) / 2)[:, None], zP=((xi_z[1:-1] + xi_z[2:]) / 2)[:, None], zC=zC,
+               Lx4=1 / (4 * xC * dx * dx), Lx=1 / (xC * dx * dx), Lz4=1 / (4 * zC * dz * dz), Lz=1 / (zC * dz * dz))
+    theta = np.asarray(op.theta).astype(R).reshape((nz, nx))
+    delta = np.asarray(op.delta).astype(R).reshape((nz, nx))
+    ct2, st2, s2t = np.cos(theta) ** 2, np.sin(theta) ** 2, np.sin(2 * theta)
+    tti = (1 + (2 * delta) * ct2, (-delta) * s2t, 1 + (2 * delta) * st2)
+    return c, b, om * om, pml, tti
+
+
+def _euNeighbours(a):
+    "{(sz, sx): a at the edge-clamped neighbour (iz + sz, ix + sx)} of a field (nz, nx)"
+    nz, nx = a.shape
+    p = np.pad(a, 1, mode='edge')
+    return {(sz, sx): p[1 + sz:1 + sz + nz, 1 + sx:1 + sx + nx] for sz, sx in LAGS}
+
+
+def _euRow(bf, Kf, pml, tti, R, dtype, magnitude, edges=True):
+    """the nine planes (9, nz, nx), matrix slot order, of the rows of M1 from the buoyancy field bf and the mass-term field Kf (both (nz, nx), read at the clamped
+    neighbours).  magnitude: every term by its modulus, every difference a sum.  Edge rows keep the centre entry alone (edges False: nothing).  bf None: the mass
+    entries alone, what the row is at b = 0 (the stiffness is linear in b), without evaluating the stiffness."""
+    nz, nx = Kf.shape
+    if bf is None:
+        K = _euNeighbours(np.abs(Kf) if magnitude else Kf)
+        wm1, wm2, wm3 = (R(w) for w in EU_MASS)
+        return _euEdgeRows({(sz, sx): (wm1 if sz == 0 and sx == 0 else wm2 if sz == 0 or sx == 0 else wm3) * K[sz, sx] for sz, sx in LAGS}, nz, nx, R, dtype, magnitude, edges)
+    if magnitude:
+        bf, Kf = np.abs(bf), np.abs(Kf)
+        pml = {k: np.abs(v) for k, v in pml.items()}
+        # (1 / |xM| is what the modulus of b / xM needs: the averages enter as divisors)
+        tti = tuple(np.abs(t) for t in tti)
+    s = 1 if magnitude else -1
+    b, K = _euNeighbours(bf), _euNeighbours(Kf)
+    xM, xP, zM, zP, xC, zC = (pml[k] for k in ('xM', 'xP', 'zM', 'zP', 'xC', 'zC'))
+    Lx4, Lx, Lz4, Lz = (pml[k] for k in ('Lx4', 'Lx', 'Lz4', 'Lz'))
+    sq1 = (b[1, -1] + b[1, 0] + b[0, -1] + b[0, 0]) / 4
+    sq2 = (b[1, 0] + b[1, 1] + b[0, 0] + b[0, 1]) / 4
+    sq3 = (b[0, -1] + b[0, 0] + b[-1, -1] + b[-1, 0]) / 4
+    sq4 = (b[0, 0] + b[0, 1] + b[-1, 0] + b[-1, 1]) / 4
+    s1x, s2x, s3x, s4x = sq1 / xM, sq2 / xP, sq3 / xM, sq4 / xP
+    s1z, s2z, s3z, s4z = sq1 / zM, sq2 / zM, sq3 / zP, sq4 / zP
+    l1, l2, l3, l4 = (b[1, 0] + b[0, 0]) / 2, (b[0, -1] + b[0, 0]) / 2, (b[0, 0] + b[0, 1]) / 2, (b[0, 0] + b[-1, 0]) / 2
+    ln1, ln2, ln3, ln4 = l1 / zM, l2 / xM, l3 / xP, l4 / zP
+    ln1c, ln2c, ln3c, ln4c = l1 / xC, l2 / zC, l3 / zC, l4 / xC
+    wm1, wm2, wm3 = (R(w) for w in EU_MASS)
+    w1, w1c = R(EU_W1), 1 - R(EU_W1)
+    Ax, Bx, Bz = tti
+    ax, bx, az, bz, axf, bzf = Lx4 * Ax, Lx4 * Bx, Lz4 * Bx, Lz4 * Bz, Lx * Ax, Lz * Bz
+    ent = {}          # by property neighbour
+    ent[-1, -1] = wm3 * K[-1, -1] + w1 * (ax * s3x + s * (bx * s3z) + s * (az * s3x) + bz * s3z) + w1c * (s * (bx * ln2c) + s * (az * ln4c))
+    ent[-1, 0] = wm2 * K[-1, 0] + w1 * (s * (ax * (s3x + s4x)) + bx * (s4z + s * s3z) + az * (s3x + s * s4x) + bz * (s3z + s4z)) \
+        + w1c * (bx * (ln3c + s * ln2c) + bzf * ln4)
+    ent[-1, 1] = wm3 * K[-1, 1] + w1 * (ax * s4x + bx * s4z + az * s4x + bz * s4z) + w1c * (bx * ln3c + az * ln4c)
+    ent[0, -1] = wm2 * K[0, -1] + w1 * (ax * (s3x + s1x) + bx * (s3z + s * s1z) + az * (s1x + s * s3x) + s * (bz * (s3z + s1z))) \
+        + w1c * (axf * ln2 + az * (ln1c + s * ln4c))
+    ent[0, 0] = wm1 * K[0, 0] + w1 * (s * (ax * (s1x + s2x + s3x + s4x)) + bx * ((s2z + s3z) + s * (s1z + s4z)) + az * ((s2x + s3x) + s * (s1x + s4x))
+                                      + s * (bz * (s1z + s2z + s3z + s4z))) + w1c * (s * (axf * (ln2 + ln3)) + s * (bzf * (ln1 + ln4)))
+    ent[0, 1] = wm2 * K[0, 1] + w1 * (ax * (s2x + s4x) + bx * (s2z + s * s4z) + az * (s4x + s * s2x) + s * (bz * (s2z + s4z))) \
+        + w1c * (axf * ln3 + az * (ln4c + s * ln1c))
+    ent[1, -1] = wm3 * K[1, -1] + w1 * (ax * s1x + bx * s1z + az * s1x + bz * s1z) + w1c * (bx * ln2c + az * ln1c)
+    ent[1, 0] = wm2 * K[1, 0] + w1 * (s * (ax * (s2x + s1x)) + bx * (s1z + s * s2z) + az * (s2x + s * s1x) + bz * (s2z + s1z)) \
+        + w1c * (bx * (ln2c + s * ln3c) + bzf * ln1)
+    ent[1, 1] = wm3 * K[1, 1] + w1 * (ax * s2x + s * (bx * s2z) + s * (az * s2x) + bz * s2z) + w1c * (s * (bx * ln3c) + s * (az * ln1c))
+    return _euEdgeRows(ent, nz, nx, R, dtype, magnitude, edges)
+
+
+def _euEdgeRows(ent, nz, nx, R, dtype, magnitude, edges):
+    'the entries by property neighbour into the nine planes by matrix slot (-sz, sx); edge rows keep the centre entry alone (edges False: nothing)'
+    C = np.zeros((9, nz, nx), dtype=R if magnitude else dtype)
+    for (sz, sx), e in ent.items():
+        C[3 * (-sz + 1) + (sx + 1)] = e
+    edge = ~_interiorMask(nz, nx)
+    centre = C[4][edge]
+    C[:, edge] = 0
+    if edges:
+        C[4][edge] = centre
+    return C
+
+
+def eurusPlanes(op, dc=None, db=None, dtype=np.complex128, magnitude=False, edges=True):
+    """V[dc] + L[db]: the nine planes (9, nz, nx) of d M1 along the real perturbations dc of the velocity and db of the buoyancy ((N,) each, either may be None)
+    for the Eurus operator `op` with eps == delta (its c, rho, theta, delta, C-PML, frequency and damping).  Edge rows carry the derivative of their centre
+    entry, with the clamped neighbours counted as the assembly counts them.  dtype np.clongdouble: 80-bit arithmetic; magnitude: the same sum with every
+    term replaced by its modulus.  edges False (for tests): the edge rows zero, as if they did not depend on the model."""
+    return _euPlanes(_euSetup(op, dtype), dc, db, dtype, magnitude, edges)
+
+
+def _euPlanes(setup, dc, db, dtype, magnitude, edges):
+    'eurusPlanes from the _euSetup of the operator; dc alone takes the mass entries only'
+    R = _real(dtype)
+    c, b, om2, pml, tti = setup
+    nz, nx = c.shape
+    field = lambda v: np.asarray(v).astype(R).reshape((nz, nx))
+    dbf = field(db) if db is not None else None if dc is not None else np.zeros((nz, nx), dtype=R)
+    if magnitude:
+        om2, c = np.abs(om2), np.abs(c)
+        dK = 2 * om2 * b * np.abs(field(dc)) / (c * c * c) if dc is not None else None
+        if dbf is not None:
+            dKb = om2 * np.abs(dbf) / (c * c)
+            dK = dKb if dK is None else dKb + dK
+    else:
+        dK = (-2 * om2) * b * field(dc) / (c * c * c) if dc is not None else None
+        if dbf is not None:
+            dKb = om2 * dbf / (c * c)
+            dK = dKb if dK is None else dKb + dK
+    return _euRow(dbf, dK, pml, tti, R, dtype, magnitude, edges)
+
+
+def eurusAdjoint(op, P, conj=False, dtype=np.complex128, magnitude=False, edges=True):
+    """(V^T P, L^T P): (N,) each with <V[dc] + L[db], P> = <dc, V^T P> + <db, L^T P> under the bilinear pairing sum_k sum_i (no conjugate), P (9, N) or (9, nz, nx)
+    complex; on edge rows its centre plane alone is read.  conj: the transposes of the conjugated maps.  magnitude: the sum of the moduli of the terms.  A row
+    reads the 3 x 3 (clamped) cells around it, so cells with equal (iz mod 3, ix mod 3) never meet in a row: the planes of the nine colour indicators are the
+    coefficients of every row with respect to its one cell of that colour, and a 3 x 3 box sum of coefficient times P gathers them at the cell.
+    Cost: one setup of the operator and, per colour, one full row evaluation (L) and one of the mass entries alone (V) -- nine assemblies of an nz x nx
+    operator per call.  It is the reference of k_eurus_adjoint and the route without a GPU; on large grids it is slow next to the kernel."""
+    nz, nx = int(op.nz), int(op.nx)
+    N = nz * nx
+    Pl = np.asarray(P).astype(dtype).reshape((9, nz, nx))
+    if magnitude:
+        Pl = np.abs(Pl)
+    iz, ix = np.divmod(np.arange(N), nx)
+    setup = _euSetup(op, dtype)
+    gc, gb = np.zeros(N, dtype=Pl.dtype), np.zeros(N, dtype=Pl.dtype)
+    for a in range(3):
+        for bcol in range(3):
+            mine = (iz % 3 == a) & (ix % 3 == bcol)
+            if not mine.any():
+                continue
+            ind = mine.astype(np.float64)
+            for g, coef in ((gc, _euPlanes(setup, ind, None, dtype, magnitude, edges)), (gb, _euPlanes(setup, None, ind, dtype, magnitude, edges))):
+                if conj and not magnitude:
+                    coef = np.conj(coef)
+                g[mine] = _boxSum((coef * Pl).sum(axis=0), nz, nx).ravel()[mine]
+    return gc, gb

@@ -39,6 +39,7 @@ from .frechet import gaussNewtonDiagonal, lagGram                               
 from .frechet import applyPlanesTransposed, massPlanes, velocityCurvature           # (and the residual part of the Newton Hessian)
 from .frechet import mixedAdjointB, mixedAdjointC                                   # (and the mixed second derivative of parameter='joint')
 from .frechet import gaussNewtonBlocks, pseudoHessianBlocks                         # (and the per-cell 2 x 2 blocks of the joint Hessian)
+from .frechet import eurusAdjoint, eurusPlanes                                      # (and the derivative maps of the Eurus block M1)
 from .frechet import viscoChain                                                     # (and the chain from (c, Q) to the complex velocity of a visco problem)
 
 EPS = 1e-15
@@ -61,6 +62,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         'shardFreqs':       (False,    '_shard',    bool),
         'hostGradient':     (False,    '_hostGradient', bool),    # force the numpy imaging condition
         'fieldsDtype':      (False,    '_fieldsDtype', str),      # what fieldsDevice() keeps: 'complex128' (default) or 'complex64' (half the memory)
+        'eurusDerivatives': (False,    '_eurusDerivatives', bool),    # an Eurus problem (eps == delta) serves the exact adjoint and the exact derivatives through M1^T
         'viscoDerivatives': (False,    '_viscoDerivatives', bool),    # a visco problem serves the exact derivatives ('operator' / 'full') through the chain from (c, Q)
     }
 
@@ -123,7 +125,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         -- the same frequencies on the same devices, the same replicas for split sources.  `sub * q` there is conj(A_f^-T (premul q)), what
         Jtvec(adjoint='transpose') back-propagates through.  It goes with the problem's cache on a model change, and `del prob.factors` releases it too.
         While both wrappers are in use the factors of A_f and of A_f^T are resident side by side: twice the device memory of `system` alone.
-        2-D MiniZephyr / MiniZephyrHD / MiniZephyr25D on one grid; Eurus, the 3-D operator and the multiscale wrappers raise NotImplementedError."""
+        2-D MiniZephyr / MiniZephyrHD / MiniZephyr25D on one grid, and Eurus / EurusHD with eurusDerivatives=True and eps == delta (M1^T, helm_set_transposed_m1);
+        Eurus otherwise, the 3-D operator and the multiscale wrappers raise NotImplementedError."""
         if getattr(self, '_adjointSystem', None) is None:
             from .distributors import MultiGridMultiFreq
             cls = type(self.system)
@@ -507,8 +510,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
                                       '(linearisation=\'full\' carries it)' % (what,))
 
     def _requireFullLinearisation(self, what):
-        """linearisation='full' serves Helm2DProblem with MiniZephyr / MiniZephyrHD on a single grid, with an explicit density or the default one: everything
-        else is refused here with the reason"""
+        """linearisation='full' serves Helm2DProblem with MiniZephyr / MiniZephyrHD on a single grid, with an explicit density or the default one -- and, with the
+        config key eurusDerivatives, Eurus / EurusHD where eps == delta (`_eurusServed`): everything else is refused here with the reason"""
         from .minizephyr import MiniZephyr
         from .discretization import DiscretizationWrapper
         self._refuseMultiscale(what)
@@ -522,8 +525,44 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         sub = self.system.subProblems[0] if self.system.subProblems else None
         if sub is not None and isinstance(sub, DiscretizationWrapper):
             raise NotImplementedError('%s does not serve the 2.5-D composite: the stored fields are the ky SUM, the exact derivative needs the fields per ky' % (what,))
+        if self._eurusServed():
+            if not all(op.elliptical for op in self.system.subProblems):
+                raise NotImplementedError('%s on %s needs eps == delta in every cell: where they differ the two fields are coupled, and the coupled 2N x 2N system '
+                                          '[[M1, M2], [M3, M4]] has no transposed solve' % (what, type(sub).__name__))
+            return
         if sub is not None and not (isinstance(sub, MiniZephyr) and getattr(sub, 'ny', None) is None):
             raise NotImplementedError('%s serves the 2-D MiniZephyr operators: %s assembles its mass term differently' % (what, type(sub).__name__))
+
+    def _eurusServed(self):
+        """the config sets eurusDerivatives=True and the operators are 2-D Eurus / EurusHD on one grid: the exact adjoint and the exact derivatives run through M1^T
+        and the maps of frechet.eurusPlanes.  Without the key an Eurus problem is refused as it always was."""
+        from .eurus import Eurus
+        if not getattr(self, '_eurusDerivatives', False):
+            return False
+        sub = self.system.subProblems[0] if self.system.subProblems else None
+        return sub is not None and isinstance(sub, Eurus)
+
+    def _refuseEurus(self, what, why):
+        if self._eurusServed():
+            raise NotImplementedError('%s does not serve Eurus problems: %s' % (what, why))
+
+    def _eurusGradientHost(self, resid, F, adj):
+        """(g_c, g_b) complex (N,) each, before the real part and the all-reduce: sum_f w_f (V_f^T P_f, L_f^T P_f) of an Eurus problem on the host, P_f the nine lag
+        products of the transposed back-propagation against the unscaled forward solves, the centre plane on the boundary lines included (an edge row of M1
+        keeps a centre entry that depends on the model), w_f = -conj(scaleTerm) / premul"""
+        N = self.nrow
+        st = complex(self.system.scaleTerm)
+        edges = bool(getattr(self, '_eurusEdgeTerms', True))          # (False only in tests: what the result is without the edge rows' derivative)
+        gc, gb = np.zeros(N, dtype=np.complex128), np.zeros(N, dtype=np.complex128)
+        qb = [q.conj() for q in self.survey.getResidualSources(np.conj(resid))]
+        for ifreq, uB in self._solveOwned(qb, adj):
+            op = self.system.subProblems[ifreq]
+            P = lagProducts(np.conj(np.asarray(uB) / st), np.conj(np.asarray(F[ifreq]) / st), op.nz, op.nx, edges=edges)
+            tc, tb = eurusAdjoint(op, P, edges=edges)
+            w = -np.conj(st) / complex(op.premul)
+            gc += w * tc
+            gb += w * tb
+        return gc, gb
 
     def _resolveLinearisation(self, linearisation, parameter, what):
         """the linearisation a route runs with, once what it does not serve is refused: 'full' with parameter='rho' is 'operator' -- the density derivative
@@ -539,9 +578,11 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             if not self._hasDensity():
                 raise NotImplementedError('%s with parameter=\'joint\' needs an explicit `rho` in the config: without one the density follows c and is '
                                           'not a free parameter' % (what,))
-            return linearisation
+            return 'full' if self._eurusServed() else linearisation
         if linearisation == 'operator':
             self._requireOperatorLinearisation(what)
+            if self._eurusServed():
+                return 'full'                                 # (the C-PML does not depend on c: the mass term is the whole velocity derivative)
         elif linearisation == 'full':
             self._requireFullLinearisation(what)
             if parameter == 'rho':
@@ -625,7 +666,11 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
                     return device_survey.gradientFromFields(self, F, self._deviceBackSources(resid), resid, system=adj, linearisation='full', chain=self._gardnerChain())
                 return device_survey.gradientFromFields(self, F, self._deviceBackSources(resid), resid, system=adj, linearisation=linearisation)
             g = np.zeros(self.nrow, dtype=np.complex128)
-            if full:
+            if (full or density) and self._eurusServed():
+                gc, gb = self._eurusGradientHost(resid, F, adj)
+                chain = None if density else self._gardnerChain()
+                g = gb if density else (gc if chain is None else gc + chain * gb)
+            elif full:
                 # the lag products of parameter='rho' against V^T, the transpose of frechet.velocityPlanes; where the density follows c the buoyancy
                 # gradient L^T P joins through the real chain d b / d c
                 st = complex(self.system.scaleTerm)
@@ -677,13 +722,16 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
                 return g
             g = np.zeros(2 * N, dtype=np.complex128)
             st = complex(self.system.scaleTerm)
-            qb = [q.conj() for q in self.survey.getResidualSources(np.conj(resid))]
-            for ifreq, uB in self._solveOwned(qb, adj):
-                op = self.system.subProblems[ifreq]
-                P = lagProducts(np.conj(np.asarray(uB) / st), np.conj(np.asarray(F[ifreq]) / st), op.nz, op.nx)
-                w = -np.conj(st) / complex(op.premul)
-                g[:N] += w * velocityAdjoint(op, P, stretch=stretch)
-                g[N:] += w * buoyancyAdjoint(op, P)
+            if self._eurusServed():
+                g[:N], g[N:] = self._eurusGradientHost(resid, F, adj)
+            else:
+                qb = [q.conj() for q in self.survey.getResidualSources(np.conj(resid))]
+                for ifreq, uB in self._solveOwned(qb, adj):
+                    op = self.system.subProblems[ifreq]
+                    P = lagProducts(np.conj(np.asarray(uB) / st), np.conj(np.asarray(F[ifreq]) / st), op.nz, op.nx)
+                    w = -np.conj(st) / complex(op.premul)
+                    g[:N] += w * velocityAdjoint(op, P, stretch=stretch)
+                    g[N:] += w * buoyancyAdjoint(op, P)
         if self._sharded:
             g = parallel.allreduce_sum(g)
         g = g.real.copy()
@@ -783,7 +831,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
                 if density or full or joint:
                     st = complex(self.system.scaleTerm)
                     subs = self.system.subProblems
-                    if joint and not full:
+                    if self._eurusServed():
+                        edges = bool(getattr(self, '_eurusEdgeTerms', True))
+                        planes = (lambda op: eurusPlanes(op, None, pert, edges=edges)) if density else (lambda op: eurusPlanes(op, pert, db, edges=edges))
+                    elif joint and not full:
                         planes = lambda op: massPlanes(op, pert) + buoyancyPlanes(op, db)
                     else:
                         planes = (lambda op: buoyancyPlanes(op, pert)) if density else (lambda op: velocityPlanes(op, pert, db))
@@ -885,6 +936,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             raise NotImplementedError('Hvec(resid=) does not serve visco problems: the second derivative of the chain from (c, Q) to the complex velocity, '
                                       'd^2 c~ / dQ^2 and d^2 c~ / dc dQ, is not built (resid=None, the Gauss-Newton product, is served)')
         if resid is not None:
+            self._refuseEurus('Hvec(resid=)', 'the second derivative of M1 and the transposed application of its planes are not built (resid=None, the Gauss-Newton '
+                                              'product, is served)')
             if pin != pout:
                 raise NotImplementedError('Hvec(resid=) serves one parameter: the mixed second derivative of the operator with respect to c and b is not local to a cell')
             if not self._hasDensity():
@@ -1042,9 +1095,12 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         self.updateModel(m)
         if kind == 'gaussNewton' and linearisation == 'scaler':
             self._requireFullLinearisation('illumination(linearisation=\'scaler\')')      # (this kind needs the transposed 2-D operator whatever the linearisation)
+            self._refuseEurus('illumination(kind=\'gaussNewton\')', 'the Hessian diagonals are not built on the derivative maps of M1')
             self._refuseViscoDiagonal('illumination(linearisation=\'scaler\')')
         if linearisation != 'scaler':
             resolved = self._resolveLinearisation(linearisation, parameter, 'illumination')
+            self._refuseEurus('illumination(linearisation=%r)' % (linearisation,), 'the Hessian diagonals are not built on the derivative maps of M1 (the '
+                                                                                    '\'scaler\' kinds \'energy\' and \'pseudoHessian\' are served)')
             self._refuseViscoDiagonal('illumination(linearisation=%r)' % (linearisation,))
             linearisation = resolved
         if kind == 'gaussNewton' and sv.mode != 'fixed':          # (after the refusals: what is not served at all says so first)
@@ -1155,6 +1211,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
                 raise ValueError('the receiver-side blocks serve fixed receiver arrays (mode is %r)' % (sv.mode,))
         self.updateModel(m)
         linearisation = self._resolveLinearisation(linearisation, 'joint', 'hessianBlocks')
+        self._refuseEurus('hessianBlocks', 'the per-cell blocks of the joint Hessian are not built on the derivative maps of M1')
         if kind == 'gaussNewton' and sv.mode != 'fixed':
             raise ValueError('kind=\'gaussNewton\' serves fixed receiver arrays (mode is %r): with an array that moves with the source the sum over '
                              'receivers depends on the source and does not factorise' % (sv.mode,))
