@@ -9,7 +9,7 @@ The same loop serves forward fields that outlive a call (`fieldstore.DeviceField
 `dpredFromFields` samples the store and `gradientFromFields` images against it, both over the items the store recorded.  `illumination` and
 `illuminationFromFields` (last section) are the same two loops again with the energy kernel in the place of the imaging kernel and a float64 partial.
 
-The ten pipelines, one row each.  Every row is a body of its own made of the shared item steps of the next section.
+The pipelines, one row each.  Every row is a body of its own made of the shared item steps of the next section.
 
     pipeline                items                what fills R                        columns solved   what consumes U                       what comes down
     dpred                   dealt                source columns                      k                sampleDevice (2.5-D: sampleSumDevice) nrec x k samples per item
@@ -32,6 +32,10 @@ The ten pipelines, one row each.  Every row is a body of its own made of the sha
                                                                                                       on P0 (k_velocity_adjoint_b, k_mixed_adjoint)
     jointGradientFromFields stored               qb of R^H r                         k                lag imaging into P, then V^T P and    one stacked partial G (2N) per worker
                                                                                                       L^T P into the halves of G
+    kyBornFromFields        stored (per ky)      per ky: the planes of the ky handle   nky k            per ky: samples accumulated on the    nrec x k samples per item
+                                                 on the block of that ky                              device into the item's result
+    kyGradientFromFields    stored (per ky)      qb of R^H r, once per item            nky k            per ky: lag imaging into P against    one stacked partial G (2N) per worker
+                                                                                                      the block of that ky, V_ky^T P, L_ky^T P
     illumination           dealt                source or receiver columns          k                energy kernel                         one partial H per worker
     illuminationFromFields  stored               --                                  0                -- (energy kernel reads the slice)    one partial H per worker
       kind='gaussNewton'                         receiver columns, once per worker   nrec, once per   lag Gram of the slice, then the       one partial H per worker
@@ -475,9 +479,11 @@ def _storedItems(sysw, F):
     return _workerDevices(sysw), items
 
 
-def fields(prob, owned, dtype='complex128'):
+def fields(prob, owned, dtype='complex128', perKy=False):
     """The forward wavefields of the owned frequencies solved into a DeviceFields: per work item the sparse sources are expanded on the item's GPU and
-    solved straight into the item's slice of the store (complex128), or into the workspace and packed into it (complex64).  Nothing comes down."""
+    solved straight into the item's slice of the store (complex128), or into the workspace and packed into it (complex64).  Nothing comes down.
+    perKy (the operators are 2.5-D composites): the slice of an item is (nky, k, Ni) and every ky operator solves into its own block, in the order and with the
+    factor scheduling of the composite's ky loop (complex64: packed block by block, one exponent per column and ky); the ky sum is not formed."""
     import torch
     from .fieldstore import DeviceFields, DTYPES
     from .survey import HelmMultiGridSurvey
@@ -490,27 +496,45 @@ def fields(prob, owned, dtype='complex128'):
     nsrc = sv.nsrc
     scale = complex(prob.system.scaleTerm)
     stamp = prob._modelStamp
+    nky, kyCoef = None, None
+    if perKy:
+        comp = prob.system.subProblems[0]
+        nky = len(comp.subProblems)
+        kyCoef = [comp._kyCoefficients(ky) for ky in range(nky)]
     if not owned:
-        return DeviceFields(sv.nfreq, nsrc, [], [], None if dtype == 'complex128' else [], stamp, scale, dtype)
+        return DeviceFields(sv.nfreq, nsrc, [], [], None if dtype == 'complex128' else [], stamp, scale, dtype, nky=nky, kyCoef=kyCoef)
     qf = sv.getSources()
     devs, items = deviceItems(prob.system, owned, nsrc)
     packed = dtype == 'complex64'
     esize = 8 if packed else 16
-    # what every GPU has to hold: its slices (and exponents), and the largest working set of an item there (R; U as well when the store is packed)
-    _checkItemsFit(items, held=lambda op, c0, c1: (c1 - c0) * (int(op.nrow) * esize + (4 if packed else 0)),
+    blocks = nky if perKy else 1
+    # what every GPU has to hold: its slices (and exponents), nky blocks of them in a per-ky store, and the largest working set of an item there (R; U as well
+    # when the store is packed)
+    _checkItemsFit(items, held=lambda op, c0, c1: blocks * (c1 - c0) * (int(op.nrow) * esize + (4 if packed else 0)),
                    work=lambda op, c0, c1: (c1 - c0) * int(op.nrow) * 16 * (2 if packed else 1))
     tdtype = torch.complex64 if packed else torch.complex128
-    slices = [torch.empty((c1 - c0, int(op.nrow)), dtype=tdtype, device=torch.device('cuda', op.device)) for _, op, _, c0, c1 in items]
-    exps = [torch.empty(c1 - c0, dtype=torch.int32, device=sl.device) for sl, (_, _, _, c0, c1) in zip(slices, items)] if packed else None
-    F = DeviceFields(sv.nfreq, nsrc, [(w, op.device, ifreq, c0, c1) for w, op, ifreq, c0, c1 in items], slices, exps, stamp, scale, dtype)
+    lead = (nky,) if perKy else ()
+    slices = [torch.empty(lead + (c1 - c0, int(op.nrow)), dtype=tdtype, device=torch.device('cuda', op.device)) for _, op, _, c0, c1 in items]
+    exps = [torch.empty(lead + (c1 - c0,), dtype=torch.int32, device=sl.device) for sl, (_, _, _, c0, c1) in zip(slices, items)] if packed else None
+    F = DeviceFields(sv.nfreq, nsrc, [(w, op.device, ifreq, c0, c1) for w, op, ifreq, c0, c1 in items], slices, exps, stamp, scale, dtype, nky=nky, kyCoef=kyCoef)
 
     def one(ws, op, ifreq, c0, c1):
         k, Ni = c1 - c0, int(op.nrow)
         sl, ex = F.slice(ifreq, c0)
         R = ws.buffer('R', k * Ni)
         _expandColumns(op, qf, ifreq, c0, c1, R)
+        U = ws.buffer('U', k * Ni) if packed and perKy else None
         _lib.wait_torch_stream(ws.device)
-        if not packed:
+        if perKy:
+            def each(ky, sub):
+                d_u, d_exp = F.pointers(ifreq, c0, ky)
+                if not packed:
+                    sub.solveDevice(R.data_ptr(), d_u, k, Ni)
+                else:
+                    sub.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+                    sub.packDevice(U.data_ptr(), k, d_u, d_exp, rows=Ni)
+            op._kyLoop(each)
+        elif not packed:
             op.solveDevice(R.data_ptr(), sl.data_ptr(), k, Ni)           # (no copy: the solve's output IS the slice)
         else:
             U = ws.buffer('U', k * Ni)
@@ -527,7 +551,7 @@ def fields(prob, owned, dtype='complex128'):
 def dpredFromFields(prob, F):
     """Predicted data (nrec, nsrc, nfreq) from forward fields already in HBM: no solve, every item samples its slice of the store (row stride 0 for a fixed
     array, nrec for one that moves with the source) and only the receiver samples come back."""
-    F.checkCurrent(prob)
+    F.checkCurrent(prob, perKy=None)
     data, stage, sample = _sampling(prob, F.ownedFreqs, F.scale)
     if not F.items:
         return data
@@ -536,14 +560,40 @@ def dpredFromFields(prob, F):
     def one(ws, op, ifreq, c0, c1):
         staged = stage(ws, ifreq, c0, c1)
         _lib.wait_torch_stream(ws.device)
+        if F.nky is not None:
+            # a per-ky store: the samples of every block accumulated with the composite's coefficients -- sampling is linear, the summed field is never formed
+            sub = op._liveSub()
+            for ky, (a, b) in enumerate(F.kyCoef):
+                _sampleAccumulate(sub, *F.pointers(ifreq, c0, ky), c1 - c0, int(op.nrow), staged[0], staged[1], a, b)
+            if op.kyRelease:
+                del sub.factors
+            sample(op, ifreq, c0, c1, staged, None)
+            return
         sample(op, ifreq, c0, c1, staged, *F.pointers(ifreq, c0))
     runOnDevices(devs, items, one, factor=False)
     return data
 
 
+def _sampleAccumulate(sub, d_u, d_exp, k, rows, csr, out, alpha, beta):
+    """out (nrec, k) = alpha R u + beta out for the k columns at d_u (d_exp: the exponents of a complex64 block, or None), csr as `_csrOnDevice` made it; beta 0:
+    `out` need not be initialised.  Returns when the samples are there."""
+    import ctypes
+    lib = _lib.load()
+    rowptr, col, val, nrec = csr[:4]
+    stride = int(csr[4]) if len(csr) > 4 else 0
+    a, b = complex(alpha), complex(beta)
+    tail = (int(k), int(rows), ctypes.c_void_p(rowptr.data_ptr()), ctypes.c_void_p(col.data_ptr()), ctypes.c_void_p(val.data_ptr()), int(nrec), stride,
+            a.real, a.imag, b.real, b.imag, ctypes.c_void_p(out.data_ptr()))
+    if d_exp is not None:
+        _lib.check(lib.helm_sample_rows_c64_device(sub.handle, ctypes.c_void_p(d_u), ctypes.c_void_p(d_exp), *tail), sub.handle)
+    else:
+        _lib.check(lib.helm_sample_rows_device(sub.handle, ctypes.c_void_p(d_u), *tail), sub.handle)
+
+
 def _factorBytes(op):
     """What the direct factors of one 2-D operator of op's grid take in device memory, from the elimination-tree plan (host only): per front the inverse of
-    its s x s pivot block and the two s x m coupling blocks, 16 B per entry.  A 2.5-D composite keeps one set per ky unless it releases them as it goes."""
+    its s x s pivot block and the two s x m coupling blocks, 16 B per entry.  A 2.5-D composite keeps one set per ky; one that releases its ky operators as it
+    goes (kyRelease) holds two groups of its ky loop at the most, the one being solved and the one prefactored ahead (minizephyr.ky_schedule)."""
     import ctypes
     lib = _lib.load()
     nz, nx, leaf = int(op.nz), int(op.nx), int(_lib.tuning().nd_leaf)
@@ -556,21 +606,31 @@ def _factorBytes(op):
     sm = plan[:, 6].astype(np.int64), plan[:, 7].astype(np.int64)
     one = int(16 * np.sum(sm[0] * (sm[0] + 2 * sm[1])))
     subs = getattr(op, 'subProblems', None)
-    return one * (len(subs) if subs is not None and not getattr(op, 'kyRelease', False) else 1)
+    if subs is None:
+        return one
+    from .minizephyr import KY_GROUP
+    return one * (min(len(subs), 2 * KY_GROUP) if getattr(op, 'kyRelease', False) else len(subs))
 
 
-def _checkSecondFactorsFit(items, planes=0, cols=None, blocks=2):
+def _checkSecondFactorsFit(items, planes=0, cols=None, blocks=2, beside=None):
     """MemoryError unless every GPU has room for what a pass through the TRANSPOSED operators adds to a resident forward pass: their factors -- the factors of
     A and of A^T are held side by side -- and the item's U and R (planes: and that many model-sized complex128 planes, the lag products of parameter='rho';
     cols: the columns solved per item where they are not the item's own, the receiver columns of kind='gaussNewton'; blocks: the column blocks of an item where
-    they are more than U and R, the four of `newtonFromFields`)"""
+    they are more than U and R, the four of `newtonFromFields`; beside: {(ifreq, c0): the forward operator an item solves with as well} where the forward
+    factors may not be resident either -- u=None of the 2.5-D routes, which walks A_ky and A_ky^T together: 2 nky factor sets per frequency, two groups of each
+    with kyRelease)"""
     seen = set()
 
-    def factors(op, c0, c1):
+    def unmade(op):
         'the factors an operator has yet to make, counted with its first item'
         first = id(op) not in seen
         seen.add(id(op))
         return _factorBytes(op) if first and not op.factors and str(getattr(op, 'method', 'auto')).lower() in ('auto', 'direct') else 0
+    partner = {} if beside is None else {id(op): beside[(ifreq, c0)] for _, op, ifreq, c0, _ in items}
+
+    def factors(op, c0, c1):
+        other = partner.get(id(op))
+        return unmade(op) + (unmade(other) if other is not None else 0)
     _checkItemsFit(items, held=factors, work=lambda op, c0, c1: (blocks * (c1 - c0 if cols is None else cols) + planes) * int(op.nrow) * 16)
 
 
@@ -831,6 +891,150 @@ def jointGradientFromFields(prob, F, qb, resid, system, linearisation):
         else:
             op.massAdjointDevice(P.data_ptr(), w, G.data_ptr(), conj=True)
         op.buoyancyAdjointDevice(P.data_ptr(), w, G.data_ptr() + 16 * N, conj=True)
+    wss = runOnDevices(devs, items, one)
+    return _sumPartials(prob, [ws.G for ws in wss if ws.G is not None], n=2 * N).real
+
+
+# ---- 2.5-D problems: the exact derivatives from the per-ky store -------------------------------------------------------------------------------------
+# The operator of an item is a MiniZephyr25D composite and the store holds the unscaled solves of every ky operator in a block of its own (`fields(perKy=True)`).
+# The derivative of the data is a sum over ky of the 2-D expressions of the SAME ky, so the two pipelines below are the item bodies of `_bornPlanesFromFields` and
+# of `jointGradientFromFields` with a ky loop inside the item: the composite's own `_kyLoop` (ascending ky, the factorisations of the next group of ky operators
+# enqueued one group ahead of their solves, a ky operator destroyed after its step with kyRelease).  Every kernel runs on the ky operator's handle, which carries
+# its ky; its premul is the quadrature weight.  What crosses PCIe per item is what the 2-D item moves; nothing crosses per ky.
+
+def _kyTotalScale(F):
+    "the wrapper's scale term times the composite's own: what multiplies the unscaled per-ky solves of a per-ky store"
+    return F.scale * F.kyCoef[-1][0]
+
+
+def liveKyFields(prob):
+    """What stands for the per-ky store with u=None: the items `fields(perKy=True)` would deal and the composite's coefficients, nothing allocated
+    (fieldstore.LiveKyFields).  Made on the calling thread: the survey caches its sources."""
+    from .fieldstore import LiveKyFields
+    sv = prob.survey
+    comp = prob.system.subProblems[0]
+    nky = len(comp.subProblems)
+    owned = prob.ownedFreqs
+    items = deviceItems(prob.system, owned, sv.nsrc)[1] if owned else []
+    return LiveKyFields(sv.nfreq, sv.nsrc, [(w, op.device, ifreq, c0, c1) for w, op, ifreq, c0, c1 in items], prob._modelStamp, complex(prob.system.scaleTerm), nky,
+                        [comp._kyCoefficients(ky) for ky in range(nky)], sv.getSources())
+
+
+def _kyLoopBoth(op, fop, each):
+    """each(ky, sub, fsub) over the ky operators of the transposed composite `op` and of the forward composite `fop` together, in the order of ky_schedule: the
+    factorisations of A_ky^T and of A_ky enqueued one group ahead of their solves; kyRelease destroys both after the step"""
+    from .discretization import prefactor_many
+    from .minizephyr import KY_GROUP, ky_schedule
+    subs, fsubs = op.subProblems, fop.subProblems
+    for step, arg in ky_schedule(len(subs), KY_GROUP):
+        if step == 'prefactor':
+            prefactor_many([subs[ky] for ky in arg])
+            prefactor_many([fsubs[ky] for ky in arg])
+        else:
+            each(arg, subs[arg], fsubs[arg])
+            if op.kyRelease:
+                del subs[arg].factors
+                del fsubs[arg].factors
+
+
+def kyBornFromFields(prob, F, dc, db, stretch):
+    """prob.JvecBorn(u=FK, linearisation='operator' | 'full') of a 2.5-D problem: the derivative of dpred along the velocity perturbation dc and the buoyancy
+    perturbation db ((N,) float64, either may be None).  Per stored item and ky: the planes V_ky[dc] (stretch False: k_mass_planes) + L_ky[db] from the ky handle,
+    k_stencil_sources on the block of that ky, the solve through A_ky, and the receiver samples accumulated into the item's nrec x k result on the device.  One
+    download per item."""
+    F.checkCurrent(prob, perKy=True)
+    data, stage, sample = _sampling(prob, F.ownedFreqs, _kyTotalScale(F))
+    if not F.items:
+        return data
+    db = None if db is None else np.ascontiguousarray(db, dtype=np.float64)
+    dc = None if dc is None else np.ascontiguousarray(dc, dtype=np.float64)
+    devs, items = _storedItems(prob.system, F)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        dev = ws.device
+        staged = stage(ws, ifreq, c0, c1)
+        dbd = None if db is None else ws.cached(('born_db', id(db)), lambda: _lib.to_device(db, dev, np.float64), keep=db)
+        dcd = None if dc is None else ws.cached(('born_dc', id(dc)), lambda: _lib.to_device(dc, dev, np.float64), keep=dc)
+        U, R, C = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni), ws.buffer('planes', 9 * Ni)
+        spare = ws.buffer('lags', 9 * Ni) if (not stretch and dcd is not None and dbd is not None) else None
+        if F.live:          # (u = None: the source columns once per item, the forward fields of a ky solved into the workspace just before they are used)
+            Q, UF = ws.buffer('Q', k * Ni), ws.buffer('UF', k * Ni)
+            _expandColumns(op, F.qf, ifreq, c0, c1, Q)
+        _lib.wait_torch_stream(dev)
+
+        def each(ky, sub):
+            if F.live:
+                sub.solveDevice(Q.data_ptr(), UF.data_ptr(), k, Ni)
+                d_uF, d_exp = UF.data_ptr(), None
+            else:
+                d_uF, d_exp = F.pointers(ifreq, c0, ky)
+            if dcd is None:
+                sub.buoyancyPlanesDevice(dbd.data_ptr(), C.data_ptr())
+            elif stretch:
+                sub.velocityPlanesDevice(dcd.data_ptr(), None if dbd is None else dbd.data_ptr(), C.data_ptr())
+            elif dbd is None:
+                sub.massPlanesDevice(dcd.data_ptr(), C.data_ptr())
+            else:
+                _jointPlanes(ws, sub, dcd, dbd, C, False, spare)
+            sub.stencilSourcesDevice(d_uF, k, C.data_ptr(), -1.0 / complex(sub.premul), R.data_ptr(), conj=True, d_exp=d_exp, rows=Ni)
+            sub.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+            _sampleAccumulate(sub, U.data_ptr(), None, k, Ni, staged[0], staged[1], 1.0, 0.0 if ky == 0 else 1.0)
+        op._kyLoop(each)
+        sample(op, ifreq, c0, c1, staged, None)
+    runOnDevices(devs, items, one)
+    return data
+
+
+def kyGradientFromFields(prob, F, qb, resid, system, stretch, wantC, wantB):
+    """prob.Jtvec(u=FK, adjoint='transpose', linearisation='operator' | 'full') of a 2.5-D problem up to the real chains: [g_c; g_b], float64 (2 N,) (a half that
+    is not wanted stays zero).  Per stored item the back-sources are made ONCE -- they are the same for all ky --; per ky: the solve through A_ky^T (`system`, the
+    transposed composites), P zeroed, k_lag_imaging against the block of the SAME ky, and the transposes with the ky handle's parameters and
+    w = -st / conj(premul_ky) into the halves of the worker's partial (k_velocity_adjoint, the mass-only one with stretch False; k_buoyancy_adjoint).  One
+    all-reduce of the stacked vector where the frequencies are sharded."""
+    import torch
+    F.checkCurrent(prob, perKy=True)
+    sv = prob.survey
+    N = prob.nrow
+    scale = _kyTotalScale(F)
+    if not F.items:
+        return _sumPartials(prob, [], n=2 * N).real
+    _prepareBackSources(sv, qb, F.ownedFreqs)
+    devs, items = _storedItems(system, F)
+    forward = {(ifreq, c0): op for _, op, ifreq, c0, _ in _storedItems(prob.system, F)[1]} if F.live else None
+    _checkSecondFactorsFit(items, planes=9, blocks=4 if F.live else 2, beside=forward)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        G = _partial(ws, 'G', 2 * N, torch.complex128)
+        U, R, P = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni), ws.buffer('lags', 9 * Ni)
+        _backSources(ws, sv, op, qb, resid, ifreq, c0, c1, R.data_ptr(), Ni)
+        if F.live:          # (u = None: see kyBornFromFields; the forward fields come from the forward composite of the same frequency and batch, on the same GPU)
+            Q, UF = ws.buffer('Q', k * Ni), ws.buffer('UF', k * Ni)
+            _expandColumns(op, F.qf, ifreq, c0, c1, Q)
+        _lib.wait_torch_stream(ws.device)
+
+        def each(ky, sub, fsub=None):
+            if F.live:
+                fsub.solveDevice(Q.data_ptr(), UF.data_ptr(), k, Ni)
+                d_uF, d_exp = UF.data_ptr(), None
+            else:
+                d_uF, d_exp = F.pointers(ifreq, c0, ky)
+            P.zero_()
+            _lib.wait_torch_stream(ws.device)
+            sub.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+            sub.lagImagingAccumulateDevice(d_uF, U.data_ptr(), k, P.data_ptr(), d_exp=d_exp, rows=Ni)
+            w = -scale / np.conj(complex(sub.premul))
+            if wantC and stretch:
+                sub.velocityAdjointDevice(P.data_ptr(), w, G.data_ptr(), conj=True)
+            elif wantC:
+                sub.massAdjointDevice(P.data_ptr(), w, G.data_ptr(), conj=True)
+            if wantB:
+                sub.buoyancyAdjointDevice(P.data_ptr(), w, G.data_ptr() + 16 * N, conj=True)
+        if F.live:
+            _kyLoopBoth(op, forward[(ifreq, c0)], each)
+        else:
+            op._kyLoop(each)
     wss = runOnDevices(devs, items, one)
     return _sumPartials(prob, [ws.G for ws in wss if ws.G is not None], n=2 * N).real
 

@@ -64,6 +64,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         'fieldsDtype':      (False,    '_fieldsDtype', str),      # what fieldsDevice() keeps: 'complex128' (default) or 'complex64' (half the memory)
         'eurusDerivatives': (False,    '_eurusDerivatives', bool),    # an Eurus problem (eps == delta) serves the exact adjoint and the exact derivatives through M1^T
         'viscoDerivatives': (False,    '_viscoDerivatives', bool),    # a visco problem serves the exact derivatives ('operator' / 'full') through the chain from (c, Q)
+        'kyDerivatives':    (False,    '_kyDerivatives', bool),       # a 2.5-D problem serves the exact derivatives from the forward fields kept PER ky (fieldsDevice(perKy=True))
     }
 
     surveyPair = HelmBaseSurvey
@@ -199,11 +200,24 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         qf = self.survey.getSources()
         return (u for _, u in self._solveOwned(qf))
 
-    def fields(self, m=None):
-        'list of forward wavefields for ALL frequencies on this rank (no sharding), on the native grid (problem.py:181-191: post-processed)'
+    def _requirePerKy(self, what):
+        'perKy=True is the fields of a 2.5-D composite per cross-line wavenumber: ValueError on any other problem'
+        from .minizephyr import MiniZephyr25D
+        subs = self.system.subProblems
+        if not (subs and isinstance(subs[0], MiniZephyr25D)) or isinstance(self.survey, HelmMultiGridSurvey):
+            raise ValueError('%s(perKy=True) serves single-grid 2.5-D problems (MiniZephyr25D): %s has no ky axis'
+                             % (what, type(subs[0]).__name__ if subs else type(self.system).__name__))
+
+    def fields(self, m=None, perKy=False):
+        """list of forward wavefields for ALL frequencies on this rank (no sharding), on the native grid (problem.py:181-191: post-processed).
+        perKy (2.5-D problems): one (nky, N, nsrc) array per frequency, the fields of every cross-line wavenumber apart -- their sum over ky is the default's
+        entry -- what the exact derivatives of a 2.5-D problem take as host `u`."""
         self._requirePaired()
         self.updateModel(m)
         qf = self.survey.getSources()
+        if perKy:
+            self._requirePerKy('fields')
+            return [self._kyFieldsHost(i, device_survey._ofFrequency(qf, i)) for i in range(self.survey.nfreq)]
         return [pp(u) for u, pp in zip(self.system * qf, self.survey.postProcessors)]
 
     @property
@@ -211,18 +225,22 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         "config key: the number format of the store fieldsDevice() fills -- 'complex128' (default), or 'complex64' with one power-of-two scale per column"
         return getattr(self, '_fieldsDtype', 'complex128')
 
-    def fieldsDevice(self, m=None):
+    def fieldsDevice(self, m=None, perKy=False):
         """The forward wavefields of the owned frequencies, solved once and LEFT in HBM: a fieldstore.DeviceFields to hand to `survey.dpred(m, u=F)` and
         `Jtvec(m, v, u=F)`, which then solve nsrc columns per frequency between them and the back-propagation instead of re-solving the forward fields.
         `F[ifreq]` downloads what `fields()[ifreq]` would be.  Single-grid surveys (2-D, and 2.5-D with the ky sum on the device); without the device
-        path (no GPU, hostGradient, a host ky reduction) this raises and `fields()` is the route."""
+        path (no GPU, hostGradient, a host ky reduction) this raises and `fields()` is the route.
+        perKy (2.5-D problems; ValueError elsewhere): every ky of an item is solved into its own block of the item's slice, nky times the memory -- what the
+        exact derivatives of a 2.5-D problem (kyDerivatives=True) read; `dpred(u=)` forms the ky sum while sampling and `F[ifreq]` still downloads the sum."""
         self._requirePaired()
         self.updateModel(m)
+        if perKy:
+            self._requirePerKy('fieldsDevice')
         if isinstance(self.survey, HelmMultiGridSurvey):
             return device_survey.fields(self, [], self.fieldsDtype)            # (raises NotImplementedError with the reason)
         if not self._deviceGradientAvailable():
             raise RuntimeError('fieldsDevice needs the device path (GPU operators with solveDevice, no hostGradient, the ky sum on the device): use fields()')
-        return device_survey.fields(self, self.ownedFreqs, self.fieldsDtype)
+        return device_survey.fields(self, self.ownedFreqs, self.fieldsDtype, perKy=bool(perKy))
 
     # ---- sensitivity times vector ------------------------------------------------------------------------
     def Jvec(self, m=None, v=None, u=None):
@@ -300,6 +318,11 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         all from ONE back-propagation per source and frequency.  The derivative is with respect to Q itself (for 1 / Q multiply by -Q^2).  parameter='rho' is what
         it is above, at the complex velocity.  'Q' / 'cQ' with 'scaler' or on a problem without Q: ValueError; parameter='joint' and a config without `rho`
         (Gardner's density is not holomorphic in c~): NotImplementedError.  'scaler' on a visco problem stays the reference's weight.
+
+        A 2.5-D problem (Helm25DProblem over MiniZephyr25D, one grid, an explicit `cmin`) with 'operator' or 'full' is served when the config sets kyDerivatives=True
+        (opt-in; without the key it is refused as it always was): the data are st R sum_k conj(u^_k), so the gradient is a sum over ky of the expressions above
+        on ky sub-operator k and fields of the SAME ky, g = Re sum_f sum_k w_fk T_k^T lag(z_k, u^_k) with w_fk = -conj(st) / premul_k (`_JtvecKy`).  u is then the
+        per-ky store of fieldsDevice(perKy=True) (the ky-SUM store: ValueError), a host list of fields(perKy=True), or None.  'scaler' is unchanged.
         """
         self._requirePaired()
         if v is None:
@@ -511,7 +534,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
 
     def _requireFullLinearisation(self, what):
         """linearisation='full' serves Helm2DProblem with MiniZephyr / MiniZephyrHD on a single grid, with an explicit density or the default one -- and, with the
-        config key eurusDerivatives, Eurus / EurusHD where eps == delta (`_eurusServed`): everything else is refused here with the reason"""
+        config key eurusDerivatives, Eurus / EurusHD where eps == delta (`_eurusServed`), with the config key kyDerivatives the 2.5-D composite of MiniZephyr
+        operators (`_kyServed`): everything else is refused here with the reason"""
         from .minizephyr import MiniZephyr
         from .discretization import DiscretizationWrapper
         self._refuseMultiscale(what)
@@ -524,7 +548,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
                                       'holomorphic in the complex velocity c~, and the chain from (c, Q) runs through the holomorphic derivative' % (what,))
         sub = self.system.subProblems[0] if self.system.subProblems else None
         if sub is not None and isinstance(sub, DiscretizationWrapper):
-            raise NotImplementedError('%s does not serve the 2.5-D composite: the stored fields are the ky SUM, the exact derivative needs the fields per ky' % (what,))
+            if not getattr(self, '_kyDerivatives', False):
+                raise NotImplementedError('%s does not serve the 2.5-D composite: the stored fields are the ky SUM, the exact derivative needs the fields per ky' % (what,))
+            self._requireKyDerivatives(what, sub)
+            return
         if self._eurusServed():
             if not all(op.elliptical for op in self.system.subProblems):
                 raise NotImplementedError('%s on %s needs eps == delta in every cell: where they differ the two fields are coupled, and the coupled 2N x 2N system '
@@ -532,6 +559,130 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             return
         if sub is not None and not (isinstance(sub, MiniZephyr) and getattr(sub, 'ny', None) is None):
             raise NotImplementedError('%s serves the 2-D MiniZephyr operators: %s assembles its mass term differently' % (what, type(sub).__name__))
+
+    # ---- 2.5-D problems: the exact derivatives from the fields per ky ---------------------------------------------
+    # d = st R sum_k conj(u^_k), u^_k = A_k^-1 premul_k q, st the product of the wrapper's and the composite's scale terms: the derivative is a sum over ky of
+    # the 2-D expressions of the SAME ky -- the maps of frechet.py on the ky sub-operator (its ky and its premul, the quadrature weight) and the weight
+    # w_fk = -conj(st) / premul_k.  DESIGN.md 11t has the derivation with the conjugations written out.
+    def _kyServed(self):
+        'the config sets kyDerivatives=True and the operators are 2.5-D composites: the exact routes run per ky.  Without the key they are refused as they always were.'
+        from .discretization import DiscretizationWrapper
+        if not getattr(self, '_kyDerivatives', False):
+            return False
+        subs = self.system.subProblems
+        return bool(subs) and isinstance(subs[0], DiscretizationWrapper)
+
+    def _requireKyDerivatives(self, what, sub):
+        'what kyDerivatives=True does not serve, refused with the reason: visco composites, a cmin that follows the model, ky sub-operators other than 2-D MiniZephyr'
+        from .minizephyr import MiniZephyr, MiniZephyr25D
+        if self._isVisco():
+            raise NotImplementedError('%s with kyDerivatives does not serve visco problems (Helm25DViscoProblem): the chain from (c, Q) to the complex velocity is not '
+                                      'built into the per-ky routes' % (what,))
+        if self.systemConfig.get('cmin', None) is None:
+            raise NotImplementedError('%s with kyDerivatives needs an explicit `cmin` in the config: without one the cross-line wavenumbers follow min(c), the quadrature '
+                                      'nodes move with the model and the data are not differentiable in c' % (what,))
+        if not (isinstance(sub, MiniZephyr25D) and isinstance(sub.Disc, type) and issubclass(sub.Disc, MiniZephyr) and getattr(sub, 'ny', None) is None):
+            raise NotImplementedError('%s with kyDerivatives serves MiniZephyr25D over the 2-D MiniZephyr operators: %s assembles its mass term differently'
+                                      % (what, type(sub).__name__))
+
+    def _refuseKy(self, what, why):
+        if self._kyServed():
+            raise NotImplementedError('%s does not serve the 2.5-D composite: %s' % (what, why))
+
+    def _kyScale(self, ifreq):
+        "st of a frequency: the wrapper's scaleTerm times the composite's own (e^{i pi} / (4 pi) times the config's), which `_solveOwned` never shows apart"
+        return complex(self.system.scaleTerm) * complex(self.system.subProblems[ifreq].scaleTerm)
+
+    def _kyFieldsHost(self, ifreq, q):
+        """(nky, N, nsrc) complex128: the forward fields of frequency ifreq PER ky on the host, st * (sub_k * q) = st conj(u^_k) for every ky sub-operator --
+        their sum over ky is fields()[ifreq].  q: the frequency's source matrix."""
+        st = self._kyScale(ifreq)
+        return np.stack([st * np.asarray(sub * q) for sub in self.system.subProblems[ifreq].subProblems])
+
+    def _kyBlocks(self, F, ifreq):
+        '(nky, N, nsrc) of a host list of per-ky fields, checked: a list of ky SUMS is refused'
+        nky = len(self.system.subProblems[ifreq].subProblems)
+        Fk = np.asarray(F[ifreq])
+        if Fk.ndim != 3 or Fk.shape[0] != nky:
+            raise ValueError('the exact derivatives of a 2.5-D problem need the forward fields per ky, (nky, N, nsrc) per frequency: fields(perKy=True) / '
+                             'fieldsDevice(perKy=True), not the ky sum of shape %s' % (Fk.shape,))
+        return Fk
+
+    def _kyGradientHost(self, resid, F, adj, stretch, wantC, wantB):
+        """(g_c, g_b) complex (N,) each (None where not wanted), before the real part and the all-reduce: sum_f sum_k w_fk (V_k^T P_k, L_k^T P_k), P_k the nine lag
+        products of z_k = A_k^-T premul_k R^H r against u^_k of the SAME ky, w_fk = -conj(st) / premul_k; stretch False: the mass term of V alone"""
+        N = self.nrow
+        gc = np.zeros(N, dtype=np.complex128) if wantC else None
+        gb = np.zeros(N, dtype=np.complex128) if wantB else None
+        qb = [q.conj() for q in self.survey.getResidualSources(np.conj(resid))]
+        for ifreq in self.ownedFreqs:
+            st = self._kyScale(ifreq)
+            Fk = self._kyBlocks(F, ifreq)
+            for k, (sub, asub) in enumerate(zip(self.system.subProblems[ifreq].subProblems, adj.subProblems[ifreq].subProblems)):
+                z = np.conj(np.asarray(asub * qb[ifreq]))          # (sub * q is conj(A^-T premul q))
+                P = lagProducts(z, np.conj(Fk[k] / st), sub.nz, sub.nx)
+                w = -np.conj(st) / complex(sub.premul)
+                if wantC:
+                    gc += w * velocityAdjoint(sub, P, stretch=stretch)
+                if wantB:
+                    gb += w * buoyancyAdjoint(sub, P)
+        return gc, gb
+
+    def _JtvecKy(self, resid, u, linearisation, parameter):
+        """Jtvec(adjoint='transpose') of a 2.5-D problem with the resolved 'operator' or 'full' once the refusals are past: float64 (N,), or [g_c; g_rho] (2 N,) for
+        'joint', from ONE back-propagation per source, frequency and ky"""
+        stretch = linearisation == 'full'
+        chain = self._gardnerChain() if parameter == 'c' and stretch else None          # (the density follows c: the buoyancy gradient joins through d b / d c)
+        wantC, wantB = parameter in ('c', 'joint'), parameter in ('rho', 'joint') or chain is not None
+        adj = self.adjointSystem
+        N = self.nrow
+        with self._forwardFields(u, perKy=True) as F:
+            if isinstance(F, DeviceFields):
+                rd = self._hermitianResidual(resid)
+                g = device_survey.kyGradientFromFields(self, F, self._deviceBackSources(rd), rd, adj, stretch, wantC, wantB)
+                gc, gb = g[:N], g[N:]
+            else:
+                gc, gb = self._kyGradientHost(resid, F, adj, stretch, wantC, wantB)
+                g = np.concatenate([np.zeros(N) if x is None else x for x in (gc, gb)])
+                if self._sharded:
+                    g = parallel.allreduce_sum(g)
+                gc, gb = g[:N].real, g[N:].real
+        if parameter == 'joint':
+            return np.concatenate((gc, self._buoyancyChain() * gb))
+        if parameter == 'rho':
+            return self._buoyancyChain() * gb
+        return np.array(gc) if chain is None else gc + chain * gb
+
+    def _JvecBornKy(self, u, dc, db, stretch):
+        """JvecBorn of a 2.5-D problem with 'operator' or 'full' once the refusals are past: the planes V_k[dc] (stretch False: their mass term) + L_k[db] of every
+        ky sub-operator applied to u^_k of the SAME ky, solved through A_k and summed -- dc / db (N,) float64, either may be None.  (nrec, nsrc, nfreq)."""
+        sv = self.survey
+        with self._forwardFields(u, perKy=True) as F:
+            if isinstance(F, DeviceFields):
+                return device_survey.kyBornFromFields(self, F, dc, db, stretch)
+            data = np.zeros((sv.nrec, sv.nsrc, sv.nfreq), dtype=np.complex128)
+
+            def planes(sub):
+                if dc is None:
+                    return buoyancyPlanes(sub, db)
+                if stretch:
+                    return velocityPlanes(sub, dc, db)
+                return massPlanes(sub, dc) if db is None else massPlanes(sub, dc) + buoyancyPlanes(sub, db)
+            for ifreq in self.ownedFreqs:
+                st = self._kyScale(ifreq)
+                Fk = self._kyBlocks(F, ifreq)
+                uB = None
+                for k, sub in enumerate(self.system.subProblems[ifreq].subProblems):
+                    qv = applyPlanes(planes(sub), np.conj(Fk[k] / st), sub.nz, sub.nx) / -complex(sub.premul)
+                    uk = np.asarray(sub * qv)
+                    uB = uk if uB is None else uB + uk
+                uB = st * uB
+                if sv.mode == 'fixed':
+                    data[:, :, ifreq] = sv.rVec(0, ifreq) * uB
+                else:
+                    for isrc in range(sv.nsrc):
+                        data[:, isrc, ifreq] = sv.rVec(isrc, ifreq) * uB[:, isrc]
+        return data
 
     def _eurusServed(self):
         """the config sets eurusDerivatives=True and the operators are 2-D Eurus / EurusHD on one grid: the exact adjoint and the exact derivatives run through M1^T
@@ -615,21 +766,30 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         return resid * ph[:, None, None]
 
     @contextlib.contextmanager
-    def _forwardFields(self, u):
+    def _forwardFields(self, u, perKy=False):
         """`with self._forwardFields(u) as F`: what the exact-adjoint routes read the forward fields from -- a DeviceFields as it is (checked), a list of host
         arrays as a list, None -> a DeviceFields solved now where the device path serves, released when the block is left whatever happened in it, else a
-        host list with the owned frequencies' fields (None elsewhere)."""
+        host list with the owned frequencies' fields (None elsewhere).  perKy (the exact routes of a 2.5-D problem): the fields of every ky apart -- a store of
+        fieldsDevice(perKy=True) (the ky-SUM store is refused with ValueError), or a host list of (nky, N, nsrc) arrays."""
         if isinstance(u, DeviceFields):
-            u.checkCurrent(self)
+            u.checkCurrent(self, perKy=perKy)
             yield u
         elif u is not None:
             yield list(u)
+        elif perKy and self._deviceGradientAvailable():
+            yield device_survey.liveKyFields(self)          # (no store: the pipelines solve the fields of a ky into their workspace just before they use them)
         elif self._deviceGradientAvailable():
             F = self.fieldsDevice()
             try:
                 yield F
             finally:
                 F.release()
+        elif perKy:
+            uF = [None] * self.survey.nfreq
+            qf = self.survey.getSources()
+            for ifreq in self.ownedFreqs:
+                uF[ifreq] = self._kyFieldsHost(ifreq, device_survey._ofFrequency(qf, ifreq))
+            yield uF
         else:
             uF = [None] * self.survey.nfreq
             pps = self.survey.postProcessors
@@ -647,6 +807,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         "Jtvec(adjoint='transpose') once the model is current and `resid` is (nrec, nsrc, nfreq)"
         self._refuseMultiscale("Jtvec(adjoint='transpose')")
         linearisation = self._resolveLinearisation(linearisation, parameter, 'Jtvec')
+        if linearisation != 'scaler' and self._kyServed():
+            return self._JtvecKy(resid, u, linearisation, parameter)
         if parameter == 'joint':
             return self._JtvecJoint(resid, u, linearisation)
         if linearisation != 'scaler' and parameter in ('c', 'Q', 'cQ') and self._isVisco():
@@ -815,6 +977,12 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             pert = np.asarray(pert, dtype=np.float64)
             chain = self._gardnerChain()
             db = None if chain is None else chain * pert                                # (the buoyancy perturbation that goes with v: the density follows c)
+        if exact and self._kyServed():
+            if density:
+                data = self._JvecBornKy(u, None, pert, False)
+            else:
+                data = self._JvecBornKy(u, np.asarray(pert, dtype=np.float64), db if (joint or full) else None, full)
+            return (parallel.allreduce_sum(data) if self._sharded else data).ravel()
         with self._forwardFields(u) as F:
             if isinstance(F, DeviceFields):
                 if joint:
@@ -936,6 +1104,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             raise NotImplementedError('Hvec(resid=) does not serve visco problems: the second derivative of the chain from (c, Q) to the complex velocity, '
                                       'd^2 c~ / dQ^2 and d^2 c~ / dc dQ, is not built (resid=None, the Gauss-Newton product, is served)')
         if resid is not None:
+            self._refuseKy('Hvec(resid=)', 'the second derivative of the ky operators and the third solve per ky are not built into the per-ky routes (resid=None, the '
+                                           'Gauss-Newton product, is served)')
             self._refuseEurus('Hvec(resid=)', 'the second derivative of M1 and the transposed application of its planes are not built (resid=None, the Gauss-Newton '
                                               'product, is served)')
             if pin != pout:
@@ -949,7 +1119,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             resid = resid.astype(np.complex128).reshape((self.survey.nrec, self.survey.nsrc, self.survey.nfreq))
             return self._HvecNewton(np.asarray(v, dtype=np.float64).reshape((2 * self.nrow if joint else self.nrow,)), u, resid,
                                     self._resolveLinearisation(linearisation, pin, 'Hvec'), pin)
-        with self._forwardFields(u) as F:
+        with self._forwardFields(u, perKy=linearisation != 'scaler' and self._kyServed()) as F:
             d = self.JvecBorn(None, v, u=F, linearisation=linearisation, parameter=pin)
             if weights is not None:
                 d = d * weights
@@ -1095,10 +1265,13 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         self.updateModel(m)
         if kind == 'gaussNewton' and linearisation == 'scaler':
             self._requireFullLinearisation('illumination(linearisation=\'scaler\')')      # (this kind needs the transposed 2-D operator whatever the linearisation)
+            self._refuseKy('illumination(kind=\'gaussNewton\')', 'the Hessian diagonals are not built per ky (the \'scaler\' kinds \'energy\' and \'pseudoHessian\' are served)')
             self._refuseEurus('illumination(kind=\'gaussNewton\')', 'the Hessian diagonals are not built on the derivative maps of M1')
             self._refuseViscoDiagonal('illumination(linearisation=\'scaler\')')
         if linearisation != 'scaler':
             resolved = self._resolveLinearisation(linearisation, parameter, 'illumination')
+            self._refuseKy('illumination(linearisation=%r)' % (linearisation,), 'the Hessian diagonals are not built per ky (the \'scaler\' kinds \'energy\' and '
+                                                                                 '\'pseudoHessian\' are served)')
             self._refuseEurus('illumination(linearisation=%r)' % (linearisation,), 'the Hessian diagonals are not built on the derivative maps of M1 (the '
                                                                                     '\'scaler\' kinds \'energy\' and \'pseudoHessian\' are served)')
             self._refuseViscoDiagonal('illumination(linearisation=%r)' % (linearisation,))
@@ -1211,6 +1384,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
                 raise ValueError('the receiver-side blocks serve fixed receiver arrays (mode is %r)' % (sv.mode,))
         self.updateModel(m)
         linearisation = self._resolveLinearisation(linearisation, 'joint', 'hessianBlocks')
+        self._refuseKy('hessianBlocks', 'the per-cell blocks of the joint Hessian are not built per ky')
         self._refuseEurus('hessianBlocks', 'the per-cell blocks of the joint Hessian are not built on the derivative maps of M1')
         if kind == 'gaussNewton' and sv.mode != 'fixed':
             raise ValueError('kind=\'gaussNewton\' serves fixed receiver arrays (mode is %r): with an array that moves with the source the sum over '
