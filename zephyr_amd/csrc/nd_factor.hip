@@ -11,9 +11,11 @@
 //   front     [separator cells | ring of cells around the subtree's region] -- the ring cells are exactly the
 //             ancestors' separator cells the subtree touches.  Index <-> cell maps are closed-form (nd_local /
 //             nd_cell, direct.hpp), so no index lists are stored.
-//   factor    a front is written once in gather form (k_nd_build_front: stencil entries + the children's Schur complements);
-//             F11^-1 in place (nd_gj.hip), G21 = F21 F11^-1, Schur complement S = F22 - G21 F12 gathered by the product that
-//             forms it (nd_gemm.hip, IDX 4); the leaf level in one kernel straight from the coefficient planes (nd_leaf.hip);
+//   factor    a front is formed in gather form (stencil entries + the children's Schur complements), each block by the kernel that needs it:
+//             [F11 | F12] by k_nd_build_front, F11^-1 in place (nd_gj.hip); F21 by the product G21 = F21 F11^-1 that is its only reader
+//             (nd_gemm.hip, IDX 3; separators above HELM_ND_GATHER21_SMAX cells: written by the build pass and read back); F22 by the
+//             product that forms the Schur complement S = F22 - G21 F12 (IDX 4); the leaf level in one kernel straight from the
+//             coefficient planes, the small separator levels likewise (nd_leaf.hip);
 //             fronts whose F11 is too ill-conditioned for an explicit inverse are eliminated again with a pivoted LU (NdStable).
 //   solve     forward: front-local vectors travel up the tree exactly like the Schur complements;
 //             backward: x_S = F11^-1 (y_S - F12 x_B), top-down.  Pure GEMMs on node-major right-hand sides
@@ -105,6 +107,8 @@ __global__ __launch_bounds__(256) void k_nd_extend_add(const NdDev *nodes, int f
     }
 }
 
+// What builds which block of a front: [F11 | F12] -- this kernel, always; F21 -- this kernel, or the product G21 = F21 F11^-1 that is its only reader
+// (GemmRows::gather21, separator fronts up to HELM_ND_GATHER21_SMAX cells); F22 -- this kernel, or the Schur-complement product (GemmRows::schur4).
 // One pass that WRITES every entry of a front exactly once (gather form of k_nd_assemble + the two k_nd_extend_add + the three
 // memsets they needed):  entry (r, c) = [stencil coefficient of the two cells, unless both lie on the ring]
 //                                       + child 0's Schur complement entry + child 1's, where both cells lie on that child's ring
@@ -126,8 +130,9 @@ __global__ __launch_bounds__(256) void k_nd_build_front(const NdDev *nodes, int 
     NdDev n;
     if (OVR) n = ovr; else n = nodes[first + (kfix >= 0 ? blockIdx.y : blockIdx.y / nf)];
     const int nmax = n.smax + n.mmax;
+    const int rend = skip22 == 2 ? n.smax : nmax;          // (skip22 == 2: the rows of [F11 | F12] alone)
     const int r0 = blockIdx.x * rb;
-    if (r0 >= nmax) return;
+    if (r0 >= rend) return;
     const bool h0 = n.kid[0] >= 0, h1 = n.kid[1] >= 0;
     NdDev c0 = NdDev(), c1 = NdDev();
     if (h0) c0 = nodes[n.kid[0]];
@@ -154,7 +159,7 @@ __global__ __launch_bounds__(256) void k_nd_build_front(const NdDev *nodes, int 
     const int ld0 = c0.smax + c0.mmax, ld1 = c1.smax + c1.mmax;
     const cplx *S0 = h0 ? arenaF + mf_off(c0.foff, (long long)c0.mmax * ld0, nf, kf) + c0.smax : nullptr;
     const cplx *S1 = h1 ? arenaF + mf_off(c1.foff, (long long)c1.mmax * ld1, nf, kf) + c1.smax : nullptr;
-    const int r1 = r0 + rb < nmax ? r0 + rb : nmax;
+    const int r1 = r0 + rb < rend ? r0 + rb : rend;
     const int tx = tid & 63, ty = tid >> 6;
     const bool colmode = n.dof > 2;
     // entry (r, c) of the front from the row table: stencil coefficient + the two children's Schur-complement entries
@@ -184,6 +189,9 @@ __global__ __launch_bounds__(256) void k_nd_build_front(const NdDev *nodes, int 
     };
     // skip22: the ring x ring block (the sum of the children's Schur complements, most of a front below the tree top) is not
     // materialised -- the Schur-complement product gathers it itself (k_zgemm3<.., 4, ..>) and writes S where F22 would have been.
+    // skip22 == 2: nor is the ring x separator block F21 -- its one reader, the product G21 = F21 F11^-1, gathers it (k_zgemm3<.., 3, ..>), and the
+    // launch covers the smax rows of [F11 | F12] only.  The F21 slots of the arena then stay unwritten; a front that is eliminated again (NdStable)
+    // is rebuilt whole (skip22 = 0) before its F21 is taken from there.
     // One entry per lane at a time, 40 registers: eight waves per SIMD cover the gathers' latency.  (Round 5 also gathered four entries per lane before storing
     // any; beside the register blow-up described at the top of the kernel that form measured 2 % ahead of this loop, A/B in one binary -- not worth a second path.)
     for (int r = r0 + ty; r < r1; r += 4) {
@@ -701,7 +709,7 @@ int factor_group_set(helm_op *op, const FacSet &S, size_t gi, cplx *arenaF, cplx
         return HELM_OK;
     }
     // the ring x ring block of a non-leaf front stays unbuilt: its Schur-complement product gathers the children's contributions itself
-    bool schur_gather = false;
+    bool schur_gather = false, gather21 = false;
     const bool packs = P.dof <= 2 ? (nmax < (1 << 14) && P.nz < 65536 && P.nx < 32768) : (nmax < 65535 && P.nz < 4096 && P.nx < 4096 && P.dof < 128);
     if ((size_t)nmax * sizeof(int2) <= 64 * 1024 && packs)
         schur_gather = !g.leaf && g.mmax > 0 && P.dof == 1;
@@ -735,15 +743,21 @@ int factor_group_set(helm_op *op, const FacSet &S, size_t gi, cplx *arenaF, cplx
         return HELM_OK;
     }
     if ((size_t)nmax * sizeof(int2) <= 64 * 1024 && packs) {      // (its row table must fit the 64 KB of LDS a launch gets by default: larger fronts take the unfused path)
+        // F21 unbuilt as well where the product G21 = F21 F11^-1 can gather it (HELM_ND_GATHER21, default 1; separators of at most HELM_ND_GATHER21_SMAX
+        // cells, 128 by default: every column tile of the product repeats the gather, and from 256 cells -- four tiles -- that costs what the build pass
+        // saves): the launch then covers the rows of [F11 | F12] only
+        gather21 = schur_gather && helm_env_int("HELM_ND_GATHER21", 1) != 0 && g.smax <= helm_env_int("HELM_ND_GATHER21_SMAX", ND_GATHER21_SMAX) &&
+                   gemm_gather21_ok(op, g.mmax, g.smax, g.smax, nbatch);
+        const int brows = gather21 ? g.smax : nmax;               // rows of the front the build pass writes
         // rows per workgroup: whole fronts while there are thousands of them, a few rows each for the handful of big ones at the top
         const int want = std::max(1, 2048 / g.cnt);
-        const int rb = std::max(std::min(nmax, 4), (nmax + want - 1) / want);
+        const int rb = std::max(std::min(brows, 4), (brows + want - 1) / want);
         NdPlanesSet ps; for (int k = 0; k < ND_NF_MAX; ++k) ps.p[k] = S.planes[k < nf ? k : 0];
         const int chunk = 65535 / nf;                             // fronts per launch (grid y = fronts x frequencies)
         for (int j0 = 0; j0 < g.cnt; j0 += chunk) {
             const int nb = std::min(chunk, g.cnt - j0);
-            HELM_LAUNCH(k_nd_build_front<false>, dim3((nmax + rb - 1) / rb, nb * nf), dim3(256), (size_t)nmax * sizeof(int2), st, d_nodes, g.first + j0, arenaF, f0->d_fac, ps,
-                               P.nz, P.nx, rb, schur_gather ? 1 : 0, NdDev(), nf, -1);
+            HELM_LAUNCH(k_nd_build_front<false>, dim3((brows + rb - 1) / rb, nb * nf), dim3(256), (size_t)nmax * sizeof(int2), st, d_nodes, g.first + j0, arenaF, f0->d_fac, ps,
+                               P.nz, P.nx, rb, gather21 ? 2 : (schur_gather ? 1 : 0), NdDev(), nf, -1);
         }
     } else {
         if (nf != 1) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "direct solver: fronts of %d unknowns take the unfused build, which factors one frequency at a time", nmax);
@@ -778,6 +792,13 @@ int factor_group_set(helm_op *op, const FacSet &S, size_t gi, cplx *arenaF, cplx
     if (watch) for (int k = 0; k < nf; ++k) { const int rcf = flag_group(op, S.f[k], gi, est, S.rtol[k]); if (rcf) return rcf; }      // (the lists travel while the products below run)
     if (g.mmax > 0) {
         // G21 = F21 F11^-1 ; F22 -= G21 F12
+        if (gather21) {
+            GemmRows R; R.gather21 = 1; R.nodes = d_nodes; R.first = g.first; R.arenaS = arenaF; R.tabCi = f0->pd->d_tab + g.roff; R.tab_stride = nmax; R.nf = nf;
+            R.nz = P.nz; R.nx = P.nx;
+            for (int k = 0; k < ND_NF_MAX; ++k) R.planes.p[k] = S.planes[k < nf ? k : 0];
+            const int rcg = gemm(op, g.mmax, g.smax, g.smax, one, F, nmax, fs, Finv, nmax, s1, zero, G21, g.smax, (long long)g.mmax * g.smax, nbatch, &R);
+            if (rcg) return rcg;
+        } else
         gemm(op, g.mmax, g.smax, g.smax, one, F, nmax, fs, Finv, nmax, s1, zero, G21, g.smax, (long long)g.mmax * g.smax, nbatch);
         if (schur_gather) {
             GemmRows R; R.schur4 = 1; R.nodes = d_nodes; R.first = g.first; R.arenaS = arenaF; R.tabCi = f0->pd->d_tab + g.roff; R.tab_stride = nmax; R.nf = nf;

@@ -39,6 +39,7 @@ void launch_mfma(hipStream_t st, int idx, int nb, int M, int Nn, int K, cplx alp
     constexpr int TM = 16 * MT * WM, TN = 16 * NT * WN;
     dim3 grid((Nn + TN - 1) / TN, (M + TM - 1) / TM, nb);
     if (idx == 4) ZG_LAUNCH((k_zgemm3<WM, WN, MT, NT, 4, KS, OCC>), grid, M, Nn, K, alpha, A, lda, sa, B, ldb, sb, beta, C, ldc, sc, R);
+    else if (idx == 3) ZG_LAUNCH((k_zgemm3<WM, WN, MT, NT, 3, KS, OCC>), grid, M, Nn, K, alpha, A, lda, sa, B, ldb, sb, beta, C, ldc, sc, R);
     else if (idx == 2) ZG_LAUNCH((k_zgemm3<WM, WN, MT, NT, 2, KS, OCC>), grid, M, Nn, K, alpha, A, lda, sa, B, ldb, sb, beta, C, ldc, sc, R);
     else if (idx) ZG_LAUNCH((k_zgemm3<WM, WN, MT, NT, 1, KS, OCC>), grid, M, Nn, K, alpha, A, lda, sa, B, ldb, sb, beta, C, ldc, sc, R);
     else ZG_LAUNCH((k_zgemm3<WM, WN, MT, NT, 0, KS, OCC>), grid, M, Nn, K, alpha, A, lda, sa, B, ldb, sb, beta, C, ldc, sc, R);
@@ -363,7 +364,10 @@ int gemm(helm_op *op, int M, int Nn, int K, cplx alpha, const cplx *A, int lda, 
     // partial product to the handle's scratch and a small launch adds them up (with alpha / beta applied there).
     // (measured on the 47 x 79 x 79 level: fewer than 96 tiles / 192 workgroups -> 5.8 ms per coarse solve, 300 / 768 -> 5.0, more changes nothing)
     bool split_done = false;
-    GemmChoice ch = gemm_choice(op != nullptr, ext, M, Nn, K, batch, rows);
+    // (an F21-gather launch takes whatever the dense call of its shape would: gemm_gather21_ok has seen to it that this is an unsplit plain tile)
+    const bool g21 = rows && rows->gather21;
+    GemmChoice ch = gemm_choice(op != nullptr, ext, M, Nn, K, batch, g21 ? nullptr : rows);
+    if (g21 && (ch.ksplit || ch.xr || K > G21_KCOL)) { helm_set_error(op, "direct solver: F21-gather product of a shape it does not exist for"); return HELM_ERR_STATE; }
     if (ch.ksplit) {
         const int ks = ch.ksplit, kc = ch.kc;
         const long long per = (long long)batch * M * Nn;
@@ -385,7 +389,7 @@ int gemm(helm_op *op, int M, int Nn, int K, cplx alpha, const cplx *A, int lda, 
     if (made) *made = ch;
     const bool latency_mode = ch.kslab == 16;
     const int vsel = ch.tile;
-    const int idxmode = rows && rows->schur4 ? 4 : (rows && !rows->dense ? (rows->fwd3 ? 2 : 1) : 0);
+    const int idxmode = rows && rows->schur4 ? 4 : (g21 ? 3 : (rows && !rows->dense ? (rows->fwd3 ? 2 : 1) : 0));
     const int xcd_map = g_gemm_xcd >= 0 ? g_gemm_xcd : helm_tuning_now().nd_xcd_map;
     for (int b0 = 0; b0 < batch && !split_done; b0 += 65535) {
         const int nb = std::min(65535, batch - b0);
@@ -394,7 +398,7 @@ int gemm(helm_op *op, int M, int Nn, int K, cplx alpha, const cplx *A, int lda, 
         R.xcd_map = xcd_map;
         // gathered products over many fronts (the row-table and forward-gather levels of both passes) store C with nontemporal stores: the rows are not read
         // again before a whole level has gone by (headline +1.5 %; the Schur complements, read back one level later: no difference either way)
-        if (rows && !rows->dense && !rows->schur4 && nb >= 64) R.ntc = 1;
+        if (rows && !rows->dense && !rows->schur4 && !g21 && nb >= 64) R.ntc = 1;
         const cplx *Ab = A + b0 * sa, *Bb = B ? B + b0 * sb : B;
         cplx *Cb = C ? C + b0 * sc : C;
         // leaf back substitution on sparse right-hand sides: the (leaf, block of 64 columns) pairs without a right-hand side go to k_leaf_bwd_idle
@@ -446,6 +450,13 @@ int gemm(helm_op *op, int M, int Nn, int K, cplx alpha, const cplx *A, int lda, 
         op->ev_used += 2;
     }
     return 0;
+}
+
+bool gemm_gather21_ok(helm_op *op, int M, int Nn, int K, int batch) {
+    if (K > G21_KCOL || M <= 0 || Nn <= 0 || batch <= 0) return false;
+    const bool ext = op && op->profiling && helm_tuning_now().prof_ext != 0;
+    const GemmChoice ch = gemm_choice(op != nullptr, ext, M, Nn, K, batch, nullptr);
+    return !ch.ksplit && !ch.xr;
 }
 
 // Back substitution of a group of small separator fronts in one launch (k_sep_bwd_small); false: not a case for it, the caller issues the two products.

@@ -20,7 +20,8 @@
 //             fragment is XOR-swizzled with (k & 3) ^ 4 (k / 4 & 1) so that those 8 lanes hit 8 different 16-byte bank groups on the
 //             store and the 16-lane groups of ds_read_b128 still cover all 64 banks on the load.
 //   C / D     lane l holds rows (l >> 4) + 4 q, q = 0..3, of column l & 15: a store is four 256-byte row segments.
-// Addressing modes (IDX), masks, split-K and the fused gathers are those of zgemm2_body, operand for operand.
+// Addressing modes (IDX), masks, split-K and the fused gathers are those of zgemm2_body, operand for operand (IDX 3, the gathered A operand, came later:
+// nd_internal.hpp lists the modes).
 static __device__ cplx g_zero_page[4];       // 64 bytes of zeros: what masked lanes load instead of branching around a load
 // XR = 1 (WM == 1 only): the tile has ONE more row than its 16 MT rows of matrix-core blocks -- row 16 MT goes through the vector ALUs, which the
 // MFMA loop leaves idle (thread = column x share of the k range, partial sums added up through LDS at the end).  98 % of the leaves of a 2^k grid
@@ -74,7 +75,7 @@ __device__ __forceinline__ void zgemm3_body(int M, int Nn, int K, cplx alpha, co
     const int m0 = byi * TM, n0 = bxi * TN;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int wm = wave / WN, wn = wave % WN, lr = lane & 15, lq = lane >> 4;
-    const long long trow = IDX ? (long long)(IDX == 4 ? (R.z0 + bzi) / R.nf : R.z0 + bzi) * R.tab_stride : 0;
+    const long long trow = IDX ? (long long)(IDX == 4 || IDX == 3 ? (R.z0 + bzi) / R.nf : R.z0 + bzi) * R.tab_stride : 0;
     const bool idxB = IDX == 1 && R.tabB != nullptr;
     if (idxB) {
         for (int k = tid; k < K; k += 256) kidx[k] = R.tabB[trow + R.offB + k].x;
@@ -141,6 +142,33 @@ __device__ __forceinline__ void zgemm3_body(int M, int Nn, int K, cplx alpha, co
     __shared__ int2 sgr[IDX == 4 ? TM : 1], sgc[IDX == 4 ? TN : 1];
     const cplx *S0 = nullptr, *S1 = nullptr;
     int ld0 = 0, ld1 = 0;
+    // (IDX 3, F21 gather) what an entry of A is formed from, per row of the tile (a ring cell) and per column k (a separator cell):
+    // x / w = z / x of the cell (x = -1: padding), y / z = its ring index in child 0 / 1 (-1: not on that child's ring)
+    __shared__ int4 g21r[IDX == 3 ? TM : 1], g21c[IDX == 3 ? G21_KCOL : 1];
+    const cplx *P3 = nullptr;
+    const long long N3 = (long long)R.nz * R.nx;
+    if (IDX == 3) {
+        const int bg = R.z0 + bzi, kf = bg % R.nf;                 // (R.nf > 1: batch index = front * nf + frequency)
+        const NdDev nd = R.nodes[R.first + bg / R.nf];
+        int base0 = 0, base1 = 0;
+        if (nd.kid[0] >= 0) { const NdDev c0 = R.nodes[nd.kid[0]]; ld0 = c0.smax + c0.mmax; S0 = R.arenaS + (long long)R.nf * c0.foff + (long long)kf * c0.mmax * ld0 + c0.smax; base0 = (int)(c0.voff + c0.smax); }
+        if (nd.kid[1] >= 0) { const NdDev c1 = R.nodes[nd.kid[1]]; ld1 = c1.smax + c1.mmax; S1 = R.arenaS + (long long)R.nf * c1.foff + (long long)kf * c1.mmax * ld1 + c1.smax; base1 = (int)(c1.voff + c1.smax); }
+        P3 = R.planes.p[kf];
+        for (int t = tid; t < TM + K; t += 256) {
+            const int q = t < TM ? nd.smax + m0 + t : t - TM;      // padded front row: ring rows of this tile, then the separator rows 0 .. K - 1
+            int4 e = make_int4(-1, -1, -1, 0);
+            if (t >= TM || m0 + t < M) {
+                const int4 t4 = R.tabCi[trow + q];
+                if (t4.x >= 0) {
+                    e.x = t4.x / R.nx; e.w = t4.x - e.x * R.nx;
+                    if (t4.y >= 0 && S0) e.y = t4.y - base0;
+                    if (t4.z >= 0 && S1) e.z = t4.z - base1;
+                }
+            }
+            if (t < TM) g21r[t] = e; else g21c[t - TM] = e;
+        }
+        __syncthreads();
+    }
     if (IDX == 4) {
         const int bg = R.z0 + bzi, kf = bg % R.nf;                 // (R.nf > 1: batch index = front * nf + frequency)
         const NdDev nd = R.nodes[R.first + bg / R.nf];
@@ -175,7 +203,25 @@ __device__ __forceinline__ void zgemm3_body(int M, int Nn, int K, cplx alpha, co
             const int idx = tid + e * 256;
             const int ar = idx / KS, ak = idx % KS;
             cplx v = cmake(0.0, 0.0);
-            if (idx < FA * 16 * KS && ar < TM && m0 + ar < M && k0 + ak < K) v = A[(long long)(m0 + ar) * lda + k0 + ak];
+            if (IDX == 3) {
+                // entry (ring cell, separator cell) of the front as k_nd_build_front forms it: the stencil coefficient where the two cells are neighbours (row = the
+                // ring cell), then child 0's Schur-complement entry, then child 1's; padding gives zero.  All three loads are issued before anything is added
+                // (what has no term reads the zero page and is not added: the sums are those of the build pass bit for bit).
+                const bool in = idx < FA * 16 * KS && ar < TM && m0 + ar < M && k0 + ak < K;
+                const int4 ia = g21r[in ? ar : 0], ib = g21c[in ? k0 + ak : 0];
+                const bool ok = in && ia.x >= 0 && ib.x >= 0;
+                const int dz = ib.x - ia.x, dx = ib.w - ia.w;
+                const bool nbr = ok && dz >= -1 && dz <= 1 && dx >= -1 && dx <= 1;
+                const bool h0 = ok && ia.y >= 0 && ib.y >= 0, h1 = ok && ia.z >= 0 && ib.z >= 0;
+                const cplx *pp = nbr ? P3 + (long long)((dz + 1) * 3 + dx + 1) * N3 + (long long)ia.x * R.nx + ia.w : g_zero_page;
+                const cplx *p0 = h0 ? S0 + (long long)ia.y * ld0 + ib.y : g_zero_page;
+                const cplx *p1 = h1 ? S1 + (long long)ia.z * ld1 + ib.z : g_zero_page;
+                const cplx pv = *pp, s0 = *p0, s1 = *p1;
+                v = pv;
+                if (h0) v = cadd(v, s0);
+                if (h1) v = cadd(v, s1);
+            }
+            else if (idx < FA * 16 * KS && ar < TM && m0 + ar < M && k0 + ak < K) v = A[(long long)(m0 + ar) * lda + k0 + ak];
             ra[e] = v;
         }
         #pragma unroll
@@ -326,7 +372,7 @@ __device__ __forceinline__ void zgemm3_body(int M, int Nn, int K, cplx alpha, co
                 cin = ix >= 0 ? R.Cix + (long long)ix * R.ldx : nullptr;
             }
             if (IDX == 4) erq[q] = sgr[rr - m0];
-            if ((IDX == 0 || IDX == 1) && (b0 || (rr >= R.zr0 && rr < R.zr1))) cin = nullptr;
+            if ((IDX == 0 || IDX == 1 || IDX == 3) && (b0 || (rr >= R.zr0 && rr < R.zr1))) cin = nullptr;
             dstq[q] = dst; cinq[q] = cin; cin2q[q] = cin2;
         }
         cplx cv[4][NT];

@@ -34,7 +34,13 @@ struct GemmRows {
     int schur4 = 0;
     const NdDev *nodes = nullptr; int first = 0;
     const cplx *arenaS = nullptr;
-    int nf = 1;                 // (schur4) batch index = front * nf + frequency: tables and node records go by the front, the children's blocks lie interleaved (direct.hpp)
+    int nf = 1;                 // (schur4, gather21) batch index = front * nf + frequency: tables and node records go by the front, the children's blocks lie interleaved (direct.hpp)
+    // F21-gather mode (k_zgemm3<.., 3, ..>): A is not loaded from a buffer -- entry (r, k) of A is the ring x separator entry of the front, formed as the
+    // build pass would have written it (stencil coefficient of the two cells, + child 0's Schur-complement entry, + child 1's); nodes / first / arenaS / nf
+    // as in Schur-complement mode, tabCi = the group's row table, planes = the coefficient planes of the nf operators, nz / nx = the grid
+    int gather21 = 0;
+    NdPlanesSet planes = {{nullptr, nullptr, nullptr, nullptr}};
+    int nz = 0, nx = 0;
     // forward pass on sparse right-hand sides (sources of a survey touch a handful of cells): act[front * nct + column / 64] != 0 when that front's
     // outgoing rows were computed for that block of 64 columns -- a front whose own right-hand-side rows and whose children's rows are all zero
     // there has nothing to add, writes zeros for its y_S rows and leaves its ring rows unwritten (its parent reads the flag, not the rows)
@@ -57,6 +63,7 @@ struct GemmRows {
     int cj_out = 0; cplx oscale = {1.0, 0.0}; cplx *Cox2 = nullptr;
 };
 #define GB_KIDX 512       // largest K with indexed B rows
+#define G21_KCOL 256      // largest K (separator size) of an F21-gather launch: its column table is staged in LDS
 // Addressing modes of the tile kernel (template parameter IDX):
 //   0  dense operands;
 //   1  rows of B / of the C that is read / of the C that is written through the row table (GemmRows), i.e. straight from / to the node-major
@@ -65,6 +72,8 @@ struct GemmRows {
 //      that land on it (table entries x / y, z) -- and the C that is read is the sum of the children's rows of a ring row; the first row-tile also
 //      stores the gathered separator rows (y_S) where the back substitution expects them.  Same additions in the same order as k_nd_fwd_rows + a
 //      dense product;
+//   3  "F21 gather": A is the ring x separator block of a front, gathered entry by entry from the coefficient planes and the children's Schur
+//      complements (the build pass does not write it): the product G21 = F21 F11^-1 is its only reader.  Same terms in the same order as k_nd_build_front;
 //   4  "Schur gather": C = (children's Schur-complement entries that land on (r, c), gathered through the row table) + alpha A B.
 // (Rounds 1-3 ran these products on the vector ALUs -- k_zgemm, k_zgemm2: 4 x 4 complex register blocks, 27-45 TFLOP/s; HISTORY.md -- and round 4
 // moved them to the matrix cores; the vector kernels were deleted in round 5.)
@@ -74,6 +83,7 @@ struct GemmRows {
 #define LEAF_MP 36           // largest ring of a leaf (2 (8 + 2) + 2 x 8)
 #define LUS_NMAX 128         // largest front the one-workgroup pivoted LU treats
 #define ND_STABLE_CAP 32     // ill-conditioned fronts treated per group at most
+#define ND_GATHER21_SMAX 128 // largest separator whose F21 the G21 product gathers by default (HELM_ND_GATHER21_SMAX): at 256 the levels come out even, profiles/gather21_levels.txt
 
 // Per-launch timing without extra packets: when gemm() has armed a pair of events, the dispatch itself carries them
 // (hipExtLaunchKernelGGL: start / stop timestamps of that kernel), instead of two hipEventRecord markers around it.
@@ -98,6 +108,9 @@ inline double gemm_operand_bytes(int M, int Nn, int K, cplx beta, const GemmRows
     const bool rd = !(beta.x == 0.0 && beta.y == 0.0);
     if (rows && rows->fwd3) return 16.0 * ((double)M * K + (double)K * Nn + (double)rows->child_rows * Nn + (double)M * Nn + (double)K * Nn);
     if (rows && rows->schur4) return 16.0 * ((double)M * K + (double)K * Nn + 1.5 * (double)M * Nn);
+    // F21 gather (gather21): A is not read as a block -- about half of its M K entries have a child's entry to fetch, a few two, and the stencil
+    // coefficients (at most three per ring cell) are noise beside them
+    if (rows && rows->gather21) return 16.0 * (0.5 * (double)M * K + (double)K * Nn + (double)M * Nn);
     return 16.0 * ((double)M * K + (double)K * Nn + (double)M * Nn * (rd ? 2.0 : 1.0));
 }
 inline double gemm_sol_ms(double flops, double bytes) { return 1e3 * std::max(flops / 78.6e12, bytes / 8.0e12); }
@@ -222,6 +235,9 @@ struct GroupTrace {
 struct GemmChoice { int tile = 0, kslab = 8, xr = 0, ksplit = 0, kc = 0; };
 int gemm(helm_op *op, int M, int Nn, int K, cplx alpha, const cplx *A, int lda, long long sa, const cplx *B, int ldb, long long sb,
          cplx beta, cplx *C, int ldc, long long sc, int batch, const GemmRows *rows = nullptr, GemmChoice *made = nullptr);
+// may the product G21 = F21 F11^-1 (M = ring, Nn = K = separator size) gather F21 itself (GemmRows::gather21)?  Only where the DENSE call of this shape runs
+// unsplit on a plain tile -- the gather launch takes that call's tile and K slab, so that G21 comes out bit for bit -- and the column table fits (G21_KCOL)
+bool gemm_gather21_ok(helm_op *op, int M, int Nn, int K, int batch);
 extern int g_gemm_tile;         // >= 0: forces the tile configuration (helm_debug_zgemm_bench, helm_debug_zgemm_ex)
 extern int g_gemm_slab;         // with g_gemm_tile 6 / 7: 16 forces the K slab of 16 (helm_debug_zgemm_ex); otherwise a forced tile takes the slab of 8
 extern int g_gemm_xcd;          // >= 0: replaces helm_tuning.nd_xcd_map (helm_debug_zgemm_ex)
