@@ -799,6 +799,15 @@ typedef struct helm_regrid helm_regrid;
 helm_regrid *helm_regrid_create(int device, int nz_a, int nx_a, double dz_a, double dx_a, int nz_b, int nx_b, double dz_b, double dx_b,
                                 double zorig, double xorig);
 void helm_regrid_destroy(helm_regrid *plan);
+/* The exact transpose of the transfer.  helm_regrid_axis_t: windows of the transpose of what helm_regrid_axis returns for the same arguments --
+ * returns WT and fills start[n_in], taps[n_in * WT]: row j (an input node of the forward axis) holds the forward taps of the contiguous
+ * range of outputs that touch it, a node no output touches an all-zero window.  WT > 64 (possible only when the axis up-samples):
+ * HELM_ERR_UNSUPPORTED.  helm_regrid_create_t: the plan from grid B to grid A with the transposed windows of both axes, for the grid
+ * arguments of helm_regrid_create; applied and destroyed like any plan (mul on grid A).  This is not the plan created with the grids
+ * exchanged: that one interpolates back, this one is the adjoint of the interpolation. */
+int helm_regrid_axis_t(int n_in, double h_in, int n_out, double h_out, int *start, double *taps, int cap);
+helm_regrid *helm_regrid_create_t(int device, int nz_a, int nx_a, double dz_a, double dx_a, int nz_b, int nx_b, double dz_b, double dx_b,
+                                  double zorig, double xorig);
 /* out[f] = beta out[f] + mul (.) (gain T in[f]) for k complex128 fields (device pointers); element i of field f at in[f in_fstride +
  * i in_estride] (a (k, N) block: fstride N, estride 1 -- the fast layout; an (N, k) block: fstride 1, estride k), likewise out.  mul: N_b
  * complex values on the device, NULL for 1; beta == 0: out is not read.  Runs on op's stream (NULL: the plan's own), so it is ordered after

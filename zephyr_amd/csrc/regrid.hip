@@ -127,6 +127,47 @@ int axis_windows(int n, double h_in, int n_out, double h_out, std::vector<int> &
     return W;
 }
 
+// Windows of the transpose of axis_windows' operator: row j (an input node of the forward axis) holds taps[i][j - start[i]] for the contiguous
+// range of forward outputs i that touch it.  The range comes from the forward windows' nonzero taps (min and max i per j), not from the
+// starts: those are not monotone (edge windows are shifted, taps below the cut are zeroed inside a window, the cap trims one end).  A node no
+// output touches gets an all-zero window.  Returns WT (>= 1), HELM_ERR_UNSUPPORTED when it exceeds 64, or axis_windows' error.
+int axis_windows_t(int n, double h_in, int n_out, double h_out, std::vector<int> &start_t, std::vector<double> &taps_t) {
+    std::vector<int> s;
+    std::vector<double> w;
+    const int W = axis_windows(n, h_in, n_out, h_out, s, w);
+    if (W < 0) return W;
+    std::vector<int> lo(n, n_out), hi(n, -1);
+    for (int i = 0; i < n_out; ++i)
+        for (int t = 0; t < W; ++t)
+            if (w[(size_t)i * W + t] != 0.0) { const int j = s[i] + t; lo[j] = std::min(lo[j], i); hi[j] = std::max(hi[j], i); }
+    int WT = 1;
+    for (int j = 0; j < n; ++j) WT = std::max(WT, hi[j] - lo[j] + 1);
+    if (WT > kRegridMaxTaps) return HELM_ERR_UNSUPPORTED;
+    start_t.assign(n, 0);
+    taps_t.assign((size_t)n * WT, 0.0);
+    for (int j = 0; j < n; ++j) {
+        if (hi[j] < lo[j]) continue;
+        const int st = std::min(lo[j], n_out - WT);   // (WT <= n_out: every window lies inside the forward's outputs)
+        start_t[j] = st;
+        for (int t = 0; t < WT; ++t) {
+            const int i = st + t, tt = j - s[i];
+            if (tt >= 0 && tt < W) taps_t[(size_t)j * WT + t] = w[(size_t)i * W + tt];
+        }
+    }
+    // an untouched node (all but every s-th one at an integer scale s) takes the start of its nearest touched neighbour below, the leading ones that of the
+    // first touched node: its zero window then lies where its neighbours read, and a column tile's LDS span stays about tile / scale + WT
+    int first = 0;
+    while (first < n && hi[first] < lo[first]) ++first;
+    if (first < n) {
+        int near = start_t[first];
+        for (int j = 0; j < n; ++j) {
+            if (hi[j] >= lo[j]) near = start_t[j];
+            else start_t[j] = near;
+        }
+    }
+    return WT;
+}
+
 __device__ inline void regrid_put(cplx *out, long long o, long long i, double ar, double ai, bool fin, cplx gain, double beta, const cplx *mul) {
     cplx v = cmake(ar, ai);
     if (fin) {
@@ -221,6 +262,20 @@ extern "C" int helm_regrid_axis(int n_in, double h_in, int n_out, double h_out, 
     return W;
 }
 
+extern "C" int helm_regrid_axis_t(int n_in, double h_in, int n_out, double h_out, int *start, double *taps, int cap) {
+    std::vector<int> s;
+    std::vector<double> w;
+    const int WT = axis_windows_t(n_in, h_in, n_out, h_out, s, w);
+    if (WT == HELM_ERR_UNSUPPORTED) { helm_set_error(nullptr, "helm_regrid_axis_t: an input node is touched by more than 64 outputs (an up-sampling axis this dense has no transposed plan)"); return WT; }
+    if (WT < 0) { helm_set_error(nullptr, "helm_regrid_axis_t: needs n_in >= 4, n_out >= 1 and positive spacings"); return WT; }
+    if (start) std::copy(s.begin(), s.end(), start);
+    if (taps) {
+        if ((size_t)cap < w.size()) { helm_set_error(nullptr, "helm_regrid_axis_t: taps holds fewer than n_in * WT entries"); return HELM_ERR_ARG; }
+        std::copy(w.begin(), w.end(), taps);
+    }
+    return WT;
+}
+
 extern "C" void helm_regrid_destroy(helm_regrid *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
@@ -236,14 +291,9 @@ static int upload_small(T **dst, const std::vector<T> &v) {
     return HELM_OK;
 }
 
-extern "C" helm_regrid *helm_regrid_create(int device, int nz_a, int nx_a, double dz_a, double dx_a, int nz_b, int nx_b, double dz_b, double dx_b,
-                                           double zorig, double xorig) {
-    (void)zorig; (void)xorig;         // (both grids start at the same origin: the transfer depends on the spacings alone)
-    helm_tuning_refresh();
-    std::vector<int> sz, sx;
-    std::vector<double> wz, wx;
-    const int Wz = axis_windows(nz_a, dz_a, nz_b, dz_b, sz, wz), Wx = axis_windows(nx_a, dx_a, nx_b, dx_b, sx, wx);
-    if (Wz < 0 || Wx < 0) { helm_set_error(nullptr, "helm_regrid_create: grids need at least 4 nodes per axis and positive spacings"); return nullptr; }
+// the plan of windows (sz, wz, Wz) / (sx, wx, Wx) that carry an (nz_a, nx_a) grid to an (nz_b, nx_b) one
+static helm_regrid *regrid_plan_from_windows(int device, int nz_a, int nx_a, int nz_b, int nx_b, int Wz, int Wx, const std::vector<int> &sz,
+                                             const std::vector<int> &sx, const std::vector<double> &wz, const std::vector<double> &wx) {
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); helm_set_error(nullptr, "helm_regrid_create: hipSetDevice failed"); return nullptr; }
     helm_regrid *p = new helm_regrid();
     p->device = device; p->nz_a = nz_a; p->nx_a = nx_a; p->nz_b = nz_b; p->nx_b = nx_b; p->Wz = Wz; p->Wx = Wx;
@@ -274,6 +324,35 @@ extern "C" helm_regrid *helm_regrid_create(int device, int nz_a, int nx_a, doubl
         helm_regrid_destroy(p); helm_set_error(nullptr, "helm_regrid_create: upload of the taps failed"); return nullptr;
     }
     return p;
+}
+
+extern "C" helm_regrid *helm_regrid_create(int device, int nz_a, int nx_a, double dz_a, double dx_a, int nz_b, int nx_b, double dz_b, double dx_b,
+                                           double zorig, double xorig) {
+    (void)zorig; (void)xorig;         // (both grids start at the same origin: the transfer depends on the spacings alone)
+    helm_tuning_refresh();
+    std::vector<int> sz, sx;
+    std::vector<double> wz, wx;
+    const int Wz = axis_windows(nz_a, dz_a, nz_b, dz_b, sz, wz), Wx = axis_windows(nx_a, dx_a, nx_b, dx_b, sx, wx);
+    if (Wz < 0 || Wx < 0) { helm_set_error(nullptr, "helm_regrid_create: grids need at least 4 nodes per axis and positive spacings"); return nullptr; }
+    return regrid_plan_from_windows(device, nz_a, nx_a, nz_b, nx_b, Wz, Wx, sz, sx, wz, wx);
+}
+
+// The exact transpose of helm_regrid_create's plan for the same arguments: it carries grid B to grid A with the transposed windows of both axes.
+// A transposed window of an axis reads forward outputs, so the plan is an ordinary one with the grids' roles exchanged: the pass order from
+// the FMA counts with WTz / WTx, the column tiles and their LDS spans from the transposed starts, k_regrid_z / k_regrid_x unchanged.
+extern "C" helm_regrid *helm_regrid_create_t(int device, int nz_a, int nx_a, double dz_a, double dx_a, int nz_b, int nx_b, double dz_b, double dx_b,
+                                             double zorig, double xorig) {
+    (void)zorig; (void)xorig;
+    helm_tuning_refresh();
+    std::vector<int> sz, sx;
+    std::vector<double> wz, wx;
+    const int Wz = axis_windows_t(nz_a, dz_a, nz_b, dz_b, sz, wz), Wx = axis_windows_t(nx_a, dx_a, nx_b, dx_b, sx, wx);
+    if (Wz == HELM_ERR_UNSUPPORTED || Wx == HELM_ERR_UNSUPPORTED) {
+        helm_set_error(nullptr, "helm_regrid_create_t: a node of grid A is touched by more than 64 nodes of grid B along an axis; this up-sampling transfer has no transposed plan");
+        return nullptr;
+    }
+    if (Wz < 0 || Wx < 0) { helm_set_error(nullptr, "helm_regrid_create_t: grids need at least 4 nodes per axis and positive spacings"); return nullptr; }
+    return regrid_plan_from_windows(device, nz_b, nx_b, nz_a, nx_a, Wz, Wx, sz, sx, wz, wx);
 }
 
 static int regrid_pass_z(const helm_regrid *p, hipStream_t st, const cplx *in, long long ifs, long long ies, cplx *out, long long ofs, long long oes,

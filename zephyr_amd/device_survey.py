@@ -488,7 +488,7 @@ def fields(prob, owned, dtype='complex128', perKy=False):
     from .fieldstore import DeviceFields, DTYPES
     from .survey import HelmMultiGridSurvey
     sv = prob.survey
-    if isinstance(sv, HelmMultiGridSurvey):
+    if isinstance(sv, HelmMultiGridSurvey) and not prob._multiscaleServed():          # (with multiscaleDerivatives every frequency's slice lives on ITS grid: Ni = op.nrow)
         raise NotImplementedError('fieldsDevice serves single-grid surveys: on a multiscale survey the u-given branch of Jtvec multiplies the native-grid forward '
                                   'field by the up-scaled back-propagated one per source (two grid transfers per source), which has not been built on the device')
     if dtype not in DTYPES:
@@ -766,6 +766,8 @@ def _jointPlanes(ws, fop, dcd, dbd, C, stretch, spare):
         fop.velocityPlanesDevice(dcd.data_ptr(), dbd.data_ptr(), C.data_ptr())
         return
     fop.massPlanesDevice(dcd.data_ptr(), C.data_ptr())
+    if dbd is None:          # (the mass term alone: 'operator' along a velocity perturbation on a multiscale pairing)
+        return
     fop.buoyancyPlanesDevice(dbd.data_ptr(), spare.data_ptr())
     C.add_(spare)
     _lib.wait_torch_stream(ws.device)
@@ -778,18 +780,23 @@ def _bornPlanesFromFields(prob, F, db, dc=None, stretch=True):
     dc given (N,) float64: prob.JvecBorn(u=F, linearisation='full'), the total derivative along the velocity perturbation dc -- the same body with
     k_velocity_planes in the place of k_buoyancy_planes: the planes V_f[dc] of the mass term and the PML stretch, plus L_f[db] where the density follows c
     (db = (d b / d c) dc then; None with an explicit density).  stretch False (parameter='joint' with linearisation='operator', dc and db both given): the
-    mass term of V[dc] alone plus L[db], `_jointPlanes`."""
+    mass term of V[dc] alone plus L[db], `_jointPlanes`.
+    A multiscale pairing hands db / dc as {ifreq: array on the grid of that frequency} (one array object per grid, so a worker uploads it once per grid)."""
     F.checkCurrent(prob)
     data, stage, sample = _sampling(prob, F.ownedFreqs, F.scale)
     if not F.items:
         return data
-    db = None if db is None else np.ascontiguousarray(db, dtype=np.float64)
-    dc = None if dc is None else np.ascontiguousarray(dc, dtype=np.float64)
+    perGrid = isinstance(db, dict) or isinstance(dc, dict)
+    if not perGrid:
+        db = None if db is None else np.ascontiguousarray(db, dtype=np.float64)
+        dc = None if dc is None else np.ascontiguousarray(dc, dtype=np.float64)
+    allDb, allDc = db, dc
     devs, items = _storedItems(prob.system, F)
 
     def one(ws, op, ifreq, c0, c1):
         k, Ni = c1 - c0, int(op.nrow)
         dev = ws.device
+        db, dc = (None if x is None else x[ifreq] for x in (allDb, allDc)) if perGrid else (allDb, allDc)
         d_uF, d_exp = F.pointers(ifreq, c0)
         staged = stage(ws, ifreq, c0, c1)
         dbd = None if db is None else ws.cached(('born_db', id(db)), lambda: _lib.to_device(db, dev, np.float64), keep=db)
@@ -893,6 +900,68 @@ def jointGradientFromFields(prob, F, qb, resid, system, linearisation):
         op.buoyancyAdjointDevice(P.data_ptr(), w, G.data_ptr() + 16 * N, conj=True)
     wss = runOnDevices(devs, items, one)
     return _sumPartials(prob, [ws.G for ws in wss if ws.G is not None], n=2 * N).real
+
+
+def multiscaleGradientFromFields(prob, F, qb, resid, system, linearisation, parameter):
+    """prob.Jtvec(u=F, adjoint='transpose') of a multiscale pairing (multiscaleDerivatives=True) with 'operator' or 'full': g = sum_f S_f^T g_f, float64 (N,), or
+    (2 N,) [g_c; g_rho] for parameter='joint'.  The item body of `jointGradientFromFields` on the grid of the item's frequency, with the adjoint kernels adding
+    into a partial of THAT grid (zeroed per item) instead of the worker's native one; what depends on the model at a cell is applied there -- -1 / rho_f^2 on
+    a density half, Gardner's d b / d c at c_f on the buoyancy gradient that joins the velocity one -- and ONE transposed grid transfer (`ds.adjoint`, k = 1 or
+    2, beta = 1, queued on the operator's stream) adds the item's partial to the worker's native G.  The real part is taken at the end: S_f is real."""
+    import torch
+    F.checkCurrent(prob)
+    sv = prob.survey
+    N = prob.nrow
+    scale = F.scale
+    stretch = linearisation == 'full'
+    joint, density = parameter == 'joint', parameter == 'rho'
+    halves = 2 if joint else 1
+    if not F.items:
+        return _sumPartials(prob, [], n=halves * N).real
+    _prepareBackSources(sv, qb, F.ownedFreqs)
+    devs, items = _storedItems(system, F)
+    _checkSecondFactorsFit(items, planes=9)
+    chains = {ifreq: prob._gridChains(ifreq) for ifreq in F.ownedFreqs}          # (host arrays, made on the calling thread)
+    ups = [ds.adjoint for ds in sv.preProcessors]
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        dev = ws.device
+        d_uF, d_exp = F.pointers(ifreq, c0)
+        G = _partial(ws, 'G', halves * N, torch.complex128)
+        gk = sv._gridKey(ifreq)
+        brho, bc = chains[ifreq]
+        gardner = stretch and not density and bc is not None
+        brho_d = ws.cached(('grid_brho', gk), lambda: _lib.to_device(brho, dev, np.float64)) if density or joint else None
+        bc_d = ws.cached(('grid_bc', gk), lambda: _lib.to_device(bc, dev, np.float64)) if gardner else None
+        U, R, P, T = ws.buffer('U', k * Ni), ws.buffer('R', k * Ni), ws.buffer('lags', 9 * Ni), ws.buffer('gridG', 2 * Ni)
+        first, second = T[:Ni], T[Ni:]
+        _backSources(ws, sv, op, qb, resid, ifreq, c0, c1, R.data_ptr(), Ni)
+        P.zero_()
+        T.zero_()
+        _lib.wait_torch_stream(dev)
+        op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+        op.lagImagingAccumulateDevice(d_uF, U.data_ptr(), k, P.data_ptr(), d_exp=d_exp, rows=Ni)
+        w = -scale / np.conj(complex(op.premul))
+        # (every adjoint call returns when its output is complete, so the torch work below reads finished partials)
+        if density:
+            op.buoyancyAdjointDevice(P.data_ptr(), w, first.data_ptr(), conj=True)
+            first.mul_(brho_d)
+        else:
+            if stretch:
+                op.velocityAdjointDevice(P.data_ptr(), w, first.data_ptr(), conj=True)
+            else:
+                op.massAdjointDevice(P.data_ptr(), w, first.data_ptr(), conj=True)
+            if gardner or joint:
+                op.buoyancyAdjointDevice(P.data_ptr(), w, second.data_ptr(), conj=True)
+                if joint:
+                    second.mul_(brho_d)
+                else:
+                    first.addcmul_(second, bc_d.to(torch.complex128))
+        _lib.wait_torch_stream(dev)
+        ups[ifreq].apply_device(T[:halves * Ni], G, k=halves, op=op, beta=1.)
+    wss = runOnDevices(devs, items, one)
+    return _sumPartials(prob, [ws.G for ws in wss if ws.G is not None], n=halves * N).real
 
 
 # ---- 2.5-D problems: the exact derivatives from the per-ky store -------------------------------------------------------------------------------------

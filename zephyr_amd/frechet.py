@@ -358,9 +358,16 @@ def viscoChain(c, Q, lam=0.0, dtype=np.complex128, magnitude=False):
     return gamma, -(cr * gamma) * (q * q) * (lam / disp + half / att)
 
 
+def _rhoGrid(op):
+    'the density of the operator as float64 (nz, nx): a scalar broadcast, an (nz, nx) array as it is, a flat one of nz nx entries (a multiscale sub-problem) reshaped'
+    nz, nx = int(op.nz), int(op.nx)
+    rho = np.asarray(op.rho, dtype=np.float64)
+    return rho.reshape((nz, nx)) if rho.size == nz * nx else np.broadcast_to(rho, (nz, nx))
+
+
 def _buoyancy(op, R):
     "b = 1 / rho (nz, nx) at the density the operator is assembled with (its config's, or the Gardner default)"
-    return 1 / np.broadcast_to(np.asarray(op.rho, dtype=np.float64), (int(op.nz), int(op.nx))).astype(R)
+    return 1 / _rhoGrid(op).astype(R)
 
 
 def _perturbation(dc, R, dtype, shape):
@@ -569,7 +576,7 @@ def pseudoHessianDiagonal(op, u, parameter='c', chain=None, dtype=np.complex128,
         planes = lambda v: buoyancyPlanes(op, v, dtype, magnitude)
     H = colourSum(nz, nx, planes, ua, magnitude)
     if parameter == 'rho':
-        rho = np.broadcast_to(np.asarray(op.rho, dtype=np.float64), (nz, nx)).astype(R).ravel()
+        rho = _rhoGrid(op).astype(R).ravel()
         H = H / (rho * rho * rho * rho)
     return H
 
@@ -708,7 +715,7 @@ def gaussNewtonDiagonal(op, uh, gh, parameter='c', chain=None, linearisation='fu
         planes = lambda v: velocityPlanes(op, v, None if ch is None else ch * v, dtype, magnitude)
     H = gaussNewtonTrace(blockCoefficients(nz, nx, planes), _gramBlocks(Cg, nz, nx), _gramBlocks(Cu, nz, nx), magnitude)
     if parameter == 'rho':
-        rho = np.broadcast_to(np.asarray(op.rho, dtype=np.float64), (nz, nx)).astype(R).ravel()
+        rho = _rhoGrid(op).astype(R).ravel()
         H = H / (rho * rho * rho * rho)
     return H
 
@@ -735,7 +742,7 @@ def _checkBlocksLinearisation(linearisation):
 
 def _densityRows(op, cc, cb, bb, R, magnitude):
     "(3, N): the (c, b) entries of a block in density units, rows cc, -cb / rho^2, bb / rho^4 (magnitude: +cb / rho^2)"
-    rho = np.broadcast_to(np.asarray(op.rho, dtype=np.float64), (int(op.nz), int(op.nx))).astype(R).ravel()
+    rho = _rhoGrid(op).astype(R).ravel()
     r2 = rho * rho
     return np.stack([cc, (cb if magnitude else -cb) / r2, bb / (r2 * r2)])
 

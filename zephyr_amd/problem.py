@@ -65,6 +65,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         'eurusDerivatives': (False,    '_eurusDerivatives', bool),    # an Eurus problem (eps == delta) serves the exact adjoint and the exact derivatives through M1^T
         'viscoDerivatives': (False,    '_viscoDerivatives', bool),    # a visco problem serves the exact derivatives ('operator' / 'full') through the chain from (c, Q)
         'kyDerivatives':    (False,    '_kyDerivatives', bool),       # a 2.5-D problem serves the exact derivatives from the forward fields kept PER ky (fieldsDevice(perKy=True))
+        'multiscaleDerivatives': (False, '_multiscaleDerivatives', bool),    # a multiscale pairing serves the exact derivatives: per-grid maps, then the transposed grid transfer
     }
 
     surveyPair = HelmBaseSurvey
@@ -127,12 +128,14 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         Jtvec(adjoint='transpose') back-propagates through.  It goes with the problem's cache on a model change, and `del prob.factors` releases it too.
         While both wrappers are in use the factors of A_f and of A_f^T are resident side by side: twice the device memory of `system` alone.
         2-D MiniZephyr / MiniZephyrHD / MiniZephyr25D on one grid, and Eurus / EurusHD with eurusDerivatives=True and eps == delta (M1^T, helm_set_transposed_m1);
-        Eurus otherwise, the 3-D operator and the multiscale wrappers raise NotImplementedError."""
+        Eurus otherwise and the 3-D operator raise NotImplementedError; so do the multiscale wrappers unless the config sets multiscaleDerivatives=True (then the
+        transposed operator of every frequency lives on that frequency's grid)."""
         if getattr(self, '_adjointSystem', None) is None:
             from .distributors import MultiGridMultiFreq
             cls = type(self.system)
-            if issubclass(cls, MultiGridMultiFreq) or isinstance(self.survey, HelmMultiGridSurvey):
+            if (issubclass(cls, MultiGridMultiFreq) or isinstance(self.survey, HelmMultiGridSurvey)) and not self._multiscaleServed():
                 raise NotImplementedError('the transposed operator serves single-grid problems: a multiscale pairing has no exact-adjoint route')
+            self._refuseMultiscale('adjointSystem')           # (with the key: the visco / 2.5-D / Eurus pairings and a transfer without a transpose say why not)
             cfg = dict(self.systemConfig)
             cfg['transposed'] = True
             adj = cls(cfg)
@@ -208,8 +211,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             raise ValueError('%s(perKy=True) serves single-grid 2.5-D problems (MiniZephyr25D): %s has no ky axis'
                              % (what, type(subs[0]).__name__ if subs else type(self.system).__name__))
 
-    def fields(self, m=None, perKy=False):
+    def fields(self, m=None, perKy=False, ownGrid=False):
         """list of forward wavefields for ALL frequencies on this rank (no sharding), on the native grid (problem.py:181-191: post-processed).
+        ownGrid (multiscale pairings; on a single grid it changes nothing): every frequency's fields on ITS grid, as they were solved and not up-scaled --
+        what the exact derivatives of a multiscale problem (multiscaleDerivatives=True) take as host `u`, and what `dpred(u=)` samples without a round trip.
         perKy (2.5-D problems): one (nky, N, nsrc) array per frequency, the fields of every cross-line wavenumber apart -- their sum over ky is the default's
         entry -- what the exact derivatives of a 2.5-D problem take as host `u`."""
         self._requirePaired()
@@ -218,6 +223,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if perKy:
             self._requirePerKy('fields')
             return [self._kyFieldsHost(i, device_survey._ofFrequency(qf, i)) for i in range(self.survey.nfreq)]
+        if ownGrid:
+            return [np.asarray(u) for u in self.system * qf]
         return [pp(u) for u, pp in zip(self.system * qf, self.survey.postProcessors)]
 
     @property
@@ -229,7 +236,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         """The forward wavefields of the owned frequencies, solved once and LEFT in HBM: a fieldstore.DeviceFields to hand to `survey.dpred(m, u=F)` and
         `Jtvec(m, v, u=F)`, which then solve nsrc columns per frequency between them and the back-propagation instead of re-solving the forward fields.
         `F[ifreq]` downloads what `fields()[ifreq]` would be.  Single-grid surveys (2-D, and 2.5-D with the ky sum on the device); without the device
-        path (no GPU, hostGradient, a host ky reduction) this raises and `fields()` is the route.
+        path (no GPU, hostGradient, a host ky reduction) this raises and `fields()` is the route.  A multiscale pairing with multiscaleDerivatives=True: every
+        frequency's fields on ITS grid (a slice is (k, N_f)), `F[ifreq]` what `fields(ownGrid=True)[ifreq]` would be; without the key it raises as it always did.
+        That store serves `dpred(u=F)` and the 'operator' / 'full' routes of Jtvec(adjoint='transpose') / JvecBorn / Hvec; the reference's `Jtvec(m, v, u=F)` and
+        `illumination(u=F)` read native-grid fields and refuse it (NotImplementedError).
         perKy (2.5-D problems; ValueError elsewhere): every ky of an item is solved into its own block of the item's slice, nky times the memory -- what the
         exact derivatives of a 2.5-D problem (kyDerivatives=True) read; `dpred(u=)` forms the ky sum while sampling and `F[ifreq]` still downloads the sum."""
         self._requirePaired()
@@ -237,7 +247,9 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if perKy:
             self._requirePerKy('fieldsDevice')
         if isinstance(self.survey, HelmMultiGridSurvey):
-            return device_survey.fields(self, [], self.fieldsDtype)            # (raises NotImplementedError with the reason)
+            if not self._multiscaleServed():
+                return device_survey.fields(self, [], self.fieldsDtype)        # (raises NotImplementedError with the reason)
+            self._refuseMultiscale('fieldsDevice')                             # (with the key: every frequency's fields on ITS grid; the other pairings say why not)
         if not self._deviceGradientAvailable():
             raise RuntimeError('fieldsDevice needs the device path (GPU operators with solveDevice, no hostGradient, the ky sum on the device): use fields()')
         return device_survey.fields(self, self.ownedFreqs, self.fieldsDtype, perKy=bool(perKy))
@@ -286,7 +298,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             g = Re sum_f w_f (.) sum_s uF_s (.) (scaleTerm S_f^T R_s^T r_s),   S_f^T q = conj(A_f^-T premul q),  w_f = gradientScaler(f),
         always real float64 (N,) -- there is no mux branch, forward and back solves use different factors -- and the exact adjoint of `JvecBorn` under
         <a, b> = Re sum conj(a) b.  u a DeviceFields: on the device; u None with the device path: fieldsDevice() internally, released afterwards;
-        u a list of host arrays, or no device path: numpy.  Fixed and moving receiver arrays; multiscale surveys raise NotImplementedError.
+        u a list of host arrays, or no device path: numpy.  Fixed and moving receiver arrays.  A multiscale pairing raises NotImplementedError unless the
+        config sets multiscaleDerivatives=True (below).
 
         linearisation='scaler' (default): the weight is the reference's gradientScaler w_f = -omega^2 / c^3, the reference's convention.  That is NOT the
         derivative of `dpred`: the assembled operator carries c as K = (omega_d^2 / c^2 - ky^2) / rho spread over nine slots by the mass weights, with
@@ -323,6 +336,17 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         (opt-in; without the key it is refused as it always was): the data are st R sum_k conj(u^_k), so the gradient is a sum over ky of the expressions above
         on ky sub-operator k and fields of the SAME ky, g = Re sum_f sum_k w_fk T_k^T lag(z_k, u^_k) with w_fk = -conj(st) / premul_k (`_JtvecKy`).  u is then the
         per-ky store of fieldsDevice(perKy=True) (the ky-SUM store: ValueError), a host list of fields(perKy=True), or None.  'scaler' is unchanged.
+
+        A multiscale pairing (MultiGridMultiFreq + Helm2DMultiGridSurvey over MiniZephyr / MiniZephyrHD) with 'operator' or 'full' is served when the config sets
+        multiscaleDerivatives=True (opt-in; without the key it is refused as it always was, and the mux gradient is untouched either way).  On the grid of
+        frequency f the sub-problem sees c_f = S_f c and rho_f = S_f rho, S_f the real, linear spline down-scaler, so g = sum_f S_f^T g_f: g_f is the expression
+        above on that grid -- chains included, -1 / rho_f^2 and Gardner's d b / d c at c_f -- and S_f^T the exact transpose of the windowed transfer
+        (`ds.adjoint`; `ds.T`, the interpolation back up that the mux gradient uses, is not that).  u is then the store of fieldsDevice() (every frequency on
+        ITS grid), a host list of fields(ownGrid=True) (a native-size array for a coarser frequency: ValueError), or None.  The result is on the native grid.
+        What it looks like: S_f SAMPLES the model, it does not average it, so S_f^T puts a coarse cell's gradient on the few native nodes around its sample
+        point -- the column sums of a 1-D axis at scale 2.47 run from -0.25 to 1.07, and at an integer scale s only every s-th node receives anything.  That IS
+        the derivative of this dpred; smoothing it is the caller's business.  'scaler' with adjoint='transpose', Hvec(resid=), the Hessian diagonals and blocks,
+        and visco / 2.5-D / Eurus multiscale pairings are refused with the key (`_refuseMultiscale`).
         """
         self._requirePaired()
         if v is None:
@@ -343,6 +367,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             return self._JtvecTranspose(resid, u, linearisation, parameter)
         if isinstance(u, DeviceFields):
             # forward fields left in HBM by fieldsDevice(): only the back-propagation is solved, on the store's own items
+            self._refusePerGridStore("Jtvec(adjoint='reciprocity', u=F)")
             u.checkCurrent(self)
             return device_survey.gradientFromFields(self, u, self._deviceBackSources(resid), resid)
         if u is None and self._deviceGradientAvailable():
@@ -366,8 +391,170 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
 
     # ---- exact adjoint, Born data, Gauss-Newton product ----------------------------------------------------
     def _refuseMultiscale(self, what):
-        if isinstance(self.survey, HelmMultiGridSurvey):
+        """a multiscale pairing is refused unless the config sets multiscaleDerivatives=True (opt-in: without the key everything is what it was); with the
+        key, what the composition through the transposed grid transfer does not serve is refused here with the reason"""
+        if not isinstance(self.survey, HelmMultiGridSurvey):
+            return
+        if not getattr(self, '_multiscaleDerivatives', False):
             raise NotImplementedError('%s serves single-grid surveys: the transposed operator and the stored forward fields live on one grid' % (what,))
+        from .discretization import DiscretizationWrapper
+        from .eurus import Eurus
+        for ds in self.survey.preProcessors:
+            if not hasattr(ds, 'adjoint'):
+                raise NotImplementedError('%s with multiscaleDerivatives needs the exact transpose of the grid transfer: %s has no `.adjoint` (its `.T` interpolates '
+                                          'back up, which is not the transpose)' % (what, type(ds).__name__))
+        if self._isVisco():
+            raise NotImplementedError('%s with multiscaleDerivatives does not serve visco problems: the chain from (c, Q) to the complex velocity is formed on the '
+                                      'native grid before the down-scaling, and that order is not built into the per-grid routes' % (what,))
+        sub = self.system.subProblems[0] if self.system.subProblems else None
+        if isinstance(sub, DiscretizationWrapper):
+            raise NotImplementedError('%s with multiscaleDerivatives does not serve the 2.5-D composite: the per-ky routes are built for one grid' % (what,))
+        if isinstance(sub, Eurus):
+            raise NotImplementedError('%s with multiscaleDerivatives does not serve Eurus problems: theta, eps and delta are down-scaled per frequency too, and the '
+                                      'derivative maps of M1 are built for one grid' % (what,))
+
+    def _refusePerGridStore(self, what):
+        """the store of fieldsDevice() on a multiscale pairing (multiscaleDerivatives=True) holds every frequency on ITS grid: the routes that image or accumulate
+        on the native grid -- the reference's u-given gradient, the 'scaler' illumination kinds -- read native-grid fields and are not built for it"""
+        if self._multiscaleServed():
+            raise NotImplementedError('%s does not read the per-grid store of a multiscale pairing: this route multiplies native-grid forward fields, and the store '
+                                      'of multiscaleDerivatives=True holds every frequency on its own grid (u=None or the host list of fields() serve it; the '
+                                      'store serves dpred and the \'operator\' / \'full\' routes)' % (what,))
+
+    def _multiscaleServed(self):
+        'the config sets multiscaleDerivatives=True and the pairing is a multiscale one: the exact routes run per grid and end in the transposed grid transfer'
+        return bool(getattr(self, '_multiscaleDerivatives', False)) and isinstance(self.survey, HelmMultiGridSurvey)
+
+    def _refuseMultiscaleScaler(self, what, linearisation):
+        if linearisation == 'scaler' and self._multiscaleServed():
+            raise NotImplementedError('%s with linearisation=\'scaler\' does not serve multiscale pairings: the reference\'s weight is up-scaled, not transposed, and has '
+                                      'no exact adjoint there (multiscaleDerivatives serves \'operator\' and \'full\')' % (what,))
+
+    def _refuseMultiscaleDiagonal(self, what):
+        if self._multiscaleServed():
+            raise NotImplementedError('%s does not serve multiscale pairings: the Hessian of frequency f is S_f^T H_f S_f, and diag(S^T H S) is not S^T diag(H) -- the '
+                                      'diagonals and blocks of the coarse grids do not compose (Hvec applies the product itself)' % (what,))
+
+    def _ownGridFields(self, u):
+        """the forward fields of a multiscale pairing as the exact routes read them: per frequency on ITS grid.  u None: solved now for the owned frequencies (None
+        elsewhere); u a host list: checked -- a native-size array for a coarser frequency is what fields() returns, not what was solved"""
+        sv = self.survey
+        subs = self.system.subProblems
+        if u is None:
+            uF = [None] * sv.nfreq
+            for ifreq, uf in self._solveOwned(sv.getSources()):
+                uF[ifreq] = np.asarray(uf)
+            return uF
+        uF = list(u)
+        for ifreq in self.ownedFreqs:
+            n = int(subs[ifreq].nz) * int(subs[ifreq].nx)
+            if uF[ifreq] is None or np.shape(uF[ifreq])[0] != n:
+                raise ValueError('the exact routes of a multiscale pairing read the fields of frequency %d on its own %d x %d grid (%d rows, not %s): pass '
+                                 'fields(ownGrid=True)' % (ifreq, subs[ifreq].nz, subs[ifreq].nx, n, None if uF[ifreq] is None else np.shape(uF[ifreq])[0]))
+        return uF
+
+    def _gridChains(self, ifreq):
+        """(d b / d rho, d b / d c) on the grid of frequency ifreq, float64 (N_f,) each: -1 / rho_f^2 at rho_f = S_f rho where the config gives the density (else
+        None), Gardner's chain at c_f = S_f c where it does not (else None).  What depends on the model at a cell is evaluated where the operator is assembled."""
+        op = self.system.subProblems[ifreq]
+        n = int(op.nz) * int(op.nx)
+        if self._hasDensity():
+            rho = np.broadcast_to(np.asarray(op.rho, dtype=np.float64).ravel(), (n,))
+            return -1.0 / (rho * rho), None
+        return None, gardnerChain(np.broadcast_to(np.asarray(op.c).ravel(), (n,)))
+
+    def _JtvecMultiscale(self, resid, u, linearisation, parameter):
+        """Jtvec(adjoint='transpose') of a multiscale pairing with 'operator' or 'full' once the refusals are past: g = sum_f S_f^T g_f, float64 (N,) or (2N,).
+        g_f is the single-grid expression on the grid of frequency f -- the lag products of the transposed back-propagation against the forward solves, V_f^T /
+        L_f^T, the weight, the real part and the chains (-1 / rho_f^2, or Gardner's at c_f) -- and S_f^T the exact transpose of the down-scaler (`ds.adjoint`)."""
+        stretch = linearisation == 'full'
+        joint, density = parameter == 'joint', parameter == 'rho'
+        adj = self.adjointSystem
+        N = self.nrow
+        sv = self.survey
+        st = complex(self.system.scaleTerm)
+        g = np.zeros(2 * N if joint else N, dtype=np.float64)
+        with self._forwardFields(u) as F:
+            if isinstance(F, DeviceFields):
+                rd = self._hermitianResidual(resid)
+                return device_survey.multiscaleGradientFromFields(self, F, self._deviceBackSources(rd), rd, adj, linearisation, parameter)
+            qb = [q.conj() for q in sv.getResidualSources(np.conj(resid))]
+            for ifreq, uB in self._solveOwned(qb, adj):
+                op = self.system.subProblems[ifreq]
+                up = sv.preProcessors[ifreq].adjoint
+                P = lagProducts(np.conj(np.asarray(uB) / st), np.conj(np.asarray(F[ifreq]) / st), op.nz, op.nx)
+                w = -np.conj(st) / complex(op.premul)
+                brho, bc = self._gridChains(ifreq)
+                if not density:
+                    gf = velocityAdjoint(op, P, stretch=stretch)
+                    if bc is not None and stretch:
+                        gf = gf + bc * buoyancyAdjoint(op, P)
+                    g[:N] += np.asarray(up * np.ascontiguousarray((w * gf).real)).ravel()
+                if density or joint:
+                    g[-N:] += np.asarray(up * np.ascontiguousarray(brho * (w * buoyancyAdjoint(op, P)).real)).ravel()
+        if self._sharded:
+            g = parallel.allreduce_sum(g)
+        return g
+
+    def _JvecBornMultiscale(self, v, u, linearisation, parameter):
+        """JvecBorn of a multiscale pairing with 'operator' or 'full' once the refusals are past: the perturbation goes down once per grid (dc_f = S_f v_c,
+        drho_f = S_f v_rho), the buoyancy perturbation is formed there (db_f = -drho_f / rho_f^2, or Gardner's chain at c_f times dc_f), and the planes, the Born
+        solve and the sampling are the single-grid ones on the grid of frequency f.  (nrec, nsrc, nfreq) raveled."""
+        stretch = linearisation == 'full'
+        joint, density = parameter == 'joint', parameter == 'rho'
+        sv = self.survey
+        N = self.nrow
+        if joint:
+            vc, vr = self._splitJoint(v, 'JvecBorn')
+        else:
+            vv = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape((N,)))
+            vc, vr = (None, vv) if density else (vv, None)
+        subs = self.system.subProblems
+        down = {}
+
+        def onGrid(i):
+            'the perturbations (dc_f, db_f) on the grid of frequency i, float64 (N_f,) or None: one transfer and one pair of arrays per grid, not per frequency'
+            ds = sv.preProcessors[i]
+            if id(ds) not in down:
+                dc, dr = (None if x is None else np.ascontiguousarray(np.asarray(ds * x, dtype=np.float64).ravel()) for x in (vc, vr))
+                brho, bc = self._gridChains(i)
+                db = None
+                if dr is not None:
+                    db = brho * dr
+                elif bc is not None and stretch:
+                    db = bc * dc
+                down[id(ds)] = (dc, db)
+            return down[id(ds)]
+
+        def planes(i):
+            dc, db = onGrid(i)
+            if dc is None:
+                return buoyancyPlanes(subs[i], db)
+            if stretch:
+                return velocityPlanes(subs[i], dc, db)
+            return massPlanes(subs[i], dc) if db is None else massPlanes(subs[i], dc) + buoyancyPlanes(subs[i], db)
+        data = np.zeros((sv.nrec, sv.nsrc, sv.nfreq), dtype=np.complex128)
+        st = complex(self.system.scaleTerm)
+        owned = self.ownedFreqs
+        with self._forwardFields(u) as F:
+            if isinstance(F, DeviceFields):
+                per = {i: onGrid(i) for i in F.ownedFreqs}
+                dcs = None if vc is None else {i: per[i][0] for i in per}
+                dbs = None if all(per[i][1] is None for i in per) else {i: per[i][1] for i in per}
+                data = device_survey._bornPlanesFromFields(self, F, dbs, dc=dcs, stretch=stretch or vc is None)
+                return (parallel.allreduce_sum(data) if self._sharded else data).ravel()
+            qv = [applyPlanes(planes(i), np.conj(np.asarray(F[i]) / st), subs[i].nz, subs[i].nx) / -complex(subs[i].premul) if i in owned else None
+                  for i in range(sv.nfreq)]
+            for ifreq, uB in self._solveOwned(qv):
+                uB = np.asarray(uB)
+                if sv.mode == 'fixed':
+                    data[:, :, ifreq] = sv.rVec(0, ifreq) * uB
+                else:
+                    for isrc in range(sv.nsrc):
+                        data[:, isrc, ifreq] = sv.rVec(isrc, ifreq) * uB[:, isrc]
+        if self._sharded:
+            data = parallel.allreduce_sum(data)
+        return data.ravel()
 
     @staticmethod
     def _checkLinearisation(linearisation):
@@ -771,7 +958,9 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         arrays as a list, None -> a DeviceFields solved now where the device path serves, released when the block is left whatever happened in it, else a
         host list with the owned frequencies' fields (None elsewhere).  perKy (the exact routes of a 2.5-D problem): the fields of every ky apart -- a store of
         fieldsDevice(perKy=True) (the ky-SUM store is refused with ValueError), or a host list of (nky, N, nsrc) arrays."""
-        if isinstance(u, DeviceFields):
+        if self._multiscaleServed() and not isinstance(u, DeviceFields) and (u is not None or not self._deviceGradientAvailable()):
+            yield self._ownGridFields(u)
+        elif isinstance(u, DeviceFields):
             u.checkCurrent(self, perKy=perKy)
             yield u
         elif u is not None:
@@ -806,7 +995,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
     def _JtvecTranspose(self, resid, u, linearisation='scaler', parameter='c'):
         "Jtvec(adjoint='transpose') once the model is current and `resid` is (nrec, nsrc, nfreq)"
         self._refuseMultiscale("Jtvec(adjoint='transpose')")
+        self._refuseMultiscaleScaler("Jtvec(adjoint='transpose')", linearisation)
         linearisation = self._resolveLinearisation(linearisation, parameter, 'Jtvec')
+        if self._multiscaleServed():
+            return self._JtvecMultiscale(resid, u, linearisation, parameter)
         if linearisation != 'scaler' and self._kyServed():
             return self._JtvecKy(resid, u, linearisation, parameter)
         if parameter == 'joint':
@@ -910,7 +1102,9 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         property.)  Only the forward factors are used -- those fieldsDevice has just made.  u a DeviceFields: per stored item the virtual sources are
         made from the slice on the device, solved there and sampled through the conjugated receiver CSR; nrec x k samples come down per item.  u None
         with the device path: fieldsDevice() internally, released afterwards.  u a list of host arrays, or no device path: numpy.  Sharded ranks end
-        in one all-reduce.  Multiscale surveys raise NotImplementedError.
+        in one all-reduce.  A multiscale pairing raises NotImplementedError unless the config sets multiscaleDerivatives=True: then ('operator' / 'full') the
+        perturbation goes down once per grid, dc_f = S_f v, the buoyancy perturbation is formed there (-(S_f v_rho) / rho_f^2, or Gardner's chain at c_f), and
+        the planes, the Born solve and the sampling are those of the grid of frequency f -- the exact adjoint of Jtvec on that pairing (see there).
 
         linearisation='scaler' (default) is the above: the reference's convention, delta A ~ diag(v (.) w_f).  It is NOT the derivative of `dpred`.
         linearisation='operator': the derivative of `dpred`, d/dh dpred(m + h v) at h = 0, from what the operator is assembled from:
@@ -957,7 +1151,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             self._checkParameter(parameter, linearisation, joint=True)
         self.updateModel(m)
         self._refuseMultiscale('JvecBorn')
+        self._refuseMultiscaleScaler('JvecBorn', linearisation)
         linearisation = self._resolveLinearisation(linearisation, parameter, 'JvecBorn')
+        if self._multiscaleServed():
+            return self._JvecBornMultiscale(v, u, linearisation, parameter)
         if linearisation != 'scaler' and parameter in ('c', 'Q', 'cQ') and self._isVisco():
             return self._JvecBornVisco(v, u, linearisation, parameter)
         exact = linearisation in ('operator', 'full')
@@ -1089,6 +1286,10 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             raise ValueError('Hvec(resid=) takes no data weights: the residual of a weighted misfit is the caller\'s to weigh')
         self.updateModel(m)
         self._refuseMultiscale('Hvec')
+        self._refuseMultiscaleScaler('Hvec', linearisation)
+        if resid is not None and self._multiscaleServed():
+            raise NotImplementedError('Hvec(resid=) does not serve multiscale pairings: the second derivatives of the per-grid chains and the third solve are not '
+                                      'built into the per-grid routes (resid=None, the Gauss-Newton product, is served)')
         for par in (pin, pout):
             self._resolveLinearisation(linearisation, par, 'Hvec')                      # (refusals before the fields are solved for both halves)
         if weights is not None:
@@ -1237,7 +1438,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         forward solves read off their autocorrelation planes at the lags of (-2..2)^2 (frechet.gaussNewtonDiagonal).  Every linearisation and parameter, served
         and refused as JvecBorn; for 'scaler' d A / d c_i is the diagonal weight and D[i] = |w_i|^2 sum_r |g_r[i]|^2 sum_s |u_s[i]|^2.  The receiver columns
         are solved through `adjointSystem`, so the factors of A and of A^T are resident side by side: Helm2DProblem with MiniZephyr / MiniZephyrHD on one
-        grid; the 2.5-D composite, visco problems, Eurus, 3-D and multiscale surveys raise NotImplementedError for every linearisation.  Fixed receiver arrays
+        grid; the 2.5-D composite, visco problems, Eurus, 3-D and multiscale surveys (with or without multiscaleDerivatives: diag(S^T H S) is not S^T diag(H)) raise
+        NotImplementedError for every linearisation.  Fixed receiver arrays
         only (with an array that moves with the source Gamma depends on the source and the sum does not factorise: ValueError), side must stay 'source', and
         there are no data weights: a general `weights` array of `Hvec` does not factorise either.
 
@@ -1263,6 +1465,8 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             if sv.mode != 'fixed':
                 raise ValueError('the receiver-side illumination serves fixed receiver arrays (mode is %r)' % (sv.mode,))
         self.updateModel(m)
+        if kind == 'gaussNewton' or linearisation != 'scaler':
+            self._refuseMultiscaleDiagonal('illumination(kind=%r, linearisation=%r)' % (kind, linearisation))
         if kind == 'gaussNewton' and linearisation == 'scaler':
             self._requireFullLinearisation('illumination(linearisation=\'scaler\')')      # (this kind needs the transposed 2-D operator whatever the linearisation)
             self._refuseKy('illumination(kind=\'gaussNewton\')', 'the Hessian diagonals are not built per ky (the \'scaler\' kinds \'energy\' and \'pseudoHessian\' are served)')
@@ -1283,6 +1487,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         if kind == 'gaussNewton' and linearisation != 'scaler' and (isinstance(u, DeviceFields) or (u is None and self._deviceGradientAvailable())):
             self._hermitianResidual(np.zeros((sv.nrec, 1, 1)))          # (the device route solves R^T for R^H: refused where the receiver columns are complex)
         if isinstance(u, DeviceFields):
+            self._refusePerGridStore('illumination(u=F)')
             u.checkCurrent(self)
             return device_survey.illuminationFromFields(self, u, kind, bool(perFreq), linearisation, parameter)
         if u is None and not isinstance(sv, HelmMultiGridSurvey) and self._deviceGradientAvailable():
@@ -1383,6 +1588,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
             if sv.mode != 'fixed':
                 raise ValueError('the receiver-side blocks serve fixed receiver arrays (mode is %r)' % (sv.mode,))
         self.updateModel(m)
+        self._refuseMultiscaleDiagonal('hessianBlocks')
         linearisation = self._resolveLinearisation(linearisation, 'joint', 'hessianBlocks')
         self._refuseKy('hessianBlocks', 'the per-cell blocks of the joint Hessian are not built per ky')
         self._refuseEurus('hessianBlocks', 'the per-cell blocks of the joint Hessian are not built on the derivative maps of M1')
