@@ -163,6 +163,15 @@ int helm_assemble(helm_op *op, double freq_re, double freq_im, double tau, doubl
 int helm_set_transposed(helm_op *op, int on);
 int helm_get_transposed(const helm_op *op);    /* 1: the planes in the handle (helm_get_diagonals) are those of A^T, 0: of A */
 
+/* The transposed 3-D operator, through an entry point of its own (helm_set_transposed keeps refusing 3-D handles).  on != 0: the NEXT helm_assemble of a
+ * helm_create3d handle leaves the 27 planes of A^T in it (on == 0: of A again) and helm_get_transposed returns 1.  With slot k = 9 (oz + 1) + 3 (oy + 1) + (ox + 1):
+ * CT[k][p] = C[26 - k][p + o]  where cell p + o is inside the grid, else 0 -- a permutation.  The 27-point operator is not symmetric: its rows are scaled by 1 / xi,
+ * its mass entries carry K of the column's cell.  The preconditioner of such a handle is the transpose of the cycle of A: the standard shifted cycle with its levels
+ * assembled transposed, the layer-preserving hierarchy built for A, its levels (Galerkin product included) transposed afterwards and its transfers exchanged
+ * (P^T = D^-1 R, R^T = P D).  Methods 'auto', 'mg' and 'bicgstab' solve A^T x = premul q; the apply reads the 27 stored planes (the on-the-fly coefficients
+ * rebuild A, not A^T).  What the call drops and when it takes effect: as helm_set_transposed.  Any other handle: HELM_ERR_UNSUPPORTED. */
+int helm_set_transposed3d(helm_op *op, int on);
+
 /* The transposed first block of an Eurus handle.  With eps == delta everywhere the Eurus system is block-triangular and an N-row right-hand side is solved
  * through M1 alone, u = M1^-1 q; on != 0 makes the NEXT helm_assemble leave the planes of M1^T in block 0 (on == 0: of M1 again), by the plane formula above, and
  * helm_get_transposed then returns 1.  helm_solve* with an N-row right-hand side returns conj(M1^-T (premul rhs)) through the direct path.  A handle that holds M1^T
@@ -311,6 +320,26 @@ int helm_virtual_sources_op_c64_device(helm_op *op, const void *dU32, const void
 int helm_imaging_op_accumulate_device(helm_op *op, const void *dUF, long long ldf, const void *dUB, long long ldb, int nsrc, const void *dW, void *dG);
 int helm_imaging_op_accumulate_c64_device(helm_op *op, const void *dUF32, const void *dExp, long long ldf, const void *dUB, long long ldb, int nsrc, const void *dW,
                                           void *dG);
+
+/* --- the velocity derivative of the 3-D 27-point operator on stored columns (survey3d.hip) -----------------------------------------------------
+ * With an explicit density the derivative of a helm_create3d operator along the velocity is its mass term alone, dA[dc] = M~ diag(chi dc), chi = -2 K / c,
+ * K = om~^2 / (rho c^2): M~ the constant 27-point stencil mu_o = a [o == 0] + (1 - a) m(ox) m(oy) m(oz) (a = 1/2, m(0) = 2/3, m(+-1) = 1/6) with the rows on the
+ * box boundary zeroed.
+ *
+ * helm_mass3_sources_device:  R[s ldr + i] = coef M~(W (.) X[s])[i], X[s] = U[s] or (conj != 0) conj(U[s]), s < nsrc, i < N; the boundary rows of R are exact
+ *     zeros.  U: nsrc columns of ldu >= N complex128; W: N complex128; R: nsrc columns of ldr >= N complex128, not overlapping U or W.
+ * helm_mass3_imaging_accumulate_device:  P[j] += sum_{s<nsrc} UF[s ldf + j] (M~^T UB[s])[j] for every cell j; the boundary rows of UB are masked, not read.
+ *     UF, UB: nsrc columns of ldf, ldb >= N complex128; P: N complex128, not overlapping them.  s ascending, one store per cell.
+ * helm_mass3_chain_device:  chi at the model and the damped frequency of the handle's last assembly, one call for both directions.  dDc != NULL (Born): dOut is N
+ *     complex128, dOut[j] = w chi_j dDc[j] (dDc N float64; dP is not read).  dDc == NULL (gradient): dOut is N float64, dOut[j] += Re(w chi_j dP[j]).
+ *
+ * Plain fp64 in an order the code fixes, no atomics: the same bits on every run.  3-D handles; any other handle: HELM_ERR_UNSUPPORTED.  Null pointers, nsrc < 1,
+ * a leading dimension < N, a misaligned (16 bytes; float64 arrays 8) or overlapping pointer: HELM_ERR_ARG.  All device pointers; each call returns when its
+ * result is complete. */
+int helm_mass3_sources_device(helm_op *op, const void *dU, int nsrc, long long ldu, const void *dW, double coef_re, double coef_im, int conj, void *dR,
+                              long long ldr);
+int helm_mass3_imaging_accumulate_device(helm_op *op, const void *dUF, long long ldf, const void *dUB, long long ldb, int nsrc, void *dP);
+int helm_mass3_chain_device(helm_op *op, const void *dP, double w_re, double w_im, const void *dDc, void *dOut);
 
 /* --- the derivative maps of the Eurus block M1 (eps == delta) ---------------------------------------------------------------------------------
  * A row of M1 is linear and homogeneous in the buoyancies b = 1 / rho and the mass terms K = omega_d^2 b / c^2 of the 3 x 3 (edge-clamped) cells around it; its PML

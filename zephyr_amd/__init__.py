@@ -10,11 +10,13 @@ from .discretization import BaseDiscretization, DiscretizationWrapper, prefactor
 from .distributors import (BaseDist, BaseMPDist, MultiFreq, SerialMultiFreq, ViscoMultiFreq, MultiGridHelper, MultiGridMultiFreq,
                            ViscoMultiGridMultiFreq)
 from .eurus import Eurus, EurusHD
-from .helm3d import Helm3D
+from .helm3d import Helm3D, Helm3DTransposed
 from .interpolation import BaseGridInterpolator, SplineGridInterpolator
 from .minizephyr import MiniZephyr, MiniZephyrHD, MiniZephyr25D
 from .source import (FakeSource, SimpleSource, StackedSimpleSource, SparseKaiserSource, KaiserSource,
                      AnisotropicKaiserSource)
+from .survey import Helm3DSurvey
+from .problem3d import Helm3DProblem
 
 def trim():
     'give the scratch memory libhelm caches between calls (tens of GB after large direct solves) back to the device'
@@ -25,6 +27,6 @@ def trim():
 __all__ = [
     'AnalyticalHelmholtz', 'BaseModelDependent', 'BaseAnisotropic', 'AttributeMapper', 'BaseSCCache', 'SCFilter',
     'BaseDiscretization', 'DiscretizationWrapper', 'prefactor_many', 'BaseDist', 'BaseMPDist', 'MultiFreq', 'SerialMultiFreq',
-    'ViscoMultiFreq', 'MultiGridHelper', 'MultiGridMultiFreq', 'ViscoMultiGridMultiFreq', 'BaseGridInterpolator', 'SplineGridInterpolator', 'Eurus', 'EurusHD', 'Helm3D', 'MiniZephyr', 'MiniZephyrHD', 'MiniZephyr25D', 'FakeSource', 'SimpleSource',
-    'StackedSimpleSource', 'SparseKaiserSource', 'KaiserSource', 'AnisotropicKaiserSource', 'trim',
+    'ViscoMultiFreq', 'MultiGridHelper', 'MultiGridMultiFreq', 'ViscoMultiGridMultiFreq', 'BaseGridInterpolator', 'SplineGridInterpolator', 'Eurus', 'EurusHD', 'Helm3D', 'Helm3DTransposed', 'MiniZephyr', 'MiniZephyrHD', 'MiniZephyr25D', 'FakeSource', 'SimpleSource',
+    'StackedSimpleSource', 'SparseKaiserSource', 'KaiserSource', 'AnisotropicKaiserSource', 'Helm3DSurvey', 'Helm3DProblem', 'trim',
 ]

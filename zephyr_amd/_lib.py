@@ -105,6 +105,7 @@ _SIGNATURES = {
                                      ctypes.c_double, ctypes.c_double]),
     'helm_set_transposed': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'helm_get_transposed': (ctypes.c_int, [ctypes.c_void_p]),
+    'helm_set_transposed3d': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'helm_set_transposed_m1': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'helm_set_eurus_derivatives': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int]),
     'helm_get_block_diagonals': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]),
@@ -126,6 +127,11 @@ _SIGNATURES = {
                                                          ctypes.c_void_p, ctypes.c_void_p]),
     'helm_imaging_op_accumulate_c64_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p,
                                                              ctypes.c_longlong, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]),
+    'helm_mass3_sources_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_double,
+                                                 ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong]),
+    'helm_mass3_imaging_accumulate_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_int,
+                                                            ctypes.c_void_p]),
+    'helm_mass3_chain_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p]),
     'helm_buoyancy_planes_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'helm_stencil_sources_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_double,
                                                    ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong]),

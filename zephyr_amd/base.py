@@ -12,14 +12,17 @@ class BaseModelDependent(AttributeMapper):
         'ny':             (False,    None,         np.int64),
         'nz':             (True,     None,         np.int64),
         'xorig':          (False,    '_xorig',     np.float64),
+        'yorig':          (False,    '_yorig',     np.float64),
         'zorig':          (False,    '_zorig',     np.float64),
         'dx':             (False,    '_dx',        np.float64),
+        'dy':             (False,    '_dy',        np.float64),
         'dz':             (False,    '_dz',        np.float64),
         'freeSurf':       (False,    '_freeSurf',  tuple),
     }
 
     # optional geometry keys and what they default to (base.py:31-65): a name means "the value of that attribute"
-    _GEOMETRY_DEFAULTS = (('xorig', 0.), ('zorig', 0.), ('dx', 1.), ('dz', 'dx'), ('freeSurf', (False, False, False, False)))
+    # (yorig and dy, the geometry of a 3-D grid, default as their x twins do: 0 and dx)
+    _GEOMETRY_DEFAULTS = (('xorig', 0.), ('yorig', 0.), ('zorig', 0.), ('dx', 1.), ('dy', 'dx'), ('dz', 'dx'), ('freeSurf', (False, False, False, False)))
 
     def __getattr__(self, name):
         # (reached only when `name` is not set: initMap stores a given value under '_' + name)
@@ -33,8 +36,9 @@ class BaseModelDependent(AttributeMapper):
 
     @property
     def modelDims(self):
+        '(nz, nx); with `ny` in the config (a 3-D grid) (nz, ny, nx), x fastest'
         if hasattr(self, 'ny'):
-            raise NotImplementedError('3-D model geometry is not part of the 2-D operator path')
+            return (self.nz, self.ny, self.nx)
         return (self.nz, self.nx)
 
     @property
@@ -42,11 +46,15 @@ class BaseModelDependent(AttributeMapper):
         return int(np.prod(self.modelDims))
 
     def toLinearIndex(self, vec):
-        """(n,2) array of (iz, ix) grid indices -> linear index iz*nx + ix (base.py:77-93)."""
+        """(n,2) array of (iz, ix) grid indices -> linear index iz*nx + ix (base.py:77-93); with `ny`: (n,3) of (iz, iy, ix) -> (iz*ny + iy)*nx + ix."""
+        if hasattr(self, 'ny'):
+            return (vec[:, 0] * self.ny + vec[:, 1]) * self.nx + vec[:, 2]
         return vec[:, 0] * self.nx + vec[:, 1]
 
     def toVecIndex(self, lind):
-        """linear index -> (n,2) array of (iz, ix) (base.py:95-109)."""
+        """linear index -> (n,2) array of (iz, ix) (base.py:95-109); with `ny`: (n,3) of (iz, iy, ix)."""
+        if hasattr(self, 'ny'):
+            return np.array([lind // (self.ny * self.nx), np.mod(lind // self.nx, self.ny), np.mod(lind, self.nx)]).T
         return np.array([lind // self.nx, np.mod(lind, self.nx)]).T
 
 

@@ -316,6 +316,23 @@ extern "C" int helm_set_transposed_m1(helm_op *op, int on) {
     op->direct_failed = false;
     return HELM_OK;
 }
+// The same for a 3-D handle (helm_create3d), through an entry point of its own as Eurus has one: the next helm_assemble leaves the 27 planes of A^T in the handle
+// (k_transpose_planes3), the levels of both multigrid set-ups are then transposed too and the apply reads stored planes.  Any other handle: HELM_ERR_UNSUPPORTED.
+extern "C" int helm_set_transposed3d(helm_op *op, int on) {
+    helm_tuning_refresh();
+    if (!op) return HELM_ERR_ARG;
+    if (op->variant != HELM_3D || op->ny <= 0) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "helm_set_transposed3d: the 27 transposed planes exist for 3-D handles (helm_create3d); 2-D MiniZephyr handles take helm_set_transposed");
+    const bool want = on != 0;
+    if (want == op->transposed_next) return HELM_OK;
+    HIP_TRY(op, hipSetDevice(op->device));
+    helm_pf_retire(op);
+    op->transposed_next = want;
+    op->scaled_ok = false;
+    if (op->mg || op->mg3) mg_destroy(op);
+    op->mg3_no_keep = false;
+    op->direct_failed = false;
+    return HELM_OK;
+}
 // on != 0: helm_stencil_sources[_c64]_device and helm_lag_imaging_accumulate[_c64]_device, which read nothing but nine planes and the grid, serve this 2-D Eurus
 // handle (the derivative routes of an Eurus problem run them on the planes of helm_eurus_planes_device); 0, the default: they refuse it as they always did.
 extern "C" int helm_set_eurus_derivatives(helm_op *op, int on) {

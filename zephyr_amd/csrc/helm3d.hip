@@ -96,6 +96,28 @@ __global__ __launch_bounds__(256) void k_kb_3d(Asm3Params P, const cplx *__restr
     }
 }
 
+// The 27 planes of A^T from the 27 planes of A (helm_set_transposed3d).  Row p of A holds A[p][p + o] = C[k(o)][p]; hence
+// A^T[p][p + o] = A[p + o][p] = C[k(-o)][p + o] with k(-o) = 26 - k(o), and zero where the cell p + o lies outside the grid (the test is per axis: p + o of a
+// cell at a row end is a valid linear index of the next grid row).  A pure permutation, out of place: one lane per cell, 27 loads and 27 stores that are each
+// contiguous across the wave, no arithmetic, no atomics.  Every read is at a cell inside the grid, so nothing outside [0, 27 N) is addressed.
+__global__ __launch_bounds__(256) void k_transpose_planes3(const cplx *__restrict__ C, cplx *__restrict__ CT, int nz, int ny, int nx) {
+    const long long N = (long long)nz * ny * nx;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= N) return;
+    const int ix = (int)(i % nx), iy = (int)((i / nx) % ny), iz = (int)(i / ((long long)nx * ny));
+#pragma unroll 1
+    for (int oz = -1; oz <= 1; ++oz)
+#pragma unroll 1
+        for (int oy = -1; oy <= 1; ++oy)
+#pragma unroll
+            for (int ox = -1; ox <= 1; ++ox) {
+                const int k = 9 * (oz + 1) + 3 * (oy + 1) + (ox + 1);
+                const bool in = iz + oz >= 0 && iz + oz < nz && iy + oy >= 0 && iy + oy < ny && ix + ox >= 0 && ix + ox < nx;
+                const long long j = i + ((long long)oz * ny + oy) * nx + ox;
+                CT[(long long)k * N + i] = in ? C[(long long)(26 - k) * N + j] : cmake(0.0, 0.0);
+            }
+}
+
 // ---- batched 27-point apply -----------------------------------------------------------------------
 struct Stencil3Params {
     const cplx *planes;      // 27 planes, stride N
@@ -372,6 +394,24 @@ int helm3d_launch_assemble(helm_op *op, double freq_re, double freq_im, double t
         op->otf3 = true;
     }
     HIP_TRY(op, hipStreamSynchronize(op->stream));
+    if (op->transposed) { const int rct = helm3d_launch_transpose_planes(op); if (rct) return rct; }
+    return HELM_OK;
+}
+
+// d_C <- the 27 planes of its transpose: into a pool buffer of the planes' own size class, which then takes d_C's place (as helm_launch_transpose_planes does
+// in 2-D).  On op->stream, behind the assembly it follows; returns when the planes are complete.  K, b and the factor tables still describe A, so the
+// on-the-fly apply is switched off for this handle: a transposed handle applies from its stored planes (helm3d_launch_apply).
+int helm3d_launch_transpose_planes(helm_op *op) {
+    if (op->ny <= 0 || op->nblocks != 1 || op->nplanes != 27) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "helm3d_launch_transpose_planes: a 3-D handle of 27 planes is what it transposes");
+    const size_t bytes = (size_t)27 * (size_t)op->N * sizeof(cplx);
+    cplx *d_T = (cplx *)helm_pool_alloc(op->device, bytes);
+    if (!d_T) HELM_FAIL(op, HELM_ERR_DEVICE, "hipMalloc of the transposed coefficient planes failed");
+    HELM_LAUNCH(k_transpose_planes3, dim3((unsigned)((op->N + 255) / 256)), dim3(256), 0, op->stream, (const cplx *)op->d_C, d_T, op->nz, op->ny, op->nx);
+    const hipError_t e1 = hipGetLastError(), e2 = hipStreamSynchronize(op->stream);
+    if (e1 != hipSuccess || e2 != hipSuccess) { helm_pool_free(op->device, d_T, bytes); HIP_TRY(op, e1); HIP_TRY(op, e2); }
+    helm_pool_free(op->device, op->d_C, bytes);       // (nothing reads the old planes any more: the stream is drained)
+    op->d_C = d_T;
+    op->otf3 = false;
     return HELM_OK;
 }
 
@@ -431,7 +471,10 @@ int helm3d_launch_apply(helm_op *op, const ApplyArgs &a, hipEvent_t e0, hipEvent
     const int per_wg = (a.nrhs + split - 1) / split;
     // mg3_otf: 0 stored planes; 1 on the fly where it pays (from 4 right-hand sides per workgroup up); 2 wherever it is possible (tests)
     const int otf_mode = helm_tuning_now().mg3_otf;
-    const bool otf = op->otf3 && a.planes == op->d_C && !a.scaled && (otf_mode == 2 || (otf_mode == 1 && per_wg >= 4));
+    // A transposed handle (helm_set_transposed3d) never takes it: K, b and the factor tables rebuild A, not A^T, so A^T is applied from its 27 stored planes --
+    // the 432 B per point the rebuild saves, 46 % of the launch's bytes at 16 right-hand sides, are read again.  (A transposed on-the-fly apply would need the
+    // row's own stretch factors of the NEIGHBOUR: not built.)
+    const bool otf = op->otf3 && !op->transposed && a.planes == op->d_C && !a.scaled && (otf_mode == 2 || (otf_mode == 1 && per_wg >= 4));
     q.K3 = op->d_K3; q.b3 = op->d_b3; q.Lx = op->d_L3; q.Ly = op->d_L3 ? op->d_L3 + 3 * (size_t)op->nx : nullptr;
     q.Lz = op->d_L3 ? op->d_L3 + 3 * (size_t)op->nx + 3 * (size_t)op->ny : nullptr;
     q.idx2 = op->otf_idx2; q.idy2 = op->otf_idy2; q.idz2 = op->otf_idz2; q.blend = op->otf_blend;

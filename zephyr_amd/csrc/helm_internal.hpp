@@ -374,6 +374,7 @@ int helm_stencil_tile_rows();     // rows of the 64-wide stencil tile (4 * STENC
 
 // ---- 3-D operator (helm3d.hip) -------------------------------------------------------------------
 int helm3d_launch_assemble(helm_op *op, double freq_re, double freq_im, double tau, double cPML);
+int helm3d_launch_transpose_planes(helm_op *op);   // d_C (27 planes) <- the planes of its transpose, out of place through a pool buffer, on op->stream; on-the-fly apply off
 int helm3d_launch_apply(helm_op *op, const ApplyArgs &a, hipEvent_t e0, hipEvent_t e1);
 int helm3d_apply_num_blocks(const helm_op *op);
 

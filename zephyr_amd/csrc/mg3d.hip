@@ -160,6 +160,21 @@ __global__ void k3_prolong_add_t(const cplx *__restrict__ coarse, TF *__restrict
     }
 }
 
+// coarse vector (.)= the product of the three axes' wc (INV: its reciprocal), per right-hand side.  The restriction of the tables is R = D P^T with
+// D = diag(wc_z wc_y wc_x) (mg3_keep.hip coarsen_axis normalises every row of P^T), so D^-1 (R r) = P^T r and P (D u) = R^T u: the transfers of the transposed
+// cycle, which a transposed handle runs (cycle_keep).
+__global__ void k3_scale_rt(cplx *__restrict__ v, int nzc, int nyc, int nxc, const RTab *__restrict__ tz, const RTab *__restrict__ ty, const RTab *__restrict__ tx,
+                            int inv) {
+    const long long Nc = (long long)nzc * nyc * nxc;
+    cplx *vb = v + (long long)blockIdx.y * Nc;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < Nc; i += (long long)gridDim.x * blockDim.x) {
+        const int X = (int)(i % nxc), Y = (int)((i / nxc) % nyc), Z = (int)(i / ((long long)nxc * nyc));
+        const double d = tz[Z].wc * ty[Y].wc * tx[X].wc, f = inv ? 1.0 / d : d;
+        const cplx a = vb[i];
+        vb[i] = cmake(a.x * f, a.y * f);
+    }
+}
+
 // smallest Re(c) of the model, on the device (positive doubles order like their bit patterns)
 __global__ void k3_min_re(const cplx *__restrict__ c, long long n, unsigned long long *out) {
     double m = 1e300;
@@ -227,7 +242,11 @@ int cycle_keep(helm_op *op, Mg3Precond *P, size_t l, int nrhs, cplx *final_out =
                          (const RTab *)K->rt[0][l], (const RTab *)K->rt[1][l], (const RTab *)K->rt[2][l]);
     else HELM_LAUNCH(k3_restrict_t<cplx>, vgrid(C.N, nrhs), dim3(256), 0, st, (const cplx *)L.r, C.f, L.ny, L.nx, C.nz, C.ny, C.nx, L.N,
                        (const RTab *)K->rt[0][l], (const RTab *)K->rt[1][l], (const RTab *)K->rt[2][l]);
+    // a transposed handle runs the transpose of the cycle of A: restriction P^T = D^-1 R, prolongation R^T = P D (k3_scale_rt; the levels hold A_l^T)
+    const bool tr = op->transposed;
+    if (tr) HELM_LAUNCH(k3_scale_rt, vgrid(C.N, nrhs), dim3(256), 0, st, C.f, C.nz, C.ny, C.nx, (const RTab *)K->rt[0][l], (const RTab *)K->rt[1][l], (const RTab *)K->rt[2][l], 1);
     rc = cycle_keep(op, P, l + 1, nrhs); if (rc) return rc;
+    if (tr) HELM_LAUNCH(k3_scale_rt, vgrid(C.N, nrhs), dim3(256), 0, st, C.u, C.nz, C.ny, C.nx, (const RTab *)K->rt[0][l], (const RTab *)K->rt[1][l], (const RTab *)K->rt[2][l], 0);
     if (f32) HELM_LAUNCH(k3_prolong_add_t<cplxf>, vgrid(L.N, nrhs), dim3(256), 0, st, (const cplx *)C.u, (cplxf *)L.u, L.nz, L.ny, L.nx, C.ny, C.nx, C.N,
                          (const PTab *)K->pt[0][l], (const PTab *)K->pt[1][l], (const PTab *)K->pt[2][l]);
     else HELM_LAUNCH(k3_prolong_add_t<cplx>, vgrid(L.N, nrhs), dim3(256), 0, st, (const cplx *)C.u, L.u, L.nz, L.ny, L.nx, C.ny, C.nx, C.N,
@@ -327,6 +346,9 @@ int mg3_setup(helm_op *op, int batch) {
         P->lv.push_back(L);
         Mg3Level &Lr = P->lv.back();
         if (helm_set_stream(Lr.op, op->stream)) return fail(HELM_ERR_DEVICE, "3-D multigrid: cannot share the stream");
+        // the levels of a transposed operator's preconditioner are transposed too.  Here R = P^T / 8 (a constant) and the smoother is point Jacobi, so
+        // the cycle of the transposed levels with the same transfers IS the transpose of the cycle of A; the layer-preserving hierarchy has more to do (mg3_keep.hip)
+        Lr.op->transposed_next = op->transposed;
         rc = helm_set_model(Lr.op, (const double *)c.data(), rho.data(), nullptr, nullptr, nullptr);
         if (!rc) rc = helm_assemble(Lr.op, op->a_freq_re, op->a_freq_im, tauM, 0.0, cpml);
         if (!rc) rc = helm_ensure_scaled(Lr.op);

@@ -1,0 +1,108 @@
+"""Device pipelines of the exact 3-D derivative: `Helm3DProblem.Jtvec(adjoint='transpose', linearisation='operator')` and `JvecBorn(linearisation='operator')`
+over forward fields in HBM.  The loops, the workspaces and the item steps are those of device_survey.py (`runOnDevices`, `Workspace`, `_backSources`,
+`_sampling`, the stored items of a `DeviceFields`); what differs is what an item runs between them -- the three kernels of csrc/survey3d.hip.
+
+    pipeline               items    what fills R                                   columns solved   what consumes U                          what comes down
+    bornFromFields3        stored   -(1 / premul) M~(chi dc (.) conj(slice))        k (A)            sampleDevice, receivers as they are      nrec x k samples per item
+    gradientFromFields3    stored   qb of R^H r                                    k (A^T)          k_mass3_imaging into P, then the chain   one float64 partial G per worker
+
+The sampling and back-source kernels work on op.N rows and CSR rows: nothing in them knows the grid's dimension.  Nothing of size N k crosses to the host.
+A 3-D item builds its multigrid hierarchy in the prepare step of `runOnDevices` (Helm3D.heavyPrepare: strictly one item ahead), for the forward and for the
+transposed wrapper alike.
+"""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from . import parallel
+from .device_survey import _backSources, _partial, _prepareBackSources, _sampling, _storedItems, runOnDevices
+
+
+def _p(t):
+    return ctypes.c_void_p(t if isinstance(t, int) else t.data_ptr())
+
+
+def massSourcesDevice(op, d_u, nsrc, d_w, coef, d_r, conj=True, ldu=None, ldr=None):
+    'R[s] = coef M~(W (.) conj-or-not(U[s])) on the device (helm_mass3_sources_device); all device pointers, leading dimensions default to N'
+    N = int(op.nrow)
+    coef = complex(coef)
+    _lib.check(_lib.load().helm_mass3_sources_device(op.handle, _p(d_u), int(nsrc), int(N if ldu is None else ldu), _p(d_w), coef.real, coef.imag, 1 if conj else 0,
+                                                     _p(d_r), int(N if ldr is None else ldr)), op.handle)
+
+
+def massImagingAccumulateDevice(op, d_uf, d_ub, nsrc, d_p, ldf=None, ldb=None):
+    'P += sum_s UF[s] (.) M~^T UB[s] on the device (helm_mass3_imaging_accumulate_device)'
+    N = int(op.nrow)
+    _lib.check(_lib.load().helm_mass3_imaging_accumulate_device(op.handle, _p(d_uf), int(N if ldf is None else ldf), _p(d_ub), int(N if ldb is None else ldb), int(nsrc),
+                                                                _p(d_p)), op.handle)
+
+
+def massChainDevice(op, d_p, w, d_dc, d_out):
+    'd_dc given: out = w chi dc (N complex128); d_dc None: out += Re(w chi P) (N float64) -- chi at the model and frequency of the handle (helm_mass3_chain_device)'
+    w = complex(w)
+    _lib.check(_lib.load().helm_mass3_chain_device(op.handle, None if d_p is None else _p(d_p), w.real, w.imag, None if d_dc is None else _p(d_dc), _p(d_out)), op.handle)
+
+
+def bornFromFields3(prob, F, dc):
+    """Born data (nrec, nsrc, nfreq) of the velocity perturbation dc (N,) float64 from forward fields in HBM.  Per stored item: W = chi dc on the item's GPU
+    (dc goes up once per worker), R = -(1 / premul) M~(W (.) conj(slice)) -- the slice is conj(u^), unscaled --, the forward operator solves the k columns and
+    the samples through the receiver CSR come down, times the scaleTerm."""
+    import torch
+    F.checkCurrent(prob)
+    data, stage, sample = _sampling(prob, F.ownedFreqs, F.scale)
+    if not F.items:
+        return data
+    dc = np.ascontiguousarray(dc, dtype=np.float64)
+    devs, items = _storedItems(prob.system, F)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        dev = ws.device
+        d_uF, _ = F.pointers(ifreq, c0)
+        staged = stage(ws, ifreq, c0, c1)
+        vd = ws.cached(('born3_dc', id(dc)), lambda: _lib.to_device(dc, dev, np.float64), keep=dc)
+        W, U, R = ws.buffer('W3', Ni), ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
+        _lib.wait_torch_stream(dev)
+        massChainDevice(op, None, 1.0, vd, W)
+        massSourcesDevice(op, d_uF, k, W, -1.0 / complex(op.premul), R, conj=True)
+        op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+        sample(op, ifreq, c0, c1, staged, U.data_ptr())
+    runOnDevices(devs, items, one)
+    return data
+
+
+def gradientFromFields3(prob, F, qb, resid, system):
+    """J^T r, float64 (N,), from forward fields in HBM: per stored item the k back-sources R_s^H r_s are made on the item's GPU (qb / resid those of the
+    Hermitian residual) and solved through the TRANSPOSED operator of `system`; U = conj(z~), z~ = premul A^-T R^H r.  k_mass3_imaging forms
+    P = sum_s slice_s (.) M~^T U_s = conj(sum_s u^_s (.) M~^T z~_s), torch conjugates the one N-plane, and the chain kernel adds Re(w chi conj(P)),
+    w = -conj(scaleTerm) / premul, to the worker's float64 partial.  The partials are summed on the host, then ONE all-reduce over ranks when sharded."""
+    import torch
+    F.checkCurrent(prob)
+    sv = prob.survey
+    N = prob.nrow
+    scale = F.scale
+    parts = []
+    if F.items:
+        _prepareBackSources(sv, qb, F.ownedFreqs)
+        devs, items = _storedItems(system, F)
+
+        def one(ws, op, ifreq, c0, c1):
+            k, Ni = c1 - c0, int(op.nrow)
+            d_uF, _ = F.pointers(ifreq, c0)
+            G = _partial(ws, 'H', N, torch.float64)          # (the workspace's float64 partial: this call accumulates nothing else there)
+            P, U, R = ws.buffer('P3', Ni), ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
+            _backSources(ws, sv, op, qb, resid, ifreq, c0, c1, R.data_ptr(), Ni)
+            P.zero_()
+            _lib.wait_torch_stream(ws.device)
+            op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+            massImagingAccumulateDevice(op, d_uF, U, k, P)
+            torch.conj_physical_(P)
+            _lib.wait_torch_stream(ws.device)
+            massChainDevice(op, P, -np.conj(scale) / complex(op.premul), None, G)
+        parts = [ws.H for ws in runOnDevices(devs, items, one) if ws.H is not None]
+    g = np.zeros(N, dtype=np.float64)
+    for G in parts:
+        torch.cuda.synchronize(G.device)
+        g += _lib.from_device(G)
+    return parallel.allreduce_sum(g) if prob._sharded else g

@@ -50,7 +50,7 @@ class BaseDiscretization(BaseModelDependent):
         'transposed':     (False,    None,         bool),       # the operator is A^T: `obj * rhs` -> conj(A^-T (premul * rhs)) (helm_set_transposed)
     }
 
-    TRANSPOSABLE = False       # classes whose device operator has a transposed assembly (the 2-D MiniZephyr family)
+    TRANSPOSABLE = False       # classes whose device operator has a transposed assembly (the 2-D MiniZephyr family; Helm3DTransposed is a class of its own)
     _SET_TRANSPOSED = 'helm_set_transposed'      # the entry point that asks the handle for the transposed planes (Eurus: helm_set_transposed_m1)
 
     # ---- model properties -----------------------------------------------------------------
@@ -87,7 +87,7 @@ class BaseDiscretization(BaseModelDependent):
     @property
     def transposed(self):
         """config key (default False): the device operator is assembled as A^T, so that `self * rhs` is conj(A^-T (premul * rhs)) -- what back-propagates a
-        residual exactly when A is not symmetric (HelmBaseProblem.Jtvec(adjoint='transpose')).  The 2-D MiniZephyr family only."""
+        residual exactly when A is not symmetric (HelmBaseProblem.Jtvec(adjoint='transpose')).  The 2-D MiniZephyr family only (the 3-D operator: the class Helm3DTransposed)."""
         return bool(self.__dict__.get('_transposed', False))
 
     @transposed.setter

@@ -7,6 +7,11 @@ freq, tau, premul, nPML, cPML) and the same result convention conj(A^-1 (premul 
 defined in oracle/helm3d_oracle.py (trilinear-element-weighted 27-point star, C-PML on all six faces).
 Solves: BiCGSTAB right-preconditioned by the layer-preserving 3-D multigrid of libhelm (mg3d.hip) whose coarsest level is solved directly;
 Jacobi-preconditioned BiCGSTAB / CGNR on request.
+
+`Helm3DTransposed` is the same operator assembled as A^T (helm_set_transposed3d): the handle holds the 27 planes of A^T, the preconditioner is the transpose of
+the cycle of A, and `op * rhs` is conj(A^-T (premul rhs)) -- what back-propagates a residual exactly: A is not symmetric (the stretch factors scale its rows, the
+mass term carries K of the column's cell).  It applies from its stored planes; methods 'auto', 'mg' and 'bicgstab' serve it ('cgnr' needs an adjoint apply,
+which the 3-D operator never had).  `Helm3D` itself refuses the config key `transposed`, as it always did; `Helm3D.Transposed` names the class.
 """
 import ctypes
 import numpy as np
@@ -78,6 +83,8 @@ class Helm3D(BaseDiscretization):
                 c = _lib.c128(self.c.reshape(self.modelDims))
                 rho = _lib.f64(self.rho.reshape(self.modelDims))
                 _lib.check(lib.helm_set_model(h, _lib.ptr(c), _lib.ptr(rho), None, None, None), h)
+                if self.transposed:
+                    _lib.check(getattr(lib, self._SET_TRANSPOSED)(h, 1), h)
                 f = complex(self.freq)
                 _lib.check(lib.helm_assemble(h, f.real, f.imag, float(self.tau), 0.0, float(self.cPML)), h)
             except Exception:
@@ -108,3 +115,23 @@ class Helm3D(BaseDiscretization):
                 rows.append(((iz * ny + iy) * nx + ix)[ok]); cols.append(((jz * ny + jy) * nx + jx)[ok]); vals.append(C[k][ok])
             self._A = sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(N, N)).tocsr()
         return self._A
+
+
+class Helm3DTransposed(Helm3D):
+    """Helm3D assembled as A^T: `self * rhs` is conj(A^-T (premul rhs)).  The same config as Helm3D (no `transposed` key: the class says it); what
+    Helm3DProblem.adjointSystem is made of.  k_transpose_planes3 permutes the 27 planes after every assembly."""
+
+    TRANSPOSABLE = True
+    _SET_TRANSPOSED = 'helm_set_transposed3d'
+
+    @property
+    def transposed(self):
+        return True
+
+    @transposed.setter
+    def transposed(self, value):
+        if not value:
+            raise ValueError('Helm3DTransposed is the transposed operator: Helm3D is the plain one')
+
+
+Helm3D.Transposed = Helm3DTransposed

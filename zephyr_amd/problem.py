@@ -128,7 +128,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         Jtvec(adjoint='transpose') back-propagates through.  It goes with the problem's cache on a model change, and `del prob.factors` releases it too.
         While both wrappers are in use the factors of A_f and of A_f^T are resident side by side: twice the device memory of `system` alone.
         2-D MiniZephyr / MiniZephyrHD / MiniZephyr25D on one grid, and Eurus / EurusHD with eurusDerivatives=True and eps == delta (M1^T, helm_set_transposed_m1);
-        Eurus otherwise and the 3-D operator raise NotImplementedError; so do the multiscale wrappers unless the config sets multiscaleDerivatives=True (then the
+        Eurus otherwise and the 3-D operator raise NotImplementedError (Helm3DProblem has an adjointSystem of its own); so do the multiscale wrappers unless the config sets multiscaleDerivatives=True (then the
         transposed operator of every frequency lives on that frequency's grid)."""
         if getattr(self, '_adjointSystem', None) is None:
             from .distributors import MultiGridMultiFreq

@@ -2,7 +2,8 @@
 
 Host-side input producers of the hot path: a unit delta at the nearest node, the stacked
 (2N) variant used with Eurus, and Hicks' Kaiser-windowed-sinc point sources returned as a
-scipy sparse (N, nsrc) matrix.  Locations are physical (x, z) pairs.
+scipy sparse (N, nsrc) matrix.  Locations are physical (x, z) pairs; with `ny` in the config (a 3-D grid, which the reference
+refuses: source.py:43-44) they are (x, y, z) triples and the Kaiser patch is the separable product of the same 1-D responses.
 """
 import warnings
 import numpy as np
@@ -29,14 +30,33 @@ class SimpleSource(BaseSource):
     def __init__(self, systemConfig):
         BaseSource.__init__(self, systemConfig)
         if hasattr(self, 'ny'):
-            raise NotImplementedError('Sources not implemented for 3D case')
+            if not self.SERVES_3D:
+                raise NotImplementedError('%s has no 3-D form (`ny` is in the config): SimpleSource, SparseKaiserSource and KaiserSource serve (x, y, z) '
+                                          'locations' % (type(self).__name__,))
+            return                  # (3-D: the nearest node is found per axis, no (nsrc, nz, ny, nx) distance field is built)
         nz, nx = int(self.nz), int(self.nx)
         # node coordinates exactly as np.mgrid[orig : orig + d*n : d] produces them (source.py:51-54)
         self._z, self._x = np.mgrid[self.zorig:self.zorig + self.dz * nz:self.dz,
                                     self.xorig:self.xorig + self.dx * nx:self.dx]
 
+    SERVES_3D = True         # (classes that have no 3-D form refuse `ny` in their constructor)
+
+    def _axes3(self):
+        '(origin, spacing, nodes) of the x, y and z axes of a 3-D grid, in the order of a location triple'
+        return ((self.xorig, self.dx, int(self.nx)), (self.yorig, self.dy, int(self.ny)), (self.zorig, self.dz, int(self.nz)))
+
+    def _nearest3(self, loc):
+        """(ix, iy, iz) of the node nearest to each (x, y, z) location, int64 (nsrc,) each.  The squared distance is a sum over the axes, so its first
+        minimum in linear-index order -- what np.argmin of the full distance field returns -- is the first minimum of every axis."""
+        loc = np.asarray(loc, dtype=np.float64)
+        if loc.ndim != 2 or loc.shape[1] != 3:
+            raise ValueError('with `ny` in the config locations are (x, y, z) triples: an array of shape (n, 3), not %s' % (loc.shape,))
+        return tuple(np.argmin(np.abs((o + d * np.arange(n))[None, :] - loc[:, a:a + 1]), axis=1) for a, (o, d, n) in enumerate(self._axes3()))
+
     def dist(self, loc):
         'distance of every node from every location, shape (nsrc, nz, nx) (source.py:56-77)'
+        if hasattr(self, 'ny'):
+            raise NotImplementedError('dist() builds the 2-D distance field: a 3-D grid finds its nearest nodes per axis (linIndexOf)')
         loc = np.asarray(loc)
         n = len(loc)
         ddx = self._x[None, :, :] - loc[:, 0].reshape((n, 1, 1))
@@ -45,6 +65,9 @@ class SimpleSource(BaseSource):
 
     def linIndexOf(self, loc):
         'linear index of the nearest node (first minimum, as np.argmin) (source.py:83-88)'
+        if hasattr(self, 'ny'):
+            ix, iy, iz = self._nearest3(loc)
+            return (iz * int(self.ny) + iy) * int(self.nx) + ix
         n = np.asarray(loc).shape[0]
         return np.argmin(self.dist(loc).reshape((n, -1)), axis=1)
 
@@ -61,6 +84,8 @@ class SimpleSource(BaseSource):
 
 class StackedSimpleSource(SimpleSource):
     """SimpleSource augmented with N zero rows for the second Eurus field (source.py:110-119)."""
+
+    SERVES_3D = False        # (Eurus is 2-D: there is no second field to stack in 3-D)
 
     def __call__(self, loc):
         q = SimpleSource.__call__(self, loc)
@@ -107,8 +132,52 @@ class SparseKaiserSource(SimpleSource):
         respX = np.sinc(dX) * (i0(b * tX) / i0(b))
         return respX * respZ
 
+    def _response1(self, off):
+        'the 2 ireg + 1 windowed-sinc responses of one axis for a source `off` cells off its nearest node: the 1-D factor of `kws`'
+        ireg = int(self.ireg)
+        b = self.HC_KAISER.get(ireg)
+        d = off + ireg - np.arange(2 * ireg + 1)
+        with warnings.catch_warnings():
+            warnings.simplefilter('ignore')
+            t = np.nan_to_num(np.sqrt(1 - (d / ireg) ** 2))
+            t[t == np.inf] = 0
+        return np.sinc(d) * (i0(b * t) / i0(b))
+
+    def _call3(self, sLocs):
+        """3-D: sparse (N, nsrc) right-hand sides, column s the separable (2 ireg + 1)^3 product of the 1-D responses of its three offsets, scaled by
+        1 / (dx dy dz) and clipped at the six faces; ireg = 0: the scaled delta.  The 3-D operator has no free surface."""
+        if any(self.freeSurf):
+            raise ValueError('freeSurf is %r: the 3-D operator has no free surface (C-PML on all six faces); leave freeSurf out of a 3-D config' % (tuple(self.freeSurf),))
+        sLocs = np.asarray(sLocs, dtype=np.float64)
+        ireg = int(self.ireg)
+        nsrc = sLocs.shape[0]
+        nz, ny, nx = int(self.nz), int(self.ny), int(self.nx)
+        N = nz * ny * nx
+        scale = 1. / (self.dx * self.dy * self.dz)
+        idx = self._nearest3(sLocs)
+        if ireg == 0:
+            node = (idx[2] * ny + idx[1]) * nx + idx[0]
+            return sp.coo_matrix((scale * np.ones(nsrc, dtype=np.complex128), (np.arange(nsrc), node)), shape=(nsrc, N)).T
+        data, rows, cols = [], [], []
+        for i in range(nsrc):
+            resp, where = [], []
+            for a, (o, d, n) in enumerate(self._axes3()):
+                node = int(idx[a][i])
+                r = self._response1(sLocs[i, a] - o - node * d)
+                j = node + np.arange(-ireg, ireg + 1)
+                keep = (j >= 0) & (j < n)                       # (clipped at the two faces of this axis)
+                resp.append(r[keep]); where.append(j[keep])
+            (rx, ry, rz), (jx, jy, jz) = resp, where
+            patch = scale * (rz[:, None, None] * ry[None, :, None] * rx[None, None, :])
+            lin = (jz[:, None, None] * ny + jy[None, :, None]) * nx + jx[None, None, :]
+            data.append(patch.ravel()); cols.append(lin.ravel()); rows.append(np.full(patch.size, i))
+        q = sp.coo_matrix((np.concatenate(data).astype(np.complex128), (np.concatenate(rows), np.concatenate(cols))), shape=(nsrc, N), dtype=np.complex128)
+        return q.T
+
     def __call__(self, sLocs):
         'sparse (N, nsrc) right-hand sides; patches are clipped (or mirrored with sign flip under a free surface) at the edges (source.py:213-317)'
+        if hasattr(self, 'ny'):
+            return self._call3(sLocs)
         sLocs = np.asarray(sLocs)
         ireg = int(self.ireg)
         fs = self.freeSurf
@@ -182,6 +251,8 @@ class KaiserSource(SparseKaiserSource):
 
 class AnisotropicKaiserSource(SparseKaiserSource, BaseAnisotropic):
     'Kaiser source on the anisotropically stretched local grid (source.py:337-351)'
+
+    SERVES_3D = False        # (theta, eps and delta are fields of the 2-D anisotropic operators)
 
     def modifyGrid(self, Zi, Xi, aZi, aXi):
         theta = self.theta[aZi, aXi]

@@ -317,6 +317,22 @@ class Helm2DSurvey(HelmBaseSurvey):
     pass
 
 
+class Helm3DSurvey(HelmBaseSurvey):
+    """Survey on a 3-D grid (no counterpart in the reference, whose sources refuse `ny`): the config carries nx, ny, nz (and dx, dy, dz, the origins), and
+    `geom` (x, y, z) triples as source and receiver locations -- for mode 'relative' the receiver triples are offsets from each source.  Everything else is
+    HelmBaseSurvey: the source generator (SparseKaiserSource by default, its separable 3-D form) makes the columns of S and the rows of R on the one grid, and
+    `dpred`, the stacked receivers and the adjoint plan work on N = nz ny nx rows.  Pairs with Helm3DProblem only."""
+
+    def __init__(self, systemConfig, **kwargs):
+        if systemConfig.get('ny', None) is None:
+            raise ValueError('Helm3DSurvey requires parameter \'ny\': without it the config describes a 2-D grid (Helm2DSurvey)')
+        HelmBaseSurvey.__init__(self, systemConfig, **kwargs)
+        for name, key in (('sLocs', 'src'), ('rLocs', 'rec')):
+            locs = getattr(self, name)
+            if locs is not None and (np.ndim(locs) != 2 or np.shape(locs)[1] != 3):
+                raise ValueError('geom[%r] of a Helm3DSurvey is an (n, 3) array of (x, y, z) locations, not of shape %s' % (key, np.shape(locs)))
+
+
 class Helm2DMultiGridSurvey(Helm2DSurvey, HelmMultiGridSurvey):
     'zephyr/middleware/survey.py:337-340'
     pass
