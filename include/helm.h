@@ -341,6 +341,28 @@ int helm_mass3_sources_device(helm_op *op, const void *dU, int nsrc, long long l
 int helm_mass3_imaging_accumulate_device(helm_op *op, const void *dUF, long long ldf, const void *dUB, long long ldb, int nsrc, void *dP);
 int helm_mass3_chain_device(helm_op *op, const void *dP, double w_re, double w_im, const void *dDc, void *dOut);
 
+/* --- the buoyancy derivative of the 3-D 27-point operator on stored columns (survey3d_density.hip) ---------------------------------------------
+ * An interior row is linear and homogeneous in b = 1 / rho: dA[db] = 1/2 diag(db) L + 1/2 L diag(db) + M~ diag(kappa db), kappa = om~^2 / c^2, L the matrix of
+ *     lap_o(p) = Lx[ox](ix) m(oy) m(oz) / dx^2 + m(ox) Ly[oy](iy) m(oz) / dy^2 + m(ox) m(oy) Lz[oz](iz) / dz^2
+ * on interior rows (boundary rows empty), the stretch tables of the handle's last assembly read at the ROW p: L is not symmetric.  The kappa part goes through
+ * the helm_mass3_* entry points with the weights the chain below makes.
+ *
+ * helm_lap3_sources_device:  R[s ldr + i] = coef (1/2 B (.) (L X[s]) + 1/2 L(B (.) X[s]))[i], X[s] = U[s] or (conj != 0) conj(U[s]); B: N float64.  add == 0: the
+ *     boundary rows of R are exact zeros; add != 0: the interior rows receive the value on top of what they hold, the boundary rows are left alone.
+ * helm_lap3_imaging_accumulate_device:  P[j] += 1/2 sum_{s<nsrc} (UB0[s][j] (L UF[s])[j] + UF[s][j] (L^T UB0[s])[j]) for every cell j, UB0 = UB with its boundary
+ *     rows masked (not read); conj != 0: both fields are conjugated as they are read.  s ascending, one store per cell.
+ * helm_buoy3_chain_device:  chain = -1 / rho^2 (gardner == 0) or d b / d c = -b / (4 Re c) (gardner != 0), b = 1 / rho, at the model of the handle.  dIn != NULL
+ *     (Born): dDb[j] = chain_j dIn[j] (N float64 each) and dOut[j] = w kappa_j dDb[j] (N complex128).  dIn == NULL (gradient): dOut is N float64,
+ *     dOut[j] += chain_j Re(w (dPlap[j] + kappa_j dPmass[j])).
+ *
+ * Plain fp64 in an order the code fixes, no atomics.  Assembled 3-D handles; any other handle: HELM_ERR_UNSUPPORTED, not assembled: HELM_ERR_STATE.  Null
+ * pointers, nsrc < 1, a leading dimension < N, a misaligned (16 bytes; float64 arrays 8) or overlapping pointer: HELM_ERR_ARG.  All device pointers; each call
+ * returns when its result is complete. */
+int helm_lap3_sources_device(helm_op *op, const void *dU, int nsrc, long long ldu, const void *dB, double coef_re, double coef_im, int conj, int add, void *dR,
+                             long long ldr);
+int helm_lap3_imaging_accumulate_device(helm_op *op, const void *dUF, long long ldf, const void *dUB, long long ldb, int nsrc, int conj, void *dP);
+int helm_buoy3_chain_device(helm_op *op, int gardner, const void *dIn, const void *dPlap, const void *dPmass, double w_re, double w_im, void *dDb, void *dOut);
+
 /* --- the derivative maps of the Eurus block M1 (eps == delta) ---------------------------------------------------------------------------------
  * A row of M1 is linear and homogeneous in the buoyancies b = 1 / rho and the mass terms K = omega_d^2 b / c^2 of the 3 x 3 (edge-clamped) cells around it; its PML
  * averages do not depend on the model.  The entry built from the neighbour (sz, sx) lies in the matrix slot (-sz, sx).  An edge row keeps its centre entry alone,

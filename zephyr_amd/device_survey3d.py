@@ -6,6 +6,10 @@ over forward fields in HBM.  The loops, the workspaces and the item steps are th
     bornFromFields3        stored   -(1 / premul) M~(chi dc (.) conj(slice))        k (A)            sampleDevice, receivers as they are      nrec x k samples per item
     gradientFromFields3    stored   qb of R^H r                                    k (A^T)          k_mass3_imaging into P, then the chain   one float64 partial G per worker
 
+With a buoyancy part (parameter 'rho' / 'joint', or the Gardner density: csrc/survey3d_density.hip) the Born right-hand side also receives
+-(1 / premul) (1/2 db (.) L u^ + 1/2 L(db (.) u^)), ADDED by k_lap3_sources to what k_mass3_sources stored (its weight then carries kappa db), and the gradient reads the same
+U once more: k_lap3_imaging into a second N-plane, k_buoy3_chain into the partial ((2 N,) for 'joint').  Still one solve per item either way.
+
 The sampling and back-source kernels work on op.N rows and CSR rows: nothing in them knows the grid's dimension.  Nothing of size N k crosses to the host.
 A 3-D item builds its multigrid hierarchy in the prepare step of `runOnDevices` (Helm3D.heavyPrepare: strictly one item ahead), for the forward and for the
 transposed wrapper alike.
@@ -44,16 +48,48 @@ def massChainDevice(op, d_p, w, d_dc, d_out):
     _lib.check(_lib.load().helm_mass3_chain_device(op.handle, None if d_p is None else _p(d_p), w.real, w.imag, None if d_dc is None else _p(d_dc), _p(d_out)), op.handle)
 
 
-def bornFromFields3(prob, F, dc):
-    """Born data (nrec, nsrc, nfreq) of the velocity perturbation dc (N,) float64 from forward fields in HBM.  Per stored item: W = chi dc on the item's GPU
-    (dc goes up once per worker), R = -(1 / premul) M~(W (.) conj(slice)) -- the slice is conj(u^), unscaled --, the forward operator solves the k columns and
-    the samples through the receiver CSR come down, times the scaleTerm."""
+def lapSourcesDevice(op, d_u, nsrc, d_b, coef, d_r, conj=True, add=False, ldu=None, ldr=None):
+    'R[s] (+)= coef (1/2 B (.) (L X[s]) + 1/2 L(B (.) X[s])), X = conj-or-not(U), B (N,) float64 on the device (helm_lap3_sources_device)'
+    N = int(op.nrow)
+    coef = complex(coef)
+    _lib.check(_lib.load().helm_lap3_sources_device(op.handle, _p(d_u), int(nsrc), int(N if ldu is None else ldu), _p(d_b), coef.real, coef.imag, 1 if conj else 0,
+                                                    1 if add else 0, _p(d_r), int(N if ldr is None else ldr)), op.handle)
+
+
+def lapImagingAccumulateDevice(op, d_uf, d_ub, nsrc, d_p, conj=False, ldf=None, ldb=None):
+    'P += 1/2 sum_s (UB0[s] (.) L UF[s] + UF[s] (.) L^T UB0[s]), both fields conjugated as they are read when conj (helm_lap3_imaging_accumulate_device)'
+    N = int(op.nrow)
+    _lib.check(_lib.load().helm_lap3_imaging_accumulate_device(op.handle, _p(d_uf), int(N if ldf is None else ldf), _p(d_ub), int(N if ldb is None else ldb), int(nsrc),
+                                                               1 if conj else 0, _p(d_p)), op.handle)
+
+
+def buoyChainDevice(op, gardner, d_in, d_plap, d_pmass, w, d_db, d_out):
+    """chain = -1 / rho^2, or d b / d c of the Gardner density when `gardner`.  d_in given: db = chain d_in (N float64) and out = w kappa db (N complex128);
+    d_in None: out += chain Re(w (Plap + kappa Pmass)) (N float64) (helm_buoy3_chain_device)"""
+    w = complex(w)
+    opt = lambda t: None if t is None else _p(t)
+    _lib.check(_lib.load().helm_buoy3_chain_device(op.handle, 1 if gardner else 0, opt(d_in), opt(d_plap), opt(d_pmass), w.real, w.imag, opt(d_db), _p(d_out)), op.handle)
+
+
+def _realBuffer(ws, name, n):
+    'n float64 over a complex128 buffer of the workspace'
+    import torch
+    return torch.view_as_real(ws.buffer(name, (n + 1) // 2)).reshape(-1)[:n]
+
+
+def bornFromFields3(prob, F, dc, dbuoy=None, gardner=False):
+    """Born data (nrec, nsrc, nfreq) from forward fields in HBM of the velocity perturbation dc (N,) float64 (None: none) and, with dbuoy (N,) float64, of the
+    density perturbation dbuoy -- or, when `gardner`, of the density that follows the velocity perturbation dbuoy.  Per stored item: W = chi dc on the item's
+    GPU (the vectors go up once per worker), with a buoyancy part db = chain dbuoy and W += kappa db; R = -(1 / premul) M~(W (.) conj(slice)) -- the slice is
+    conj(u^), unscaled --, plus -(1 / premul) (1/2 db (.) L u^ + 1/2 L(db (.) u^)) ADDED by k_lap3_sources: ONE right-hand side, the forward operator solves
+    the k columns once and the samples through the receiver CSR come down, times the scaleTerm."""
     import torch
     F.checkCurrent(prob)
     data, stage, sample = _sampling(prob, F.ownedFreqs, F.scale)
     if not F.items:
         return data
-    dc = np.ascontiguousarray(dc, dtype=np.float64)
+    dc = None if dc is None else np.ascontiguousarray(dc, dtype=np.float64)
+    dbuoy = None if dbuoy is None else np.ascontiguousarray(dbuoy, dtype=np.float64)
     devs, items = _storedItems(prob.system, F)
 
     def one(ws, op, ifreq, c0, c1):
@@ -61,27 +97,45 @@ def bornFromFields3(prob, F, dc):
         dev = ws.device
         d_uF, _ = F.pointers(ifreq, c0)
         staged = stage(ws, ifreq, c0, c1)
-        vd = ws.cached(('born3_dc', id(dc)), lambda: _lib.to_device(dc, dev, np.float64), keep=dc)
         W, U, R = ws.buffer('W3', Ni), ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
+        if dc is not None:
+            vd = ws.cached(('born3_dc', id(dc)), lambda: _lib.to_device(dc, dev, np.float64), keep=dc)
+        if dbuoy is not None:
+            bd = vd if dbuoy is dc else ws.cached(('born3_db', id(dbuoy)), lambda: _lib.to_device(dbuoy, dev, np.float64), keep=dbuoy)
+            DB, Wb = _realBuffer(ws, 'DB3', Ni), (ws.buffer('W3b', Ni) if dc is not None else W)
         _lib.wait_torch_stream(dev)
-        massChainDevice(op, None, 1.0, vd, W)
+        if dc is not None:
+            massChainDevice(op, None, 1.0, vd, W)
+        if dbuoy is not None:
+            buoyChainDevice(op, gardner, bd, None, None, 1.0, DB, Wb)
+            if dc is not None:
+                W.add_(Wb)
+                _lib.wait_torch_stream(dev)
         massSourcesDevice(op, d_uF, k, W, -1.0 / complex(op.premul), R, conj=True)
+        if dbuoy is not None:
+            lapSourcesDevice(op, d_uF, k, DB, -1.0 / complex(op.premul), R, conj=True, add=True)
         op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
         sample(op, ifreq, c0, c1, staged, U.data_ptr())
     runOnDevices(devs, items, one)
     return data
 
 
-def gradientFromFields3(prob, F, qb, resid, system):
-    """J^T r, float64 (N,), from forward fields in HBM: per stored item the k back-sources R_s^H r_s are made on the item's GPU (qb / resid those of the
-    Hermitian residual) and solved through the TRANSPOSED operator of `system`; U = conj(z~), z~ = premul A^-T R^H r.  k_mass3_imaging forms
-    P = sum_s slice_s (.) M~^T U_s = conj(sum_s u^_s (.) M~^T z~_s), torch conjugates the one N-plane, and the chain kernel adds Re(w chi conj(P)),
-    w = -conj(scaleTerm) / premul, to the worker's float64 partial.  The partials are summed on the host, then ONE all-reduce over ranks when sharded."""
+def gradientFromFields3(prob, F, qb, resid, system, parameter='c', gardner=False):
+    """J^T r, float64 (N,) -- (2 N,), [g_c; g_rho], for parameter='joint' --, from forward fields in HBM: per stored item the k back-sources R_s^H r_s are made
+    on the item's GPU (qb / resid those of the Hermitian residual) and solved ONCE through the TRANSPOSED operator of `system`; U = conj(z~),
+    z~ = premul A^-T R^H r.  k_mass3_imaging forms P = sum_s slice_s (.) M~^T U_s = conj(sum_s u^_s (.) M~^T z~_s), torch conjugates the one N-plane, and the
+    chain kernel adds Re(w chi conj(P)), w = -conj(scaleTerm) / premul, to the worker's float64 partial ('c', 'joint', and the Gardner total).  The buoyancy
+    half ('rho', 'joint', gardner) reads the same U and the same mass plane: k_lap3_imaging forms Plap = 1/2 sum_s (z~0_s (.) L u^_s + u^_s (.) L^T z~0_s),
+    conjugating both columns as it stages them (L is complex), and k_buoy3_chain adds chain Re(w (Plap + kappa conj(P))), chain = -1 / rho^2 or the Gardner
+    d b / d c.  The partials are summed on the host, then ONE all-reduce over ranks when sharded."""
     import torch
     F.checkCurrent(prob)
     sv = prob.survey
     N = prob.nrow
     scale = F.scale
+    wantC = gardner or parameter in ('c', 'joint')
+    wantB = gardner or parameter in ('rho', 'joint')
+    nG = 2 * N if parameter == 'joint' else N
     parts = []
     if F.items:
         _prepareBackSources(sv, qb, F.ownedFreqs)
@@ -90,18 +144,26 @@ def gradientFromFields3(prob, F, qb, resid, system):
         def one(ws, op, ifreq, c0, c1):
             k, Ni = c1 - c0, int(op.nrow)
             d_uF, _ = F.pointers(ifreq, c0)
-            G = _partial(ws, 'H', N, torch.float64)          # (the workspace's float64 partial: this call accumulates nothing else there)
+            G = _partial(ws, 'H', nG, torch.float64)         # (the workspace's float64 partial: this call accumulates nothing else there)
             P, U, R = ws.buffer('P3', Ni), ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
             _backSources(ws, sv, op, qb, resid, ifreq, c0, c1, R.data_ptr(), Ni)
             P.zero_()
+            if wantB:
+                Pl = ws.buffer('P3l', Ni)
+                Pl.zero_()
             _lib.wait_torch_stream(ws.device)
             op.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
             massImagingAccumulateDevice(op, d_uF, U, k, P)
             torch.conj_physical_(P)
             _lib.wait_torch_stream(ws.device)
-            massChainDevice(op, P, -np.conj(scale) / complex(op.premul), None, G)
+            w = -np.conj(scale) / complex(op.premul)
+            if wantC:
+                massChainDevice(op, P, w, None, G)
+            if wantB:
+                lapImagingAccumulateDevice(op, d_uF, U, k, Pl, conj=True)
+                buoyChainDevice(op, gardner, None, Pl, P, w, None, G[N:] if parameter == 'joint' else G)
         parts = [ws.H for ws in runOnDevices(devs, items, one) if ws.H is not None]
-    g = np.zeros(N, dtype=np.float64)
+    g = np.zeros(nG, dtype=np.float64)
     for G in parts:
         torch.cuda.synchronize(G.device)
         g += _lib.from_device(G)

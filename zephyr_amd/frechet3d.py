@@ -1,4 +1,4 @@
-"""Host maps of the exact velocity derivative of the 3-D 27-point operator (numpy / scipy): what `Helm3DProblem` runs when the device routes do not serve
+"""Host maps of the exact velocity and buoyancy derivatives of the 3-D 27-point operator (numpy / scipy): what `Helm3DProblem` runs when the device routes do not serve
 (hostGradient, host lists of fields, no GPU), and the reference the device kernels of csrc/survey3d.hip are tested against.
 
 With an explicit density the derivative of `Helm3D.A` along the velocity is its mass term alone (oracle/helm3d_oracle.py: the C-PML profiles do not depend on
@@ -83,3 +83,94 @@ def imagingSum3(op, uh, lam, M=None):
     'P_j = sum_s u^_{s,j} (M~^T lam_s)_j, (N,) complex128: uh, lam (N, nsrc); the boundary rows of lam drop out through the empty rows of M~'
     M = massStencil3(op.modelDims) if M is None else M
     return (np.asarray(uh) * (M.T @ np.asarray(lam))).sum(axis=1)
+
+
+# ---- the derivative along the buoyancy b = 1 / rho ------------------------------------------------------------------------------------------------------
+# An interior row of the operator is C_o(p) = (b_p + b_{p+o}) / 2 lap_o(p) + b_{p+o} kappa_{p+o} mu_o, kappa = om~^2 / c^2,
+#     lap_o(p) = Lx[ox](ix) m(oy) m(oz) / dx^2 + m(ox) Ly[oy](iy) m(oz) / dy^2 + m(ox) m(oy) Lz[oz](iz) / dz^2,
+# the stretch tables read at the ROW p: linear and homogeneous in b, so with L the matrix of lap_o(p) on interior rows (boundary rows empty)
+#     dA[db] = 1/2 diag(db) L + 1/2 L diag(db) + M~ diag(kappa db).
+# L is not symmetric (the stretch factors sit at the row): the adjoint needs L^T.
+GARDNER_FACTOR, GARDNER_POWER = 310., 0.25
+
+
+def stretchTables3(op):
+    """((Lx(-1), Lx(0), Lx(+1)), (Ly...), (Lz...)): the Laplacian factors of the C-PML per axis, complex128 arrays of nx, ny, nz entries -- the tables the
+    assembly reads (gamma = cPML cos(pi/2 dist / L) over nPML nodes at each end, xi = 1 - i gamma / om~, L(+-1) = 1 / (xi_i (xi_i + xi_{i+-1}) / 2))"""
+    nz, ny, nx = (int(d) for d in op.modelDims)
+    om = dampedOmega3(op)
+    npml, cpml = int(getattr(op, 'nPML', 10)), float(getattr(op, 'cPML', 300.))
+
+    def axis(n, h):
+        g = np.zeros(n)
+        k = np.arange(npml)
+        ell = h * (npml - 1)
+        g[:npml] = cpml * np.cos((np.pi / 2) * (k * h / ell))
+        g[n - npml:] = cpml * np.cos((np.pi / 2) * ((npml - 1 - k) * h / ell))
+        xi = 1 - (1j * np.pad(g, 1, mode='edge')) / om
+        c = xi[1:-1]
+        lm, lp = 1.0 / (c * (c + xi[:-2]) / 2), 1.0 / (c * (c + xi[2:]) / 2)
+        return lm, -(lm + lp), lp
+    return axis(nx, float(op.dx)), axis(ny, float(getattr(op, 'dy', op.dx))), axis(nz, float(op.dz))
+
+
+def lapStencil3(op):
+    'L as CSR (N, N), complex128: row p = lap_o(p) at the columns p + o for an interior p, an empty row for a boundary p'
+    nz, ny, nx = (int(d) for d in op.modelDims)
+    N = nz * ny * nx
+    Lx, Ly, Lz = stretchTables3(op)
+    dx, dy, dz = float(op.dx), float(getattr(op, 'dy', op.dx)), float(op.dz)
+    iz, iy, ix = (a[1:-1, 1:-1, 1:-1].ravel() for a in np.mgrid[0:nz, 0:ny, 0:nx])
+    row = (iz * ny + iy) * nx + ix
+    rows, cols, vals = [], [], []
+    for oz in (-1, 0, 1):
+        for oy in (-1, 0, 1):
+            for ox in (-1, 0, 1):
+                rows.append(row)
+                cols.append(((iz + oz) * ny + (iy + oy)) * nx + (ix + ox))
+                vals.append(Lx[ox + 1][ix] * (_m(oy) * _m(oz) / dx ** 2) + Ly[oy + 1][iy] * (_m(ox) * _m(oz) / dy ** 2) + Lz[oz + 1][iz] * (_m(ox) * _m(oy) / dz ** 2))
+    return sp.coo_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))), shape=(N, N)).tocsr()
+
+
+def kappa3(op):
+    'kappa = om~^2 / c^2 per cell, (N,) complex128: K = b kappa'
+    N = int(np.prod(op.modelDims))
+    c = np.broadcast_to(np.asarray(op.c, dtype=np.complex128).ravel(), (N,))
+    om = dampedOmega3(op)
+    return om * om / (c * c)
+
+
+def buoyancySources3(op, db, uh, L=None, M=None):
+    """(dA[db]) u^_s = 1/2 db (.) (L u^_s) + 1/2 L(db (.) u^_s) + M~(kappa db (.) u^_s) for the columns of uh (N, nsrc); db (N,) real.  The boundary rows are
+    exact zeros.  L, M: lapStencil3(op), massStencil3(op.modelDims) if the caller keeps them."""
+    L = lapStencil3(op) if L is None else L
+    M = massStencil3(op.modelDims) if M is None else M
+    db = np.asarray(db, dtype=np.float64).ravel()[:, None]
+    uh = np.asarray(uh)
+    return 0.5 * db * (L @ uh) + 0.5 * (L @ (db * uh)) + M @ ((kappa3(op)[:, None] * db) * uh)
+
+
+def buoyancyImaging3(op, uh, lam, L=None, M=None, LT=None):
+    """(N,) complex128: sum_s [ 1/2 lam0_s (.) (L u^_s) + 1/2 u^_s (.) (L^T lam0_s) + kappa (.) u^_s (.) (M~^T lam0_s) ], the transpose of buoyancySources3 in db
+    contracted with lam; lam0 = lam with its boundary rows masked (they drop out through the empty rows of L and M~: every cell receives a value, boundary
+    nodes included).  LT: what stands in the place of L^T (tests put L there to show that it is not the transpose)."""
+    L = lapStencil3(op) if L is None else L
+    M = massStencil3(op.modelDims) if M is None else M
+    LT = sp.csr_matrix(L.T) if LT is None else LT
+    uh = np.asarray(uh)
+    lam0 = np.asarray(lam) * interiorMask3(op.modelDims)[:, None]
+    return (0.5 * lam0 * (L @ uh) + 0.5 * uh * (LT @ lam0) + kappa3(op)[:, None] * uh * (M.T @ lam0)).sum(axis=1)
+
+
+def densityChain3(op):
+    'd b / d rho = -1 / rho^2 per cell, (N,) float64'
+    N = int(np.prod(op.modelDims))
+    rho = np.broadcast_to(np.asarray(op.rho, dtype=np.float64).ravel(), (N,))
+    return -1.0 / (rho * rho)
+
+
+def gardnerChain3(op):
+    'd b / d c = -b / (4 Re c) per cell of the default density rho = 310 Re(c)^0.25 (b = Re(c)^-0.25 / 310), (N,) float64'
+    N = int(np.prod(op.modelDims))
+    cr = np.broadcast_to(np.asarray(op.c, dtype=np.complex128).ravel(), (N,)).real
+    return -(cr ** -GARDNER_POWER / GARDNER_FACTOR) / (4.0 * cr)

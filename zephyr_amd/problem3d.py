@@ -10,7 +10,17 @@ term, dA[dc] = M~ diag(chi dc), chi = -2 K / c (frechet3d.py), so
 
 and Re <r, JvecBorn(v)> = <Jtvec(r), v>.  A is not symmetric, so the back-propagation runs through A^-T: `adjointSystem`, the same wrapper over
 `Disc.Transposed` (Helm3DTransposed).  'operator' and 'full' are the same derivative here (as on Eurus: the C-PML does not depend on c).  Without `rho` in the config the Gardner
-density moves the Laplacian part with c; that derivative is not built and the exact routes are refused.
+density moves the Laplacian part with c; without the config key derivatives3D the exact routes are then refused.
+
+With derivatives3D=True the derivative along the buoyancy b = 1 / rho is served too (frechet3d.py).  A row is linear in b,
+dA[db] = 1/2 diag(db) L + 1/2 L diag(db) + M~ diag(kappa db), kappa = om~^2 / c^2, L the Laplacian part with the stretch tables at the row (not symmetric), so
+
+    Born sources:  R_s = -(1 / premul) [ 1/2 db (.) (L u^_s) + 1/2 L(db (.) u^_s) + M~(kappa db (.) u^_s) ]
+    gradient:      g_b = Re sum_f w_f sum_s [ 1/2 z~0_s (.) (L u^_s) + 1/2 u^_s (.) (L^T z~0_s) + kappa (.) u^_s (.) (M~^T z~0_s) ]
+
+(z~0: z~ with its boundary rows masked), g_rho = -g_b / rho^2, db = -drho / rho^2: parameter='rho' and 'joint' ([c; rho] stacked; ONE back-solve, ONE Born solve).  Without `rho`
+b = Re(c)^-0.25 / 310 and d b / d c = -b / (4 Re c): linearisation='full', parameter='c' is the mass chain at fixed rho plus the buoyancy maps at db = (d b / d c) dc.  `Hvec` is
+the Gauss-Newton product of the two halves.
 """
 import numpy as np
 
@@ -36,10 +46,16 @@ class Helm3DProblem(HelmBaseProblem):
     TWO hierarchies per frequency are resident, that of A_f and that of A_f^T (`del prob.factors` releases both).
 
     Refused with the reason: the exact routes without `rho`; parameter other than 'c'; `Jvec`, `Hvec`, `hessianBlocks` and the illumination kinds that need the
-    derivative planes; fieldsDtype='complex64' with the exact routes; perKy / ownGrid."""
+    derivative planes; fieldsDtype='complex64' with the exact routes; perKy / ownGrid.
+
+    With the config key derivatives3D=True (without it all of the above is unchanged): parameter 'rho' and 'joint' on `Jtvec(adjoint='transpose')` and `JvecBorn` with
+    linearisation 'operator' | 'full'; without `rho` in the config linearisation='full', parameter='c', the total derivative through the Gardner density ('operator', 'rho'
+    and 'joint' stay refused there); `Hvec(m, v, u, weights, linearisation, parameter)`, the Gauss-Newton product; `m` may be {'c': ..., 'rho': ...}.  Still refused: 'Q' / 'cQ',
+    `Hvec(resid=)`, `hessianBlocks`, the non-'scaler' illumination kinds, `Jvec`, fieldsDtype='complex64', perKy / ownGrid, the multiscale and visco wrappers."""
 
     initMap = {
         'SystemWrapper':    (False,    None,        None),
+        'derivatives3D':    (False,    '_derivatives3D', bool),    # serve the density, joint and Gardner derivatives and Hvec (the buoyancy maps of frechet3d.py)
     }
 
     surveyPair = Helm3DSurvey
@@ -75,8 +91,24 @@ class Helm3DProblem(HelmBaseProblem):
         return self._adjointSystem
 
     # ---- what is refused ---------------------------------------------------------------------------------------------------------------------
-    def _requireExact3(self, what, parameter):
-        'the exact routes serve parameter=\'c\' of a config with an explicit `rho` and a complex128 store'
+    def _requireExact3(self, what, parameter, linearisation='operator'):
+        """the exact routes serve parameter='c' of a config with an explicit `rho` and a complex128 store; with derivatives3D=True also 'rho' and 'joint', and
+        without `rho` the total velocity derivative through the Gardner density (linearisation='full', parameter='c').  Returns (parameter, gardner)."""
+        if getattr(self, '_derivatives3D', False):
+            if isinstance(parameter, str) and parameter in ('Q', 'cQ'):
+                raise NotImplementedError('%s with parameter=%r is not built in 3-D: the visco wrappers and the chain from (c, Q) to the complex velocity are those of '
+                                          'the 2-D operators (parameter \'c\', \'rho\' and \'joint\' are served)' % (what, parameter))
+            self._checkParameter(parameter, linearisation, joint=True)
+            if self.fieldsDtype != 'complex128':
+                raise NotImplementedError('%s reads a complex128 store: fieldsDtype=%r is not served by the 3-D kernels (leave fieldsDtype at its default)'
+                                          % (what, self.fieldsDtype))
+            if self._hasDensity():
+                return parameter, False
+            if parameter != 'c' or linearisation != 'full':
+                raise NotImplementedError('%s without `rho` in the config serves linearisation=\'full\', parameter=\'c\': the density follows the velocity '
+                                          '(Gardner), so it is no parameter of its own and the derivative at fixed density (\'operator\') is not the derivative '
+                                          'of dpred (give `rho`, e.g. 310 c^0.25 as an array, for \'operator\', \'rho\' and \'joint\')' % (what,))
+            return 'c', True
         if parameter != 'c':
             raise NotImplementedError('%s with parameter=%r is not built in 3-D: the density, joint and Q derivatives exist for the 2-D operators only (parameter=\'c\' '
                                       'is served)' % (what, parameter))
@@ -86,6 +118,7 @@ class Helm3DProblem(HelmBaseProblem):
         if self.fieldsDtype != 'complex128':
             raise NotImplementedError('%s reads a complex128 store: fieldsDtype=%r is not served by the 3-D kernels (leave fieldsDtype at its default)'
                                       % (what, self.fieldsDtype))
+        return 'c', False
 
     @staticmethod
     def _refuse3(what, remedy):
@@ -105,10 +138,41 @@ class Helm3DProblem(HelmBaseProblem):
         self._refuse3('Jvec', 'the reference\'s one-column outer-product approximation is written for 2-D grids; JvecBorn(linearisation=\'operator\') is the '
                               'derivative of dpred')
 
-    def Hvec(self, *args, **kwargs):
-        self._refuse3('Hvec', 'apply Jtvec(JvecBorn(v, linearisation=\'operator\'), adjoint=\'transpose\', linearisation=\'operator\') for the Gauss-Newton product')
+    def Hvec(self, m=None, v=None, u=None, weights=None, linearisation='operator', parameter='c', resid=None):
+        """With derivatives3D=True: the Gauss-Newton product J^T W J v, Jtvec(JvecBorn(v) (.) weights, adjoint='transpose') on the same forward fields -- float64
+        (N,), or (2 N,) for parameter='joint' (v = [v_c; v_rho]).  linearisation 'operator' or 'full', parameter 'c', 'rho' or 'joint' as the two halves serve
+        them; weights: optional, real, non-negative, of the size of the data.  Two solves of nsrc columns per frequency, no forward re-solve; only the
+        nrec x nsrc samples cross to the host between the halves.  resid= (the Newton term) is refused.  Without the key: refused as it always was."""
+        if not getattr(self, '_derivatives3D', False):
+            self._refuse3('Hvec', 'apply Jtvec(JvecBorn(v, linearisation=\'operator\'), adjoint=\'transpose\', linearisation=\'operator\') for the Gauss-Newton product')
+        self._requirePaired()
+        if v is None:
+            raise Exception('Actually, Hvec requires a vector')
+        if resid is not None:
+            self._refuse3('Hvec(resid=)', 'the second derivative of the 27-point operator and the third solve of the Newton term are not built; resid=None, the '
+                                          'Gauss-Newton product, is served')
+        self._checkLinearisation(linearisation)
+        if linearisation == 'scaler':
+            raise ValueError('Hvec of a 3-D problem composes the exact halves: linearisation is \'operator\' or \'full\'')
+        self.updateModel(m)
+        self._requireExact3('Hvec(linearisation=%r)' % (linearisation,), parameter, linearisation)
+        if weights is not None:
+            weights = np.asarray(weights)
+            if np.iscomplexobj(weights) or weights.size != self.survey.nD or not np.all(weights >= 0):
+                raise ValueError('weights are real, non-negative and of the size of the data (%d)' % (self.survey.nD,))
+            weights = weights.astype(np.float64).ravel()
+        if parameter == 'joint':
+            self._splitJoint(v, 'Hvec')
+        with self._forwardFields(u) as F:
+            d = self.JvecBorn(None, v, u=F, linearisation=linearisation, parameter=parameter)
+            if weights is not None:
+                d = d * weights
+            return self.Jtvec(None, d, u=F, adjoint='transpose', linearisation=linearisation, parameter=parameter)
 
     def hessianBlocks(self, *args, **kwargs):
+        if getattr(self, '_derivatives3D', False):
+            self._refuse3('hessianBlocks', 'the per-cell blocks are built on the derivative planes of the 2-D operators; Hvec(parameter=\'joint\') applies the '
+                                           'Gauss-Newton Hessian and illumination(kind=\'pseudoHessian\') preconditions a gradient')
         self._refuse3('hessianBlocks', 'there is no density derivative in 3-D to pair the velocity with; illumination(kind=\'pseudoHessian\') preconditions a gradient')
 
     def illumination(self, m=None, u=None, kind='pseudoHessian', side='source', perFreq=False, linearisation='scaler', parameter='c'):
@@ -133,7 +197,10 @@ class Helm3DProblem(HelmBaseProblem):
         self._checkLinearisation(linearisation)
         if adjoint not in ('reciprocity', 'transpose'):
             raise ValueError('adjoint is %r: \'reciprocity\' or \'transpose\'' % (adjoint,))
-        self._requireExact3('Jtvec(linearisation=%r)' % (linearisation,), parameter)
+        if getattr(self, '_derivatives3D', False):
+            self.updateModel(m)              # (a dict may bring the `rho` that decides what is served)
+            m = None
+        parameter, gardner = self._requireExact3('Jtvec(linearisation=%r)' % (linearisation,), parameter, linearisation)
         if adjoint != 'transpose':
             raise ValueError('linearisation=%r needs adjoint=\'transpose\': the exact derivative back-propagates through A^-T' % (linearisation,))
         self.updateModel(m)
@@ -144,16 +211,24 @@ class Helm3DProblem(HelmBaseProblem):
             if isinstance(F, DeviceFields):
                 from . import device_survey3d
                 rd = self._hermitianResidual(resid)
-                return device_survey3d.gradientFromFields3(self, F, self._deviceBackSources(rd), rd, adj)
-            g = np.zeros(self.nrow, dtype=np.float64)
+                return device_survey3d.gradientFromFields3(self, F, self._deviceBackSources(rd), rd, adj, parameter, gardner)
+            N = self.nrow
+            wantC, wantB = gardner or parameter in ('c', 'joint'), gardner or parameter in ('rho', 'joint')
+            g = np.zeros(2 * N if parameter == 'joint' else N, dtype=np.float64)
+            gb = g[N:] if parameter == 'joint' else g
             st = complex(self.system.scaleTerm)
             qb = [q.conj() for q in sv.getResidualSources(np.conj(resid))]        # R_s^H r_s = conj(R_s^T conj(r_s))
             M = None
             for ifreq, uB in self._solveOwned(qb, adj):
                 op = self.system.subProblems[ifreq]
                 M = frechet3d.massStencil3(op.modelDims) if M is None else M
-                P = frechet3d.imagingSum3(op, np.conj(np.asarray(F[ifreq]) / st), np.conj(np.asarray(uB) / st), M)
-                g += ((-np.conj(st) / complex(op.premul)) * frechet3d.velocityChain3(op) * P).real
+                uh, lam, w = np.conj(np.asarray(F[ifreq]) / st), np.conj(np.asarray(uB) / st), -np.conj(st) / complex(op.premul)
+                if wantC:
+                    P = frechet3d.imagingSum3(op, uh, lam, M)
+                    g[:N] += (w * frechet3d.velocityChain3(op) * P).real
+                if wantB:
+                    chain = frechet3d.gardnerChain3(op) if gardner else frechet3d.densityChain3(op)
+                    gb += chain * (w * frechet3d.buoyancyImaging3(op, uh, lam, frechet3d.lapStencil3(op), M)).real
         if self._sharded:
             g = parallel.allreduce_sum(g)
         return g
@@ -168,22 +243,36 @@ class Helm3DProblem(HelmBaseProblem):
         if v is None:
             raise Exception('Actually, JvecBorn requires a perturbation vector')
         self._checkLinearisation(linearisation)
-        self._requireExact3('JvecBorn(linearisation=%r)' % (linearisation,), parameter)
+        if getattr(self, '_derivatives3D', False):
+            self.updateModel(m)
+            m = None
+        parameter, gardner = self._requireExact3('JvecBorn(linearisation=%r)' % (linearisation,), parameter, linearisation)
         self.updateModel(m)
         sv = self.survey
-        dc = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape((self.nrow,)))
+        if parameter == 'joint':
+            dc, dbuoy = self._splitJoint(v, 'JvecBorn')
+        else:
+            dc = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape((self.nrow,)))
+            dc, dbuoy = (None, dc) if parameter == 'rho' else (dc, dc if gardner else None)
         with self._forwardFields(u) as F:
             if isinstance(F, DeviceFields):
                 from . import device_survey3d
-                data = device_survey3d.bornFromFields3(self, F, dc)
+                data = device_survey3d.bornFromFields3(self, F, dc) if dbuoy is None else device_survey3d.bornFromFields3(self, F, dc, dbuoy, gardner)
             else:
                 data = np.zeros((sv.nrec, sv.nsrc, sv.nfreq), dtype=np.complex128)
                 st = complex(self.system.scaleTerm)
                 subs = self.system.subProblems
                 owned = self.ownedFreqs
                 M = frechet3d.massStencil3(subs[0].modelDims) if owned else None
-                qv = [frechet3d.bornSources3(subs[i], dc, np.conj(np.asarray(F[i]) / st), M) / -complex(subs[i].premul) if i in owned else None
-                      for i in range(sv.nfreq)]
+
+                def sources(i):
+                    uh = np.conj(np.asarray(F[i]) / st)
+                    q = 0.0 if dc is None else frechet3d.bornSources3(subs[i], dc, uh, M)
+                    if dbuoy is not None:
+                        chain = frechet3d.gardnerChain3(subs[i]) if gardner else frechet3d.densityChain3(subs[i])
+                        q = q + frechet3d.buoyancySources3(subs[i], chain * dbuoy, uh, frechet3d.lapStencil3(subs[i]), M)
+                    return q / -complex(subs[i].premul)
+                qv = [sources(i) if i in owned else None for i in range(sv.nfreq)]
                 for ifreq, uB in self._solveOwned(qv):
                     uB = np.asarray(uB)
                     if sv.mode == 'fixed':
