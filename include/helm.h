@@ -363,6 +363,24 @@ int helm_lap3_sources_device(helm_op *op, const void *dU, int nsrc, long long ld
 int helm_lap3_imaging_accumulate_device(helm_op *op, const void *dUF, long long ldf, const void *dUB, long long ldb, int nsrc, int conj, void *dP);
 int helm_buoy3_chain_device(helm_op *op, int gardner, const void *dIn, const void *dPlap, const void *dPmass, double w_re, double w_im, void *dDb, void *dOut);
 
+/* --- the pseudo-Hessian diagonal and the (c, rho) blocks of the 3-D 27-point operator from stored columns (survey3d_hessian.hip) ----------------------
+ * H_p[i] = sum_s ||(dA / dp_i) X[s]||^2 and B_ab[i] = sum_s Re <(dA / da_i) X[s], (dA / db_i) X[s]>.  The column of a unit perturbation of cell i touches the 27 rows
+ * p = i + d; per cell and column only X[s][i] and T = (L X[s])[i] enter, through r = A0_i X[s][i] + h_i T and the moments E = sum |X[i]|^2, D = sum |r|^2,
+ * Y = sum conj(X[i]) r.  The rest is per-cell coefficients of the model of the handle's last assembly:
+ *
+ * helm_ph3_coefficients_device:  mode 0 (buoyancy): A0 = a_i(i), h = 1/2, S' = sum_{d != 0} |a_{i+d}(i)|^2, a_p(i) = [p interior] (1/2 lap_{-d}(i + d) + kappa_i mu_d),
+ *     the tables read at the neighbour's row.  mode 1 (the total velocity derivative through the Gardner density, g = d b / d c = -b / (4 Re c)):
+ *     A0 = chi mu_0 [i interior] + g a_i(i), h = g / 2, S' = sum_{d != 0} |chi mu_d [p interior] + g a_p(i)|^2, chi = -2 kappa b / c.  mode 2 (blocks): those of mode 0 and
+ *     C' = sum_{d != 0} mu_d a_{i+d}(i), Smu = sum_{p interior} mu_d^2.  dA0, dC: N complex128; dH, dS, dSmu: N float64 (dC, dSmu may be NULL for modes 0, 1).
+ * helm_ph3_moments_accumulate_device:  blocks == 0: dH[i] += alpha W_i (S'_i E + D) (dW NULL: no weight).  blocks != 0: three rows at stride ldh,
+ *     dH[i] += alpha W_i |chi|^2 Smu E,  dH[ldh + i] += -alpha W_i Re conj(chi) (C' E + mu_0 [i interior] Y) / rho^2,  dH[2 ldh + i] += alpha W_i (S' E + D) / rho^4
+ *     -- H_cc, H_crho, H_rhorho.  X[s] = U[s] or (conj != 0) conj(U[s]).  s ascending in one workgroup, one load and one store of dH per cell, no atomics.
+ *
+ * Handles, arguments and return codes as helm_lap3_sources_device (blocks != 0: ldh >= N). */
+int helm_ph3_coefficients_device(helm_op *op, int mode, void *dA0, void *dH, void *dS, void *dC, void *dSmu);
+int helm_ph3_moments_accumulate_device(helm_op *op, const void *dU, int nsrc, long long ldu, int conj, int blocks, const void *dA0, const void *dHh, const void *dS,
+                                       const void *dC, const void *dSmu, double alpha, const void *dW, void *dH, long long ldh);
+
 /* --- the derivative maps of the Eurus block M1 (eps == delta) ---------------------------------------------------------------------------------
  * A row of M1 is linear and homogeneous in the buoyancies b = 1 / rho and the mass terms K = omega_d^2 b / c^2 of the 3 x 3 (edge-clamped) cells around it; its PML
  * averages do not depend on the model.  The entry built from the neighbour (sz, sx) lies in the matrix slot (-sz, sx).  An edge row keeps its centre entry alone,

@@ -138,6 +138,10 @@ _SIGNATURES = {
                                                            ctypes.c_int, ctypes.c_void_p]),
     'helm_buoy3_chain_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_double,
                                                ctypes.c_void_p, ctypes.c_void_p]),
+    'helm_ph3_coefficients_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    'helm_ph3_moments_accumulate_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
+                                                          ctypes.c_void_p, ctypes.c_longlong]),
     'helm_buoyancy_planes_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
     'helm_stencil_sources_device': (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_double,
                                                    ctypes.c_double, ctypes.c_int, ctypes.c_void_p, ctypes.c_longlong]),

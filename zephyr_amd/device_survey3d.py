@@ -168,3 +168,80 @@ def gradientFromFields3(prob, F, qb, resid, system, parameter='c', gardner=False
         torch.cuda.synchronize(G.device)
         g += _lib.from_device(G)
     return parallel.allreduce_sum(g) if prob._sharded else g
+
+
+# ---- the pseudo-Hessian diagonal and the (c, rho) blocks (csrc/survey3d_hessian.hip) ------------------------------------------------------------------------
+PH3_MODES = {'buoyancy': 0, 'gardner': 1, 'blocks': 2}
+
+
+def ph3CoefficientsDevice(op, mode, d_a0, d_h, d_s, d_c=None, d_smu=None):
+    """the coefficient planes of the handle's model (helm_ph3_coefficients_device): mode 'buoyancy', 'gardner' or 'blocks'; d_a0 (and d_c) N complex128, d_h, d_s (and
+    d_smu) N float64, all on the device"""
+    opt = lambda t: None if t is None else _p(t)
+    _lib.check(_lib.load().helm_ph3_coefficients_device(op.handle, PH3_MODES[mode], _p(d_a0), _p(d_h), _p(d_s), opt(d_c), opt(d_smu)), op.handle)
+
+
+def ph3MomentsAccumulateDevice(op, d_u, nsrc, planes, alpha, d_w, d_h, blocks=False, conj=True, ldu=None, ldh=None):
+    """H += alpha W (S' E + D), or with `blocks` the three rows H_cc, H_crho, H_rhorho at stride ldh, over the columns of U (helm_ph3_moments_accumulate_device);
+    planes = (A0, h, S') or (A0, h, S', C', Smu) as ph3CoefficientsDevice made them, d_w None: no weight"""
+    N = int(op.nrow)
+    opt = lambda t: None if t is None else _p(t)
+    pl = list(planes) + [None] * (5 - len(planes))
+    _lib.check(_lib.load().helm_ph3_moments_accumulate_device(op.handle, _p(d_u), int(nsrc), int(N if ldu is None else ldu), 1 if conj else 0, 1 if blocks else 0,
+                                                              _p(pl[0]), _p(pl[1]), _p(pl[2]), opt(pl[3]), opt(pl[4]), float(alpha), opt(d_w), _p(d_h),
+                                                              int(N if ldh is None else ldh)), op.handle)
+
+
+def pseudoHessianFromFields3(prob, F, parameter='c', gardner=False, perFreq=False, blocks=False):
+    """The exact pseudo-Hessian from forward fields in HBM: float64 (N,) -- (nfreq, N) with perFreq --, or with `blocks` the rows H_cc, H_crho, H_rhorho, (3, N) --
+    (nfreq, 3, N).  No solve: every stored item reads its slice where it lies and adds to its worker's partial.  The slice is conj(u^), unscaled: the kernels
+    conjugate it as they stage it and |scaleTerm|^2 is the factor alpha.
+    parameter 'c' with an explicit density: the closed form, k_energy with the weight Smu / |c^3 rho|^2 (made by torch once per worker and model, as the 2-D
+    'operator' route makes its weight) and 4 |om~^2|^2 |scaleTerm|^2 in alpha; neither kernel of survey3d_hessian.hip runs.  Otherwise k_ph3_coefficients fills the coefficient planes of the item's operator in the workspace -- once per worker
+    and frequency -- and k_ph3_moments walks the columns: 'rho' with W = 1 / rho^4, the Gardner total derivative without a weight, the blocks with the density
+    factors of the kernel.  The partials are summed on the host, then ONE all-reduce over ranks when sharded."""
+    from . import frechet3d
+    from .device_survey import _blocksRow, _cachedInverseC3Rho, _energyRow, _sumEnergyPartials
+    F.checkCurrent(prob)
+    sv = prob.survey
+    N = prob.nrow
+    shape = ((sv.nfreq, 3, N) if perFreq else (3, N)) if blocks else ((sv.nfreq, N) if perFreq else (N,))
+    if not F.items:
+        return _sumEnergyPartials(prob, [], shape)
+    scale = F.scale
+    a2 = scale.real * scale.real + scale.imag * scale.imag
+    closed = not blocks and parameter == 'c' and not gardner
+    mode = 'blocks' if blocks else ('gardner' if gardner else 'buoyancy')
+    devs, items = _storedItems(prob.system, F)
+
+    def one(ws, op, ifreq, c0, c1):
+        k, Ni = c1 - c0, int(op.nrow)
+        dev = ws.device
+        d_uF, _ = F.pointers(ifreq, c0)
+        row = (_blocksRow if blocks else _energyRow)(ws, shape, ifreq)
+        if closed:
+            # |chi|^2 Smu = 4 |om~^2|^2 Smu / |c^3 rho|^2: the frequency goes into alpha, the rest is one array per worker and model
+            cm, rho = op.c, op.rho
+
+            def weight():
+                inv = _cachedInverseC3Rho(ws, op)
+                return (inv.real * inv.real + inv.imag * inv.imag) * _lib.to_device(frechet3d.massWeightSquares3(op.modelDims), dev, np.float64)
+            W = ws.cached(('ph3_velocity_weight', id(cm), id(rho)), weight, keep=(cm, rho))
+            om = frechet3d.dampedOmega3(op)
+            _lib.wait_torch_stream(dev)
+            op.energyAccumulateDevice(d_uF, k, 4.0 * abs(om * om) ** 2 * a2, W.data_ptr(), row, rows=Ni)
+            return
+        W = None
+        if parameter == 'rho' and not blocks:
+            rho = op.rho
+            W = ws.cached(('ph_inv_rho4', id(rho)), lambda: _lib.to_device(np.broadcast_to(np.asarray(rho, dtype=np.float64).ravel(), (Ni,)) ** -4.0, dev, np.float64), keep=rho)
+        planes = [ws.buffer('ph3_A0', Ni), _realBuffer(ws, 'ph3_h', Ni), _realBuffer(ws, 'ph3_S', Ni)]
+        if blocks:
+            planes += [ws.buffer('ph3_C', Ni), _realBuffer(ws, 'ph3_Smu', Ni)]
+        state = ws.cached('ph3_planes_of', dict)
+        _lib.wait_torch_stream(dev)                       # (covers the zeroed partial and the weight)
+        if state.get('key') != (ifreq, id(op)):
+            ph3CoefficientsDevice(op, mode, *planes)
+            state['key'] = (ifreq, id(op))
+        ph3MomentsAccumulateDevice(op, d_uF, k, planes, a2, W, row, blocks=blocks, conj=True, ldh=Ni)
+    return _sumEnergyPartials(prob, [ws.H for ws in runOnDevices(devs, items, one, factor=False) if ws.H is not None], shape)

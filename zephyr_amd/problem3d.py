@@ -51,11 +51,22 @@ class Helm3DProblem(HelmBaseProblem):
     With the config key derivatives3D=True (without it all of the above is unchanged): parameter 'rho' and 'joint' on `Jtvec(adjoint='transpose')` and `JvecBorn` with
     linearisation 'operator' | 'full'; without `rho` in the config linearisation='full', parameter='c', the total derivative through the Gardner density ('operator', 'rho'
     and 'joint' stay refused there); `Hvec(m, v, u, weights, linearisation, parameter)`, the Gauss-Newton product; `m` may be {'c': ..., 'rho': ...}.  Still refused: 'Q' / 'cQ',
-    `Hvec(resid=)`, `hessianBlocks`, the non-'scaler' illumination kinds, `Jvec`, fieldsDtype='complex64', perKy / ownGrid, the multiscale and visco wrappers."""
+    `Hvec(resid=)`, `hessianBlocks`, the non-'scaler' illumination kinds, `Jvec`, fieldsDtype='complex64', perKy / ownGrid, the multiscale and visco wrappers.
+
+    With the config key hessian3D=True (without it all of the above is unchanged): what a 3-D gradient is divided by -- the pseudo-Hessian of the exact derivatives, which
+    costs no solve.  `illumination(m, u, kind='pseudoHessian', linearisation='operator' | 'full', parameter='c' | 'rho', perFreq)`: float64 (N,) or
+    (nfreq, N), H_p[i] = |scaleTerm|^2 sum_f sum_s ||(d A_f / d p_i) u^_s||^2; `hessianBlocks(m, u, kind='pseudoHessian', linearisation=, perFreq)`: the rows H_cc, H_crho,
+    H_rhorho, (3, N) or (nfreq, 3, N), for frechet.blockSolve with the 'joint' gradient.  Served by the rules of the gradient being preconditioned: 'c' with an explicit
+    `rho` needs this key alone (the closed form |chi|^2 Smu sum_s |u^_s[i]|^2); 'rho', the blocks and -- without `rho` in the config -- linearisation='full', parameter='c'
+    (the Gardner total derivative) need derivatives3D=True beside it.  u None, a DeviceFields or the host list; fixed and moving arrays; sharded ranks end in one
+    all-reduce.  Refused with a sentence, the key set or not: kind='gaussNewton' (nrec back-solves through A^T per frequency), side='receiver' on the exact kinds,
+    fieldsDtype='complex64', 'Q' / 'cQ', illumination(parameter='joint') (use hessianBlocks), hessianBlocks without `rho`.  kind='energy' and the 'scaler'
+    pseudo-Hessian return the bits they returned."""
 
     initMap = {
         'SystemWrapper':    (False,    None,        None),
         'derivatives3D':    (False,    '_derivatives3D', bool),    # serve the density, joint and Gardner derivatives and Hvec (the buoyancy maps of frechet3d.py)
+        'hessian3D':        (False,    '_hessian3D', bool),        # serve the exact pseudo-Hessian diagonal and the (c, rho) blocks (illumination, hessianBlocks)
     }
 
     surveyPair = Helm3DSurvey
@@ -170,17 +181,94 @@ class Helm3DProblem(HelmBaseProblem):
             return self.Jtvec(None, d, u=F, adjoint='transpose', linearisation=linearisation, parameter=parameter)
 
     def hessianBlocks(self, *args, **kwargs):
+        """With hessian3D=True (and derivatives3D=True, an explicit `rho`): hessianBlocks(m, u, kind='pseudoHessian', side='source', perFreq, linearisation) -- the rows
+        H_cc, H_crho, H_rhorho of the per-cell 2 x 2 blocks of the pseudo-Hessian of the joint (c, rho) derivative, float64 (3, N) or (nfreq, 3, N), for
+        frechet.blockSolve.  Rows 0 and 2 are illumination(linearisation=, parameter='c' / 'rho'); B[1]^2 <= B[0] B[2].  Without the key: refused as it always was."""
+        if getattr(self, '_hessian3D', False):
+            return self._hessianBlocks3(*args, **kwargs)
         if getattr(self, '_derivatives3D', False):
             self._refuse3('hessianBlocks', 'the per-cell blocks are built on the derivative planes of the 2-D operators; Hvec(parameter=\'joint\') applies the '
                                            'Gauss-Newton Hessian and illumination(kind=\'pseudoHessian\') preconditions a gradient')
         self._refuse3('hessianBlocks', 'there is no density derivative in 3-D to pair the velocity with; illumination(kind=\'pseudoHessian\') preconditions a gradient')
 
     def illumination(self, m=None, u=None, kind='pseudoHessian', side='source', perFreq=False, linearisation='scaler', parameter='c'):
+        """kind 'energy' and 'pseudoHessian' with the default linearisation='scaler': as in 2-D.  With hessian3D=True also the pseudo-Hessian diagonal of the exact
+        derivatives, H_p[i] = |scaleTerm|^2 sum_f sum_s ||(d A_f / d p_i) u^_s||^2: linearisation 'operator' | 'full' with parameter 'c' (an explicit `rho`: the
+        closed form |chi|^2 Smu sum_s |u^_s[i]|^2) and, with derivatives3D=True too, parameter 'rho' and -- without `rho` in the config -- linearisation='full',
+        parameter='c', the total derivative through the Gardner density.  float64 (N,), or (nfreq, N) with perFreq.  u: None, a DeviceFields or the host list."""
         if kind == 'gaussNewton' or linearisation != 'scaler' or parameter != 'c':
+            if getattr(self, '_hessian3D', False):
+                return self._pseudoHessian3(m, u, kind, side, perFreq, linearisation, parameter, blocks=False)
             self._refuse3('illumination(kind=%r, linearisation=%r, parameter=%r)' % (kind, linearisation, parameter),
                           'the Hessian diagonals are built on the derivative planes of the 2-D operators; kind \'energy\' and \'pseudoHessian\' with the default '
                           'linearisation=\'scaler\' are served')
         return HelmBaseProblem.illumination(self, m, u, kind, side, perFreq)
+
+    def _hessianBlocks3(self, m=None, u=None, kind='gaussNewton', side='source', perFreq=False, linearisation='full'):
+        return self._pseudoHessian3(m, u, kind, side, perFreq, linearisation, 'joint', blocks=True)
+
+    def _pseudoHessian3(self, m, u, kind, side, perFreq, linearisation, parameter, blocks):
+        """illumination of the exact kinds and hessianBlocks with hessian3D=True.  What is served follows the gradient being preconditioned (`_requireExact3`): 'c'
+        with an explicit `rho` needs this key alone; 'rho', the blocks and the Gardner total derivative need derivatives3D=True beside it."""
+        what = 'hessianBlocks' if blocks else 'illumination'
+        self._requirePaired()
+        if kind not in (('pseudoHessian', 'gaussNewton') if blocks else ('energy', 'pseudoHessian', 'gaussNewton')):
+            raise ValueError('kind is %r: %s' % (kind, '\'pseudoHessian\' (the energy has no density entry)' if blocks else '\'energy\' or \'pseudoHessian\''))
+        if side not in ('source', 'receiver'):
+            raise ValueError('side is %r: \'source\' or \'receiver\'' % (side,))
+        self._checkLinearisation(linearisation)
+        if kind == 'gaussNewton':
+            self._refuse3('%s(kind=\'gaussNewton\')' % (what,), 'the Gauss-Newton diagonal needs nrec back-solves through A^T per frequency, and a 3-D solve is iterative; '
+                                                             'kind=\'pseudoHessian\' reads the forward fields alone and Hvec applies the Gauss-Newton Hessian')
+        if kind == 'energy':
+            raise ValueError('kind=\'energy\' has no linearisation: linearisation=%r, parameter=%r go with kind=\'pseudoHessian\'' % (linearisation, parameter))
+        if isinstance(parameter, str) and parameter in ('Q', 'cQ'):
+            self._refuse3('%s(parameter=%r)' % (what, parameter), 'the visco wrappers and the chain from (c, Q) to the complex velocity are those of the 2-D '
+                                                                   'operators (parameter \'c\' and \'rho\' are served)')
+        if not blocks and isinstance(parameter, str) and parameter == 'joint':
+            raise ValueError('illumination returns one value per cell: parameter=\'joint\' has a 2 x 2 block per cell, which hessianBlocks(kind=\'pseudoHessian\') returns')
+        self._checkParameter(parameter, linearisation, joint=blocks)
+        if side == 'receiver':
+            self._refuse3('%s(side=\'receiver\', linearisation=%r)' % (what, linearisation),
+                          'the exact kinds are the source-side sums over the forward fields; side=\'receiver\' is served by the \'scaler\' kinds \'energy\' and \'pseudoHessian\'')
+        self.updateModel(m)                # (a dict may bring the `rho` that decides what is served)
+        if blocks and not self._hasDensity():
+            raise NotImplementedError('hessianBlocks needs an explicit `rho` in the config: without one the density follows the velocity (Gardner) and is no parameter '
+                                      'of its own, so there is no (c, rho) block -- illumination(linearisation=\'full\', parameter=\'c\') is the diagonal of the total '
+                                      'derivative (give `rho`, e.g. 310 c^0.25 as an array, for the blocks)')
+        if self.fieldsDtype != 'complex128':
+            raise NotImplementedError('%s(linearisation=%r) reads a complex128 store: fieldsDtype=%r is not served by the 3-D kernels (leave fieldsDtype at its default)'
+                                      % (what, linearisation, self.fieldsDtype))
+        if not getattr(self, '_derivatives3D', False) and (parameter != 'c' or not self._hasDensity()):
+            raise NotImplementedError('%s(linearisation=%r, parameter=%r)%s needs derivatives3D=True beside hessian3D=True: the density rows and the Gardner total '
+                                      'derivative are built on the buoyancy maps that key serves (parameter=\'c\' with an explicit `rho` needs hessian3D alone)'
+                                      % (what, linearisation, parameter, '' if self._hasDensity() else ' without `rho` in the config'))
+        parameter, gardner = self._requireExact3('%s(linearisation=%r)' % (what, linearisation), parameter, linearisation)
+        sv = self.survey
+        N = self.nrow
+        with self._forwardFields(u) as F:
+            if isinstance(F, DeviceFields):
+                from . import device_survey3d
+                return device_survey3d.pseudoHessianFromFields3(self, F, parameter, gardner, bool(perFreq), blocks)
+            shape = (3, N) if blocks else (N,)
+            H = np.zeros(((sv.nfreq,) + shape) if perFreq else shape, dtype=np.float64)
+            st = complex(self.system.scaleTerm)
+            a2 = st.real * st.real + st.imag * st.imag
+            for ifreq in self.ownedFreqs:
+                op = self.system.subProblems[ifreq]
+                uf = np.asarray(F[ifreq])
+                uh = np.conj(uf.reshape((uf.shape[0], -1)) / st)
+                if blocks:
+                    E = frechet3d.pseudoHessianBlocks3(op, uh)
+                else:
+                    E = frechet3d.pseudoHessianDiagonal3(op, uh, parameter, frechet3d.gardnerChain3(op) if gardner else None)
+                if perFreq:
+                    H[ifreq] = a2 * E
+                else:
+                    H += a2 * E
+        if self._sharded:
+            H = parallel.allreduce_sum(H)
+        return H
 
     # ---- gradient and Born data ------------------------------------------------------------------------------------------------------------------
     def Jtvec(self, m=None, v=None, u=None, adjoint='reciprocity', linearisation='scaler', parameter='c'):
