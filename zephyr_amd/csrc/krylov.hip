@@ -630,7 +630,7 @@ int solve_block_krylov(helm_op *op, int block, const cplx *dRHS, long long rhs_l
                 if (rc) return rc;
             }
         }
-        std::vector<int> restarts(n, 0);
+        std::vector<int> restarts(n, 0), refinements(n, 0);     // after a breakdown (at most 25) / for a refinement round (at most max_refine)
         std::vector<int> method_used(n, (o.method == HELM_CGNR || sys2) ? HELM_CGNR : (use_mg ? HELM_MG : HELM_BICGSTAB));
         std::vector<int> total_iters(n, 0);
         std::vector<double> relres(n, 0.0);
@@ -719,9 +719,11 @@ int solve_block_krylov(helm_op *op, int block, const cplx *dRHS, long long rhs_l
             }
             if (!refine) break;
             if (o.method == HELM_CGNR || sys2) {
-                for (int b = 0; b < n; ++b) if (B.h_mask[b]) op->h_scal[b].status = ST_ACTIVE;
+                // (run_cgnr counts every round from zero: what the finished round used goes to the total here)
+                for (int b = 0; b < n; ++b) if (B.h_mask[b]) { total_iters[b] += op->h_scal[b].iters; op->h_scal[b].status = ST_ACTIVE; }
                 upload_scal(op, n);
             } else {
+                for (int b = 0; b < n; ++b) if (B.h_mask[b]) refinements[b] += 1;      // a restart like those after a breakdown: helm_solve_info.restarts counts it
                 rc = restart_masked(op, block, B);
                 if (rc) return rc;
             }
@@ -733,7 +735,7 @@ int solve_block_krylov(helm_op *op, int block, const cplx *dRHS, long long rhs_l
             if (info) {
                 helm_solve_info &I = info[first + b];
                 I.iterations += total_iters[b] + S.iters;
-                I.restarts += restarts[b];
+                I.restarts += restarts[b] + refinements[b];
                 I.method = method_used[b];
                 I.relres = std::max(I.relres, relres[b]);
                 const int st = (relres[b] <= o.rtol * 1.0000001) ? 0 : (S.status == ST_BREAKDOWN ? 2 : 1);
