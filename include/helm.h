@@ -842,6 +842,64 @@ typedef struct helm_nm_stage {
     int report[5];                       /* out */
 } helm_nm_stage;
 int helm_debug_nm_stage(helm_nm_stage *p);
+/* (test hook) One stage of the 2-D multigrid preconditioner (zephyr_amd/csrc/mg.hip) on host data, through the kernels and with the launch shapes vcycle /
+ * apply_typed use: grid-stride launches of vblocks(N) x nrhs workgroups of 256 lanes, the dense coarse solve on ceil(nc / 256) x nrhs, the line solve on
+ * 4 W x nrhs waves.  Complex operands are (re, im) pairs of doubles and every length counts complex elements.  Vectors are [nrhs][N], planes [9][N] in the
+ * order of the assembled operator.  `active`: NULL or one byte per column; a column whose byte is 0 is handed to the kernels as a stopped right-hand side
+ * (RhsScal.status), which they must leave alone.  Every output goes up as the caller filled it and comes back whole, so that what a stage leaves alone can
+ * be seen.  Malformed input is refused with HELM_ERR_ARG before a device is touched.
+ * Free-standing stages (no handle; device, nz, nx, nrhs from the structure):
+ *   JAC0          y = omega_j m (.) x, m = dinv [N]                                             leaves alone: inactive columns
+ *   AXPY1         y += x                                                                        inactive columns
+ *   RESTRICT      y [nrhs][nzc nxc] = full weighting of x [nrhs][nz nx], nzc = (nz + 1) / 2     inactive columns
+ *   PROLONG_ADD   y [nrhs][nz nx] += bilinear prolongation of x [nrhs][nzc nxc]                  inactive columns
+ *   COARSE_DENSE  y = m^T x, m = invT [nc][nc] (the inverse stored transposed), nz = nc, nx = 1  inactive columns
+ *   LINE_FACTOR   m = nine planes; zl[0..2] = m, cp, af of the 2 W z-lines [2 W][nz], xl[0..2] of the 2 W x-lines [2 W][nx - 2 W]; needs 2 W + 2 <= nz, nx
+ *   LINE_SOLVE    k_line_factor, then y += wstrip T^-1 r on every strip line (zl / xl as LINE_FACTOR, or NULL).  Leaves alone: inactive columns and every
+ *                 element of y outside the lines.  r is in / out and what it holds afterwards is unspecified (the forward sweep stages its result in it).
+ * Hierarchy stages (op: a 2-D handle assembled at a frequency; mg_setup(op, nrhs) runs first and the hierarchy stays with the handle):
+ *   LEVELS        out: nlevels, lev_* per level, W, sweeps, nu1, nu2, fdepth, omega_j, wstrip, beta, tau (shifted), cpml (weak), nc, ntiles and up to
+ *                 tiles_cap entries of the tile list in tiles
+ *   PLANES        level >= 0: y = the nine planes of that level [9 N_l], r = its dinv [N_l]; level == -1: y = the strip operator's planes, zl / xl its six
+ *                 line-factor arrays (HELM_ERR_STATE when the strip is off); cinvT, when given: the transposed dense inverse [nc][nc]
+ *   STRIP_RESID   y = x - A_strip r on the points of the listed tiles (x = in, r = out of one sweep; y stands for strip_r).  Leaves alone: other points,
+ *                 inactive columns.  The handle's strip_r is zero again afterwards.
+ *   CYCLE         y = vcycle(level, x) with fmode; x, y [nrhs][N_level].  Leaves alone: inactive columns
+ *   APPLY         y = mg_apply(x), the whole M^-1.  Leaves alone: inactive columns
+ *   nu1, nu2, fdepth, sweeps: -1 the solver's own, else that value for this call only (CYCLE, APPLY; sweeps > 0 with the strip off: HELM_ERR_STATE). */
+#define HELM_MG_JAC0          0
+#define HELM_MG_AXPY1         1
+#define HELM_MG_RESTRICT      2
+#define HELM_MG_PROLONG_ADD   3
+#define HELM_MG_COARSE_DENSE  4
+#define HELM_MG_LINE_FACTOR   5
+#define HELM_MG_LINE_SOLVE    6
+#define HELM_MG_LEVELS        7
+#define HELM_MG_PLANES        8
+#define HELM_MG_STRIP_RESID   9
+#define HELM_MG_CYCLE         10
+#define HELM_MG_APPLY         11
+#define HELM_MG_MAX_LEVELS    16
+typedef struct helm_mg_stage {
+    int device, stage, nz, nx, nrhs, W;
+    helm_op *op;                         /* hierarchy stages */
+    double omega_j, wstrip;
+    const unsigned char *active;
+    const double *x; long long x_len;    /* the vector a stage reads */
+    double *y; long long y_len;          /* in / out */
+    const double *m; long long m_len;    /* dinv, invT or the nine planes */
+    double *r; long long r_len;          /* LINE_SOLVE: residual, in / out; STRIP_RESID: the iterate (read); PLANES: dinv (out) */
+    double *zl[3], *xl[3]; long long zl_len, xl_len;
+    double *cinvT; long long cinvT_len;
+    int level, fmode, nu1, nu2, fdepth, sweeps;
+    /* out (LEVELS) */
+    int nlevels, lev_nz[HELM_MG_MAX_LEVELS], lev_nx[HELM_MG_MAX_LEVELS], lev_npml[HELM_MG_MAX_LEVELS];
+    double lev_dx[HELM_MG_MAX_LEVELS], lev_dz[HELM_MG_MAX_LEVELS];
+    int o_W, o_sweeps, o_nu1, o_nu2, o_fdepth, o_nc, o_ntiles, o_tile_rows;
+    double o_omega_j, o_wstrip, o_beta, o_tau, o_cpml;
+    int *tiles; long long tiles_cap;
+} helm_mg_stage;
+int helm_debug_mg_stage(helm_mg_stage *p);
 int helm_debug_inverse_bench(int device, int n, const double *A, int reps, int recurse_n, double *ms_out);
 
 /* --- diagnostics of the 3-D multigrid hierarchy (host only, no GPU needed; zephyr_amd/csrc/mg3_keep.hip) ------------------ */

@@ -261,6 +261,7 @@ _SIGNATURES = {
     'helm_debug_zgemm_choice': (ctypes.c_int, [ctypes.c_int] * 9 + [ctypes.POINTER(ctypes.c_int)]),
     'helm_debug_zgemm_ex': (ctypes.c_int, [ctypes.POINTER(ZgemmEx)]),
     'helm_debug_nm_stage': (ctypes.c_int, [ctypes.c_void_p]),            # (helm_nm_stage *: the structure lives with its tests, tests/resid_cases.py)
+    'helm_debug_mg_stage': (ctypes.c_int, [ctypes.c_void_p]),            # (helm_mg_stage *: the structure lives with its tests, tests/mg_cases.py)
     'helm_debug_inverse': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int]),
     'helm_debug_zgemm_bench': (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                               ctypes.POINTER(ctypes.c_double)]),

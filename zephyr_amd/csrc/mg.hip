@@ -642,3 +642,233 @@ int mg_apply(helm_op *op, const cplx *in, cplx *out, int nrhs, const RhsScal *sc
     if (nrhs > P->batch) HELM_FAIL(op, HELM_ERR_ARG, "preconditioner batch too small");
     return P->f32 ? apply_typed<cplxf>(op, P, in, out, nrhs, scal) : apply_typed<cplx>(op, P, in, out, nrhs, scal);
 }
+
+// ---- test hook: one stage of this file on host data (include/helm.h, helm_debug_mg_stage) --------------------------------------------------
+int ensure_part(helm_op *op, int nrhs);        // krylov.hip: op->d_part, where the residual launches leave their partial sums (the Krylov driver's call in a solve)
+
+namespace {
+
+// host-side check of a helm_mg_stage: every address a stage can form lies inside a buffer the caller handed in
+bool mg_stage_ok(const helm_mg_stage &p) {
+    if (p.device < 0 || p.stage < HELM_MG_JAC0 || p.stage > HELM_MG_APPLY) return false;
+    const bool hier = p.stage >= HELM_MG_LEVELS;
+    const bool batched = p.stage != HELM_MG_LINE_FACTOR && p.stage != HELM_MG_LEVELS && p.stage != HELM_MG_PLANES;
+    if (batched && (p.nrhs < 1 || p.nrhs > 64)) return false;
+    const long long k = p.nrhs;
+    if (hier) {
+        // (the dimensions are the handle's: lengths are checked against them once the hierarchy stands, still before any launch)
+        if (!p.op || p.op->ny > 0 || !p.op->assembled) return false;
+        if (p.nu1 < -1 || p.nu2 < -1 || p.fdepth < -1 || p.sweeps < -1 || p.nu1 == 0 || p.nu1 > 8 || p.nu2 > 8 || p.sweeps > 16) return false;
+        if (p.stage == HELM_MG_LEVELS) return p.tiles_cap >= 0 && (p.tiles_cap == 0 || p.tiles);
+        if (p.stage == HELM_MG_PLANES) return p.level >= -1 && p.y != nullptr;
+        if (!p.x || !p.y || p.x == p.y) return false;
+        if (p.stage == HELM_MG_STRIP_RESID) return p.r != nullptr && p.r != p.y;
+        if (p.stage == HELM_MG_CYCLE) return p.level >= 0 && (p.fmode == 0 || p.fmode == 1);
+        return true;
+    }
+    if (p.nz < 1 || p.nx < 1 || (long long)p.nz * p.nx > (1LL << 24)) return false;
+    const long long N = (long long)p.nz * p.nx, Nc = (long long)((p.nz + 1) / 2) * ((p.nx + 1) / 2);
+    switch (p.stage) {
+    case HELM_MG_JAC0:          return p.m && p.m_len >= N && p.x && p.x_len >= k * N && p.y && p.y_len >= k * N && std::isfinite(p.omega_j);
+    case HELM_MG_AXPY1:         return p.x && p.x_len >= k * N && p.y && p.y_len >= k * N;
+    case HELM_MG_RESTRICT:      return p.x && p.x_len >= k * N && p.y && p.y_len >= k * Nc;
+    case HELM_MG_PROLONG_ADD:   return p.x && p.x_len >= k * Nc && p.y && p.y_len >= k * N;
+    case HELM_MG_COARSE_DENSE:  return p.nx == 1 && p.nz <= 4096 && p.m && p.m_len >= N * N && p.x && p.x_len >= k * N && p.y && p.y_len >= k * N;
+    default: break;
+    }
+    // the line stages
+    if (p.W < 1 || p.W > 64 || 2 * p.W + 2 > p.nz || 2 * p.W + 2 > p.nx || !p.m || p.m_len < 9 * N) return false;
+    const long long zl = 2LL * p.W * p.nz, xl = 2LL * p.W * (p.nx - 2 * p.W);
+    const bool lines = p.zl[0] != nullptr;
+    for (int i = 0; i < 3; ++i) if ((p.zl[i] != nullptr) != lines || (p.xl[i] != nullptr) != lines) return false;
+    if (lines && (p.zl_len < zl || p.xl_len < xl)) return false;
+    if (p.stage == HELM_MG_LINE_FACTOR) return lines;
+    return p.r && p.r_len >= k * N && p.y && p.y_len >= k * N && p.r != p.y && std::isfinite(p.wstrip);
+}
+
+// host buffers up, device copies freed when the hook returns
+struct MgStageBufs {
+    std::vector<void *> dev;
+    bool bad = false;
+    void *up(const void *h, size_t bytes) {
+        if (!h || bytes == 0) return nullptr;
+        void *d = nullptr;
+        if (hipMalloc(&d, bytes) != hipSuccess) { bad = true; return nullptr; }
+        dev.push_back(d);
+        if (hipMemcpy(d, h, bytes, hipMemcpyHostToDevice) != hipSuccess) bad = true;
+        return d;
+    }
+    void *room(size_t bytes) {
+        void *d = nullptr;
+        if (hipMalloc(&d, bytes ? bytes : 16) != hipSuccess) { bad = true; return nullptr; }
+        dev.push_back(d);
+        return d;
+    }
+    void down(void *h, const void *d, size_t bytes) { if (h && d && bytes && hipMemcpy(h, d, bytes, hipMemcpyDeviceToHost) != hipSuccess) bad = true; }
+    ~MgStageBufs() { for (void *d : dev) hipFree(d); }
+};
+
+RhsScal *mg_stage_scal(MgStageBufs &B, const unsigned char *act, int nrhs) {
+    std::vector<RhsScal> h((size_t)std::max(nrhs, 1), RhsScal());
+    for (int b = 0; b < nrhs; ++b) h[b].status = (!act || act[b]) ? ST_ACTIVE : ST_CONVERGED;
+    return (RhsScal *)B.up(h.data(), h.size() * sizeof(RhsScal));
+}
+
+int mg_stage_free(helm_mg_stage &p) {
+    if (hipSetDevice(p.device) != hipSuccess) return HELM_ERR_DEVICE;
+    MgStageBufs B;
+    const long long k = p.nrhs;
+    const long long N = (long long)p.nz * p.nx;
+    const int nzc = (p.nz + 1) / 2, nxc = (p.nx + 1) / 2;
+    const long long Nc = (long long)nzc * nxc;
+    hipStream_t st = nullptr;
+    if (p.stage == HELM_MG_LINE_FACTOR || p.stage == HELM_MG_LINE_SOLVE) {
+        const int W = p.W;
+        const size_t zl = (size_t)2 * W * p.nz, xl = (size_t)2 * W * (p.nx - 2 * W);
+        const cplx *dC = (const cplx *)B.up(p.m, (size_t)9 * N * 16);
+        cplx *dz[3], *dx[3];
+        for (int i = 0; i < 3; ++i) {
+            dz[i] = (cplx *)(p.zl[i] ? B.up(p.zl[i], zl * 16) : B.room(zl * 16));
+            dx[i] = (cplx *)(p.xl[i] ? B.up(p.xl[i], xl * 16) : B.room(xl * 16));
+        }
+        cplx *dR = nullptr, *dU = nullptr; RhsScal *dS = nullptr;
+        if (p.stage == HELM_MG_LINE_SOLVE) { dR = (cplx *)B.up(p.r, (size_t)(k * N) * 16); dU = (cplx *)B.up(p.y, (size_t)(k * N) * 16); dS = mg_stage_scal(B, p.active, p.nrhs); }
+        if (B.bad) return HELM_ERR_DEVICE;
+        HELM_LAUNCH(k_line_factor, dim3((2 * W + 63) / 64), dim3(64), 0, st, dC, p.nz, p.nx, W, 1, dz[0], dz[1], dz[2]);
+        HELM_LAUNCH(k_line_factor, dim3((2 * W + 63) / 64), dim3(64), 0, st, dC, p.nz, p.nx, W, 0, dx[0], dx[1], dx[2]);
+        if (p.stage == HELM_MG_LINE_SOLVE) {
+            LineFactors<cplx> zf = {dz[0], dz[1], dz[2]}, xf = {dx[0], dx[1], dx[2]};
+            HELM_LAUNCH((k_line_solve<cplx>), dim3(4 * W, p.nrhs), dim3(64), 0, st, p.nz, p.nx, W, zf, xf, (const cplx *)dR, dU, p.wstrip, (const RhsScal *)dS);
+        }
+        if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return HELM_ERR_DEVICE;
+        for (int i = 0; i < 3; ++i) { B.down(p.zl[i], dz[i], zl * 16); B.down(p.xl[i], dx[i], xl * 16); }
+        if (p.stage == HELM_MG_LINE_SOLVE) { B.down(p.y, dU, (size_t)(k * N) * 16); B.down(p.r, dR, (size_t)(k * N) * 16); }
+        return B.bad ? HELM_ERR_DEVICE : HELM_OK;
+    }
+    const bool to_coarse = p.stage == HELM_MG_RESTRICT, from_coarse = p.stage == HELM_MG_PROLONG_ADD;
+    const long long nx_in = from_coarse ? Nc : N, ny_out = to_coarse ? Nc : N;
+    const cplx *dX = (const cplx *)B.up(p.x, (size_t)(k * nx_in) * 16);
+    cplx *dY = (cplx *)B.up(p.y, (size_t)(k * ny_out) * 16);
+    const cplx *dM = (const cplx *)B.up(p.m, p.stage == HELM_MG_JAC0 ? (size_t)N * 16 : p.stage == HELM_MG_COARSE_DENSE ? (size_t)(N * N) * 16 : 0);
+    const RhsScal *dS = mg_stage_scal(B, p.active, p.nrhs);
+    if (B.bad) return HELM_ERR_DEVICE;
+    switch (p.stage) {
+    case HELM_MG_JAC0:         HELM_LAUNCH((k_jac0<cplx>), dim3(vblocks(N), p.nrhs), dim3(256), 0, st, dM, dX, dY, N, p.omega_j, dS); break;
+    case HELM_MG_AXPY1:        HELM_LAUNCH((k_axpy1<cplx>), dim3(vblocks(N), p.nrhs), dim3(256), 0, st, dX, dY, N, dS); break;
+    case HELM_MG_RESTRICT:     HELM_LAUNCH((k_restrict<cplx>), dim3(vblocks(Nc), p.nrhs), dim3(256), 0, st, dX, dY, p.nz, p.nx, nzc, nxc, dS); break;
+    case HELM_MG_PROLONG_ADD:  HELM_LAUNCH((k_prolong_add<cplx>), dim3(vblocks(N), p.nrhs), dim3(256), 0, st, dX, dY, p.nz, p.nx, nzc, nxc, dS); break;
+    default: {
+        const int nc = p.nz;
+        HELM_LAUNCH((k_coarse_dense<cplx>), dim3((nc + 255) / 256, p.nrhs), dim3(256), (size_t)nc * sizeof(cplx), st, dM, dX, dY, nc, dS);
+        break;
+    }
+    }
+    if (hipStreamSynchronize(st) != hipSuccess || hipGetLastError() != hipSuccess) return HELM_ERR_DEVICE;
+    B.down(p.y, dY, (size_t)(k * ny_out) * 16);
+    return B.bad ? HELM_ERR_DEVICE : HELM_OK;
+}
+
+// the overrides of one call, taken back when it returns
+struct MgOverride {
+    MgPrecond *P; int nu1, nu2, fdepth, sweeps;
+    MgOverride(MgPrecond *P_, const helm_mg_stage &p) : P(P_), nu1(P_->nu1), nu2(P_->nu2), fdepth(P_->fdepth), sweeps(P_->sweeps) {
+        if (p.nu1 >= 0) P->nu1 = p.nu1;
+        if (p.nu2 >= 0) P->nu2 = p.nu2;
+        if (p.fdepth >= 0) P->fdepth = p.fdepth;
+        if (p.sweeps >= 0) P->sweeps = p.sweeps;
+    }
+    ~MgOverride() { P->nu1 = nu1; P->nu2 = nu2; P->fdepth = fdepth; P->sweeps = sweeps; }
+};
+
+int mg_stage_hier(helm_mg_stage &p) {
+    helm_op *op = p.op;
+    HIP_TRY(op, hipSetDevice(op->device));
+    const int batch = std::max(p.nrhs, 1);
+    int rc = ensure_part(op, batch);
+    if (rc) return rc;
+    rc = mg_setup(op, batch);
+    if (rc) return rc;
+    MgPrecond *P = op->mg;
+    if (!P || P->f32) HELM_FAIL(op, HELM_ERR_STATE, "helm_debug_mg_stage: no double-precision 2-D hierarchy on this handle");
+    const int nl = (int)P->lv.size();
+    const bool strip = P->sop != nullptr;
+    hipStream_t st = op->stream;
+    MgStageBufs B;
+    if (p.stage == HELM_MG_LEVELS) {
+        if (nl > HELM_MG_MAX_LEVELS) HELM_FAIL(op, HELM_ERR_UNSUPPORTED, "helm_debug_mg_stage: more than %d levels", HELM_MG_MAX_LEVELS);
+        p.nlevels = nl;
+        for (int l = 0; l < nl; ++l) {
+            const helm_op *lo = P->lv[l].op;
+            p.lev_nz[l] = lo->nz; p.lev_nx[l] = lo->nx; p.lev_npml[l] = lo->nPML; p.lev_dx[l] = lo->dx; p.lev_dz[l] = lo->dz;
+        }
+        p.o_W = P->W; p.o_sweeps = P->sweeps; p.o_nu1 = P->nu1; p.o_nu2 = P->nu2; p.o_fdepth = P->fdepth; p.o_nc = P->nc; p.o_ntiles = P->ntiles;
+        p.o_tile_rows = helm_stencil_tile_rows();
+        p.o_omega_j = P->omega_j; p.o_wstrip = P->wstrip; p.o_beta = P->beta; p.o_tau = P->lv[0].op->a_tau; p.o_cpml = P->lv[0].op->a_cpml;
+        const long long n = std::min<long long>(p.tiles_cap, P->ntiles);
+        if (n > 0) HIP_TRY(op, hipMemcpy(p.tiles, P->d_tiles, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+        return HELM_OK;
+    }
+    if (p.stage == HELM_MG_PLANES) {
+        if (p.level >= nl) HELM_FAIL(op, HELM_ERR_ARG, "helm_debug_mg_stage: level %d of %d", p.level, nl);
+        if (p.cinvT) {
+            if (p.cinvT_len < (long long)P->nc * P->nc) HELM_FAIL(op, HELM_ERR_ARG, "helm_debug_mg_stage: cinvT holds fewer than nc^2 elements");
+            HIP_TRY(op, hipMemcpy(p.cinvT, P->d_cinvT, (size_t)P->nc * P->nc * 16, hipMemcpyDeviceToHost));
+        }
+        if (p.level < 0) {
+            if (!strip || P->sweeps <= 0) HELM_FAIL(op, HELM_ERR_STATE, "helm_debug_mg_stage: the strip relaxation is off on this grid");
+            const long long N = op->N, zl = 2LL * P->W * op->nz, xl = 2LL * P->W * (op->nx - 2 * P->W);
+            if (p.y_len < 9 * N) HELM_FAIL(op, HELM_ERR_ARG, "helm_debug_mg_stage: y holds fewer than nine planes");
+            HIP_TRY(op, hipMemcpy(p.y, P->sC, (size_t)(9 * N) * 16, hipMemcpyDeviceToHost));
+            for (int i = 0; i < 3; ++i) {
+                if (p.zl[i]) { if (p.zl_len < zl) HELM_FAIL(op, HELM_ERR_ARG, "helm_debug_mg_stage: zl too short"); HIP_TRY(op, hipMemcpy(p.zl[i], P->zl[i], (size_t)zl * 16, hipMemcpyDeviceToHost)); }
+                if (p.xl[i]) { if (p.xl_len < xl) HELM_FAIL(op, HELM_ERR_ARG, "helm_debug_mg_stage: xl too short"); HIP_TRY(op, hipMemcpy(p.xl[i], P->xl[i], (size_t)xl * 16, hipMemcpyDeviceToHost)); }
+            }
+            return HELM_OK;
+        }
+        const MgLevel &L = P->lv[p.level];
+        const long long N = L.op->N;
+        if (p.y_len < 9 * N || (p.r && p.r_len < N)) HELM_FAIL(op, HELM_ERR_ARG, "helm_debug_mg_stage: buffers shorter than the level");
+        HIP_TRY(op, hipMemcpy(p.y, L.C, (size_t)(9 * N) * 16, hipMemcpyDeviceToHost));
+        if (p.r) HIP_TRY(op, hipMemcpy(p.r, L.dinv, (size_t)N * 16, hipMemcpyDeviceToHost));
+        return HELM_OK;
+    }
+    const long long k = p.nrhs;
+    if (p.stage == HELM_MG_CYCLE && p.level >= nl) HELM_FAIL(op, HELM_ERR_ARG, "helm_debug_mg_stage: level %d of %d", p.level, nl);
+    const long long N = p.stage == HELM_MG_CYCLE ? P->lv[p.level].op->N : op->N;
+    if (p.x_len < k * N || p.y_len < k * N || (p.stage == HELM_MG_STRIP_RESID && p.r_len < k * N)) HELM_FAIL(op, HELM_ERR_ARG, "helm_debug_mg_stage: vectors shorter than nrhs x N");
+    if (p.nrhs > P->batch) HELM_FAIL(op, HELM_ERR_ARG, "helm_debug_mg_stage: preconditioner batch too small");
+    MgOverride over(P, p);
+    if (P->sweeps > 0 && !strip) HELM_FAIL(op, HELM_ERR_STATE, "helm_debug_mg_stage: the strip relaxation is off on this grid");
+    if (p.stage == HELM_MG_STRIP_RESID && !strip) HELM_FAIL(op, HELM_ERR_STATE, "helm_debug_mg_stage: the strip relaxation is off on this grid");
+    const cplx *dX = (const cplx *)B.up(p.x, (size_t)(k * N) * 16);
+    cplx *dY = p.stage == HELM_MG_STRIP_RESID ? (cplx *)P->strip_r : (cplx *)B.up(p.y, (size_t)(k * N) * 16);
+    const cplx *dR = p.stage == HELM_MG_STRIP_RESID ? (const cplx *)B.up(p.r, (size_t)(k * N) * 16) : nullptr;
+    const RhsScal *dS = mg_stage_scal(B, p.active, p.nrhs);
+    if (B.bad) HELM_FAIL(op, HELM_ERR_DEVICE, "helm_debug_mg_stage: upload failed");
+    if (p.stage == HELM_MG_STRIP_RESID) {
+        HIP_TRY(op, hipMemcpyAsync(dY, p.y, (size_t)(k * N) * 16, hipMemcpyHostToDevice, st));
+        HIP_TRY(op, hipStreamSynchronize(st));
+        rc = stencil_level<cplx>(op, P->sop, P->sC, dR, dY, dX, p.nrhs, EPI_RESID, dS, nullptr, 0.0, P->d_tiles, P->ntiles);
+    } else if (p.stage == HELM_MG_CYCLE) {
+        rc = vcycle<cplx>(op, P, p.level, dX, dY, p.nrhs, dS, p.fmode != 0);
+    } else {
+        rc = mg_apply(op, dX, dY, p.nrhs, dS);
+    }
+    const hipError_t e = hipStreamSynchronize(st);
+    if (rc) return rc;
+    HIP_TRY(op, e);
+    HIP_TRY(op, hipGetLastError());
+    B.down(p.y, dY, (size_t)(k * N) * 16);
+    if (p.stage == HELM_MG_STRIP_RESID) HIP_TRY(op, hipMemset(P->strip_r, 0, (size_t)P->batch * op->N * sizeof(cplx)));
+    if (B.bad) HELM_FAIL(op, HELM_ERR_DEVICE, "helm_debug_mg_stage: download failed");
+    return HELM_OK;
+}
+
+}  // namespace
+
+extern "C" int helm_debug_mg_stage(helm_mg_stage *pp) {
+    if (!pp) return HELM_ERR_ARG;
+    if (!mg_stage_ok(*pp)) { helm_set_error(pp->stage >= HELM_MG_LEVELS ? pp->op : nullptr, "helm_debug_mg_stage: malformed arguments"); return HELM_ERR_ARG; }
+    helm_tuning_refresh();
+    return pp->stage >= HELM_MG_LEVELS ? mg_stage_hier(*pp) : mg_stage_free(*pp);
+}
