@@ -40,6 +40,10 @@
  *   helm_imaging_accumulate_c64_device,
  *   helm_sample_rows_c64_device    <- forward fields handed to dpred / Jtvec as `u=` (problem.py:124-164, survey.py:190-198),
  *                                     kept in HBM at half size
+ *   helm_misfit_moments_device,
+ *   helm_misfit_terms_device,
+ *   helm_misfit_adjoint_device     <- (no counterpart; the reference left the objective to SimPEG's l2_DataMisfit) zephyr_amd/misfit.py: the data misfit,
+ *                                     its source estimate and its adjoint source on the sample panels of a work item
  *   helm_destroy                   <- `del obj.factors` / __del__         discretization.py:86-99
  *
  * Conventions
@@ -633,6 +637,27 @@ int helm_energy_accumulate_c64_device(helm_op *op, const void *dU32, const void 
 int helm_sample_rows_c64_device(helm_op *op, const void *dU32, const void *dExp, int nsrc, long long ld, const void *d_rowptr, const void *d_col,
                                 const void *d_val, int nrec, long long row_stride, double alpha_re, double alpha_im, double beta_re, double beta_im,
                                 void *d_out);
+
+/* The data misfit on the sample panels of a work item (zephyr_amd/misfit.py states the functional).  A panel is [nrec][ld] with the item's ncol <= ld columns
+ * adjacent, sample [r][j] at r * ld + j, as the sampling entry points write it: dP the samples p, dD dobs, both complex128 and 16-byte aligned, dW2 the
+ * weights w2 >= 0 as doubles (NULL: ones).  A sample with w2 == 0 is selected away: it may hold NaN in dD.  Every per-column sum is one lane walking
+ * r = 0, 1, ... : a column has the same bits alone, anywhere in a batch and on every run.  No atomics.  Each call returns when its outputs are complete.
+ * kind: 0 'l2', 1 'huber' (par0 = threshold > 0), 2 'hybrid' (par0 = epsilon > 0), 3 'logarithmic' (par0 = amplitude, par1 = phase weight, both >= 0; dobs
+ * and the scaled samples must not be zero where w2 > 0).
+ *
+ * dMom[j] = (Re a_j, Im a_j, b_j), a_j = sum_r w2 conj(p) d, b_j = sum_r w2 |p|^2: 3 ncol doubles.  The source estimate of a group is sum a / sum b. */
+int helm_misfit_moments_device(helm_op *op, const void *dP, const void *dD, const void *dW2, long long ld, int nrec, int ncol, void *dMom);
+/* At the source factors dS[j] (ncol complex128), q = s p: dPsi = grad_q phi ([nrec][ld] complex128, 0 where w2 == 0; not one of the input panels) and
+ * dOut[j] = (phi_j, Re c_j, Im c_j), c_j = sum_r conj(psi) p: 3 ncol doubles. */
+int helm_misfit_terms_device(helm_op *op, int kind, double par0, double par1, const void *dP, const void *dD, const void *dW2, const void *dS, long long ld,
+                             int nrec, int ncol, void *dPsi, void *dOut);
+/* The adjoint source dV[r][j] = phase_r (conj(s_j) psi + w2 (e_j d - f_j p)), 0 where w2 == 0.  dCoef[j] = (Re e_j, Im e_j, f_j), e = c / b and
+ * f = 2 Re(c s) / b of the column's group (3 ncol doubles), or NULL: a given source, the first term alone.  dPhase: nrec complex128 factors per receiver
+ * (conj(t_r) / t_r of complex receiver terms, which makes the transposed sampling of the back-sources act as its conjugate transpose), or NULL.  dV may be dP:
+ * the adjoint source then replaces the samples.  dGn: NULL, or a [nrec][ld] panel of doubles that receives the Gauss-Newton weights at fixed s (|s|^2 w2 for
+ * 'l2'; 'logarithmic' needs par0 == par1, HELM_ERR_UNSUPPORTED otherwise). */
+int helm_misfit_adjoint_device(helm_op *op, int kind, double par0, double par1, const void *dPsi, const void *dS, const void *dCoef, const void *dP,
+                               const void *dD, const void *dW2, const void *dPhase, long long ld, int nrec, int ncol, void *dV, void *dGn);
 
 /* Device buffers are recycled by size class; a class holds as many as the busiest moment so far needed.  How many operators a pipelined job has alive at its
  * busiest is a matter of thread timing, so a job that got by with three buffers of a class in its first items may ask for a fourth later -- a hipMalloc of GBs

@@ -13,6 +13,7 @@ from .eurus import Eurus, EurusHD
 from .helm3d import Helm3D, Helm3DTransposed
 from .interpolation import BaseGridInterpolator, SplineGridInterpolator
 from .minizephyr import MiniZephyr, MiniZephyrHD, MiniZephyr25D
+from .misfit import DataMisfit
 from .source import (FakeSource, SimpleSource, StackedSimpleSource, SparseKaiserSource, KaiserSource,
                      AnisotropicKaiserSource)
 from .survey import Helm3DSurvey
@@ -28,5 +29,5 @@ __all__ = [
     'AnalyticalHelmholtz', 'BaseModelDependent', 'BaseAnisotropic', 'AttributeMapper', 'BaseSCCache', 'SCFilter',
     'BaseDiscretization', 'DiscretizationWrapper', 'prefactor_many', 'BaseDist', 'BaseMPDist', 'MultiFreq', 'SerialMultiFreq',
     'ViscoMultiFreq', 'MultiGridHelper', 'MultiGridMultiFreq', 'ViscoMultiGridMultiFreq', 'BaseGridInterpolator', 'SplineGridInterpolator', 'Eurus', 'EurusHD', 'Helm3D', 'Helm3DTransposed', 'MiniZephyr', 'MiniZephyrHD', 'MiniZephyr25D', 'FakeSource', 'SimpleSource',
-    'StackedSimpleSource', 'SparseKaiserSource', 'KaiserSource', 'AnisotropicKaiserSource', 'Helm3DSurvey', 'Helm3DProblem', 'trim',
+    'StackedSimpleSource', 'SparseKaiserSource', 'KaiserSource', 'AnisotropicKaiserSource', 'Helm3DSurvey', 'Helm3DProblem', 'DataMisfit', 'trim',
 ]

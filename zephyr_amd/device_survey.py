@@ -36,6 +36,10 @@ The pipelines, one row each.  Every row is a body of its own made of the shared 
                                                  on the block of that ky                              device into the item's result
     kyGradientFromFields    stored (per ky)      qb of R^H r, once per item            nky k            per ky: lag imaging into P against    one stacked partial G (2N) per worker
                                                                                                       the block of that ky, V_ky^T P, L_ky^T P
+    misfitFromFields        stored               -- (the samples of the slice become   0, then the k    the misfit kernels on the sample      3 k doubles per item, twice; then what
+                                                 the adjoint source, in place)        of the gradient  panel, then the gradient pipeline     the gradient pipeline brings down
+    misfitOnePass           dealt                source columns, then the gather      2k               sampling and the misfit kernels, then 3 k doubles per item, twice; one
+                                                 from the item's adjoint source                        the imaging or plane kernels on U     partial G per worker
     illumination           dealt                source or receiver columns          k                energy kernel                         one partial H per worker
     illuminationFromFields  stored               --                                  0                -- (energy kernel reads the slice)    one partial H per worker
       kind='gaussNewton'                         receiver columns, once per worker   nrec, once per   lag Gram of the slice, then the       one partial H per worker
@@ -154,6 +158,20 @@ def runOnDevices(devs, items, fn, factor=True):
     return [ws for worker in workers for ws in worker.values()]
 
 
+class DevicePanels(object):
+    """(nrec, k) complex128 panels of work items, each on the GPU of its item: what stands for `resid` in the gradient pipelines when the adjoint source was made
+    on the device (`misfitFromFields`).  panel(ifreq, c0, c1) is the tensor of the item with the sources c0 .. c1-1 of frequency ifreq."""
+
+    def __init__(self):
+        self._panels = {}
+
+    def put(self, ifreq, c0, c1, tensor):
+        self._panels[(int(ifreq), int(c0), int(c1))] = tensor
+
+    def panel(self, ifreq, c0, c1):
+        return self._panels[(int(ifreq), int(c0), int(c1))]
+
+
 # ---- [qf | qb] of an item ----------------------------------------------------------------------------------------------------------------------
 def _muxTriplets(mats, c0, c1, rows):
     """(row, col, val, shape) of [m_0[:, c0:c1] | m_1[:, c0:c1] | ...] from the matrices' own arrays (no format conversion, no sort of 10^5..10^6 entries):
@@ -217,7 +235,15 @@ def _prepareBackSources(sv, qb, freqs):
 def _backSources(ws, sv, op, qb, resid, ifreq, c0, c1, d_R, rows):
     """d_R ([k][rows], k = c1 - c0) = the back-sources R_s^T resid[:, s, ifreq] of the sources c0 .. c1-1.  qb given (fixed array): the host-built
     sparse matrix as triplets.  qb None (the array moves with the source): the gather of the survey's adjoint plan from the item's residual samples
-    resid[:, c0:c1, ifreq] -- 16 nrec k bytes up instead of ~81 entries of 28 B per sample, and no sparse products on the host."""
+    resid[:, c0:c1, ifreq] -- 16 nrec k bytes up instead of ~81 entries of 28 B per sample, and no sparse products on the host.  resid a `DevicePanels`
+    (the adjoint source of a misfit, made on the device): the item's panel is used where it lies, nothing goes up; qb is None then, for a fixed array too --
+    the adjoint plan is built from the stacked receivers, which serve both modes."""
+    if isinstance(resid, DevicePanels):
+        plan = _planOnDevice(ws, sv, ifreq)
+        panel = resid.panel(ifreq, c0, c1)
+        _lib.wait_torch_stream(ws.device)
+        op.rhsFromSamplesDevice(panel.data_ptr(), c1 - c0, plan, c0, c1, d_R, rows=rows)
+        return
     if qb is not None:
         op.rhsFromSparseDevice(_muxTriplets((qb[ifreq],), c0, c1, rows), d_R)
         return
@@ -1633,3 +1659,305 @@ def hessianBlocksFromFields(prob, F, kind, perFreq, linearisation='full'):
         _lib.wait_torch_stream(ws.device)
         op.pseudoHessianBlocksDevice(d_uF, k, stretch, a2, row, ldh=Ni, d_exp=d_exp, rows=Ni)
     return _sumEnergyPartials(prob, [ws.H for ws in runOnDevices(devs, items, one, factor=False) if ws.H is not None], shape)
+
+
+# ---- the data misfit: value, source estimate and gradient with the data kept in HBM ----------------------------------------------------------------------
+# misfit.DataMisfit on what these pipelines serve (Helm2DProblem over MiniZephyr / MiniZephyrHD on one grid; 'c', 'rho', 'joint'; 'operator', 'full').  The
+# samples of an item stay where the sampling kernel wrote them: the kernels of csrc/survey_misfit.hip turn the panel into the adjoint source in place, the
+# back-sources are gathered from it (`_backSources` with a DevicePanels) and what comes down per item is 3 k doubles twice.  `misfitFromFields` runs over a store
+# and hands its panels to the existing gradient pipelines; `misfitOnePass` solves the forward columns of an item, images against them and forgets them.
+#
+# The sums of a group that spans columns (source='perFrequency') and the division a / b are formed on the host, from the per-column sums in column order by
+# the same function in every route (`_misfitSources`, `_misfitCoefficients`): a route changes where the columns come from, not the bits of s.
+
+MISFIT_KINDS = {'l2': 0, 'huber': 1, 'hybrid': 2, 'logarithmic': 3}
+
+
+def _misfitSetup(prob, phi):
+    "calling-thread half of the misfit item steps: the kernel's kind and parameters, the receiver phase of `_hermitianResidual` (None: real receiver terms)"
+    pr = phi.params
+    par = {'l2': (0., 0.), 'huber': (pr.get('threshold', 0.), 0.), 'hybrid': (pr.get('epsilon', 0.), 0.),
+           'logarithmic': (pr.get('amplitude', 0.), pr.get('phase', 0.))}[phi.kind]
+    return dict(kind=MISFIT_KINDS[phi.kind], par=(float(par[0]), float(par[1])), phase=prob._hermitianPhase())
+
+
+def _misfitData(ws, phi, ifreq, c0, c1):
+    "the item's dobs and w2 panels (w2: None without weights) on the worker's GPU: uploaded once per DataMisfit and GPU, kept with the DataMisfit"
+    key = (ws.device.index, int(ifreq), int(c0), int(c1))
+    held = phi._devicePanels
+    if key not in held:
+        D = _lib.to_device(np.ascontiguousarray(phi.dobs[:, c0:c1, ifreq]), ws.device, np.complex128)
+        W = None if phi.weights is None else _lib.to_device(np.ascontiguousarray(phi.weights[:, c0:c1, ifreq]), ws.device, np.float64)
+        held[key] = (D, W)
+    return held[key]
+
+
+def _ptr(t):
+    import ctypes
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def misfitMomentsDevice(op, P, D, W):
+    "(k, 3) float64 on the host: (Re a_j, Im a_j, b_j) of the columns of the (nrec, k) panels P, D (complex128) and W (float64 or None) on op's GPU"
+    import torch
+    nrec, k = P.shape
+    mom = torch.empty((k, 3), dtype=torch.float64, device=P.device)
+    _lib.wait_torch_stream(P.device)
+    _lib.check(_lib.load().helm_misfit_moments_device(op.handle, _ptr(P), _ptr(D), _ptr(W), int(P.stride(0)), int(nrec), int(k), _ptr(mom)), op.handle)
+    return _lib.from_device(mom)
+
+
+def misfitTermsDevice(op, kind, par, P, D, W, s, PSI):
+    "PSI (a panel like P) = psi at the source factors s (k complex128, host) and (k, 3) float64 on the host: (phi_j, Re c_j, Im c_j)"
+    import torch
+    nrec, k = P.shape
+    S = _lib.to_device(np.ascontiguousarray(s, dtype=np.complex128), P.device, np.complex128)
+    out = torch.empty((k, 3), dtype=torch.float64, device=P.device)
+    _lib.wait_torch_stream(P.device)
+    _lib.check(_lib.load().helm_misfit_terms_device(op.handle, int(kind), par[0], par[1], _ptr(P), _ptr(D), _ptr(W), _ptr(S), int(P.stride(0)), int(nrec), int(k),
+                                                    _ptr(PSI), _ptr(out)), op.handle)
+    return _lib.from_device(out)
+
+
+def misfitAdjointDevice(op, kind, par, PSI, s, coef, P, D, W, phase, V, GN=None):
+    """V (P itself, or a panel like it) = phase (conj(s) psi + w2 (e d - f p)); coef (k, 3) float64 on the host or None (a given source); phase a device tensor of
+    nrec complex128 or None; GN: None or a float64 panel like P for the Gauss-Newton weights"""
+    nrec, k = P.shape
+    S = _lib.to_device(np.ascontiguousarray(s, dtype=np.complex128), P.device, np.complex128)
+    C = None if coef is None else _lib.to_device(np.ascontiguousarray(coef, dtype=np.float64), P.device, np.float64)
+    _lib.wait_torch_stream(P.device)
+    _lib.check(_lib.load().helm_misfit_adjoint_device(op.handle, int(kind), par[0], par[1], _ptr(PSI), _ptr(S), _ptr(C), _ptr(P), _ptr(D), _ptr(W), _ptr(phase),
+                                                      int(P.stride(0)), int(nrec), int(k), _ptr(V), _ptr(GN)), op.handle)
+
+
+def _misfitSources(phi, ifreq, mom, c0=0):
+    """s of the columns c0 .. c0 + len(mom) - 1 of frequency ifreq, complex128, from their moments (len, 3).  The columns are a whole group or several: one
+    (source, frequency) each, or -- 'perFrequency' -- all the columns of the frequency"""
+    if phi.source == 'given':
+        return np.ones(len(mom), dtype=np.complex128) if phi._given is None else np.array(phi._given[c0:c0 + len(mom), ifreq])
+    a, b = mom[:, 0] + 1j * mom[:, 1], mom[:, 2]
+    if phi.source == 'perFrequency':
+        a, b = np.full(a.shape, a.sum()), np.full(b.shape, b.sum())
+    if np.any(b == 0):
+        from .misfit import _groupName
+        raise ValueError('no source estimate for %s: its weighted predicted energy sum w2 |p|^2 is zero' % _groupName(phi.source, c0 + int(np.flatnonzero(b == 0)[0]), ifreq))
+    return a / b
+
+
+def _misfitCoefficients(phi, mom, out, s):
+    "(e, f) of the same columns as the adjoint kernel takes them, (len, 3) float64: e = c / b, f = 2 Re(c s) / b of the column's group (an estimated source)"
+    c, b = out[:, 1] + 1j * out[:, 2], mom[:, 2]
+    if phi.source == 'perFrequency':
+        c, b = np.full(c.shape, c.sum()), np.full(b.shape, b.sum())
+    e = c / b
+    return np.stack([e.real, e.imag, 2 * (c * s).real / b], axis=1)
+
+
+def _misfitSampler(prob, freqs, scale):
+    """sampled(ws, op, ifreq, c0, c1, d_u, d_exp) -> a fresh (nrec, k) panel on the item's GPU with p = scale R u of the k wavefields at d_u; the receiver CSR is
+    the one `_sampling` uploads (made here, on the calling thread)"""
+    import torch
+    sv = prob.survey
+    nrec = sv.nrec
+    stride = nrec if sv.mode != 'fixed' else 0
+    Rms = _receiverMatrices(sv, freqs)
+
+    def sampled(ws, op, ifreq, c0, c1, d_u, d_exp):
+        gk = sv._gridKey(ifreq)
+        csr = _csrOnDevice(ws, Rms[gk], gk, nrec, stride, c0)
+        P = torch.empty((nrec, c1 - c0), dtype=torch.complex128, device=ws.device)
+        _lib.wait_torch_stream(ws.device)
+        op.sampleDevice(d_u, c1 - c0, csr, P.data_ptr(), d_exp=d_exp)
+        if scale != 1.0:
+            P.mul_(scale)
+        return P
+    return sampled
+
+
+class _MisfitState(object):
+    "what the passes of a misfit evaluation share: per-column sums of every owned frequency on the host, the panels of every item on its GPU"
+
+    def __init__(self, prob, phi):
+        _, nsrc, nfreq = phi.shape
+        self.phi, self.setup = phi, _misfitSetup(prob, phi)
+        self.mom = np.zeros((nfreq, nsrc, 3))
+        self.out = np.zeros((nfreq, nsrc, 3))
+        self.S = np.zeros((nsrc, nfreq), dtype=np.complex128)
+        self.coef = np.zeros((nfreq, nsrc, 3))
+        self.held = {}                     # (ifreq, c0) -> (P, D, W, PSI)
+        self.panels = DevicePanels()
+
+    def moments(self, ws, op, ifreq, c0, c1, P):
+        import torch
+        D, W = _misfitData(ws, self.phi, ifreq, c0, c1)
+        self.held[(ifreq, c0)] = (P, D, W, torch.empty_like(P))
+        if self.phi.source != 'given':
+            self.mom[ifreq, c0:c1] = misfitMomentsDevice(op, P, D, W)
+
+    def sources(self, ifreq, c0=0, c1=None):
+        self.S[c0:c1, ifreq] = _misfitSources(self.phi, ifreq, self.mom[ifreq, c0:c1], c0)
+
+    def terms(self, op, ifreq, c0, c1):
+        P, D, W, PSI = self.held[(ifreq, c0)]
+        self.out[ifreq, c0:c1] = misfitTermsDevice(op, self.setup['kind'], self.setup['par'], P, D, W, self.S[c0:c1, ifreq], PSI)
+
+    def coefficients(self, ifreq, c0=0, c1=None):
+        if self.phi.source != 'given':
+            self.coef[ifreq, c0:c1] = _misfitCoefficients(self.phi, self.mom[ifreq, c0:c1], self.out[ifreq, c0:c1], self.S[c0:c1, ifreq])
+
+    def adjoint(self, ws, op, ifreq, c0, c1):
+        P, D, W, PSI = self.held.pop((ifreq, c0))
+        ph = self.setup['phase']
+        phase = None if ph is None else ws.cached(('misfit_phase', id(ph)), lambda: _lib.to_device(ph, ws.device, np.complex128), keep=ph)
+        coef = None if self.phi.source == 'given' else self.coef[ifreq, c0:c1]
+        misfitAdjointDevice(op, self.setup['kind'], self.setup['par'], PSI, self.S[c0:c1, ifreq], coef, P, D, W, phase, P)
+        self.panels.put(ifreq, c0, c1, P)
+
+    def item(self, ws, op, ifreq, c0, c1, P):
+        "all passes of an item whose groups lie inside it"
+        self.moments(ws, op, ifreq, c0, c1, P)
+        self.sources(ifreq, c0, c1)
+        self.terms(op, ifreq, c0, c1)
+        self.coefficients(ifreq, c0, c1)
+        self.adjoint(ws, op, ifreq, c0, c1)
+
+    def result(self, prob, owned):
+        "(value, source terms): summed over the owned frequencies, then over ranks where the frequencies are sharded"
+        nsrc, nfreq = self.S.shape
+        pack = np.zeros(1 + 2 * nsrc * nfreq)
+        pack[0] = sum(float(np.add.reduce(self.out[ifreq, :, 0])) for ifreq in owned)
+        own = np.zeros(nfreq, dtype=bool)
+        own[list(owned)] = True
+        pack[1:] = np.where(own[None, :], self.S, 0).ravel().view(np.float64)
+        if prob._sharded:
+            pack = parallel.allreduce_sum(pack)
+        return float(pack[0]), np.array(pack[1:]).view(np.complex128).reshape(nsrc, nfreq)
+
+
+def _itemsPerFrequency(items):
+    n = {}
+    for it in items:
+        n[it[2]] = n.get(it[2], 0) + 1
+    return n
+
+
+def misfitInOnePass(phi, items):
+    "True when no group of the misfit spans two items: a given or per-source factor, or every frequency's columns in one item"
+    return phi.source in ('given', 'perSource') or all(n == 1 for n in _itemsPerFrequency(items).values())
+
+
+def _panelGradient(prob, F, panels, linearisation, parameter):
+    "the device branch of Jtvec(adjoint='transpose') with the adjoint source in `panels`, up to the real chain on a density half (the caller applies d b / d rho)"
+    adj = prob.adjointSystem
+    if parameter == 'joint':
+        return jointGradientFromFields(prob, F, None, panels, adj, linearisation)
+    if parameter == 'rho':
+        return gradientFromFields(prob, F, None, panels, system=adj, linearisation=linearisation, parameter='rho')
+    if linearisation == 'full':
+        return gradientFromFields(prob, F, None, panels, system=adj, linearisation='full', chain=prob._gardnerChain())
+    return gradientFromFields(prob, F, None, panels, system=adj, linearisation=linearisation)
+
+
+def misfitFromFields(prob, F, phi, linearisation, parameter):
+    """(value, source terms (nsrc, nfreq), gradient) of the misfit `phi` from forward fields in HBM; linearisation 'operator' or 'full' as `_resolveLinearisation`
+    left it, parameter 'c', 'rho' or 'joint'; the gradient is what the pipeline of that pair returns (a density half still wants d b / d rho).
+    Pass 1 over the store's own items: sample, scale, k_misfit_moments -- 3 k doubles per item come down.  Host: s per group.  Pass 2: k_misfit_terms, 3 k doubles
+    down.  Host: c per group.  Pass 3: k_misfit_adjoint in place of the samples.  Then the gradient pipeline with the panels as `resid`.  Where no group spans
+    two items (`misfitInOnePass`) the three passes are one."""
+    F.checkCurrent(prob)
+    owned = F.ownedFreqs
+    st = _MisfitState(prob, phi)
+    if F.items:
+        sampled = _misfitSampler(prob, owned, F.scale)
+        devs, items = _storedItems(prob.system, F)
+        collapse = misfitInOnePass(phi, items)
+
+        def first(ws, op, ifreq, c0, c1):
+            P = sampled(ws, op, ifreq, c0, c1, *F.pointers(ifreq, c0))
+            if collapse:
+                st.item(ws, op, ifreq, c0, c1, P)
+            else:
+                st.moments(ws, op, ifreq, c0, c1, P)
+        runOnDevices(devs, items, first, factor=False)
+        if not collapse:
+            for ifreq in owned:
+                st.sources(ifreq)
+            runOnDevices(devs, items, lambda ws, op, ifreq, c0, c1: st.terms(op, ifreq, c0, c1), factor=False)
+            for ifreq in owned:
+                st.coefficients(ifreq)
+            runOnDevices(devs, items, st.adjoint, factor=False)
+    g = _panelGradient(prob, F, st.panels, linearisation, parameter)
+    val, S = st.result(prob, owned)
+    return val, S, g
+
+
+def misfitOnePass(prob, phi, linearisation, parameter):
+    """`misfitFromFields` without a store, for a misfit whose groups lie inside the items (`misfitInOnePass`): per freshly dealt item the sources are expanded and
+    solved forward into the workspace, sampled, the misfit kernels make the adjoint source in place of the samples, the back-sources are gathered from the panel,
+    solved through the transposed operator of the same GPU and replica, and the imaging or plane kernels of the gradient pipeline of (linearisation, parameter)
+    run against the workspace's forward fields.  Only the fields of one item are held; the factors of A and of A^T are resident side by side.  The kernels, their
+    inputs and the order in which a worker adds to its partial are those of the store route over a complex128 store: the same bits where the items coincide."""
+    import torch
+    sv = prob.survey
+    N = prob.nrow
+    owned = prob.ownedFreqs
+    scale = complex(prob.system.scaleTerm)
+    joint, density = parameter == 'joint', parameter == 'rho'
+    planes = joint or density or linearisation == 'full'
+    stretch = linearisation == 'full'
+    chain = prob._gardnerChain() if (linearisation == 'full' and not joint and not density) else None
+    gardner = chain is not None
+    n = 2 * N if joint else N
+    st = _MisfitState(prob, phi)
+    wss = []
+    if owned:
+        qf = sv.getSources()
+        adj = prob.adjointSystem
+        devs, items = deviceItems(prob.system, owned, sv.nsrc)
+        back = deviceItems(adj, owned, sv.nsrc)[1]                # (the same deal: the transposed operator of the same frequency, batch and GPU)
+        partner = {(ifreq, c0): aop for _, aop, ifreq, c0, _ in back}
+        _prepareBackSources(sv, None, owned)
+        _checkSecondFactorsFit(back, planes=9 if planes else 0, blocks=3, beside={(ifreq, c0): op for _, op, ifreq, c0, _ in items})
+        sampled = _misfitSampler(prob, owned, scale)
+        add = None if planes else _addOperator(prob, scale)
+
+        def one(ws, op, ifreq, c0, c1):
+            k, Ni = c1 - c0, int(op.nrow)
+            aop = partner[(ifreq, c0)]
+            G = _partial(ws, 'G', n, torch.complex128)
+            Gb = _partial(ws, 'Gb', N, torch.complex128) if gardner else None
+            UF, U, R = ws.buffer('UF', k * Ni), ws.buffer('U', k * Ni), ws.buffer('R', k * Ni)
+            _expandColumns(op, qf, ifreq, c0, c1, R)
+            _lib.wait_torch_stream(ws.device)
+            op.solveDevice(R.data_ptr(), UF.data_ptr(), k, Ni)
+            st.item(ws, op, ifreq, c0, c1, sampled(ws, op, ifreq, c0, c1, UF.data_ptr(), None))
+            _backSources(ws, sv, aop, None, st.panels, ifreq, c0, c1, R.data_ptr(), Ni)
+            if not planes:
+                scaler, target, _ = add(ws, aop, ifreq, Ni)
+                _lib.wait_torch_stream(ws.device)
+                aop.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+                aop.imagingOpAccumulateDevice(UF.data_ptr(), U.data_ptr(), k, scaler.data_ptr(), target.data_ptr(), d_exp=None, rows=Ni)
+                return
+            P = ws.buffer('lags', 9 * Ni)
+            P.zero_()
+            _lib.wait_torch_stream(ws.device)
+            aop.solveDevice(R.data_ptr(), U.data_ptr(), k, Ni)
+            aop.lagImagingAccumulateDevice(UF.data_ptr(), U.data_ptr(), k, P.data_ptr(), d_exp=None, rows=Ni)
+            w = -scale / np.conj(complex(aop.premul))
+            if density:
+                aop.buoyancyAdjointDevice(P.data_ptr(), w, G.data_ptr(), conj=True)
+                return
+            if stretch:
+                aop.velocityAdjointDevice(P.data_ptr(), w, G.data_ptr(), conj=True)
+            else:
+                aop.massAdjointDevice(P.data_ptr(), w, G.data_ptr(), conj=True)
+            if joint:
+                aop.buoyancyAdjointDevice(P.data_ptr(), w, G.data_ptr() + 16 * N, conj=True)
+            elif gardner:
+                aop.buoyancyAdjointDevice(P.data_ptr(), w, Gb.data_ptr(), conj=True)
+        wss = runOnDevices(devs, items, one)
+    g = _sumPartials(prob, [ws.G for ws in wss if ws.G is not None], n=n).real
+    if gardner:
+        g = g + chain * _sumPartials(prob, [ws.Gb for ws in wss if ws.Gb is not None]).real
+    val, S = st.result(prob, owned)
+    return val, S, g

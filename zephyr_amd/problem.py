@@ -66,6 +66,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         'viscoDerivatives': (False,    '_viscoDerivatives', bool),    # a visco problem serves the exact derivatives ('operator' / 'full') through the chain from (c, Q)
         'kyDerivatives':    (False,    '_kyDerivatives', bool),       # a 2.5-D problem serves the exact derivatives from the forward fields kept PER ky (fieldsDevice(perKy=True))
         'multiscaleDerivatives': (False, '_multiscaleDerivatives', bool),    # a multiscale pairing serves the exact derivatives: per-grid maps, then the transposed grid transfer
+        'misfitHostData':   (False,    '_misfitHostData', bool),      # a DataMisfit keeps to its generic route: the data come down, the adjoint source goes up
     }
 
     surveyPair = HelmBaseSurvey
@@ -938,10 +939,15 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         """resid' with R_s^T resid'_s = R_s^H resid_s, for the device pipelines (which build R_s^T r): a receiver matrix is diag(srTerms) R0 with R0 the real
         columns of the source generator, so resid' = resid (.) conj(srTerms) / srTerms per receiver (0 where the term is 0: that row of R is zero).  A
         generator with complex columns has no such form and is refused."""
+        ph = self._hermitianPhase()
+        return resid if ph is None else resid * ph[:, None, None]
+
+    def _hermitianPhase(self):
+        "conj(srTerms) / srTerms per receiver, (nrec,) complex128: the factor of `_hermitianResidual`; None where the receiver terms are real (nothing to do)"
         sv = self.survey
         t = np.asarray(sv.srTerms, dtype=np.complex128).ravel()
         if not np.any(t.imag):
-            return resid
+            return None
         Rm = sp.csr_matrix(sv.rVec(0, 0))
         rows = np.repeat(np.arange(Rm.shape[0]), np.diff(Rm.indptr))
         base = Rm.data * np.conj(t[rows])
@@ -950,7 +956,7 @@ class HelmBaseProblem(BaseModelDependent, BaseSCCache):
         nz = t != 0
         ph = np.zeros_like(t)
         ph[nz] = np.conj(t[nz]) / t[nz]
-        return resid * ph[:, None, None]
+        return ph
 
     @contextlib.contextmanager
     def _forwardFields(self, u, perKy=False):
